@@ -2,7 +2,7 @@
 """Headline benchmark: clips/s of a VideoMAE-B 16x224x224 forward with ToMe r=16 (BASELINE.json
 configs[1]), bf16, synthetic clips resident in HBM, one process per GPU.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -11,11 +11,18 @@ each with the HIP merge path between attention and MLP -> head -> top-1/top-5 co
 are independent replicas on different clips (weak scaling, no data-path collective); one RCCL
 all-reduce of [top1, top5, clips] closes the timed region.  Rank 0 prints ONE JSON line.
 
-Besides the throughput the line carries
+A plain run sets up, warms up, times the steps and prints the line.  --dump-outputs DIR writes what rank 0's last
+timed step computed (DUMPED below) as DIR/<name>.npy; the clips and weights are seeded, so two builds given the same
+arguments can be compared output for output.
+
+With --full (each leg can be left out with its --no-* switch) the line also carries
   roofline      the dominant merge-path kernel against its bound (HBM 8 TB/s or fp32-MFMA 157.3 TF/s,
                 /opt/skills/guides/MI355X_MICROARCH.md), from HIP-event timings taken in this run
   cpu_baseline  the reference's PyTorch-CPU path (restated in oracle/torch_port.py, kind "port") timed
                 on this host's cores on a bounded sample of the same workload
+  merge_path_kernels, merge_path, attention_kernel
+                per-kernel figures of the merge path and of the attention (taken with the roofline)
+  also          the other BASELINE.json workloads and the reference's batch-8 protocol
 """
 from __future__ import annotations
 
@@ -42,7 +49,7 @@ EMBED, HEADS, HEAD_DIM, LAYERS = 768, 12, 64, 12
 DEFAULT_BATCH = 384  # clips per GPU per step: 64 -> 128 is +4.7 % clips/s (GEMM / attention efficiency), 128 -> 256 -> 384 -> 512: 2327 -> 2369 -> 2396 -> 2396
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -65,7 +72,17 @@ def parse():
                     "rehearse N>1 on a one-GPU box)")
     ap.add_argument("--force-group", action="store_true", help="form the torch.distributed group at N=1 too (a group of "
                     "one: RCCL initialisation and the job's collectives run on a single GPU; tests/test_launch_gpu.py)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the roofline and per-kernel figures, the `also` workloads "
+                         "and the CPU baseline (each can be left out with its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what rank 0's last timed step computed to DIR/<name>.npy (float32 / float64)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run measures the headline figure and nothing else
+        args.no_roofline = args.no_also = args.no_cpu_baseline = True
+    return args
 
 
 def token_schedule(t0: int, r: int, layers: int):
@@ -578,6 +595,26 @@ def cpu_baseline(frames: int, r: int, clips: int, iters: int):
                       f"oracle/torch_port.py (op sequence of tome/merge.py + tome/patch/videomae.py), {dt:.1f}s"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+# what --dump-outputs writes: what a caller of the timed step receives from its last step
+DUMPED = {"logits": "float32 [batch, 400]: the classification head's output for this rank's clips",
+          "topk_counts": "float64 [3]: top-1 hits, top-5 hits and clips of that step, before the all-reduce"}
+
+
+def dump_outputs(path: str, arrays) -> None:
+    """arrays[name] -> path/<name>.npy as float32 (float64 for integers); an array over its share of DUMP_LIMIT_BYTES
+    is cut to a fixed, seeded sample of its rows."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = (t.detach().float() if t.is_floating_point() else t.detach().double()).cpu().numpy()
+        if a.nbytes > share:
+            keep = max(1, share // (a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def worker(args):
     """One rank of the job (the whole job at N=1): everything that touches the GPU happens in here."""
     from hosts import launch
@@ -614,9 +651,12 @@ def worker(args):
     counts = torch.zeros(3, dtype=torch.int64, device=dev)  # top1, top5, clips
 
     from hosts.evalloop import all_reduce_counts, topk_counts
+    last = {}  # what the latest step computed (in a captured graph: the tensors its replays write)
 
     def step():
-        counts.add_(topk_counts(model([clips]), labels))
+        logits = model([clips])
+        last["logits"], last["topk_counts"] = logits, topk_counts(logits, labels)
+        counts.add_(last["topk_counts"])
 
     graphed = False
     with torch.no_grad():
@@ -668,6 +708,8 @@ def worker(args):
     launch.check_census(census, args.backend, world)  # all ranks answered; under RCCL on distinct devices
     total_clips = int(counts[2].item())
     assert total_clips == B * args.steps * world, (total_clips, B, args.steps, world)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {name: last[name] for name in DUMPED})
 
     out = None
     if rank == 0:

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -45,11 +46,11 @@ def test_model_benchmark_two_self_spawned_ranks(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_line_carries_the_other_workloads():
-    """The default bench line (here at small batch, `--also-quick`): headline + roofline with both byte counts + the
+    """The `--full` bench line (here at small batch, `--also-quick`): headline + roofline with both byte counts + the
     `also` object with the other BASELINE.json sizes, each with its merge kernel's roofline, and the reference's
     batch-8 protocol eager / HIP graph."""
-    out = _run([sys.executable, "bench.py", "--batch", "8", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                "--also-quick"])
+    out = _run([sys.executable, "bench.py", "--full", "--batch", "8", "--steps", "2", "--warmup", "1",
+                "--no-cpu-baseline", "--also-quick"])
     roof = out["roofline"]
     assert roof["bound"] == "hbm" and 0 < roof["frac_8d"] < roof["frac"] < 1 and roof["bytes_8d"] < roof["bytes_fused"]
     also = out["also"]
@@ -62,6 +63,20 @@ def test_bench_line_carries_the_other_workloads():
     for fam in ("videomae_b_16x224", "timesformer_divst_8x224", "vivit_b_32x224", "motionformer_224_16x4"):
         vals = [v for k, v in proto[fam].items() if not k.endswith("_error")]
         assert len(vals) == 3 and all(v is not None and v > 0 for v in vals), proto[fam]
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_its_outputs(tmp_path):
+    """A plain run (no --full) times the headline and measures nothing else; --dump-outputs writes the logits and
+    top-k counts of its last timed step."""
+    out = _run([sys.executable, "bench.py", "--gpus", "1", "--batch", "4", "--steps", "3", "--warmup", "1",
+                "--dump-outputs", str(tmp_path)])
+    assert out["unit"] == "clips/s" and out["higher_is_better"] is True and out["dtype"] == "bf16"
+    assert out["steps"] == 3 and out["value"] > 0 and out["ms_per_step"] > 0
+    assert not {"roofline", "also", "cpu_baseline", "attention_kernel"} & set(out)
+    logits, counts = np.load(tmp_path / "logits.npy"), np.load(tmp_path / "topk_counts.npy")
+    assert logits.dtype == np.float32 and logits.shape == (4, 400) and np.isfinite(logits).all()
+    assert counts.dtype == np.float64 and counts[2] == 4 and 0 <= counts[0] <= counts[1] <= 4
 
 
 @pytest.mark.gpu
