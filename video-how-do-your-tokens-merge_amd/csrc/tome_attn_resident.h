@@ -21,14 +21,11 @@
 #pragma once
 
 #define RES_ROWS 224  // K / V rows resident per workgroup: 3 full 64-key tiles + the first half of a fourth
-#ifndef RES_VS
-#define RES_VS ATT_VS  // V row stride in LDS (elements)
-#endif
 
 template <typename TX, bool BIAS>
 __global__ __launch_bounds__(512, 4) void k_resident_attention(AttnArgs a) {
     __shared__ __attribute__((aligned(16))) short lds_k[RES_ROWS * ATT_KS];  // 32256 B
-    __shared__ __attribute__((aligned(16))) short lds_v[RES_ROWS * RES_VS];  // 43008 B
+    __shared__ __attribute__((aligned(16))) short lds_v[RES_ROWS * ATT_VS];  // 43008 B
     // A FIFTH k-step carries what would otherwise be vector work on 16 accumulator registers per block:
     //   channels 2, 3: K side 1, Q side -m_ref split into two terms hi + lo of the 16-bit format (residual < 2^-15 |m|:
     //              a common factor of at most 2^(1e-4) between the first block's weights and the later ones, far below
@@ -88,7 +85,7 @@ __global__ __launch_bounds__(512, 4) void k_resident_attention(AttnArgs a) {
             const int idx = tid + 512 * i, key = idx >> 3, c = idx & 7;
             if (idx < NCH) {
                 *reinterpret_cast<uint4 *>(lds_k + key * ATT_KS + 8 * c) = kr[i];
-                *reinterpret_cast<uint4 *>(lds_v + key * RES_VS + 8 * c) = vr[i];
+                *reinterpret_cast<uint4 *>(lds_v + key * ATT_VS + 8 * c) = vr[i];
             }
         }
         if (tid < RES_ROWS) {
@@ -108,7 +105,7 @@ __global__ __launch_bounds__(512, 4) void k_resident_attention(AttnArgs a) {
 
     typedef __attribute__((address_space(3))) att_s16x4 *lds_s16x4_p;
     const short *const kbase = lds_k + col * ATT_KS + 8 * hf;
-    const short *const vbase = lds_v + (4 * hf + ((lane & 15) >> 2)) * RES_VS + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+    const short *const vbase = lds_v + (4 * hf + ((lane & 15) >> 2)) * ATT_VS + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
     const float sl = a.scale * LOG2E;
 
     for (int qt = wave; qt < ntq; qt += 8) {
@@ -167,11 +164,11 @@ __global__ __launch_bounds__(512, 4) void k_resident_attention(AttnArgs a) {
         auto pv = [&](int blk) __attribute__((always_inline)) {
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
-                const short *va = vbase + (blk * 32 + 16 * p) * RES_VS;
+                const short *va = vbase + (blk * 32 + 16 * p) * ATT_VS;
                 const att_s16x4 f0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(va));
-                const att_s16x4 f1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(va + 8 * RES_VS));
+                const att_s16x4 f1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(va + 8 * ATT_VS));
                 const att_s16x4 f2 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(va + 32));
-                const att_s16x4 f3 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(va + 8 * RES_VS + 32));
+                const att_s16x4 f3 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(va + 8 * ATT_VS + 32));
                 att_s16x8 vf0, vf1;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {

@@ -25,6 +25,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "../../include/tome_hip.h"
 #include "tome_common.h"
 #include "tome_match.h"
@@ -238,12 +240,9 @@ static int match_tail(const MatchWs &w, int64_t n, int64_t T, int64_t D, int64_t
     const int T1 = (int)((T + 1) / 2), T2 = (int)(T / 2);
     const int prof_reps = prof_reps_now();
     // 2. similarity + row max/argmax: one single-wave workgroup per (group, A tile, j-part); the B tiles are
-    // split into WJ parts so that the launch has >= ~6 waves per SIMD (1024 SIMDs) whatever the batch
-    static const long target_waves = [] {
-        const char *e = getenv("TOME_SCORES_WAVES");  // tuning knob, default from measurements on MI355X
-        long v = e ? atol(e) : 0;
-        return v > 0 ? v : 6144L;
-    }();
+    // split into WJ parts so that the launch has >= ~6 waves per SIMD (1024 SIMDs) whatever the batch (target
+    // measured on MI355X)
+    const long target_waves = 6144L;
     int WJ = (int)((target_waves + n * w.ntA - 1) / (n * w.ntA));
     if (WJ > MAX_WJ) WJ = MAX_WJ;
     if (WJ > w.ntB) WJ = w.ntB;
@@ -468,6 +467,55 @@ static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 static TokLayout contiguous_layout(int64_t T, int64_t C) { return TokLayout{0, T * C, 0, C, 1}; }
 
+// The dtype dispatch of the merge family: f(Dt<TX>{}) for token dtype code `dtype` (fp32 only where F32), otherwise
+// bad() -- the entry point's own error.
+template <typename T> struct Dt { using type = T; };
+template <int V> using Op = std::integral_constant<int, V>;
+
+template <bool F32, typename F, typename Bad>
+static int dispatch_x(int dtype, F &&f, Bad &&bad) {
+    switch (dtype) {
+    case TOME_F32:
+        if constexpr (F32) return f(Dt<float>{});
+        break;
+    case TOME_BF16: return f(Dt<bf16_t>{});
+    case TOME_F16: return f(Dt<f16_t>{});
+    }
+    return bad();
+}
+
+// ... and f(Dt<TX>{}, Dt<TS>{}) for the (token, size) pairs of the weighted merges: sizes in the token dtype or fp32
+template <bool F32, typename F, typename Bad>
+static int dispatch_xs(int x_dtype, int size_dtype, F &&f, Bad &&bad) {
+    return dispatch_x<F32>(x_dtype, [&](auto tx) {
+        if (size_dtype == TOME_F32) return f(tx, Dt<float>{});
+        if (size_dtype == x_dtype) return f(tx, tx);
+        return bad();
+    }, bad);
+}
+
+// XCD-aware numbering of the workgroups (MergeSched, csrc/tome_merge.h) for the launches where many destinations
+// receive sources (8 r >= T: TimeSformer / Motionformer frame groups at r = 32, late layers at r = 16) -- there the
+// edge blocks at the end of every group otherwise land on the same XCDs in every group; measured per layer with
+// tools/regroup_kernel_times.py: -4 ... -7 % at r = 32, +-1 % at r = 16, +3 % at r = 8 and +3.6 % on the
+// benchmark's VideoMAE launches (598 vs 577 us), hence not there.
+static MergeSched merge_sched(bool drop, int64_t T, int64_t r, int64_t bpg, int64_t ny) {
+    const int64_t total = bpg * ny;
+    MergeSched sch{(unsigned)bpg, (unsigned)total, 0u, 0, 0ull};
+    if (!drop && r <= 64 && 8 * r >= T && total < (1ll << 28) && bpg < (1ll << 12) && total >= 64) {
+        sch.per_xcd = (unsigned)((total + 7) / 8);
+        sch.on = 1;
+        sch.magic = ((1ull << 40) + (unsigned long long)bpg - 1ull) / (unsigned long long)bpg;
+    }
+    return sch;
+}
+
+// the template arguments of one k_merge_rows_fast form, handed to launch_merge_rows' launch site
+template <int NIT, bool LN, bool EAGER> struct FastForm {
+    static constexpr int nit = NIT;
+    static constexpr bool ln = LN, eager = EAGER;
+};
+
 template <typename TX, typename TS, int OP>
 static int launch_merge_rows(const void *x, const void *size, int64_t n, int64_t T, int64_t C, int64_t r,
                              const int64_t *src, const int64_t *dst, const int64_t *unm, int distill,
@@ -483,20 +531,9 @@ static int launch_merge_rows(const void *x, const void *size, int64_t n, int64_t
     const LnArgs no_ln{nullptr, nullptr, nullptr, 0.0f, nullptr, 0, TokLayout{0, 0, 0, 0, 1}, nullptr, 0, nullptr};
     if (vec_ok && cpr <= FAST_NIT * WAVE) {
         // rows per wave: measured on MI355X, NIT=6 (four 1536-byte rows per wave for 768-channel bf16 tokens)
-        // beats NIT=3 by ~4 %; TOME_MERGE_NIT=3 keeps the other variant reachable for re-measurement
-        static const int nit_pref = [] {
-            const char *e = getenv("TOME_MERGE_NIT");
-            int v = e ? atoi(e) : 0;
-            return (v == 3 || v == 6) ? v : 6;
-        }();
-        // with the LayerNorm fused: 6 chunks per lane for x alone; with the residual stream next to it 3 per lane
+        // beats NIT=3 by ~4 %; with the LayerNorm fused and the residual stream next to x 3 chunks per lane
         // (77 instead of 107 VGPRs, six instead of four waves per SIMD) measured 5 % faster (124 vs 131 us)
-        static const int nit_ln = [] {
-            const char *e = getenv("TOME_MERGE_LN_NIT");
-            int v = e ? atoi(e) : 0;
-            return (v == 3 || v == 6) ? v : 0;
-        }();
-        const int nit = (cpr <= 3 * WAVE) ? (ln_p ? (nit_ln ? nit_ln : (ln_p->addend ? 3 : 6)) : nit_pref) : FAST_NIT;
+        const int nit = (cpr <= 3 * WAVE && ln_p && ln_p->addend) ? 3 : FAST_NIT;
         int R = (int)((nit * WAVE) / cpr);
         if (R > FAST_MAXR) R = FAST_MAXR;
         // grid.x = the blocks of one group (streaming waves, then the edge waves), (y, z) = group (+ rows of blocks
@@ -505,67 +542,29 @@ static int launch_merge_rows(const void *x, const void *size, int64_t n, int64_t
         const int64_t ny = n + (cls_rows ? (cls_rows + 4 * bpg - 1) / (4 * bpg) : 0);
         const int64_t gy = ny < 65535 ? ny : 65535, gz = (ny + gy - 1) / gy;
         if (gz > 65535) return fail(TOME_EINVAL, "merge: too many groups (%lld)", (long long)n);
-        dim3 grid((unsigned)bpg, (unsigned)gy, (unsigned)gz);
-        // XCD-aware numbering of the workgroups (MergeSched, csrc/tome_merge.h) for the launches where many destinations
-        // receive sources (8 r >= T: TimeSformer / Motionformer frame groups at r = 32, late layers at r = 16) -- there the
-        // edge blocks at the end of every group otherwise land on the same XCDs in every group; measured per layer with
-        // tools/regroup_kernel_times.py: -4 ... -7 % at r = 32, +-1 % at r = 16, +3 % at r = 8 and +3.6 % on the
-        // benchmark's VideoMAE launches (598 vs 577 us), hence not there.  TOME_MERGE_XCD=0 / 1 forces it off / on
-        // (measurement switch, read per call).
-        MergeSched sch{(unsigned)bpg, (unsigned)(bpg * ny), 0u, 0, 0ull};
-        {
-            const char *xe = getenv("TOME_MERGE_XCD");
-            const int64_t total = bpg * ny;
-            const bool want = xe ? xe[0] == '1' : (OP != OP_DROP && r <= 64 && 8 * r >= T);
-            if (want && total < (1ll << 28) && bpg < (1ll << 12) && total >= 64) {
-                sch.per_xcd = (unsigned)((total + 7) / 8);
-                sch.on = 1;
-                sch.magic = ((1ull << 40) + (unsigned long long)bpg - 1ull) / (unsigned long long)bpg;
-                grid = dim3(8u * sch.per_xcd, 1u, 1u);
-            }
-        }
-#ifdef TOME_OCC_PROBE
-        const char *lds_e = getenv("TOME_MERGE_LDS");
-        const unsigned occ_lds = lds_e ? (unsigned)atoi(lds_e) : 0u;
-#define OCC_LDS occ_lds
-#else
-#define OCC_LDS 0
-#endif
+        const MergeSched sch = merge_sched(OP == OP_DROP, T, r, bpg, ny);
+        const dim3 grid = sch.on ? dim3(8u * sch.per_xcd, 1u, 1u) : dim3((unsigned)bpg, (unsigned)gy, (unsigned)gz);
+        const LnArgs &ln = ln_p ? *ln_p : no_ln;
+        auto launch = [&](auto form) {
+            using F = decltype(form);
+            hipLaunchKernelGGL((k_merge_rows_fast<TX, TS, OP, F::nit, F::ln, F::eager>), grid, dim3(256), 0, st,
+                               (const TX *)x, (const TS *)size, (int)n, (int)T, (int)C, (int)r, R, (int)cpr,
+                               (int)((To + R - 1) / R), src, dst, unm, distill, keep, (TX *)xout, (TS *)sout, lin, lout,
+                               cls_rows, ln, (TS *)lsout, sch);
+            return check_launch("k_merge_rows_fast");
+        };
         if (ln_p) {
             if (OP != OP_WAVG || sizeof(TX) != 2 || cpr > 2 * WAVE || !aligned16(ln_p->y) || !aligned16(ln_p->weight) ||
                 !aligned16(ln_p->bias))
                 return fail(TOME_EINVAL, "fused LayerNorm needs 16-bit tokens with C <= 1024 and 16-byte aligned buffers");
             if constexpr (OP == OP_WAVG && sizeof(TX) == 2) {
-                // many destinations receive sources: the streaming waves skip those rows (EAGER, csrc/tome_merge.h);
-                // TOME_MERGE_EAGER=0 / 1 forces it off / on where r <= 64 (measurement switch, read per call)
-                const char *ee = getenv("TOME_MERGE_EAGER");
-                const bool eager = r <= 64 && ((ee && ee[0] == '1') || (!(ee && ee[0] == '0') && 8 * r >= T));
-                if (eager && nit == 3)
-                    hipLaunchKernelGGL((k_merge_rows_fast<TX, TS, OP, 3, true, true>), grid, dim3(256), OCC_LDS, st, (const TX *)x,
-                                       (const TS *)size, (int)n, (int)T, (int)C, (int)r, R, (int)cpr, (int)((To + R - 1) / R), src, dst, unm,
-                                       distill, keep, (TX *)xout, (TS *)sout, lin, lout, cls_rows, *ln_p, (TS *)lsout, sch);
-                else if (eager)
-                    hipLaunchKernelGGL((k_merge_rows_fast<TX, TS, OP, 6, true, true>), grid, dim3(256), OCC_LDS, st, (const TX *)x,
-                                       (const TS *)size, (int)n, (int)T, (int)C, (int)r, R, (int)cpr, (int)((To + R - 1) / R), src, dst, unm,
-                                       distill, keep, (TX *)xout, (TS *)sout, lin, lout, cls_rows, *ln_p, (TS *)lsout, sch);
-                else if (nit == 3)
-                    hipLaunchKernelGGL((k_merge_rows_fast<TX, TS, OP, 3, true>), grid, dim3(256), OCC_LDS, st, (const TX *)x,
-                                       (const TS *)size, (int)n, (int)T, (int)C, (int)r, R, (int)cpr, (int)((To + R - 1) / R), src, dst, unm,
-                                       distill, keep, (TX *)xout, (TS *)sout, lin, lout, cls_rows, *ln_p, (TS *)lsout, sch);
-                else
-                    hipLaunchKernelGGL((k_merge_rows_fast<TX, TS, OP, 6, true>), grid, dim3(256), OCC_LDS, st, (const TX *)x,
-                                       (const TS *)size, (int)n, (int)T, (int)C, (int)r, R, (int)cpr, (int)((To + R - 1) / R), src, dst, unm,
-                                       distill, keep, (TX *)xout, (TS *)sout, lin, lout, cls_rows, *ln_p, (TS *)lsout, sch);
+                // many destinations receive sources: the streaming waves skip those rows (EAGER, csrc/tome_merge.h)
+                if (r <= 64 && 8 * r >= T)
+                    return nit == 3 ? launch(FastForm<3, true, true>{}) : launch(FastForm<6, true, true>{});
+                return nit == 3 ? launch(FastForm<3, true, false>{}) : launch(FastForm<6, true, false>{});
             }
-        } else if (nit == 3)
-            hipLaunchKernelGGL((k_merge_rows_fast<TX, TS, OP, 3>), grid, dim3(256), OCC_LDS, st, (const TX *)x,
-                               (const TS *)size, (int)n, (int)T, (int)C, (int)r, R, (int)cpr, (int)((To + R - 1) / R), src, dst, unm, distill,
-                               keep, (TX *)xout, (TS *)sout, lin, lout, cls_rows, no_ln, (TS *)lsout, sch);
-        else
-            hipLaunchKernelGGL((k_merge_rows_fast<TX, TS, OP, 6>), grid, dim3(256), OCC_LDS, st, (const TX *)x,
-                               (const TS *)size, (int)n, (int)T, (int)C, (int)r, R, (int)cpr, (int)((To + R - 1) / R), src, dst, unm, distill,
-                               keep, (TX *)xout, (TS *)sout, lin, lout, cls_rows, no_ln, (TS *)lsout, sch);
-        return check_launch("k_merge_rows_fast");
+        }
+        return launch(FastForm<FAST_NIT, false, false>{});
     }
     if (cls_rows || ln_p)
         return fail(TOME_EINVAL, "regrouped / LayerNorm-fused merge needs rows of whole 16-byte chunks (C=%lld)", (long long)C);
@@ -597,17 +596,11 @@ extern "C" int tome_merge_wavg(const void *x, int x_dtype, const void *size, int
     if (int rc = check_merge_args("tome_merge_wavg", x, n, T, C, r, x_out)) return rc;
     if (!src_idx || !dst_idx || (!unm_idx && (T + 1) / 2 > r) || !size_out)
         return fail(TOME_EINVAL, "tome_merge_wavg: null buffer");
-    hipStream_t st = (hipStream_t)stream;
-#define WAVG(TX, TS)                                                                                         \
-    return launch_merge_rows<TX, TS, OP_WAVG>(x, size, n, T, C, r, src_idx, dst_idx, unm_idx, distill_token, \
-                                              edge_keep, x_out, size_out, st, nullptr, nullptr, 0, nullptr, log_size_out)
-    if (x_dtype == TOME_F32 && size_dtype == TOME_F32) WAVG(float, float);
-    if (x_dtype == TOME_BF16 && size_dtype == TOME_BF16) WAVG(bf16_t, bf16_t);
-    if (x_dtype == TOME_BF16 && size_dtype == TOME_F32) WAVG(bf16_t, float);
-    if (x_dtype == TOME_F16 && size_dtype == TOME_F16) WAVG(f16_t, f16_t);
-    if (x_dtype == TOME_F16 && size_dtype == TOME_F32) WAVG(f16_t, float);
-#undef WAVG
-    return fail(TOME_EINVAL, "tome_merge_wavg: unsupported dtypes x=%d size=%d", x_dtype, size_dtype);
+    return dispatch_xs<true>(x_dtype, size_dtype, [&](auto tx, auto ts) {
+        return launch_merge_rows<typename decltype(tx)::type, typename decltype(ts)::type, OP_WAVG>(
+            x, size, n, T, C, r, src_idx, dst_idx, unm_idx, distill_token, edge_keep, x_out, size_out,
+            (hipStream_t)stream, nullptr, nullptr, 0, nullptr, log_size_out);
+    }, [&] { return fail(TOME_EINVAL, "tome_merge_wavg: unsupported dtypes x=%d size=%d", x_dtype, size_dtype); });
 }
 
 extern "C" int tome_merge_wavg_ln(const void *x, int x_dtype, const void *size, int size_dtype, int64_t n, int64_t T,
@@ -622,16 +615,11 @@ extern "C" int tome_merge_wavg_ln(const void *x, int x_dtype, const void *size, 
     if (!src_idx || !dst_idx || (!unm_idx && (T + 1) / 2 > r) || !size_out || !y_out || !ln_weight || !ln_bias)
         return fail(TOME_EINVAL, "tome_merge_wavg_ln: null buffer");
     const LnArgs ln{ln_weight, ln_bias, y_out, eps, addend, 0, TokLayout{0, 0, 0, 0, 1}, nullptr, 0, x_out_bias};
-    hipStream_t st = (hipStream_t)stream;
-#define WAVGLN(TX, TS)                                                                                         \
-    return launch_merge_rows<TX, TS, OP_WAVG>(x, size, n, T, C, r, src_idx, dst_idx, unm_idx, distill_token,   \
-                                              edge_keep, x_out, size_out, st, nullptr, nullptr, 0, &ln, log_size_out)
-    if (x_dtype == TOME_BF16 && size_dtype == TOME_BF16) WAVGLN(bf16_t, bf16_t);
-    if (x_dtype == TOME_BF16 && size_dtype == TOME_F32) WAVGLN(bf16_t, float);
-    if (x_dtype == TOME_F16 && size_dtype == TOME_F16) WAVGLN(f16_t, f16_t);
-    if (x_dtype == TOME_F16 && size_dtype == TOME_F32) WAVGLN(f16_t, float);
-#undef WAVGLN
-    return fail(TOME_EINVAL, "tome_merge_wavg_ln: 16-bit tokens only (x=%d size=%d)", x_dtype, size_dtype);
+    return dispatch_xs<false>(x_dtype, size_dtype, [&](auto tx, auto ts) {
+        return launch_merge_rows<typename decltype(tx)::type, typename decltype(ts)::type, OP_WAVG>(
+            x, size, n, T, C, r, src_idx, dst_idx, unm_idx, distill_token, edge_keep, x_out, size_out,
+            (hipStream_t)stream, nullptr, nullptr, 0, &ln, log_size_out);
+    }, [&] { return fail(TOME_EINVAL, "tome_merge_wavg_ln: 16-bit tokens only (x=%d size=%d)", x_dtype, size_dtype); });
 }
 
 static int merge_wavg_regrouped_impl(const char *who, const void *x, int x_dtype, const void *size, int size_dtype,
@@ -646,17 +634,11 @@ static int merge_wavg_regrouped_impl(const char *who, const void *x, int x_dtype
     const int cls = has_cls ? 1 : 0;
     const TokLayout lin{cls * C, (cls + P * F) * C, C, F * C, (int)F};
     const TokLayout lout{cls * C, (cls + (P - r) * F) * C, C, F * C, (int)F};
-    hipStream_t st = (hipStream_t)stream;
-#define WAVGR(TX, TS)                                                                                         \
-    return launch_merge_rows<TX, TS, OP_WAVG>(x, size, n, P, C, r, src_idx, dst_idx, unm_idx, 0, edge_keep, x_out, \
-                                              size_out, st, &lin, &lout, cls ? (int)B : 0, ln, log_size_out)
-    if (x_dtype == TOME_F32 && size_dtype == TOME_F32) WAVGR(float, float);
-    if (x_dtype == TOME_BF16 && size_dtype == TOME_BF16) WAVGR(bf16_t, bf16_t);
-    if (x_dtype == TOME_BF16 && size_dtype == TOME_F32) WAVGR(bf16_t, float);
-    if (x_dtype == TOME_F16 && size_dtype == TOME_F16) WAVGR(f16_t, f16_t);
-    if (x_dtype == TOME_F16 && size_dtype == TOME_F32) WAVGR(f16_t, float);
-#undef WAVGR
-    return fail(TOME_EINVAL, "%s: unsupported dtypes x=%d size=%d", who, x_dtype, size_dtype);
+    return dispatch_xs<true>(x_dtype, size_dtype, [&](auto tx, auto ts) {
+        return launch_merge_rows<typename decltype(tx)::type, typename decltype(ts)::type, OP_WAVG>(
+            x, size, n, P, C, r, src_idx, dst_idx, unm_idx, 0, edge_keep, x_out, size_out, (hipStream_t)stream, &lin,
+            &lout, cls ? (int)B : 0, ln, log_size_out);
+    }, [&] { return fail(TOME_EINVAL, "%s: unsupported dtypes x=%d size=%d", who, x_dtype, size_dtype); });
 }
 
 extern "C" int tome_merge_wavg_regrouped(const void *x, int x_dtype, const void *size, int size_dtype, int64_t B,
@@ -725,28 +707,23 @@ static int add_layernorm_impl(const void *x, const void *addend, int dtype, int6
     if (C % 8 || cpr > 2 * WAVE || !aligned16(x) || !aligned16(addend) || (addend && !aligned16(x_out)) ||
         !aligned16(y_out) || !aligned16(ln_weight) || !aligned16(ln_bias))
         return fail(TOME_EINVAL, "tome_add_layernorm: C %% 8 == 0, C <= 1024 and 16-byte aligned buffers required");
-    static const int nit_env = [] {
-        const char *e = getenv("TOME_ADD_LN_NIT");  // 3 chunks per lane: 100.6 us vs 105 us with 6 (batch 64)
-        int v = e ? atoi(e) : 0;
-        return (v == 3 || v == 6) ? v : 3;
-    }();
-    const int nit = (cpr <= 3 * WAVE) ? nit_env : FAST_NIT;
+    const int nit = (cpr <= 3 * WAVE) ? 3 : FAST_NIT;  // 3 chunks per lane: 100.6 us vs 105 us with 6 (batch 64)
     int R = (int)((nit * WAVE) / cpr);
     if (R > FAST_MAXR) R = FAST_MAXR;
     const int64_t waves = (rows + R - 1) / R;
     const LnArgs ln{ln_weight, ln_bias, y_out, eps, nullptr, 0, TokLayout{0, 0, 0, 0, 1}, nullptr, (int)y_group, nullptr};
     const dim3 grid((unsigned)((waves + 3) / 4));
     hipStream_t st = (hipStream_t)stream;
-#define ADDLN(TX, N)                                                                                              \
-    hipLaunchKernelGGL((k_add_ln_rows<TX, N>), grid, dim3(256), 0, st, (const TX *)x, (const TX *)addend, rows, \
-                       (int)C, R, (int)cpr, ln, (TX *)x_out)
-    if (dtype == TOME_BF16) {
-        if (nit == 3) ADDLN(bf16_t, 3); else ADDLN(bf16_t, 6);
-    } else {
-        if (nit == 3) ADDLN(f16_t, 3); else ADDLN(f16_t, 6);
-    }
-#undef ADDLN
-    return check_launch("k_add_ln_rows");
+    return dispatch_x<false>(dtype, [&](auto tx) {
+        using TX = typename decltype(tx)::type;
+        if (nit == 3)
+            hipLaunchKernelGGL((k_add_ln_rows<TX, 3>), grid, dim3(256), 0, st, (const TX *)x, (const TX *)addend, rows,
+                               (int)C, R, (int)cpr, ln, (TX *)x_out);
+        else
+            hipLaunchKernelGGL((k_add_ln_rows<TX, FAST_NIT>), grid, dim3(256), 0, st, (const TX *)x, (const TX *)addend,
+                               rows, (int)C, R, (int)cpr, ln, (TX *)x_out);
+        return check_launch("k_add_ln_rows");
+    }, [&] { return fail(TOME_EINVAL, "tome_add_layernorm: 16-bit tokens only"); });
 }
 
 extern "C" int tome_add_layernorm_regrouped(const void *x, const void *addend, int dtype, int64_t B, int64_t F, int64_t P,
@@ -770,39 +747,12 @@ extern "C" int tome_add_layernorm_regrouped(const void *x, const void *addend, i
     const LnArgs ln{ln_weight, ln_bias, y_out, eps, nullptr, 0, TokLayout{0, 0, 0, 0, 1}, nullptr, 0, nullptr};
     const dim3 grid((unsigned)((waves + 3) / 4));
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == TOME_BF16)
-        hipLaunchKernelGGL((k_add_ln_regroup<bf16_t, 3>), grid, dim3(256), 0, st, (const bf16_t *)x, (const bf16_t *)addend,
-                           (int)B, (int)F, (int)P, (int)C, R, (int)cpr, ln, (bf16_t *)x_out);
-    else
-        hipLaunchKernelGGL((k_add_ln_regroup<f16_t, 3>), grid, dim3(256), 0, st, (const f16_t *)x, (const f16_t *)addend,
-                           (int)B, (int)F, (int)P, (int)C, R, (int)cpr, ln, (f16_t *)x_out);
-    return check_launch("k_add_ln_regroup");
-}
-
-template <typename TX>
-static int merge_mode_dispatch(int mode, const void *x, int64_t n, int64_t T, int64_t C, int64_t r,
-                               const int64_t *src, const int64_t *dst, const int64_t *unm, int distill,
-                               const uint8_t *keep, void *out, hipStream_t st) {
-    switch (mode) {
-    case TOME_SUM: return launch_merge_rows<TX, float, TOME_SUM>(x, nullptr, n, T, C, r, src, dst, unm, distill, keep, out, nullptr, st);
-    case TOME_MEAN: return launch_merge_rows<TX, float, TOME_MEAN>(x, nullptr, n, T, C, r, src, dst, unm, distill, keep, out, nullptr, st);
-    case TOME_AMAX: return launch_merge_rows<TX, float, TOME_AMAX>(x, nullptr, n, T, C, r, src, dst, unm, distill, keep, out, nullptr, st);
-    case TOME_PROD: return launch_merge_rows<TX, float, TOME_PROD>(x, nullptr, n, T, C, r, src, dst, unm, distill, keep, out, nullptr, st);
-    case TOME_AMIN: return launch_merge_rows<TX, float, TOME_AMIN>(x, nullptr, n, T, C, r, src, dst, unm, distill, keep, out, nullptr, st);
-    case OP_DROP: return launch_merge_rows<TX, float, OP_DROP>(x, nullptr, n, T, C, r, src, dst, unm, distill, keep, out, nullptr, st);
-    }
-    return fail(TOME_EINVAL, "tome_merge: mode %d", mode);
-}
-
-static int merge_dtype_dispatch(const char *who, int dtype, int mode, const void *x, int64_t n, int64_t T,
-                                int64_t C, int64_t r, const int64_t *src, const int64_t *dst, const int64_t *unm,
-                                int distill, const uint8_t *keep, void *out, hipStream_t st) {
-    switch (dtype) {
-    case TOME_F32: return merge_mode_dispatch<float>(mode, x, n, T, C, r, src, dst, unm, distill, keep, out, st);
-    case TOME_BF16: return merge_mode_dispatch<bf16_t>(mode, x, n, T, C, r, src, dst, unm, distill, keep, out, st);
-    case TOME_F16: return merge_mode_dispatch<f16_t>(mode, x, n, T, C, r, src, dst, unm, distill, keep, out, st);
-    }
-    return fail(TOME_EINVAL, "%s: dtype %d", who, dtype);
+    return dispatch_x<false>(dtype, [&](auto tx) {
+        using TX = typename decltype(tx)::type;
+        hipLaunchKernelGGL((k_add_ln_regroup<TX, 3>), grid, dim3(256), 0, st, (const TX *)x, (const TX *)addend, (int)B,
+                           (int)F, (int)P, (int)C, R, (int)cpr, ln, (TX *)x_out);
+        return check_launch("k_add_ln_regroup");
+    }, [&] { return fail(TOME_EINVAL, "tome_add_layernorm_regrouped: 16-bit tokens only"); });
 }
 
 extern "C" int tome_merge(const void *x, int dtype, int64_t n, int64_t T, int64_t C, int64_t r,
@@ -812,16 +762,30 @@ extern "C" int tome_merge(const void *x, int dtype, int64_t n, int64_t T, int64_
     if (!src_idx || !dst_idx || (!unm_idx && (T + 1) / 2 > r))
         return fail(TOME_EINVAL, "tome_merge: null index buffer");
     if (mode < TOME_SUM || mode > TOME_AMIN) return fail(TOME_EINVAL, "tome_merge: mode %d", mode);
-    return merge_dtype_dispatch("tome_merge", dtype, mode, x, n, T, C, r, src_idx, dst_idx, unm_idx, distill_token,
-                                edge_keep, out, (hipStream_t)stream);
+    return dispatch_x<true>(dtype, [&](auto tx) {
+        auto go = [&](auto op) {
+            return launch_merge_rows<typename decltype(tx)::type, float, decltype(op)::value>(
+                x, nullptr, n, T, C, r, src_idx, dst_idx, unm_idx, distill_token, edge_keep, out, nullptr,
+                (hipStream_t)stream);
+        };
+        switch (mode) {
+        case TOME_SUM: return go(Op<TOME_SUM>{});
+        case TOME_MEAN: return go(Op<TOME_MEAN>{});
+        case TOME_AMAX: return go(Op<TOME_AMAX>{});
+        case TOME_PROD: return go(Op<TOME_PROD>{});
+        default: return go(Op<TOME_AMIN>{});  // (mode range checked above)
+        }
+    }, [&] { return fail(TOME_EINVAL, "tome_merge: dtype %d", dtype); });
 }
 
 extern "C" int tome_drop(const void *x, int dtype, int64_t n, int64_t T, int64_t C, int64_t r,
                          const int64_t *und_idx, int distill_token, void *out, tome_stream_t stream) {
     if (int rc = check_merge_args("tome_drop", x, n, T, C, r, out)) return rc;
     if (!und_idx && (T + 1) / 2 > r) return fail(TOME_EINVAL, "tome_drop: null index buffer");
-    return merge_dtype_dispatch("tome_drop", dtype, OP_DROP, x, n, T, C, r, nullptr, nullptr, und_idx, distill_token,
-                                nullptr, out, (hipStream_t)stream);
+    return dispatch_x<true>(dtype, [&](auto tx) {
+        return launch_merge_rows<typename decltype(tx)::type, float, OP_DROP>(
+            x, nullptr, n, T, C, r, nullptr, nullptr, und_idx, distill_token, nullptr, out, nullptr, (hipStream_t)stream);
+    }, [&] { return fail(TOME_EINVAL, "tome_drop: dtype %d", dtype); });
 }
 
 // tome_drop on the interleaved layout of TimeSformer / Motionformer (class token kept aside and copied through)
@@ -834,15 +798,11 @@ extern "C" int tome_drop_regrouped(const void *x, int dtype, int64_t B, int64_t 
     const int cls = has_cls ? 1 : 0;
     const TokLayout lin{cls * C, (cls + P * F) * C, C, F * C, (int)F};
     const TokLayout lout{cls * C, (cls + (P - r) * F) * C, C, F * C, (int)F};
-    hipStream_t st = (hipStream_t)stream;
-#define DROPR(TX)                                                                                              \
-    return launch_merge_rows<TX, float, OP_DROP>(x, nullptr, n, P, C, r, nullptr, nullptr, und_idx, 0, nullptr, \
-                                                 x_out, nullptr, st, &lin, &lout, cls ? (int)B : 0)
-    if (dtype == TOME_F32) DROPR(float);
-    if (dtype == TOME_BF16) DROPR(bf16_t);
-    if (dtype == TOME_F16) DROPR(f16_t);
-#undef DROPR
-    return fail(TOME_EINVAL, "tome_drop_regrouped: dtype %d", dtype);
+    return dispatch_x<true>(dtype, [&](auto tx) {
+        return launch_merge_rows<typename decltype(tx)::type, float, OP_DROP>(
+            x, nullptr, n, P, C, r, nullptr, nullptr, und_idx, 0, nullptr, x_out, nullptr, (hipStream_t)stream, &lin,
+            &lout, cls ? (int)B : 0);
+    }, [&] { return fail(TOME_EINVAL, "tome_drop_regrouped: dtype %d", dtype); });
 }
 
 static int prop_attention_impl(const void *q, const void *k, const void *v, int dtype, int64_t B, int64_t H,
@@ -1159,11 +1119,8 @@ extern "C" int tome_unmerge(const void *x, int dtype, int64_t n, int64_t T, int6
     if (int rc = check_merge_args("tome_unmerge", x, n, T, C, r, out)) return rc;
     if (!src_idx || !dst_idx || (!unm_idx && (T + 1) / 2 > r))
         return fail(TOME_EINVAL, "tome_unmerge: null index buffer");
-    hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-    case TOME_F32: return launch_unmerge<float>(x, n, T, C, r, src_idx, dst_idx, unm_idx, out, st);
-    case TOME_BF16: return launch_unmerge<bf16_t>(x, n, T, C, r, src_idx, dst_idx, unm_idx, out, st);
-    case TOME_F16: return launch_unmerge<f16_t>(x, n, T, C, r, src_idx, dst_idx, unm_idx, out, st);
-    }
-    return fail(TOME_EINVAL, "tome_unmerge: dtype %d", dtype);
+    return dispatch_x<true>(dtype, [&](auto tx) {
+        return launch_unmerge<typename decltype(tx)::type>(x, n, T, C, r, src_idx, dst_idx, unm_idx, out,
+                                                           (hipStream_t)stream);
+    }, [&] { return fail(TOME_EINVAL, "tome_unmerge: dtype %d", dtype); });
 }

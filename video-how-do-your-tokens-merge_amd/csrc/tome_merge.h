@@ -67,28 +67,18 @@ __device__ __forceinline__ uint4 add_xbias(const uint4 &v, const TX *__restrict_
 
 // 16-byte moves of the streaming kernels (k_merge_rows_fast, k_add_ln_rows, k_add_ln_regroup): tokens are read once
 // and written once, 0.3-1.2 GB per launch against 256 MB of Infinity Cache, so both directions are issued
-// non-temporal (TOME_NT bit 0 loads, bit 1 stores).  Measured at batch 128, same box, alternating builds: merge+LN
-// 226 -> 214 us (5.12 -> 5.40 TB/s), add+LN 215 -> 189 us (5.37 -> 6.12 TB/s); inside the model (rocprofv3) 228 -> 221
-// and 204 -> 188 us with the GEMMs that read the results unchanged (581 vs 578 us).
-#ifndef TOME_NT
-#define TOME_NT 3
-#endif
+// non-temporal.  Measured at batch 128, same box, alternating builds: merge+LN 226 -> 214 us (5.12 -> 5.40 TB/s),
+// add+LN 215 -> 189 us (5.37 -> 6.12 TB/s); inside the model (rocprofv3) 228 -> 221 and 204 -> 188 us with the GEMMs
+// that read the results unchanged (581 vs 578 us).
 typedef unsigned int nt_u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint4 ld16(const void *p) {
-    if (TOME_NT & 1) {
-        const nt_u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_u32x4 *>(p));
-        return uint4{v.x, v.y, v.z, v.w};
-    }
-    return *reinterpret_cast<const uint4 *>(p);
+    const nt_u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_u32x4 *>(p));
+    return uint4{v.x, v.y, v.z, v.w};
 }
 __device__ __forceinline__ void st16(void *p, const uint4 &v) {
-    if (TOME_NT & 2) {
-        nt_u32x4 w;
-        w.x = v.x; w.y = v.y; w.z = v.z; w.w = v.w;
-        __builtin_nontemporal_store(w, reinterpret_cast<nt_u32x4 *>(p));
-    } else {
-        *reinterpret_cast<uint4 *>(p) = v;
-    }
+    nt_u32x4 w;
+    w.x = v.x; w.y = v.y; w.z = v.z; w.w = v.w;
+    __builtin_nontemporal_store(w, reinterpret_cast<nt_u32x4 *>(p));
 }
 
 // round(x + a) in the token dtype, element-wise on two 16-byte packs (what torch's `x + a` stores)
@@ -371,10 +361,7 @@ __device__ __forceinline__ void merge_dst_row_r64(const TX *__restrict__ xg, con
                                                   int distill, int lane, const LnArgs *ln, TX *__restrict__ yg,
                                                   const TX *__restrict__ ag, int64_t astride) {
     typedef Pack<TX, VEC> __attribute__((aligned(sizeof(TX) * VEC))) PK;
-#ifndef TOME_R64_NB
-#define TOME_R64_NB 1
-#endif
-    constexpr int NB = TOME_R64_NB;  // source rows requested together with the own row
+    constexpr int NB = 1;  // source rows requested together with the own row
     // ---- batch 1: the group's index lists, one rank per lane
     const int li = lane < r ? lane : 0;
     const int d_l = lane < r ? (int)dstg[li] : -1;
