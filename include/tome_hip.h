@@ -39,7 +39,7 @@ enum tome_status {
     TOME_ELAUNCH = 3     /* HIP reported a launch error (text in tome_last_error()) */
 };
 
-#define TOME_ABI_VERSION 9
+#define TOME_ABI_VERSION 10
 
 int tome_abi_version(void);
 
@@ -318,6 +318,48 @@ int tome_row_map(int64_t n, int64_t T, int64_t r, int distill_token, const int64
                  const int64_t *dst_idx, const int64_t *unm_idx, int32_t *row_map, tome_stream_t stream);
 int tome_source_init(int64_t n, int64_t T, int64_t r, int distill_token, int drop, const int32_t *row_map,
                      float *source_out, tome_stream_t stream);
+
+/*
+ * Partition matchings  <-  kth_bipartite_soft_matching (merge.py:105-158) and random_bipartite_soft_matching
+ * (merge.py:161-212).  Per group an ordered source set A (Na token positions) and an ordered destination set B (Nb
+ * positions); EVERY source row is merged into its best destination and the merged sequence is the destination set
+ * alone ([n,Nb,C]).  The sets are given either by
+ *   k > 1:  the kth rule (merge.py:119-126): tokens in groups of k, the first k-1 of a group are sources (A row
+ *           g*(k-1)+j), the last one the destination (B row g); tokens past (T/k)*k belong to neither set.
+ *           Na = (T/k)*(k-1), Nb = T/k; a_idx / b_idx are ignored (may be null);
+ *   k == 0: explicit position lists a_idx [n,Na], b_idx [n,Nb] (int64, values in [0,T), disjoint; merge.py:176-177).
+ * k <= 1 otherwise, Nb <= 0, Na <= 0, null or misaligned buffers give TOME_EINVAL.
+ *
+ * tome_partition_workspace_bytes: scratch of tome_match_partition.
+ * tome_match_partition  <-  merge.py:128-135 / :188-196.  metric [n,T,D], element strides (stride_n, stride_t, 1).
+ *     out: dst_idx [n,Na] int64 = first-index row argmax of the cosine similarity A.B^T (same arithmetic contract as
+ *          tome_match: fp32 unit vectors, k-ordered fma chain on the fp32 matrix pipe; torch.max's NaN rule);
+ *          offsets [n,Nb+1], sources [n,Na] int32: the inverted list -- sources[offsets[j] .. offsets[j+1]) are the
+ *          A rows merged into B row j, ascending.  Bit-identical on every run.
+ * tome_merge_partition  <-  merge(x, mode) (merge.py:137-142 / :198-203): out [n,Nb,C]; a destination's own row
+ *     first, then its sources in ascending A-row order (the order of torch's CPU scatter_reduce), fp32 accumulation.
+ * tome_merge_wavg_partition  <-  merge_wavg(merge, x, size) (merge.py:355-369) on such a matching, one launch:
+ *     x*size summed, size summed, one division; size may be null (all ones); log_size_out optional (log(size')).
+ *     size / size_out / log_size_out [n,T,1] / [n,Nb,1] of size_dtype (= x_dtype or TOME_F32).
+ * tome_unmerge_partition  <-  unmerge(x) (merge.py:144-156 / :205-210): x [n,Nb,C] -> out [n,Tout,C],
+ *     Tout = (T/k)*k for the kth rule (the reference loses the tail too), T for lists; every row written once.
+ * x / out are contiguous.
+ */
+size_t tome_partition_workspace_bytes(int64_t n, int64_t Na, int64_t Nb, int64_t D);
+int tome_match_partition(const void *metric, int dtype, int64_t n, int64_t T, int64_t D, int64_t stride_n,
+                         int64_t stride_t, int64_t k, const int64_t *a_idx, const int64_t *b_idx, int64_t Na,
+                         int64_t Nb, int64_t *dst_idx, int32_t *offsets, int32_t *sources, void *workspace,
+                         size_t workspace_bytes, tome_stream_t stream);
+int tome_merge_partition(const void *x, int dtype, int64_t n, int64_t T, int64_t C, int64_t k, const int64_t *a_idx,
+                         const int64_t *b_idx, int64_t Na, int64_t Nb, const int32_t *offsets,
+                         const int32_t *sources, int mode, void *out, tome_stream_t stream);
+int tome_merge_wavg_partition(const void *x, int x_dtype, const void *size, int size_dtype, int64_t n, int64_t T,
+                              int64_t C, int64_t k, const int64_t *a_idx, const int64_t *b_idx, int64_t Na,
+                              int64_t Nb, const int32_t *offsets, const int32_t *sources, void *x_out,
+                              void *size_out, void *log_size_out, tome_stream_t stream);
+int tome_unmerge_partition(const void *x, int dtype, int64_t n, int64_t T, int64_t C, int64_t k,
+                           const int64_t *a_idx, const int64_t *b_idx, int64_t Na, int64_t Nb,
+                           const int64_t *dst_idx, void *out, tome_stream_t stream);
 
 #ifdef TOME_PROFILE_HOOKS
 /*

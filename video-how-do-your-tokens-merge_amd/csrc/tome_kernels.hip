@@ -2,7 +2,8 @@
 // C ABI declared in include/tome_hip.h.  Built with: hipcc --offload-arch=gfx950 -O3
 // -ffp-contract=off -shared -fPIC (csrc/build.py).  No torch, no CUDA, no portability layer.
 //
-// One translation unit: tome_common.h (types), tome_match.h and tome_merge.h (kernels), this file (host).
+// One translation unit: tome_common.h (types), tome_match.h, tome_merge.h and tome_partition.h (kernels), this file
+// (host).
 //
 // Launch sequence of one matching (tome_match / tome_match_keys), kernels in tome_match.h:
 //   k_unit_rows[_heads]  keys -> fp32 unit vectors, even/odd split, MFMA-fragment order (HBM bound)
@@ -15,6 +16,8 @@
 //                        <LN>: residual add in front and LayerNorm behind fused in (tome_merge_wavg_ln)
 //   k_add_ln_rows        second residual + the next block's first LayerNorm (tome_add_layernorm)
 //   k_merge_rows / k_unmerge_rows   generic one-wave-per-row forms                        (HBM bound)
+// The partition matchings (kth_ / random_bipartite_soft_matching: arbitrary source / destination sets, every source
+// merged) have their own sequence, written out at the top of tome_partition.h.
 //
 // The arithmetic contract (summation orders, tie rules) is the one written at the top of
 // oracle/tome_oracle.c; the kernels reproduce it bit for bit.
@@ -32,6 +35,7 @@
 #include "tome_match.h"
 #include "tome_match_filter.h"
 #include "tome_merge.h"
+#include "tome_partition.h"
 #include "tome_attn.h"
 #include "tome_attn_stream.h"
 #include "tome_attn_resident.h"
@@ -1123,4 +1127,253 @@ extern "C" int tome_unmerge(const void *x, int dtype, int64_t n, int64_t T, int6
         return launch_unmerge<typename decltype(tx)::type>(x, n, T, C, r, src_idx, dst_idx, unm_idx, out,
                                                            (hipStream_t)stream);
     }, [&] { return fail(TOME_EINVAL, "tome_unmerge: dtype %d", dtype); });
+}
+
+// ------------------------------------------------------------------------------------------------
+// partition matching (kernels in tome_partition.h): kth_bipartite_soft_matching (merge.py:105-158),
+// random_bipartite_soft_matching (merge.py:161-212)
+// ------------------------------------------------------------------------------------------------
+struct PartWs {
+    float *unitA, *unitB, *part_max;
+    int *part_idx;
+    uint8_t *badA, *badB;
+    int ntA, ntB, nchunk;
+    int64_t groupA_f4, groupB_f4;
+    size_t bytes;
+};
+
+static PartWs carve_part(void *base, int64_t n, int64_t Na, int64_t Nb, int64_t D) {
+    PartWs w;
+    w.nchunk = (int)((D + 63) / 64);
+    w.ntA = (int)((Na + TILE_ROWS - 1) / TILE_ROWS);
+    w.ntB = (int)((Nb + TILE_ROWS - 1) / TILE_ROWS);
+    w.groupA_f4 = (int64_t)w.ntA * w.nchunk * 512;
+    w.groupB_f4 = (int64_t)w.ntB * w.nchunk * 512;
+    size_t off = 0;
+    char *b = (char *)base;
+    w.unitA = (float *)(b + off); off = align_up(off + 16 * (size_t)(n * w.groupA_f4), 256);
+    w.unitB = (float *)(b + off); off = align_up(off + 16 * (size_t)(n * w.groupB_f4), 256);
+    w.part_max = (float *)(b + off); off = align_up(off + sizeof(float) * (size_t)(n * MAX_WJ * Na), 256);
+    w.part_idx = (int *)(b + off); off = align_up(off + sizeof(int) * (size_t)(n * MAX_WJ * Na), 256);
+    w.badA = (uint8_t *)(b + off); off = align_up(off + (size_t)(n * Na), 256);
+    w.badB = (uint8_t *)(b + off); off = align_up(off + (size_t)(n * Nb), 256);
+    w.bytes = off;
+    return w;
+}
+
+extern "C" size_t tome_partition_workspace_bytes(int64_t n, int64_t Na, int64_t Nb, int64_t D) {
+    if (n <= 0 || Na <= 0 || Nb <= 0 || D <= 0) return 0;
+    return carve_part(nullptr, n, Na, Nb, D).bytes;
+}
+
+// the two sets of a partition call, checked: k > 1 (the kth rule, Na / Nb must be what it gives) or k == 0 with two
+// position lists
+static int check_part_sets(const char *who, int64_t n, int64_t T, int64_t k, const int64_t *a_idx, const int64_t *b_idx,
+                           int64_t Na, int64_t Nb, PartSets *S) {
+    if (n <= 0 || T <= 0) return fail(TOME_EINVAL, "%s: bad shape", who);
+    if (Nb <= 0) return fail(TOME_EINVAL, "%s: empty destination set (Nb=%lld)", who, (long long)Nb);
+    if (Na <= 0) return fail(TOME_EINVAL, "%s: empty source set (Na=%lld)", who, (long long)Na);
+    if (k != 0) {
+        if (k <= 1) return fail(TOME_EINVAL, "%s: k=%lld (k > 1 expected, or k = 0 with a_idx / b_idx)", who, (long long)k);
+        if (k > T || Nb != T / k || Na != (T / k) * (k - 1))
+            return fail(TOME_EINVAL, "%s: k=%lld on T=%lld gives Na=%lld, Nb=%lld, not Na=%lld, Nb=%lld", who, (long long)k,
+                        (long long)T, (long long)((T / k) * (k - 1)), (long long)(T / k), (long long)Na, (long long)Nb);
+    } else {
+        if (!a_idx || !b_idx) return fail(TOME_EINVAL, "%s: null a_idx / b_idx (and k = 0)", who);
+        if (((uintptr_t)a_idx & 7) || ((uintptr_t)b_idx & 7)) return fail(TOME_EINVAL, "%s: misaligned a_idx / b_idx", who);
+        if (Na + Nb > T) return fail(TOME_EINVAL, "%s: Na + Nb = %lld > T = %lld", who, (long long)(Na + Nb), (long long)T);
+    }
+    if (n * T > 0x7fffffffLL || n * (Nb + 1) > 0x7fffffffLL) return fail(TOME_EINVAL, "%s: too many rows", who);
+    *S = PartSets{(int)k, (int)Na, (int)Nb, k ? nullptr : a_idx, k ? nullptr : b_idx};
+    return TOME_OK;
+}
+
+extern "C" int tome_match_partition(const void *metric, int dtype, int64_t n, int64_t T, int64_t D, int64_t stride_n,
+                                    int64_t stride_t, int64_t k, const int64_t *a_idx, const int64_t *b_idx,
+                                    int64_t Na, int64_t Nb, int64_t *dst_idx, int32_t *offsets, int32_t *sources,
+                                    void *workspace, size_t workspace_bytes, tome_stream_t stream) {
+    if (!metric || D <= 0) return fail(TOME_EINVAL, "tome_match_partition: bad shape/pointer");
+    PartSets S;
+    if (int rc = check_part_sets("tome_match_partition", n, T, k, a_idx, b_idx, Na, Nb, &S)) return rc;
+    if ((int64_t)n * T * ((D + 63) / 64 * 64) > (int64_t)1 << 40)
+        return fail(TOME_EINVAL, "tome_match_partition: problem too large");
+    if (!dst_idx || !offsets || !sources) return fail(TOME_EINVAL, "tome_match_partition: null output buffer");
+    if (((uintptr_t)dst_idx & 7) || ((uintptr_t)offsets & 3) || ((uintptr_t)sources & 3))
+        return fail(TOME_EINVAL, "tome_match_partition: misaligned output buffer");
+    const size_t need = tome_partition_workspace_bytes(n, Na, Nb, D);
+    if (!workspace || workspace_bytes < need)
+        return fail(TOME_EWORKSPACE, "tome_match_partition: workspace %zu < %zu bytes", workspace_bytes, need);
+    if (((uintptr_t)workspace & 255) != 0)
+        return fail(TOME_EINVAL, "tome_match_partition: workspace not 256-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const PartWs w = carve_part(workspace, n, Na, Nb, D);
+    // 1. unit vectors of both sets
+    const size_t es = dtype == TOME_F32 ? 4 : 2;
+    const bool fast = (D % 8 == 0) && (((uintptr_t)metric) % 16 == 0) && ((stride_n * es) % 16 == 0) &&
+                      ((stride_t * es) % 16 == 0);
+    const int64_t items = n * (Na + Nb);
+    bool launched = false;
+#define PUNIT_FAST(TY, NCH)                                                                                   \
+    hipLaunchKernelGGL((k_unit_rows_part<TY, NCH>), dim3((unsigned)((items + 31) / 32)), dim3(256), 0, st,     \
+                       (const TY *)metric, stride_n, stride_t, (int)n, (int)T, (int)D, S, w.unitA, w.unitB,    \
+                       w.groupA_f4, w.groupB_f4, w.badA, w.badB);                                              \
+    launched = true
+#define PUNIT_NCH(TY)                                       \
+    switch (w.nchunk) {                                     \
+    case 1: PUNIT_FAST(TY, 1); break;                       \
+    case 2: PUNIT_FAST(TY, 2); break;                       \
+    case 3: PUNIT_FAST(TY, 3); break;                       \
+    case 4: PUNIT_FAST(TY, 4); break;                       \
+    case 6: PUNIT_FAST(TY, 6); break;                       \
+    case 8: PUNIT_FAST(TY, 8); break;                       \
+    case 12: PUNIT_FAST(TY, 12); break;                     \
+    case 16: PUNIT_FAST(TY, 16); break;                     \
+    default: break;                                         \
+    }
+#define PUNIT_GENERIC(TY)                                                                                          \
+    hipLaunchKernelGGL((k_unit_rows_part_generic<TY>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st,     \
+                       (const TY *)metric, stride_n, stride_t, (int)n, (int)T, (int)D, w.nchunk * 64, S, w.unitA,   \
+                       w.unitB, w.groupA_f4, w.groupB_f4, w.badA, w.badB)
+    switch (dtype) {
+    case TOME_F32:
+        if (fast) { PUNIT_NCH(float) }
+        if (!launched) PUNIT_GENERIC(float);
+        break;
+    case TOME_BF16:
+        if (fast) { PUNIT_NCH(bf16_t) }
+        if (!launched) PUNIT_GENERIC(bf16_t);
+        break;
+    case TOME_F16:
+        if (fast) { PUNIT_NCH(f16_t) }
+        if (!launched) PUNIT_GENERIC(f16_t);
+        break;
+    default: return fail(TOME_EINVAL, "tome_match_partition: dtype %d", dtype);
+    }
+#undef PUNIT_FAST
+#undef PUNIT_NCH
+#undef PUNIT_GENERIC
+    if (int rc = check_launch("k_unit_rows_part")) return rc;
+
+    // 2. similarity + row max / argmax: k_scores_rowmax as tome_match launches it (match_tail), T1 = Na, T2 = Nb
+    const long target_waves = 6144L;
+    int WJ = (int)((target_waves + n * w.ntA - 1) / (n * w.ntA));
+    if (WJ > MAX_WJ) WJ = MAX_WJ;
+    if (WJ > w.ntB) WJ = w.ntB;
+    if (WJ < 1) WJ = 1;
+    const int64_t nb2 = ((n + 7) / 8) * 8 * w.ntA * WJ;
+    if (nb2 > 0x7fffffffLL) return fail(TOME_EINVAL, "tome_match_partition: problem too large");
+    if (w.nchunk == 1)
+        hipLaunchKernelGGL(k_scores_rowmax<true>, dim3((unsigned)nb2), dim3(64), 0, st, (const f32x4 *)w.unitA,
+                           (const f32x4 *)w.unitB, (int)n, (int)Na, (int)Nb, w.nchunk, w.ntA, w.ntB, WJ, w.groupA_f4,
+                           w.groupB_f4, 0, w.part_max, w.part_idx, nullptr);
+    else
+        hipLaunchKernelGGL(k_scores_rowmax<false>, dim3((unsigned)nb2), dim3(64), 0, st, (const f32x4 *)w.unitA,
+                           (const f32x4 *)w.unitB, (int)n, (int)Na, (int)Nb, w.nchunk, w.ntA, w.ntB, WJ, w.groupA_f4,
+                           w.groupB_f4, 0, w.part_max, w.part_idx, nullptr);
+    if (int rc = check_launch("k_scores_rowmax")) return rc;
+
+    // 3. fold the column parts -> dst_idx
+    if (n > 65535) return fail(TOME_EINVAL, "tome_match_partition: more than 65535 groups");
+    hipLaunchKernelGGL(k_part_fold, dim3((unsigned)((Na + 255) / 256), (unsigned)n), dim3(256), 0, st, w.part_max,
+                       w.part_idx, WJ, (int)Na, (int)Nb, w.badA, w.badB, dst_idx);
+    if (int rc = check_launch("k_part_fold")) return rc;
+
+    // 4. inverted list; groups whose indices and counts fit 48 KiB of LDS take the LDS form
+    const size_t lds = sizeof(int) * (size_t)(((Na + 3) & ~(int64_t)3) + Nb + 1);
+    if (lds <= 48 * 1024)
+        hipLaunchKernelGGL(k_part_lists<true>, dim3((unsigned)n), dim3(1024), lds, st, dst_idx, (int)Na, (int)Nb, offsets,
+                           sources);
+    else
+        hipLaunchKernelGGL(k_part_lists<false>, dim3((unsigned)n), dim3(1024), 0, st, dst_idx, (int)Na, (int)Nb, offsets,
+                           sources);
+    return check_launch("k_part_lists");
+}
+
+template <typename TX, typename TS, int OP>
+static int launch_merge_part(const void *x, const void *size, int64_t n, int64_t T, int64_t C, const PartSets &S,
+                             const int32_t *offsets, const int32_t *sources, void *xout, void *sout, void *lsout,
+                             hipStream_t st) {
+    constexpr int VEC = 16 / sizeof(TX);
+    const int64_t rows = n * S.Nb;
+    const unsigned nb = (unsigned)((rows + 3) / 4);
+    if ((C % VEC == 0) && aligned16(x) && aligned16(xout))
+        hipLaunchKernelGGL((k_merge_part<TX, TS, VEC, OP>), dim3(nb), dim3(256), 0, st, (const TX *)x, (const TS *)size,
+                           (int)n, (int)T, (int)C, S, offsets, sources, (TX *)xout, (TS *)sout, (TS *)lsout);
+    else
+        hipLaunchKernelGGL((k_merge_part<TX, TS, 1, OP>), dim3(nb), dim3(256), 0, st, (const TX *)x, (const TS *)size,
+                           (int)n, (int)T, (int)C, S, offsets, sources, (TX *)xout, (TS *)sout, (TS *)lsout);
+    return check_launch("k_merge_part");
+}
+
+static int check_part_merge_args(const char *who, const void *x, int64_t C, const void *out, const int32_t *offsets,
+                                 const int32_t *sources) {
+    if (!x || !out || C <= 0) return fail(TOME_EINVAL, "%s: bad shape/pointer", who);
+    if (!offsets || !sources) return fail(TOME_EINVAL, "%s: null list buffer", who);
+    if (((uintptr_t)offsets & 3) || ((uintptr_t)sources & 3)) return fail(TOME_EINVAL, "%s: misaligned list buffer", who);
+    return TOME_OK;
+}
+
+extern "C" int tome_merge_partition(const void *x, int dtype, int64_t n, int64_t T, int64_t C, int64_t k,
+                                    const int64_t *a_idx, const int64_t *b_idx, int64_t Na, int64_t Nb,
+                                    const int32_t *offsets, const int32_t *sources, int mode, void *out,
+                                    tome_stream_t stream) {
+    if (int rc = check_part_merge_args("tome_merge_partition", x, C, out, offsets, sources)) return rc;
+    PartSets S;
+    if (int rc = check_part_sets("tome_merge_partition", n, T, k, a_idx, b_idx, Na, Nb, &S)) return rc;
+    if (mode < TOME_SUM || mode > TOME_AMIN) return fail(TOME_EINVAL, "tome_merge_partition: mode %d", mode);
+    return dispatch_x<true>(dtype, [&](auto tx) {
+        auto go = [&](auto op) {
+            return launch_merge_part<typename decltype(tx)::type, float, decltype(op)::value>(
+                x, nullptr, n, T, C, S, offsets, sources, out, nullptr, nullptr, (hipStream_t)stream);
+        };
+        switch (mode) {
+        case TOME_SUM: return go(Op<TOME_SUM>{});
+        case TOME_MEAN: return go(Op<TOME_MEAN>{});
+        case TOME_AMAX: return go(Op<TOME_AMAX>{});
+        case TOME_PROD: return go(Op<TOME_PROD>{});
+        default: return go(Op<TOME_AMIN>{});  // (mode range checked above)
+        }
+    }, [&] { return fail(TOME_EINVAL, "tome_merge_partition: dtype %d", dtype); });
+}
+
+extern "C" int tome_merge_wavg_partition(const void *x, int x_dtype, const void *size, int size_dtype, int64_t n,
+                                         int64_t T, int64_t C, int64_t k, const int64_t *a_idx, const int64_t *b_idx,
+                                         int64_t Na, int64_t Nb, const int32_t *offsets, const int32_t *sources,
+                                         void *x_out, void *size_out, void *log_size_out, tome_stream_t stream) {
+    if (int rc = check_part_merge_args("tome_merge_wavg_partition", x, C, x_out, offsets, sources)) return rc;
+    if (!size_out) return fail(TOME_EINVAL, "tome_merge_wavg_partition: null buffer");
+    PartSets S;
+    if (int rc = check_part_sets("tome_merge_wavg_partition", n, T, k, a_idx, b_idx, Na, Nb, &S)) return rc;
+    return dispatch_xs<true>(x_dtype, size_dtype, [&](auto tx, auto ts) {
+        return launch_merge_part<typename decltype(tx)::type, typename decltype(ts)::type, OP_WAVG>(
+            x, size, n, T, C, S, offsets, sources, x_out, size_out, log_size_out, (hipStream_t)stream);
+    }, [&] { return fail(TOME_EINVAL, "tome_merge_wavg_partition: unsupported dtypes x=%d size=%d", x_dtype, size_dtype); });
+}
+
+template <typename TX>
+static int launch_unmerge_part(const void *x, int64_t n, int64_t T, int64_t Tout, int64_t C, const PartSets &S,
+                               const int64_t *dst, void *out, hipStream_t st) {
+    constexpr int VEC = 16 / sizeof(TX);
+    const int64_t items = n * ((int64_t)S.Na + S.Nb);
+    const unsigned nb = (unsigned)((items + 3) / 4);
+    if ((C % VEC == 0) && aligned16(x) && aligned16(out))
+        hipLaunchKernelGGL((k_unmerge_part<TX, VEC>), dim3(nb), dim3(256), 0, st, (const TX *)x, (int)n, (int)T, (int)Tout,
+                           (int)C, S, dst, (TX *)out);
+    else
+        hipLaunchKernelGGL((k_unmerge_part<TX, 1>), dim3(nb), dim3(256), 0, st, (const TX *)x, (int)n, (int)T, (int)Tout,
+                           (int)C, S, dst, (TX *)out);
+    return check_launch("k_unmerge_part");
+}
+
+extern "C" int tome_unmerge_partition(const void *x, int dtype, int64_t n, int64_t T, int64_t C, int64_t k,
+                                      const int64_t *a_idx, const int64_t *b_idx, int64_t Na, int64_t Nb,
+                                      const int64_t *dst_idx, void *out, tome_stream_t stream) {
+    if (!x || !out || C <= 0) return fail(TOME_EINVAL, "tome_unmerge_partition: bad shape/pointer");
+    if (!dst_idx || ((uintptr_t)dst_idx & 7)) return fail(TOME_EINVAL, "tome_unmerge_partition: null or misaligned dst_idx");
+    PartSets S;
+    if (int rc = check_part_sets("tome_unmerge_partition", n, T, k, a_idx, b_idx, Na, Nb, &S)) return rc;
+    const int64_t Tout = k ? (T / k) * k : T;
+    return dispatch_x<true>(dtype, [&](auto tx) {
+        return launch_unmerge_part<typename decltype(tx)::type>(x, n, T, Tout, C, S, dst_idx, out, (hipStream_t)stream);
+    }, [&] { return fail(TOME_EINVAL, "tome_unmerge_partition: dtype %d", dtype); });
 }

@@ -22,9 +22,11 @@ SYMBOLS = (
     "tome_drop",
     "tome_drop_regrouped",
     "tome_unmerge", "tome_row_map", "tome_source_init", "tome_gelu_erf", "tome_tubelet_rows",
+    "tome_partition_workspace_bytes", "tome_match_partition", "tome_merge_partition", "tome_merge_wavg_partition",
+    "tome_unmerge_partition",
 )
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 MODES = {"sum": 0, "mean": 1, "amax": 2, "max": 2, "prod": 3, "amin": 4, "min": 4}
 
@@ -114,6 +116,17 @@ def bind(path: str) -> ctypes.CDLL:
     L.tome_row_map.argtypes = [i64, i64, i64, i32, vp, vp, vp, vp, vp]
     L.tome_source_init.restype = i32
     L.tome_source_init.argtypes = [i64, i64, i64, i32, i32, vp, vp, vp]
+    L.tome_partition_workspace_bytes.restype = sz
+    L.tome_partition_workspace_bytes.argtypes = [i64, i64, i64, i64]
+    L.tome_match_partition.restype = i32
+    L.tome_match_partition.argtypes = [vp, i32, i64, i64, i64, i64, i64, i64, vp, vp, i64, i64, vp, vp, vp, vp, sz, vp]
+    L.tome_merge_partition.restype = i32
+    L.tome_merge_partition.argtypes = [vp, i32, i64, i64, i64, i64, vp, vp, i64, i64, vp, vp, i32, vp, vp]
+    L.tome_merge_wavg_partition.restype = i32
+    L.tome_merge_wavg_partition.argtypes = [vp, i32, vp, i32, i64, i64, i64, i64, vp, vp, i64, i64, vp, vp, vp, vp, vp,
+                                            vp]
+    L.tome_unmerge_partition.restype = i32
+    L.tome_unmerge_partition.argtypes = [vp, i32, i64, i64, i64, i64, vp, vp, i64, i64, vp, vp, vp]
     if L.tome_abi_version() != ABI_VERSION:
         raise TomeHipError(f"{os.path.basename(path)} ABI {L.tome_abi_version()} != expected {ABI_VERSION}")
     return L
@@ -322,7 +335,7 @@ def edge_keep(plan: MatchPlan, threshold: float) -> torch.Tensor:
     return keep
 
 
-def _prep_x(plan: MatchPlan, x: torch.Tensor, what: str, tokens: int) -> torch.Tensor:
+def _prep_x(plan, x: torch.Tensor, what: str, tokens: int) -> torch.Tensor:
     require_device(x, what)
     if x.dim() != 3 or x.shape[0] != plan.n or x.shape[1] != tokens:
         raise TomeHipError(f"{what}: expected [{plan.n}, {tokens}, C], got {tuple(x.shape)}")
@@ -868,4 +881,127 @@ def source_init(plan: MatchPlan, drop: bool = False) -> torch.Tensor:
         out = torch.empty((plan.n, plan.T - plan.r, plan.T), dtype=torch.float32, device=plan.device)
         _check(lib().tome_source_init(plan.n, plan.T, plan.r, int(plan.distill_token), int(bool(drop)),
                                       plan.row_map.data_ptr(), out.data_ptr(), st), "tome_source_init")
+    return out
+
+
+class PartitionPlan:
+    """Device-resident result of one partition matching (kth_ / random_bipartite_soft_matching): per group an ordered
+    source set A (Na positions) and destination set B (Nb positions), given by the kth rule (`k` > 1) or by the index
+    lists `a_idx` [n,Na,1] / `b_idx` [n,Nb,1] (`k` = 0); `dst_idx` (int64 [n,Na,1], the reference's closure variable)
+    and the inverted list the merge kernel walks (`offsets` [n,Nb+1], `sources` [n,Na], int32)."""
+
+    __slots__ = ("n", "T", "Na", "Nb", "k", "a_idx", "b_idx", "dst_idx", "offsets", "sources", "device")
+
+    def __init__(self, n, T, Na, Nb, k, a_idx, b_idx, dst_idx, offsets, sources, device):
+        self.n, self.T, self.Na, self.Nb, self.k = n, T, Na, Nb, k
+        self.a_idx, self.b_idx = a_idx, b_idx
+        self.dst_idx, self.offsets, self.sources = dst_idx, offsets, sources
+        self.device = device
+
+    @property
+    def tokens_out(self) -> int:
+        """Rows `unmerge` writes: the kth rule loses the tail past (T // k) * k (merge.py:120), lists cover T."""
+        return (self.T // self.k) * self.k if self.k else self.T
+
+
+def _partition_index(idx: torch.Tensor, n: int, T: int, device, what: str) -> torch.Tensor:
+    require_device(idx, what)
+    if idx.dim() == 2:
+        idx = idx[..., None]
+    if idx.dim() != 3 or idx.shape[0] != n or idx.shape[2] != 1 or idx.dtype != torch.int64:
+        raise TomeHipError(f"{what}: expected int64 [{n}, rows, 1], got {idx.dtype} {tuple(idx.shape)}")
+    if idx.device != device:
+        raise TomeHipError(f"{what}: tensor on {idx.device}, metric on {device}")
+    return idx if idx.is_contiguous() else idx.contiguous()
+
+
+def match_partition(metric: torch.Tensor, k: int = 0, a_idx: Optional[torch.Tensor] = None,
+                    b_idx: Optional[torch.Tensor] = None) -> PartitionPlan:
+    """tome_match_partition on `metric` [n,T,D]: the kth rule (k > 1) or the position lists a_idx / b_idx (k = 0;
+    int64 [n,Na,1] / [n,Nb,1], disjoint positions in [0,T) -- the caller's promise, as in the reference)."""
+    require_device(metric, "partition matching(metric)")
+    if metric.dim() != 3:
+        raise TomeHipError(f"metric must be [batch, tokens, channels], got {tuple(metric.shape)}")
+    code = dtype_code(metric, "metric")
+    n, T, D = metric.shape
+    dev = metric.device
+    k = int(k)
+    if k:
+        if k <= 1:
+            raise TomeHipError(f"partition matching: k={k} (k > 1 expected)")
+        Na, Nb = (T // k) * (k - 1), T // k
+        a_idx = b_idx = None
+    else:
+        if a_idx is None or b_idx is None:
+            raise TomeHipError("partition matching: k or both of a_idx / b_idx are needed")
+        a_idx = _partition_index(a_idx, n, T, dev, "partition matching(a_idx)")
+        b_idx = _partition_index(b_idx, n, T, dev, "partition matching(b_idx)")
+        Na, Nb = a_idx.shape[1], b_idx.shape[1]
+    if n == 0 or Na <= 0 or Nb <= 0:
+        raise TomeHipError(f"partition matching: empty set (n={n}, Na={Na}, Nb={Nb})")
+    if metric.stride(2) != 1:
+        metric = metric.contiguous()
+    L = lib()
+    with _on_device(dev):
+        st = _stream(dev)
+        ws = _workspace(dev, st, L.tome_partition_workspace_bytes(n, Na, Nb, D))
+        dst = torch.empty((n, Na, 1), dtype=torch.int64, device=dev)
+        offsets = torch.empty((n, Nb + 1), dtype=torch.int32, device=dev)
+        sources = torch.empty((n, Na), dtype=torch.int32, device=dev)
+        rc = L.tome_match_partition(metric.data_ptr(), code, n, T, D, metric.stride(0), metric.stride(1), k,
+                                    _ptr(a_idx), _ptr(b_idx), Na, Nb, dst.data_ptr(), offsets.data_ptr(),
+                                    sources.data_ptr(), ws.data_ptr(), ws.numel(), st)
+    _check(rc, "tome_match_partition")
+    return PartitionPlan(n, T, Na, Nb, k, a_idx, b_idx, dst, offsets, sources, dev)
+
+
+def merge_partition(plan: PartitionPlan, x: torch.Tensor, mode: str) -> torch.Tensor:
+    if mode not in MODES:
+        raise TomeHipError(f"merge: unknown reduce mode {mode!r}")
+    x = _prep_x(plan, x, "merge(x)", plan.T)
+    n, T, C = x.shape
+    out = torch.empty((n, plan.Nb, C), dtype=x.dtype, device=x.device)
+    with _on_device(x.device):
+        rc = lib().tome_merge_partition(x.data_ptr(), dtype_code(x, "x"), n, T, C, plan.k, _ptr(plan.a_idx),
+                                        _ptr(plan.b_idx), plan.Na, plan.Nb, plan.offsets.data_ptr(),
+                                        plan.sources.data_ptr(), MODES[mode], out.data_ptr(), _stream(x.device))
+    _check(rc, "tome_merge_partition")
+    return out
+
+
+def merge_wavg_partition(plan: PartitionPlan, x: torch.Tensor, size: Optional[torch.Tensor], log_size: bool = False):
+    x = _prep_x(plan, x, "merge_wavg(x)", plan.T)
+    n, T, C = x.shape
+    xcode = dtype_code(x, "x")
+    if size is not None:
+        require_device(size, "merge_wavg(size)")
+        if size.shape != (n, T, 1):
+            raise TomeHipError(f"size must be [{n}, {T}, 1], got {tuple(size.shape)}")
+        if size.dtype not in (x.dtype, torch.float32):
+            size = size.to(x.dtype)
+        size = size.contiguous()
+        sdtype = size.dtype
+    else:
+        sdtype = x.dtype  # torch.ones_like(x[..., 0, None]) -- merge.py:362-363
+    x_out = torch.empty((n, plan.Nb, C), dtype=x.dtype, device=x.device)
+    s_out = torch.empty((n, plan.Nb, 1), dtype=sdtype, device=x.device)
+    log = _log_size_like(s_out, log_size)
+    with _on_device(x.device):
+        rc = lib().tome_merge_wavg_partition(x.data_ptr(), xcode, _ptr(size), DTYPES[sdtype], n, T, C, plan.k,
+                                             _ptr(plan.a_idx), _ptr(plan.b_idx), plan.Na, plan.Nb,
+                                             plan.offsets.data_ptr(), plan.sources.data_ptr(), x_out.data_ptr(),
+                                             s_out.data_ptr(), _ptr(log), _stream(x.device))
+    _check(rc, "tome_merge_wavg_partition")
+    return x_out, s_out
+
+
+def unmerge_partition(plan: PartitionPlan, x: torch.Tensor) -> torch.Tensor:
+    x = _prep_x(plan, x, "unmerge(x)", plan.Nb)
+    n, _, C = x.shape
+    out = torch.empty((n, plan.tokens_out, C), dtype=x.dtype, device=x.device)
+    with _on_device(x.device):
+        rc = lib().tome_unmerge_partition(x.data_ptr(), dtype_code(x, "x"), n, plan.T, C, plan.k, _ptr(plan.a_idx),
+                                          _ptr(plan.b_idx), plan.Na, plan.Nb, plan.dst_idx.data_ptr(),
+                                          out.data_ptr(), _stream(x.device))
+    _check(rc, "tome_unmerge_partition")
     return out

@@ -6,13 +6,17 @@ Reference lines each function stands in for (sjpollard/video-how-do-your-tokens-
   bipartite_soft_matching         tome/merge.py:17-102
   bipartite_soft_matching_drop    tome/merge.py:215-271
   bipartite_soft_matching_hybrid  tome/merge.py:274-352
+  kth_bipartite_soft_matching     tome/merge.py:105-158
+  random_bipartite_soft_matching  tome/merge.py:161-212
   merge_wavg                      tome/merge.py:355-369
   merge_source                    tome/merge.py:372-384
   do_nothing                      tome/merge.py:13-14
 
 The returned ``merge`` / ``unmerge`` / ``drop`` are real closures over ``unm_idx``, ``src_idx``,
 ``dst_idx`` (int64 device tensors shaped [n,r,1] / [n,T1-r,1]) and ``r`` exactly like the reference's,
-so code that introspects them keeps working; they also carry ``.plan`` for the fused paths.
+so code that introspects them keeps working; they also carry ``.plan`` for the fused paths.  The kth_ / random_
+matchings (every source row merged into its best destination, the merged sequence is the destination set alone) are
+closures over ``dst_idx`` [n,Na,1], ``r`` and ``k`` / ``a_idx``, ``b_idx``; their ``.plan`` is an ``_abi.PartitionPlan``.
 
 Tensors must live on a HIP device: there is no CPU implementation in this package.
 
@@ -178,8 +182,8 @@ def _make_merge_pair(plan: _abi.MatchPlan) -> Tuple[Callable, Callable]:
     def unmerge(x: torch.Tensor) -> torch.Tensor:
         _closure = (unm_idx, src_idx, dst_idx, r)  # noqa: F841
         if _wants_autograd(x):
-            if distill_token:
-                raise _abi.TomeHipError("unmerge: the distillation layout has no differentiable form here")
+            # (also with a distillation token: the reference's unmerge, merge.py:87-100, reads `x` as
+            # [unmerged, destinations] whatever the layout `merge` wrote, and so does the kernel)
             return _unmerge_with_autograd(plan, x)
         return _abi.unmerge(plan, x)
 
@@ -236,19 +240,110 @@ def bipartite_soft_matching_hybrid(
     return merge, unmerge
 
 
-def kth_bipartite_soft_matching(metric: torch.Tensor, k: int):
-    """tome/merge.py:105-158 (every k-th token as destination set).  No patch, driver or notebook of the reference
-    calls it (outside the hot path); the name exists so that `from tome.merge import ...` of code written
-    against the reference fails here, with the reason, instead of at import."""
-    raise _abi.TomeHipError("kth_bipartite_soft_matching is not provided by the MI355X path (no caller in the "
-                            "reference's patches; see INTEGRATION.md, API table)")
+def _partition_split(plan, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The reference's `split(x)` on framework ops: the rows of the source set and of the destination set
+    (merge.py:119-126 for the kth rule, :179-183 for index lists)."""
+    n, t, c = x.shape
+    if n != plan.n or t != plan.T:
+        raise _abi.TomeHipError(f"merge(x): expected [{plan.n}, {plan.T}, C], got {tuple(x.shape)}")
+    if plan.k:
+        k = plan.k
+        groups = x[:, :(t // k) * k].reshape(n, -1, k, c)
+        return groups[:, :, :k - 1].reshape(n, -1, c), groups[:, :, k - 1]
+    return x.gather(1, plan.a_idx.expand(n, plan.Na, c)), x.gather(1, plan.b_idx.expand(n, plan.Nb, c))
 
 
-def random_bipartite_soft_matching(metric: torch.Tensor, r: int):
-    """tome/merge.py:161-212 (a random source set).  As kth_bipartite_soft_matching: present by name, refused loudly.
-    (The random MODES of the patches -- mode='random_merge' / 'random_drop', merge.py:54-57 -- are implemented.)"""
-    raise _abi.TomeHipError("random_bipartite_soft_matching is not provided by the MI355X path (no caller in the "
-                            "reference's patches; use mode='random_merge' of bipartite_soft_matching)")
+def _partition_merge_with_autograd(plan, x: torch.Tensor, mode: str) -> torch.Tensor:
+    """merge.py:137-142 / :198-203 on differentiable ops: every source row scattered onto its destination."""
+    if mode not in _SCATTER_MODE:
+        raise _abi.TomeHipError(f"merge: unknown reduce mode {mode!r}")
+    src, dst = _partition_split(plan, x)
+    n, _, c = src.shape
+    return dst.scatter_reduce(1, plan.dst_idx.expand(n, plan.Na, c), src, reduce=_SCATTER_MODE[mode])
+
+
+def _partition_unmerge_with_autograd(plan, x: torch.Tensor) -> torch.Tensor:
+    """merge.py:144-156 / :205-210 on differentiable ops."""
+    n, nb, c = x.shape
+    if n != plan.n or nb != plan.Nb:
+        raise _abi.TomeHipError(f"unmerge(x): expected [{plan.n}, {plan.Nb}, C], got {tuple(x.shape)}")
+    src = x.gather(1, plan.dst_idx.expand(n, plan.Na, c))
+    if plan.k:
+        return torch.cat([src.reshape(n, -1, plan.k - 1, c), x.reshape(n, -1, 1, c)], dim=2).reshape(n, -1, c)
+    out = x.new_zeros((n, plan.T, c)).scatter(1, plan.a_idx.expand(n, plan.Na, c), src)
+    return out.scatter(1, plan.b_idx.expand(n, plan.Nb, c), x)
+
+
+def _partition_metric(metric, who: str) -> torch.Tensor:
+    if isinstance(metric, HeadMeanKeys):
+        metric = metric.materialize()
+    _abi.require_device(metric, f"{who}(metric)")
+    if metric.dim() != 3:
+        raise _abi.TomeHipError(f"metric must be [batch, tokens, channels], got {tuple(metric.shape)}")
+    return metric
+
+
+def kth_bipartite_soft_matching(metric: torch.Tensor, k: int) -> Tuple[Callable, Callable]:
+    """The two sets as (every k-th token = destination, the k-1 before it = sources); T // k tokens remain and the
+    tokens past (T // k) * k are discarded, as in the reference (merge.py:105-158).  Returns (merge, unmerge)."""
+    if k <= 1:
+        return do_nothing, do_nothing
+    t = metric.shape[1]
+    if k > t:
+        raise ValueError(f"kth_bipartite_soft_matching: k={k} leaves no destination among {t} tokens")
+    with torch.no_grad():
+        plan = _abi.match_partition(_partition_metric(metric, "kth_bipartite_soft_matching"), k=int(k))
+    dst_idx, r, k = plan.dst_idx, plan.Na, plan.k
+
+    def merge(x: torch.Tensor, mode="mean") -> torch.Tensor:
+        _closure = (dst_idx, r, k)  # noqa: F841  (closure variables as in the reference; the kernels read `plan`)
+        if _wants_autograd(x):
+            return _partition_merge_with_autograd(plan, x, mode)
+        return _abi.merge_partition(plan, x, mode)
+
+    def unmerge(x: torch.Tensor) -> torch.Tensor:
+        _closure = (dst_idx, r, k)  # noqa: F841
+        if _wants_autograd(x):
+            return _partition_unmerge_with_autograd(plan, x)
+        return _abi.unmerge_partition(plan, x)
+
+    merge.plan = plan
+    unmerge.plan = plan
+    return merge, unmerge
+
+
+def random_bipartite_soft_matching(metric: torch.Tensor, r: int) -> Tuple[Callable, Callable]:
+    """The two sets as (r tokens chosen at random = sources, the rest = destinations); T - r tokens remain
+    (merge.py:161-212).  The permutation is drawn with torch's generator on the metric's device, exactly as the
+    reference draws it (merge.py:174), so `torch.manual_seed` makes a call repeatable.  Returns (merge, unmerge)."""
+    if r <= 0:
+        return do_nothing, do_nothing
+    B, N, _ = metric.shape
+    if r >= N:
+        raise ValueError(f"random_bipartite_soft_matching: r={r} leaves no destination among {N} tokens")
+    with torch.no_grad():
+        metric = _partition_metric(metric, "random_bipartite_soft_matching")
+        rand_idx = torch.rand(B, N, 1, device=metric.device).argsort(dim=1)
+        a_idx = rand_idx[:, :r, :].contiguous()
+        b_idx = rand_idx[:, r:, :].contiguous()
+        plan = _abi.match_partition(metric, a_idx=a_idx, b_idx=b_idx)
+    dst_idx = plan.dst_idx
+
+    def merge(x: torch.Tensor, mode="mean") -> torch.Tensor:
+        _closure = (a_idx, b_idx, dst_idx, r, B, N)  # noqa: F841  (closure variables as in the reference)
+        if _wants_autograd(x):
+            return _partition_merge_with_autograd(plan, x, mode)
+        return _abi.merge_partition(plan, x, mode)
+
+    def unmerge(x: torch.Tensor) -> torch.Tensor:
+        _closure = (a_idx, b_idx, dst_idx, r, B, N)  # noqa: F841
+        if _wants_autograd(x):
+            return _partition_unmerge_with_autograd(plan, x)
+        return _abi.unmerge_partition(plan, x)
+
+    merge.plan = plan
+    unmerge.plan = plan
+    return merge, unmerge
 
 
 def merge_wavg(merge: Callable, x: torch.Tensor, size: Optional[torch.Tensor] = None, log_size: bool = False
@@ -259,6 +354,8 @@ def merge_wavg(merge: Callable, x: torch.Tensor, size: Optional[torch.Tensor] = 
     next block's proportional-attention bias; consumers fetch it with ``_abi.log_of_size(size)``."""
     plan = getattr(merge, "plan", None)
     if plan is not None and not (_wants_autograd(x) or (size is not None and _wants_autograd(size))):
+        if isinstance(plan, _abi.PartitionPlan):
+            return _abi.merge_wavg_partition(plan, x, size, log_size=log_size)
         return _abi.merge_wavg(plan, x, size, log_size=log_size)
     # foreign callables, do_nothing, and tensors that require grad (the closure then runs on the framework's
     # differentiable ops): the reference's op sequence on the tensors' own device
@@ -274,11 +371,12 @@ def merge_source(merge: Callable, x: torch.Tensor, source: Optional[torch.Tensor
     """Source tracking: adjacency between the initial tokens and the merged groups."""
     plan = getattr(merge, "plan", None)
     if source is None:
-        if plan is not None and plan.edge_keep is None:
+        if isinstance(plan, _abi.MatchPlan) and plan.edge_keep is None:
             # merging the identity with "max" = the one-hot rows of the matching's row map: written directly
             # (tome_source_init), the [n, T, T] identity is never allocated.  (Not for a hybrid matching: there a
             # destination with an incoming edge below the threshold is zeroed before the amax, merge.py:326-331, so its
-            # own column is 0 -- the generic path below keeps that.)
+            # own column is 0 -- the generic path below keeps that.  A partition matching, kth_ / random_, takes the
+            # generic path with the identity as well: `merge(source, mode="max")`, rows of C = T channels.)
             _abi.require_device(x, "merge_source(x)")
             if x.shape[0] != plan.n or x.shape[1] != plan.T or x.device != plan.device:
                 raise _abi.TomeHipError(f"merge_source: x {tuple(x.shape)} on {x.device} does not fit the matching "
