@@ -39,7 +39,7 @@ enum tome_status {
     TOME_ELAUNCH = 3     /* HIP reported a launch error (text in tome_last_error()) */
 };
 
-#define TOME_ABI_VERSION 10
+#define TOME_ABI_VERSION 11
 
 int tome_abi_version(void);
 
@@ -289,6 +289,32 @@ int tome_drop(const void *x, int dtype, int64_t n, int64_t T, int64_t C, int64_t
 int tome_unmerge(const void *x, int dtype, int64_t n, int64_t T, int64_t C, int64_t r,
                  const int64_t *src_idx, const int64_t *dst_idx, const int64_t *unm_idx, void *out,
                  tome_stream_t stream);
+
+/*
+ * tome_merge_backward  <-  what autograd derives from the merge closure and merge_wavg in the reference (only the
+ *     matching is under no_grad, merge.py:49; models are patched for training, tools/train_net.py:727-741): the
+ *     gradient with respect to the tokens of
+ *         merge(x, "sum")                 merge.py:75-85        out_div = in_mul = NULL
+ *         merge(x, "mean")                merge.py:75-85        out_div = 1 + number of sources of each merged row
+ *         merge_wavg(merge, x, size)      merge.py:355-369      out_div = the returned size, in_mul = size (or NULL)
+ *         drop(x)                         merge.py:253-262      drop != 0: merged-away tokens get a zero gradient
+ *     as one gather:  grad_in[t, :] = (grad_out[row of t, :] / out_div[row of t]) * in_mul[t], fp32 arithmetic (division,
+ *     then product: the order of the reference's chain x*size -> sum -> /size walked back), one rounding, no atomics,
+ *     every row written once, same bits on every run.
+ *     grad_out [n,T-r,C], grad_in [n,T,C] of x_dtype; out_div [n,T-r], in_mul [n,T] of size_dtype (= x_dtype or
+ *     TOME_F32; ignored when both are NULL); row_map [n,ceil(T/2)] as tome_row_map / tome_match write it.
+ *     The backward of unmerge (merge.py:87-100) is tome_merge in mode TOME_SUM, its adjoint.
+ * tome_merge_backward_regrouped: the same on the layout of tome_merge_wavg_regrouped / tome_drop_regrouped
+ *     (timesformer.py:89-107, :111-131; motionformer.py:150-168, :172-193): grad_out [B, has_cls + (P-r)*F, C] ->
+ *     grad_in [B, has_cls + P*F, C], class rows copied through; out_div [B*F,P-r], in_mul [B*F,P], row_map
+ *     [B*F,ceil(P/2)].  C * sizeof(dtype) must be a multiple of 16.
+ */
+int tome_merge_backward(const void *grad_out, int x_dtype, const void *out_div, const void *in_mul, int size_dtype,
+                        int64_t n, int64_t T, int64_t C, int64_t r, const int32_t *row_map, int distill_token,
+                        int drop, void *grad_in, tome_stream_t stream);
+int tome_merge_backward_regrouped(const void *grad_out, int x_dtype, const void *out_div, const void *in_mul,
+                                  int size_dtype, int64_t B, int64_t F, int64_t P, int64_t C, int64_t r, int has_cls,
+                                  const int32_t *row_map, int drop, void *grad_in, tome_stream_t stream);
 
 /* tome_gelu_erf  <-  the activation of the MLP the patched block calls between merge and second residual
  * (`x = x + self.drop_path(self.mlp(self.norm2(x)))`, tome/patch/videomae.py:29, timesformer.py:56,

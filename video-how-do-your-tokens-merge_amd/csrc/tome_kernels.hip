@@ -2,7 +2,8 @@
 // C ABI declared in include/tome_hip.h.  Built with: hipcc --offload-arch=gfx950 -O3
 // -ffp-contract=off -shared -fPIC (csrc/build.py).  No torch, no CUDA, no portability layer.
 //
-// One translation unit: tome_common.h (types), tome_match.h, tome_merge.h and tome_partition.h (kernels), this file
+// One translation unit: tome_common.h (types), tome_match.h, tome_merge.h, tome_merge_bwd.h and tome_partition.h
+// (kernels), this file
 // (host).
 //
 // Launch sequence of one matching (tome_match / tome_match_keys), kernels in tome_match.h:
@@ -16,6 +17,8 @@
 //                        <LN>: residual add in front and LayerNorm behind fused in (tome_merge_wavg_ln)
 //   k_add_ln_rows        second residual + the next block's first LayerNorm (tome_add_layernorm)
 //   k_merge_rows / k_unmerge_rows   generic one-wave-per-row forms                        (HBM bound)
+// and of its backward (tome_merge_backward[_regrouped]), tome_merge_bwd.h:
+//   k_merge_rows_bwd     gx[t] = gy[row of t] / out_div * in_mul, streaming gather             (HBM bound)
 // The partition matchings (kth_ / random_bipartite_soft_matching: arbitrary source / destination sets, every source
 // merged) have their own sequence, written out at the top of tome_partition.h.
 //
@@ -35,6 +38,7 @@
 #include "tome_match.h"
 #include "tome_match_filter.h"
 #include "tome_merge.h"
+#include "tome_merge_bwd.h"
 #include "tome_partition.h"
 #include "tome_attn.h"
 #include "tome_attn_stream.h"
@@ -1127,6 +1131,79 @@ extern "C" int tome_unmerge(const void *x, int dtype, int64_t n, int64_t T, int6
         return launch_unmerge<typename decltype(tx)::type>(x, n, T, C, r, src_idx, dst_idx, unm_idx, out,
                                                            (hipStream_t)stream);
     }, [&] { return fail(TOME_EINVAL, "tome_unmerge: dtype %d", dtype); });
+}
+
+// ------------------------------------------------------------------------------------------------
+// backward of merge / merge_wavg / drop with respect to the tokens (kernels in tome_merge_bwd.h)
+// ------------------------------------------------------------------------------------------------
+template <typename TX, typename TS>
+static int launch_merge_bwd(const void *gy, const void *out_div, const void *in_mul, int64_t n, int64_t T, int64_t C,
+                            int64_t r, const int32_t *row_map, int distill, int drop, void *gx, hipStream_t st,
+                            const TokLayout *lgy_p = nullptr, const TokLayout *lgx_p = nullptr, int cls_rows = 0) {
+    constexpr int VEC = 16 / sizeof(TX);
+    const int64_t To = T - r;
+    const bool vec_ok = (C % VEC == 0) && aligned16(gy) && aligned16(gx);
+    const int64_t cpr = C / VEC;
+    if (vec_ok && cpr <= FAST_NIT * WAVE) {
+        const TokLayout lgy = lgy_p ? *lgy_p : contiguous_layout(To, C);
+        const TokLayout lgx = lgx_p ? *lgx_p : contiguous_layout(T, C);
+        int R = (int)((FAST_NIT * WAVE) / cpr);
+        if (R > FAST_MAXR) R = FAST_MAXR;
+        const int64_t wpg = (T + R - 1) / R, bpg = (wpg + 3) / 4;
+        const int64_t ny = n + (cls_rows ? (cls_rows + 4 * bpg - 1) / (4 * bpg) : 0);
+        const int64_t gy_ = ny < 65535 ? ny : 65535, gz = (ny + gy_ - 1) / gy_;
+        if (gz > 65535) return fail(TOME_EINVAL, "merge backward: too many groups (%lld)", (long long)n);
+        hipLaunchKernelGGL((k_merge_rows_bwd<TX, TS, FAST_NIT>), dim3((unsigned)bpg, (unsigned)gy_, (unsigned)gz),
+                           dim3(256), 0, st, (const TX *)gy, (const TS *)out_div, (const TS *)in_mul, (int)n, (int)T,
+                           (int)C, (int)r, R, (int)cpr, (int)wpg, row_map, distill, drop, (TX *)gx, lgy, lgx, cls_rows);
+        return check_launch("k_merge_rows_bwd");
+    }
+    if (lgy_p || lgx_p || cls_rows)
+        return fail(TOME_EINVAL, "regrouped merge backward needs rows of whole 16-byte chunks (C=%lld)", (long long)C);
+    const unsigned nb = (unsigned)((n * T + 3) / 4);
+    if (vec_ok)
+        hipLaunchKernelGGL((k_merge_rows_bwd_any<TX, TS, VEC>), dim3(nb), dim3(256), 0, st, (const TX *)gy,
+                           (const TS *)out_div, (const TS *)in_mul, (int)n, (int)T, (int)C, (int)r, row_map, distill, drop,
+                           (TX *)gx);
+    else
+        hipLaunchKernelGGL((k_merge_rows_bwd_any<TX, TS, 1>), dim3(nb), dim3(256), 0, st, (const TX *)gy,
+                           (const TS *)out_div, (const TS *)in_mul, (int)n, (int)T, (int)C, (int)r, row_map, distill, drop,
+                           (TX *)gx);
+    return check_launch("k_merge_rows_bwd_any");
+}
+
+extern "C" int tome_merge_backward(const void *grad_out, int x_dtype, const void *out_div, const void *in_mul,
+                                   int size_dtype, int64_t n, int64_t T, int64_t C, int64_t r, const int32_t *row_map,
+                                   int distill_token, int drop, void *grad_in, tome_stream_t stream) {
+    if (int rc = check_merge_args("tome_merge_backward", grad_out, n, T, C, r, grad_in)) return rc;
+    if (!row_map) return fail(TOME_EINVAL, "tome_merge_backward: null row_map");
+    if (drop && (out_div || in_mul)) return fail(TOME_EINVAL, "tome_merge_backward: drop takes no scales");
+    return dispatch_xs<true>(x_dtype, size_dtype, [&](auto tx, auto ts) {
+        return launch_merge_bwd<typename decltype(tx)::type, typename decltype(ts)::type>(
+            grad_out, out_div, in_mul, n, T, C, r, row_map, distill_token ? 1 : 0, drop ? 1 : 0, grad_in,
+            (hipStream_t)stream);
+    }, [&] { return fail(TOME_EINVAL, "tome_merge_backward: unsupported dtypes x=%d size=%d", x_dtype, size_dtype); });
+}
+
+extern "C" int tome_merge_backward_regrouped(const void *grad_out, int x_dtype, const void *out_div, const void *in_mul,
+                                             int size_dtype, int64_t B, int64_t F, int64_t P, int64_t C, int64_t r,
+                                             int has_cls, const int32_t *row_map, int drop, void *grad_in,
+                                             tome_stream_t stream) {
+    if (B <= 0 || F <= 0) return fail(TOME_EINVAL, "tome_merge_backward_regrouped: bad shape");
+    const int64_t n = B * F;
+    if (int rc = check_merge_args("tome_merge_backward_regrouped", grad_out, n, P, C, r, grad_in)) return rc;
+    if (!row_map) return fail(TOME_EINVAL, "tome_merge_backward_regrouped: null row_map");
+    if (drop && (out_div || in_mul)) return fail(TOME_EINVAL, "tome_merge_backward_regrouped: drop takes no scales");
+    const int cls = has_cls ? 1 : 0;
+    const TokLayout lgy{cls * C, (cls + (P - r) * F) * C, C, F * C, (int)F};
+    const TokLayout lgx{cls * C, (cls + P * F) * C, C, F * C, (int)F};
+    return dispatch_xs<true>(x_dtype, size_dtype, [&](auto tx, auto ts) {
+        return launch_merge_bwd<typename decltype(tx)::type, typename decltype(ts)::type>(
+            grad_out, out_div, in_mul, n, P, C, r, row_map, 0, drop ? 1 : 0, grad_in, (hipStream_t)stream, &lgy, &lgx,
+            cls ? (int)B : 0);
+    }, [&] {
+        return fail(TOME_EINVAL, "tome_merge_backward_regrouped: unsupported dtypes x=%d size=%d", x_dtype, size_dtype);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -21,12 +21,12 @@ SYMBOLS = (
     "tome_merge_wavg_regrouped_ln", "tome_add_layernorm", "tome_add_layernorm_skip_first", "tome_add_layernorm_regrouped", "tome_prop_attention", "tome_prop_attention_segments", "tome_trajectory_mix", "tome_short_attention", "tome_merge",
     "tome_drop",
     "tome_drop_regrouped",
-    "tome_unmerge", "tome_row_map", "tome_source_init", "tome_gelu_erf", "tome_tubelet_rows",
+    "tome_unmerge", "tome_merge_backward", "tome_merge_backward_regrouped", "tome_row_map", "tome_source_init", "tome_gelu_erf", "tome_tubelet_rows",
     "tome_partition_workspace_bytes", "tome_match_partition", "tome_merge_partition", "tome_merge_wavg_partition",
     "tome_unmerge_partition",
 )
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 MODES = {"sum": 0, "mean": 1, "amax": 2, "max": 2, "prod": 3, "amin": 4, "min": 4}
 
@@ -108,6 +108,10 @@ def bind(path: str) -> ctypes.CDLL:
     L.tome_drop.argtypes = [vp, i32, i64, i64, i64, i64, vp, i32, vp, vp]
     L.tome_unmerge.restype = i32
     L.tome_unmerge.argtypes = [vp, i32, i64, i64, i64, i64, vp, vp, vp, vp, vp]
+    L.tome_merge_backward.restype = i32
+    L.tome_merge_backward.argtypes = [vp, i32, vp, vp, i32, i64, i64, i64, i64, vp, i32, i32, vp, vp]
+    L.tome_merge_backward_regrouped.restype = i32
+    L.tome_merge_backward_regrouped.argtypes = [vp, i32, vp, vp, i32, i64, i64, i64, i64, i64, i32, vp, i32, vp, vp]
     L.tome_gelu_erf.restype = i32
     L.tome_gelu_erf.argtypes = [vp, i32, i64, vp, vp]
     L.tome_tubelet_rows.restype = i32
@@ -203,7 +207,7 @@ class MatchPlan:
     row_map for source tracking)."""
 
     __slots__ = ("n", "T", "r", "class_token", "distill_token", "src_idx", "dst_idx", "unm_idx", "node_max",
-                 "row_map", "edge_keep", "device")
+                 "row_map", "edge_keep", "device", "count")
 
     def __init__(self, n, T, r, class_token, distill_token, src_idx, dst_idx, unm_idx, node_max, row_map, device):
         self.n, self.T, self.r = n, T, r
@@ -212,6 +216,7 @@ class MatchPlan:
         self.node_max, self.row_map = node_max, row_map
         self.edge_keep = None
         self.device = device
+        self.count = None  # [n, T-r, 1] fp32, 1 + sources of every merged row (plan_count: backward of "mean")
 
 
 def _alloc_plan(n, T, re, class_token, distill_token, device, want_node_max, want_row_map):
@@ -866,18 +871,108 @@ def tubelet_rows(x: torch.Tensor, kt: int, kh: int, kw: int) -> torch.Tensor:
     return rows
 
 
+def plan_row_map(plan: MatchPlan) -> torch.Tensor:
+    """The matching's row map [n, T1] int32 (merged row of every even token); made once per plan by tome_row_map when
+    the matching was not asked for it."""
+    if plan.row_map is None:
+        T1 = (plan.T + 1) // 2
+        row_map = torch.empty((plan.n, T1), dtype=torch.int32, device=plan.device)
+        with _on_device(plan.device):
+            _check(lib().tome_row_map(plan.n, plan.T, plan.r, int(plan.distill_token), plan.src_idx.data_ptr(),
+                                      plan.dst_idx.data_ptr(), plan.unm_idx.data_ptr(), row_map.data_ptr(),
+                                      _stream(plan.device)), "tome_row_map")
+        plan.row_map = row_map
+    return plan.row_map
+
+
+def plan_count(plan: MatchPlan) -> torch.Tensor:
+    """[n, T-r, 1] fp32: how many tokens every merged row holds (the divisor of merge(x, "mean")); made once per plan
+    by tome_merge of a column of ones in mode sum."""
+    if plan.count is None:
+        with torch.no_grad():
+            plan.count = merge(plan, torch.ones((plan.n, plan.T, 1), dtype=torch.float32, device=plan.device), "sum")
+    return plan.count
+
+
+def _prep_grad(g: torch.Tensor, shape, dtype, device, what: str) -> torch.Tensor:
+    require_device(g, what)
+    if tuple(g.shape) != tuple(shape) or g.dtype != dtype or g.device != device:
+        raise TomeHipError(f"{what}: expected a gradient {tuple(shape)} of {dtype} on {device}, got {tuple(g.shape)} of "
+                           f"{g.dtype} on {g.device}")
+    g = g.detach()
+    return g if g.is_contiguous() else g.contiguous()
+
+
+def _prep_scales(out_div, in_mul, n, T, To, x_dtype, device, what: str):
+    """out_div [n, To, 1] / in_mul [n, T, 1] (either may be None) in one dtype the kernel takes: x's or fp32."""
+    given = [s for s in (out_div, in_mul) if s is not None]
+    if not given:
+        return None, None, x_dtype
+    for s, rows in ((out_div, To), (in_mul, T)):
+        if s is not None and (s.numel() != n * rows or s.device != device):
+            raise TomeHipError(f"{what}: a scale with {n * rows} values on {device} expected, got {tuple(s.shape)} on "
+                               f"{s.device}")
+    sdtype = given[0].dtype if all(s.dtype == given[0].dtype for s in given) else torch.float32
+    if sdtype not in (x_dtype, torch.float32):
+        sdtype = torch.float32
+    conv = lambda s: None if s is None else s.detach().to(sdtype).contiguous()  # noqa: E731
+    return conv(out_div), conv(in_mul), sdtype
+
+
+def merge_backward(plan: MatchPlan, grad_out: torch.Tensor, out_div: Optional[torch.Tensor] = None,
+                   in_mul: Optional[torch.Tensor] = None, drop: bool = False) -> torch.Tensor:
+    """tome_merge_backward: grad_in[t] = grad_out[row of t] / out_div[row of t] * in_mul[t] for a gradient
+    [n, T-r, C] of merge / merge_wavg / drop; returns [n, T, C]."""
+    if grad_out.dim() != 3:
+        raise TomeHipError(f"merge_backward: gradient must be [n, tokens, C], got {tuple(grad_out.shape)}")
+    n, T, To, C = plan.n, plan.T, plan.T - plan.r, grad_out.shape[-1]
+    g = _prep_grad(grad_out, (n, To, C), grad_out.dtype, plan.device, "merge_backward(grad)")
+    xcode = dtype_code(g, "grad")
+    out_div, in_mul, sdtype = _prep_scales(out_div, in_mul, n, T, To, g.dtype, plan.device, "merge_backward")
+    row_map = plan_row_map(plan)
+    gx = torch.empty((n, T, C), dtype=g.dtype, device=g.device)
+    with _on_device(g.device):
+        rc = lib().tome_merge_backward(g.data_ptr(), xcode, _ptr(out_div), _ptr(in_mul), DTYPES[sdtype], n, T, C, plan.r,
+                                       row_map.data_ptr(), int(plan.distill_token), int(bool(drop)), gx.data_ptr(),
+                                       _stream(g.device))
+    _check(rc, "tome_merge_backward")
+    return gx
+
+
+def merge_backward_regrouped(plan: MatchPlan, grad_out: torch.Tensor, frames: int, has_cls: bool = True,
+                             out_div: Optional[torch.Tensor] = None, in_mul: Optional[torch.Tensor] = None,
+                             drop: bool = False) -> torch.Tensor:
+    """tome_merge_backward_regrouped: the gradient [B, has_cls + (P-r)*F, C] of merge_wavg_regrouped / drop_regrouped
+    taken back to [B, has_cls + P*F, C]; class rows pass through."""
+    if grad_out.dim() != 3:
+        raise TomeHipError(f"merge_backward_regrouped: gradient must be [B, tokens, C], got {tuple(grad_out.shape)}")
+    cls = 1 if has_cls else 0
+    F, P = int(frames), plan.T
+    if F <= 0 or plan.n % F:
+        raise TomeHipError(f"merge_backward_regrouped: {plan.n} groups do not split into clips of {F} frames")
+    B, C = plan.n // F, grad_out.shape[-1]
+    g = _prep_grad(grad_out, (B, cls + (P - plan.r) * F, C), grad_out.dtype, plan.device,
+                   "merge_backward_regrouped(grad)")
+    xcode = dtype_code(g, "grad")
+    out_div, in_mul, sdtype = _prep_scales(out_div, in_mul, plan.n, P, P - plan.r, g.dtype, plan.device,
+                                           "merge_backward_regrouped")
+    row_map = plan_row_map(plan)
+    gx = torch.empty((B, cls + P * F, C), dtype=g.dtype, device=g.device)
+    with _on_device(g.device):
+        rc = lib().tome_merge_backward_regrouped(g.data_ptr(), xcode, _ptr(out_div), _ptr(in_mul), DTYPES[sdtype], B, F, P,
+                                                 C, plan.r, cls, row_map.data_ptr(), int(bool(drop)), gx.data_ptr(),
+                                                 _stream(g.device))
+    _check(rc, "tome_merge_backward_regrouped")
+    return gx
+
+
 def source_init(plan: MatchPlan, drop: bool = False) -> torch.Tensor:
     """The first layer's source matrix [n, T-r, T] fp32 (merge_source with source=None, merge.py:372-384; `drop`:
     what the drop closure makes of the identity) written straight from the matching's row map -- no [n,T,T]
     identity, no reduction over its zeros."""
+    plan_row_map(plan)
     with _on_device(plan.device):
         st = _stream(plan.device)
-        if plan.row_map is None:
-            T1 = (plan.T + 1) // 2
-            plan.row_map = torch.empty((plan.n, T1), dtype=torch.int32, device=plan.device)
-            _check(lib().tome_row_map(plan.n, plan.T, plan.r, int(plan.distill_token), plan.src_idx.data_ptr(),
-                                      plan.dst_idx.data_ptr(), plan.unm_idx.data_ptr(), plan.row_map.data_ptr(), st),
-                   "tome_row_map")
         out = torch.empty((plan.n, plan.T - plan.r, plan.T), dtype=torch.float32, device=plan.device)
         _check(lib().tome_source_init(plan.n, plan.T, plan.r, int(plan.distill_token), int(bool(drop)),
                                       plan.row_map.data_ptr(), out.data_ptr(), st), "tome_source_init")

@@ -21,10 +21,17 @@ closures over ``dst_idx`` [n,Na,1], ``r`` and ``k`` / ``a_idx``, ``b_idx``; thei
 Tensors must live on a HIP device: there is no CPU implementation in this package.
 
 Autograd (only the index computation is ``no_grad`` in the reference, merge.py:49; tools/train_net.py:727-741
-patches models for training): the kernels are inference code.  When a tensor handed to ``merge`` / ``unmerge`` /
-``drop`` / ``merge_wavg`` requires grad (and grad mode is on), the closure applies its index tensors with the
-framework's own differentiable gather / scatter_reduce ops on the tensor's device instead (``_merge_with_autograd``
-below: the op sequence of merge.py:75-100) -- the matching itself always runs on the HIP kernels.
+patches models for training).  When a tensor handed to ``merge`` / ``unmerge`` / ``drop`` / ``merge_wavg`` requires grad
+(and grad mode is on) the call becomes a ``torch.autograd.Function`` of this module: its forward is the same inference
+kernel on the detached tensor, its backward one launch of ``tome_merge_backward`` (``k_merge_rows_bwd``: the gather
+``gx[t] = gy[row of t] / out_div * in_mul``, no atomics, same bits on every run) -- or ``tome_merge`` in mode sum for
+``unmerge``, its adjoint.  Covered (``native_backward_covers``): the even/odd matchings without a threshold, modes
+``sum`` / ``mean``, fp32 / bf16 / fp16 tokens on the device, a ``size`` that does not itself require grad, ``unmerge``
+without a distillation token.  Everything else (other reduce modes, hybrid and kth_ / random_ partition matchings, a
+differentiable ``size``, foreign callables) applies the index tensors with the framework's own differentiable gather /
+scatter_reduce ops instead (``_merge_with_autograd`` below: the op sequence of merge.py:75-100), as does every case
+when ``NATIVE_BACKWARD`` is switched off.  The Functions are once-differentiable: double backward raises.  The
+matching itself always runs on the HIP kernels.
 """
 from __future__ import annotations
 
@@ -121,6 +128,180 @@ def _wants_autograd(x: torch.Tensor) -> bool:
     return torch.is_grad_enabled() and x.requires_grad
 
 
+# Tokens that require grad take the native Functions below where `native_backward_covers` says so.  False: every such
+# call takes the framework's gather / scatter_reduce chain (the behaviour before the backward kernel existed) -- for
+# A/B in tests and tools/merge_backward_bench.py.
+NATIVE_BACKWARD = True
+
+_NATIVE_MODES = {"merge": ("sum", "mean"), "merge_wavg": (None,), "drop": (None,), "unmerge": (None,)}
+
+
+def native_backward_covers(kind: str, *, even_odd: bool, hybrid: bool = False, distill_token: bool = False,
+                           on_device: bool = True, dtype=torch.float32, mode: Optional[str] = None,
+                           size_requires_grad: bool = False, enabled: Optional[bool] = None) -> bool:
+    """Does a call of `kind` ("merge", "merge_wavg", "drop", "unmerge") on tokens that require grad run as a native
+    Function (forward kernel + tome_merge_backward)?  Facts only, no tensors: testable without a device."""
+    if kind not in _NATIVE_MODES:
+        raise ValueError(f"native_backward_covers: unknown kind {kind!r}")
+    if not (NATIVE_BACKWARD if enabled is None else enabled):
+        return False
+    if not even_odd or hybrid or not on_device or dtype not in _abi.DTYPES:
+        return False  # kth_ / random_ partition plans, threshold flags, CPU tensors, fp64
+    if mode not in _NATIVE_MODES[kind]:
+        return False  # "max" (source tracking) and the other reduce modes are never differentiated
+    if kind == "merge_wavg" and size_requires_grad:
+        return False
+    if kind == "unmerge" and distill_token:
+        return False  # unmerge reads [unmerged, destinations] whatever merge wrote: not the adjoint of merge there
+    return True
+
+
+def _covers(kind: str, plan, x: torch.Tensor, mode: Optional[str] = None, size: Optional[torch.Tensor] = None) -> bool:
+    return native_backward_covers(
+        kind, even_odd=isinstance(plan, _abi.MatchPlan), hybrid=getattr(plan, "edge_keep", None) is not None,
+        distill_token=bool(getattr(plan, "distill_token", False)),
+        on_device=x.is_cuda and x.device == getattr(plan, "device", None) and x.dim() == 3, dtype=x.dtype, mode=mode,
+        size_requires_grad=size is not None and _wants_autograd(size))
+
+
+def _grad_like(ctx, g: torch.Tensor) -> torch.Tensor:
+    return g if g.dtype == ctx.dtype else g.to(ctx.dtype)
+
+
+class _MergeFunction(torch.autograd.Function):
+    """merge(x, "sum" | "mean"): tome_merge forward, tome_merge_backward backward."""
+
+    @staticmethod
+    def forward(ctx, x, plan, mode):
+        ctx.plan, ctx.dtype = plan, x.dtype
+        ctx.count = _abi.plan_count(plan) if mode == "mean" else None
+        _abi.plan_row_map(plan)
+        return _abi.merge(plan, x.detach(), mode)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        return _abi.merge_backward(ctx.plan, _grad_like(ctx, g), out_div=ctx.count), None, None
+
+
+class _DropFunction(torch.autograd.Function):
+    """drop(x): tome_drop forward; backward = the gather with zero rows for the tokens that were dropped."""
+
+    @staticmethod
+    def forward(ctx, x, plan):
+        ctx.plan, ctx.dtype = plan, x.dtype
+        _abi.plan_row_map(plan)
+        return _abi.drop(plan, x.detach())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        return _abi.merge_backward(ctx.plan, _grad_like(ctx, g), drop=True), None
+
+
+class _UnmergeFunction(torch.autograd.Function):
+    """unmerge(x): tome_unmerge forward; backward = merge(g, "sum"), its adjoint (own term, then the sources in rank
+    order: deterministic)."""
+
+    @staticmethod
+    def forward(ctx, x, plan):
+        ctx.plan, ctx.dtype = plan, x.dtype
+        return _abi.unmerge(plan, x.detach())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        g = _grad_like(ctx, g)
+        plan = ctx.plan
+        if g.dim() != 3 or g.shape[0] != plan.n or g.shape[1] != plan.T or g.device != plan.device:
+            raise _abi.TomeHipError(f"unmerge backward: expected a gradient [{plan.n}, {plan.T}, C] on {plan.device}, "
+                                    f"got {tuple(g.shape)} on {g.device}")
+        return _abi.merge(plan, g.detach(), "sum"), None
+
+
+class _MergeWavgFunction(torch.autograd.Function):
+    """merge_wavg(merge, x, size): tome_merge_wavg forward (sizes and their log are side outputs without a
+    gradient), backward gx[t] = g[row of t] / size'[row of t] * size[t]."""
+
+    @staticmethod
+    def forward(ctx, x, size, plan, log_size):
+        ctx.plan, ctx.dtype = plan, x.dtype
+        _abi.plan_row_map(plan)
+        x_out, s_out = _abi.merge_wavg(plan, x.detach(), None if size is None else size.detach(), log_size=log_size)
+        log = getattr(s_out, "_tome_log", None)
+        ctx.save_for_backward(size, s_out)
+        ctx.mark_non_differentiable(*(t for t in (s_out, log) if t is not None))
+        return x_out, s_out, log
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _gs, _gl):
+        size, s_out = ctx.saved_tensors
+        return _abi.merge_backward(ctx.plan, _grad_like(ctx, g), out_div=s_out, in_mul=size), None, None, None
+
+
+class _MergeWavgRegroupedFunction(torch.autograd.Function):
+    """_abi.merge_wavg_regrouped (TimeSformer / Motionformer layout) with tome_merge_backward_regrouped behind it."""
+
+    @staticmethod
+    def forward(ctx, x_full, size, plan, frames, has_cls, log_size):
+        ctx.plan, ctx.dtype, ctx.frames, ctx.has_cls = plan, x_full.dtype, frames, has_cls
+        _abi.plan_row_map(plan)
+        x_out, s_out = _abi.merge_wavg_regrouped(plan, x_full.detach(), None if size is None else size.detach(), frames,
+                                                 has_cls=has_cls, log_size=log_size)
+        log = getattr(s_out, "_tome_log", None)
+        ctx.save_for_backward(size, s_out)
+        ctx.mark_non_differentiable(*(t for t in (s_out, log) if t is not None))
+        return x_out, s_out, log
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _gs, _gl):
+        size, s_out = ctx.saved_tensors
+        gx = _abi.merge_backward_regrouped(ctx.plan, _grad_like(ctx, g), ctx.frames, has_cls=ctx.has_cls, out_div=s_out,
+                                           in_mul=size)
+        return gx, None, None, None, None, None
+
+
+class _DropRegroupedFunction(torch.autograd.Function):
+    """_abi.drop_regrouped with tome_merge_backward_regrouped (drop) behind it."""
+
+    @staticmethod
+    def forward(ctx, x_full, plan, frames, has_cls):
+        ctx.plan, ctx.dtype, ctx.frames, ctx.has_cls = plan, x_full.dtype, frames, has_cls
+        _abi.plan_row_map(plan)
+        return _abi.drop_regrouped(plan, x_full.detach(), frames, has_cls=has_cls)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        gx = _abi.merge_backward_regrouped(ctx.plan, _grad_like(ctx, g), ctx.frames, has_cls=ctx.has_cls, drop=True)
+        return gx, None, None, None
+
+
+def _with_log(s_out: torch.Tensor, log: Optional[torch.Tensor]) -> torch.Tensor:
+    # the size a Function returns is a new tensor object: log(size') travels on it again (`_abi.log_of_size`)
+    if log is not None:
+        s_out._tome_log = log
+    return s_out
+
+
+def merge_wavg_native(plan, x, size, log_size: bool = False):
+    x_out, s_out, log = _MergeWavgFunction.apply(x, size, plan, bool(log_size))
+    return x_out, _with_log(s_out, log)
+
+
+def merge_wavg_regrouped_native(plan, x_full, size, frames: int, has_cls: bool = True, log_size: bool = False):
+    """`_abi.merge_wavg_regrouped(plan, x_full, size, frames)` for tokens that require grad."""
+    x_out, s_out, log = _MergeWavgRegroupedFunction.apply(x_full, size, plan, int(frames), bool(has_cls), bool(log_size))
+    return x_out, _with_log(s_out, log)
+
+
+def drop_regrouped_native(plan, x_full, frames: int, has_cls: bool = True):
+    """`_abi.drop_regrouped(plan, x_full, frames)` for tokens that require grad."""
+    return _DropRegroupedFunction.apply(x_full, plan, int(frames), bool(has_cls))
+
+
 _SCATTER_MODE = {"sum": "sum", "mean": "mean", "prod": "prod", "max": "amax", "amax": "amax", "min": "amin", "amin": "amin"}
 
 
@@ -176,6 +357,8 @@ def _make_merge_pair(plan: _abi.MatchPlan) -> Tuple[Callable, Callable]:
         # `merge.__closure__` introspection keeps working); the kernels read them through `plan`
         _closure = (unm_idx, src_idx, dst_idx, r, distill_token)  # noqa: F841
         if _wants_autograd(x):
+            if _covers("merge", plan, x, mode=mode):
+                return _MergeFunction.apply(x, plan, mode)
             return _merge_with_autograd(plan, x, mode)
         return _abi.merge(plan, x, mode)
 
@@ -184,6 +367,8 @@ def _make_merge_pair(plan: _abi.MatchPlan) -> Tuple[Callable, Callable]:
         if _wants_autograd(x):
             # (also with a distillation token: the reference's unmerge, merge.py:87-100, reads `x` as
             # [unmerged, destinations] whatever the layout `merge` wrote, and so does the kernel)
+            if _covers("unmerge", plan, x):
+                return _UnmergeFunction.apply(x, plan)
             return _unmerge_with_autograd(plan, x)
         return _abi.unmerge(plan, x)
 
@@ -212,6 +397,8 @@ def bipartite_soft_matching_drop(
     def drop(x: torch.Tensor) -> torch.Tensor:
         _closure = (und_idx, src_idx, r, distill_token)  # noqa: F841  (closure variables as in the reference)
         if _wants_autograd(x):
+            if _covers("drop", plan, x):
+                return _DropFunction.apply(x, plan)
             return _merge_with_autograd(plan, x, "sum", keep_sources=False)
         return _abi.drop(plan, x)
 
@@ -357,8 +544,16 @@ def merge_wavg(merge: Callable, x: torch.Tensor, size: Optional[torch.Tensor] = 
         if isinstance(plan, _abi.PartitionPlan):
             return _abi.merge_wavg_partition(plan, x, size, log_size=log_size)
         return _abi.merge_wavg(plan, x, size, log_size=log_size)
-    # foreign callables, do_nothing, and tensors that require grad (the closure then runs on the framework's
-    # differentiable ops): the reference's op sequence on the tensors' own device
+    if plan is not None and _covers("merge_wavg", plan, x, size=size) and _wants_autograd(x):
+        return merge_wavg_native(plan, x, size, log_size=log_size)
+    # foreign callables, do_nothing, and the tensors that require grad without being covered by the native Functions
+    # (the closure's index tensors then run on the framework's differentiable ops): the reference's op sequence on
+    # the tensors' own device
+    if isinstance(plan, _abi.MatchPlan):
+        closure = merge
+
+        def merge(t, mode):
+            return _merge_with_autograd(plan, t, mode) if _wants_autograd(t) else closure(t, mode=mode)
     if size is None:
         size = torch.ones_like(x[..., 0, None])
     x = merge(x * size, mode="sum")

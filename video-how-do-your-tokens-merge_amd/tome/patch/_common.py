@@ -417,13 +417,25 @@ def _training_tokens(x) -> bool:
     return torch.is_grad_enabled() and x.requires_grad
 
 
+def _native_regrouped(kind: str, x_full, size=None) -> bool:
+    """Tokens that require grad: does the regrouped reduction run as a native Function (tome/merge.py: the regrouped
+    kernel forward, tome_merge_backward_regrouped backward) instead of `_regrouped_by_views`?  Plain merge and drop
+    on 16-byte rows; the matching of these models has no distillation token and, here, no threshold."""
+    from .. import merge as tm
+    return (tm.native_backward_covers(kind, even_odd=True, on_device=x_full.is_cuda and x_full.dim() == 3,
+                                      dtype=x_full.dtype,
+                                      size_requires_grad=size is not None and _training_tokens(size))
+            and (x_full.shape[-1] * x_full.element_size()) % 16 == 0)
+
+
 def reduce_merge_regrouped(metric, x_full, info, r, frames, hybrid=False):
     """reduce_merge / reduce_hybrid for the models whose merge groups are interleaved in the token sequence
     (TimeSformer '(p t)', Motionformer '(s f)'): x_full is [B, 1 + P*F, C] with the class token in front; the
     kernel addresses the groups in place and returns [B, 1 + (P-r)*F, C] (no permuted copies of x)."""
     from .. import _abi
     from ..merge import do_nothing
-    if _training_tokens(x_full):
+    training = _training_tokens(x_full)
+    if training and (hybrid or info["trace_source"] or not _native_regrouped("merge_wavg", x_full, info["size"])):
         return _regrouped_by_views(reduce_hybrid if hybrid else reduce_merge, metric, x_full, info, r, frames)
     if hybrid:
         merge, _ = bipartite_soft_matching_hybrid(metric, r, info["class_token"], info["distill_token"], info["mode"],
@@ -436,8 +448,13 @@ def reduce_merge_regrouped(metric, x_full, info, r, frames, hybrid=False):
     if info["trace_source"]:
         shape_only = x_full.new_empty((plan.n, plan.T, 0))
         info["source"] = merge_source(merge, shape_only, info["source"])
-    x_out, info["size"] = _abi.merge_wavg_regrouped(plan, x_full, info["size"], frames, has_cls=True,
-                                                    log_size=info["prop_attn"])
+    if training:
+        from ..merge import merge_wavg_regrouped_native
+        x_out, info["size"] = merge_wavg_regrouped_native(plan, x_full, info["size"], frames, has_cls=True,
+                                                          log_size=info["prop_attn"])
+    else:
+        x_out, info["size"] = _abi.merge_wavg_regrouped(plan, x_full, info["size"], frames, has_cls=True,
+                                                        log_size=info["prop_attn"])
     if info["verbose"]:
         print(f"Merged {plan.T} to {plan.T - plan.r} tokens")
     return x_out
@@ -539,7 +556,8 @@ def reduce_drop_regrouped(metric, x_full, info, r, frames: int):
     are addressed in place by the kernel (tome_drop_regrouped) instead of regrouped by permuted copies
     (timesformer.py:111-131, motionformer.py:172-193)."""
     from .. import _abi
-    if _training_tokens(x_full):
+    training = _training_tokens(x_full)
+    if training and (info["trace_source"] or not _native_regrouped("drop", x_full)):
         return _regrouped_by_views(reduce_drop, metric, x_full, info, r, frames)
     drop = bipartite_soft_matching_drop(metric, r, info["class_token"], info["distill_token"], info["mode"])
     if isinstance(drop, tuple):
@@ -547,7 +565,11 @@ def reduce_drop_regrouped(metric, x_full, info, r, frames: int):
     plan = drop.plan
     if info["trace_source"]:
         info["source"] = _drop_source(drop, info["source"], plan.n, plan.T, x_full.device)
-    x_out = _abi.drop_regrouped(plan, x_full, frames, has_cls=True)
+    if training:
+        from ..merge import drop_regrouped_native
+        x_out = drop_regrouped_native(plan, x_full, frames, has_cls=True)
+    else:
+        x_out = _abi.drop_regrouped(plan, x_full, frames, has_cls=True)
     info["size"] = torch.ones((plan.n, plan.T - plan.r, 1), device=x_full.device)
     if info["verbose"]:
         print(f"Dropped {plan.T} to {plan.T - plan.r} tokens")
