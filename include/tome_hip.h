@@ -135,7 +135,8 @@ int tome_merge_wavg(const void *x, int x_dtype, const void *size, int size_dtype
  * `x = x + attn(norm1(x))` in front of the merge (videomae.py:20, vivit.py:35) is taken while loading and the
  * separate add pass disappears as well.
  * x_out_bias: NULL, or [C] of the token dtype: x_out is stored as round(x' + x_out_bias) while y_out stays
- * LayerNorm(x').  For callers that let the MLP's second GEMM accumulate onto x_out in place
+ * LayerNorm(x').  x' is the ROUNDED row, the x_out the same call stores without x_out_bias (the bias is added to the
+ * 16-bit value, and the LayerNorm reads that 16-bit value: both roundings are visible in x_out).  For callers that let the MLP's second GEMM accumulate onto x_out in place
  * (`x = x + self.mlp(self.norm2(x))`, videomae.py:29, as `x_out.addmm_(h, W2^T)`): that GEMM's bias is in the buffer
  * beforehand, and the block's second residual add is no pass of its own.
  */

@@ -505,3 +505,70 @@ def test_patched_model_trains_in_bf16_on_the_full_schedule(which, monkeypatch):
     grads = {k: q.grad for k, q in model.named_parameters()}
     assert not [k for k, q in grads.items() if q is not None and not torch.isfinite(q).all()]
     assert not [k for k, q in grads.items() if q is None and "blocks" in k and ("qkv" in k or "mlp" in k or "norm" in k)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# width sweep of k_merge_rows_bwd: the same rows-per-wave packing as the fused LayerNorm kernels (R rows of cpr 16-byte
+# chunks over the lanes of a wave, csrc/tome_kernels.hip launch_merge_bwd), at every width the fast path takes
+# ---------------------------------------------------------------------------------------------------------------------
+SWEEP_SHAPES = [(16, False), (17, False), (197, True)]
+
+
+def _sweep_widths(dtype):
+    """every multiple of the 16-byte vector up to the fast path's limit (6 chunks per lane * 64 lanes), one beyond it
+    and one that is no multiple (both run k_merge_rows_bwd_any)"""
+    vec = 16 // torch.empty((), dtype=dtype).element_size()
+    limit = 6 * 64 * vec
+    return list(range(vec, limit + 1, vec)) + [limit + vec, 12 * vec + 1]
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "bf16", "fp16"])
+def test_backward_at_every_width_of_the_fast_path(dtype):
+    """Upstream gradient = signature rows (tests/ln_oracle.py: every output row carries the mean of its class, rows
+    that share a wave differ by many standard deviations, so a chunk taken from the neighbouring row cannot pass),
+    T = 16, 17 and 197 with class token, r = 1 and r = clamp.  sum and drop: grad_in bit-equal to the gather of the
+    upstream gradient through the row map computed on the CPU from the plan's index tensors (dropped tokens: zero).
+    mean / merge_wavg: RTOL / ATOL above against the fp64 autograd of oracle/torch_port.py."""
+    import ln_oracle as lo
+    M, _abi, torch_port = _mods()
+    seed = 900
+    n = 2
+    for T, cls in SWEEP_SHAPES:
+        for r in (1, (T - int(cls)) // 2):
+            seed += 1
+            merge, _ = _matching(M, n, T, cls, False, r, seed)
+            drop = _matching(M, n, T, cls, False, r, seed, drop=True)
+            plan = merge.plan
+            tp = _cpu_plan(torch_port, plan)
+            row, _ = lo.merged_row_of_token(plan.src_idx, plan.dst_idx, plan.unm_idx, T)
+            drow, _ = lo.merged_row_of_token(drop.plan.src_idx, drop.plan.dst_idx, drop.plan.unm_idx, T)
+            dropped = torch.zeros(n, T, dtype=torch.bool)
+            dropped[torch.arange(n)[:, None], 2 * drop.plan.src_idx.cpu().reshape(n, -1)] = True
+            To = T - plan.r
+            size = torch.randint(1, 5, (n, T, 1), device=DEV, generator=_gen(seed)).to(dtype)
+            s64 = size.double().cpu()
+            for C in _sweep_widths(dtype):
+                tag = f"T={T} cls={cls} r={plan.r} C={C} {dtype}"
+                g = lo.signature_rows((n, To, C), torch.bfloat16, seed * 4096 + C, 1 if C % 16 else -1).to(dtype).to(DEV)
+                x = torch.randn(n, T, C, device=DEV, generator=_gen(seed + C)).to(dtype)
+                g64 = g.double().cpu()
+
+                def native(fn):
+                    xg = x.clone().requires_grad_(True)
+                    out = fn(xg)
+                    assert "Function" in type(out.grad_fn).__name__, (tag, out.grad_fn)
+                    out.backward(g)
+                    return xg.grad.cpu()
+
+                gcpu = g.cpu()
+                idx = torch.arange(n)[:, None]
+                assert torch.equal(native(lambda t: merge(t, mode="sum")), gcpu[idx, row]), (tag, "sum")
+                want = gcpu[idx, drow].masked_fill(dropped[:, :, None], 0.0)
+                assert torch.equal(native(drop), want), (tag, "drop")
+                x64 = x.double().cpu()
+                ref = _ref_grad(lambda t: torch_port.merge(tp, t, "mean"), x64, g64)
+                _assert_within(native(lambda t: merge(t, mode="mean")), ref, dtype, f"mean {tag}")
+                for sz, sz64 in ((None, None), (size, s64)):
+                    ref = _ref_grad(lambda t: torch_port.merge_wavg(tp, t, sz64)[0], x64, g64)
+                    _assert_within(native(lambda t: M.merge_wavg(merge, t, sz)[0]), ref, dtype,
+                                   f"merge_wavg size={'given' if sz is not None else None} {tag}")
