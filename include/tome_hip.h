@@ -317,6 +317,30 @@ int tome_merge_backward_regrouped(const void *grad_out, int x_dtype, const void 
                                   int size_dtype, int64_t B, int64_t F, int64_t P, int64_t C, int64_t r, int has_cls,
                                   const int32_t *row_map, int drop, void *grad_in, tome_stream_t stream);
 
+/*
+ * tome_layernorm_backward  <-  what autograd derives from the LayerNorms of the patched block when the tokens require
+ *     grad (additions to ABI v11, no entry changed; models are patched for training, tools/train_net.py:727-741):
+ *         self.norm1(x) / self.norm2(x)                        tome/patch/videomae.py:19,29
+ *         x = x + mlp(...); next block: self.norm1(x)          tome/patch/videomae.py:29,19
+ *         self.temporal_norm1(x)[:, 1:]                        tome/patch/timesformer.py:24-26   (skip_first)
+ *     i.e. the backward of tome_add_layernorm / tome_add_layernorm_skip_first.  With xs the STORED 16-bit rows the
+ *     forward normalised (its x_out, or its x when there was no addend), gw = gy * weight, xhat = (xs - mean) * rstd:
+ *         gx = gx_in + rstd * (gw - mean(gw) - xhat * mean(gw * xhat))              one rounding to `dtype`
+ *         dweight[c] = sum over rows of gy * xhat,   dbias[c] = sum over rows of gy  one rounding to `dtype`
+ *     mean and rstd are recomputed from xs with the forward's arithmetic: nothing is saved by the forward.  fp32
+ *     arithmetic, no atomics, every row written once, same bits on every run.
+ *     rows = groups * group_rows.  gy [rows, C], or with skip_first != 0 [groups * (group_rows - 1), C]: every group's
+ *     first row (a class token) has no row in gy, gets gx = gx_in (0 without gx_in) and adds nothing to dweight / dbias.
+ *     xs, gx [rows, C]; gx_in [rows, C] or NULL: the gradient that reaches xs through the residual stream.
+ *     weight, dweight, dbias [C] of `dtype` (16-bit, C <= 1024, C % 8 == 0); dweight / dbias may be NULL one by one; both
+ *     NULL (frozen LayerNorm): no parameter work at all and no workspace.  Otherwise workspace holds
+ *     tome_layernorm_backward_workspace_bytes(rows, C) bytes (fp32 partial rows [parts, 2, C]; 0 for an illegal shape).
+ */
+size_t tome_layernorm_backward_workspace_bytes(int64_t rows, int64_t C);
+int tome_layernorm_backward(const void *gy, const void *xs, const void *gx_in, int dtype, int64_t groups,
+                            int64_t group_rows, int skip_first, int64_t C, const void *weight, float eps, void *gx,
+                            void *dweight, void *dbias, void *workspace, tome_stream_t stream);
+
 /* tome_gelu_erf  <-  the activation of the MLP the patched block calls between merge and second residual
  * (`x = x + self.drop_path(self.mlp(self.norm2(x)))`, tome/patch/videomae.py:29, timesformer.py:56,
  * motionformer.py:29; the models' `act_layer=nn.GELU`): y = x * 0.5 * (1 + erf(x / sqrt(2))) on `elements` 16-bit

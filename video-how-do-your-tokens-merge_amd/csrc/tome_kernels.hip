@@ -2,9 +2,8 @@
 // C ABI declared in include/tome_hip.h.  Built with: hipcc --offload-arch=gfx950 -O3
 // -ffp-contract=off -shared -fPIC (csrc/build.py).  No torch, no CUDA, no portability layer.
 //
-// One translation unit: tome_common.h (types), tome_match.h, tome_merge.h, tome_merge_bwd.h and tome_partition.h
-// (kernels), this file
-// (host).
+// One translation unit: tome_common.h (types), tome_match.h, tome_merge.h, tome_merge_bwd.h, tome_ln_bwd.h and
+// tome_partition.h (kernels), this file (host).
 //
 // Launch sequence of one matching (tome_match / tome_match_keys), kernels in tome_match.h:
 //   k_unit_rows[_heads]  keys -> fp32 unit vectors, even/odd split, MFMA-fragment order (HBM bound)
@@ -19,6 +18,10 @@
 //   k_merge_rows / k_unmerge_rows   generic one-wave-per-row forms                        (HBM bound)
 // and of its backward (tome_merge_backward[_regrouped]), tome_merge_bwd.h:
 //   k_merge_rows_bwd     gx[t] = gy[row of t] / out_div * in_mul, streaming gather             (HBM bound)
+// and of the add + LayerNorm backward (tome_layernorm_backward), tome_ln_bwd.h:
+//   k_ln_rows_bwd        gx = gx_in + rstd (gw - mean gw - xhat mean(gw xhat)), statistics recomputed from the stored
+//                        rows; per-workgroup partial rows of dweight / dbias                    (HBM bound)
+//   k_ln_param_grad      the partial rows summed in a fixed order
 // The partition matchings (kth_ / random_bipartite_soft_matching: arbitrary source / destination sets, every source
 // merged) have their own sequence, written out at the top of tome_partition.h.
 //
@@ -39,6 +42,7 @@
 #include "tome_match_filter.h"
 #include "tome_merge.h"
 #include "tome_merge_bwd.h"
+#include "tome_ln_bwd.h"
 #include "tome_partition.h"
 #include "tome_attn.h"
 #include "tome_attn_stream.h"
@@ -761,6 +765,73 @@ extern "C" int tome_add_layernorm_regrouped(const void *x, const void *addend, i
                            (int)F, (int)P, (int)C, R, (int)cpr, ln, (TX *)x_out);
         return check_launch("k_add_ln_regroup");
     }, [&] { return fail(TOME_EINVAL, "tome_add_layernorm_regrouped: 16-bit tokens only"); });
+}
+
+// The launch form of k_ln_rows_bwd for `rows` rows of C channels: R rows per wave as add_layernorm_impl picks them,
+// and -- when the parameter gradients are wanted -- how many slabs every wave of a workgroup walks (spw) and how many
+// workgroups (= partial rows of the workspace) that makes.  At most LN_BWD_MAX_PARTS workgroups: two per CU at
+// the kernel's register count (206-209 VGPRs with the 48 column sums), so every workgroup is resident from the start
+// and all of them end together.
+#define LN_BWD_MAX_PARTS 512
+struct LnBwdForm { int R; int64_t wgs; int64_t spw; int64_t parts; };
+static LnBwdForm ln_bwd_form(int64_t rows, int64_t C) {
+    const int64_t cpr = C / 8;
+    int R = (int)((3 * WAVE) / cpr);
+    if (R > FAST_MAXR) R = FAST_MAXR;
+    const int64_t waves = (rows + R - 1) / R;
+    const int64_t wgs = (waves + 3) / 4;
+    const int64_t spw = (wgs + LN_BWD_MAX_PARTS - 1) / LN_BWD_MAX_PARTS;
+    return LnBwdForm{R, wgs, spw, (wgs + spw - 1) / spw};
+}
+
+static bool ln_bwd_shape_ok(int64_t rows, int64_t C) {
+    return rows > 0 && rows <= 0x7fffffffLL && C > 0 && C % 8 == 0 && C / 8 <= 2 * WAVE;
+}
+
+extern "C" size_t tome_layernorm_backward_workspace_bytes(int64_t rows, int64_t C) {
+    if (!ln_bwd_shape_ok(rows, C)) return 0;
+    return align_up((size_t)ln_bwd_form(rows, C).parts * 2 * (size_t)C * sizeof(float), 256);
+}
+
+extern "C" int tome_layernorm_backward(const void *gy, const void *xs, const void *gx_in, int dtype, int64_t groups,
+                                       int64_t group_rows, int skip_first, int64_t C, const void *weight, float eps,
+                                       void *gx, void *dweight, void *dbias, void *workspace, tome_stream_t stream) {
+    if (!gy || !xs || !weight || !gx) return fail(TOME_EINVAL, "tome_layernorm_backward: null buffer");
+    if (dtype != TOME_BF16 && dtype != TOME_F16) return fail(TOME_EINVAL, "tome_layernorm_backward: 16-bit tokens only");
+    if (groups <= 0 || group_rows <= 0 || group_rows > 0x7fffffffLL || groups > 0x7fffffffLL ||
+        !ln_bwd_shape_ok(groups * group_rows, C))
+        return fail(TOME_EINVAL, "tome_layernorm_backward: C %% 8 == 0, C <= 1024 and 1 .. 2^31 - 1 rows required");
+    if (skip_first && group_rows < 2)
+        return fail(TOME_EINVAL, "tome_layernorm_backward: skip_first needs groups of at least two rows");
+    if (!aligned16(gy) || !aligned16(xs) || !aligned16(gx_in) || !aligned16(weight) || !aligned16(gx) ||
+        !aligned16(workspace))
+        return fail(TOME_EINVAL, "tome_layernorm_backward: 16-byte aligned buffers required");
+    const bool params = dweight || dbias;
+    if (params && !workspace)
+        return fail(TOME_EWORKSPACE, "tome_layernorm_backward: parameter gradients need a workspace of "
+                                     "tome_layernorm_backward_workspace_bytes()");
+    const int64_t rows = groups * group_rows, cpr = C / 8;
+    const int64_t gy_rows = skip_first ? groups * (group_rows - 1) : rows;
+    const LnBwdForm f = ln_bwd_form(rows, C);
+    hipStream_t st = (hipStream_t)stream;
+    return dispatch_x<false>(dtype, [&](auto tx) {
+        using TX = typename decltype(tx)::type;
+        if (params) {
+            hipLaunchKernelGGL((k_ln_rows_bwd<TX, 3, true>), dim3((unsigned)f.parts), dim3(256), 0, st, (const TX *)gy,
+                               (const TX *)xs, (const TX *)gx_in, (const TX *)weight, (int)rows, (int)gy_rows, (int)C, f.R,
+                               (int)cpr, eps, skip_first ? (int)group_rows : 0, (int)f.spw, (TX *)gx, (float *)workspace);
+            if (int rc = check_launch("k_ln_rows_bwd")) return rc;
+            hipLaunchKernelGGL((k_ln_param_grad<TX>), dim3((unsigned)((2 * C + WAVE - 1) / WAVE)),
+                               dim3(LN_PG_RUNS * WAVE), 0, st, (const float *)workspace, (int)f.parts, (int)C,
+                               (TX *)dweight, (TX *)dbias);
+            return check_launch("k_ln_param_grad");
+        }
+        // frozen LayerNorm: one slab per wave, no column sums, no workspace
+        hipLaunchKernelGGL((k_ln_rows_bwd<TX, 3, false>), dim3((unsigned)f.wgs), dim3(256), 0, st, (const TX *)gy,
+                           (const TX *)xs, (const TX *)gx_in, (const TX *)weight, (int)rows, (int)gy_rows, (int)C, f.R,
+                           (int)cpr, eps, skip_first ? (int)group_rows : 0, 1, (TX *)gx, (float *)nullptr);
+        return check_launch("k_ln_rows_bwd");
+    }, [&] { return fail(TOME_EINVAL, "tome_layernorm_backward: 16-bit tokens only"); });
 }
 
 extern "C" int tome_merge(const void *x, int dtype, int64_t n, int64_t T, int64_t C, int64_t r,

@@ -24,7 +24,10 @@ SYMBOLS = (
     "tome_unmerge", "tome_merge_backward", "tome_merge_backward_regrouped", "tome_row_map", "tome_source_init", "tome_gelu_erf", "tome_tubelet_rows",
     "tome_partition_workspace_bytes", "tome_match_partition", "tome_merge_partition", "tome_merge_wavg_partition",
     "tome_unmerge_partition",
+    "tome_layernorm_backward_workspace_bytes", "tome_layernorm_backward",
 )
+# entries added to ABI v11 after its first release: a v11 library built before them binds, and says so when one is called
+_LATER_V11 = ("tome_layernorm_backward_workspace_bytes", "tome_layernorm_backward")
 
 ABI_VERSION = 11
 DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
@@ -131,9 +134,30 @@ def bind(path: str) -> ctypes.CDLL:
                                             vp]
     L.tome_unmerge_partition.restype = i32
     L.tome_unmerge_partition.argtypes = [vp, i32, i64, i64, i64, i64, vp, vp, i64, i64, vp, vp, vp]
+    if all(_exports(L, name) for name in _LATER_V11):
+        L.tome_layernorm_backward_workspace_bytes.restype = sz
+        L.tome_layernorm_backward_workspace_bytes.argtypes = [i64, i64]
+        L.tome_layernorm_backward.restype = i32
+        L.tome_layernorm_backward.argtypes = [vp, vp, vp, i32, i64, i64, i32, i64, vp, ctypes.c_float, vp, vp, vp, vp, vp]
     if L.tome_abi_version() != ABI_VERSION:
         raise TomeHipError(f"{os.path.basename(path)} ABI {L.tome_abi_version()} != expected {ABI_VERSION}")
     return L
+
+
+def _exports(L, name: str) -> bool:
+    try:
+        getattr(L, name)
+    except AttributeError:
+        return False
+    return True
+
+
+def require_symbol(L, name: str):
+    """`L.name`, or a TomeHipError that says the library predates the entry (ABI v11 grew by entries, not by number)."""
+    if not _exports(L, name):
+        raise TomeHipError(f"{name} is missing from the loaded library: it reports ABI {ABI_VERSION} but was built before "
+                           "this entry was added; rebuild it with `python video-how-do-your-tokens-merge_amd/csrc/build.py`")
+    return getattr(L, name)
 
 
 def _check(rc: int, what: str) -> None:
@@ -403,6 +427,16 @@ def ln_fusable(x: torch.Tensor, norm) -> bool:
             and tuple(norm.normalized_shape) == (C,) and x.dtype in (torch.bfloat16, torch.float16)
             and norm.weight.dtype == x.dtype and C % 8 == 0 and C <= 1024 and x.is_cuda
             and not (torch.is_grad_enabled() and (x.requires_grad or norm.weight.requires_grad)))
+
+
+def ln_trainable(x: torch.Tensor, norm) -> bool:
+    """ln_fusable without its grad clause: can this LayerNorm of x run on the add + LayerNorm kernels with
+    tome_layernorm_backward behind them (tome/_ln.py) when x or its parameters require grad?  The stock module only: a
+    subclass may carry a forward of its own, which a training run must keep."""
+    C = x.shape[-1]
+    return (type(norm) is torch.nn.LayerNorm and norm.elementwise_affine and norm.bias is not None
+            and tuple(norm.normalized_shape) == (C,) and x.dtype in (torch.bfloat16, torch.float16)
+            and norm.weight.dtype == x.dtype and norm.bias.dtype == x.dtype and C % 8 == 0 and C <= 1024 and x.is_cuda)
 
 
 def _out_bias(out_bias, x, C):
@@ -964,6 +998,54 @@ def merge_backward_regrouped(plan: MatchPlan, grad_out: torch.Tensor, frames: in
                                                  _stream(g.device))
     _check(rc, "tome_merge_backward_regrouped")
     return gx
+
+
+def layernorm_backward(gy: torch.Tensor, xs: torch.Tensor, gx_in: Optional[torch.Tensor], weight: torch.Tensor,
+                       eps: float, skip_first: bool = False, want_weight: bool = True, want_bias: bool = True):
+    """tome_layernorm_backward: the gradient of y = LayerNorm(xs) (and of the residual stream through xs) for the
+    stored 16-bit rows xs [..., C] the forward kernels normalised.  gy: gradient of y, xs's shape -- or, skip_first
+    (xs [B, N, C]), [B, N-1, C]: every clip's first row has no row in y.  gx_in: optional gradient that reaches xs
+    directly, xs's shape.  Returns (gx, dweight, dbias); a gradient that is not wanted is None.  No CPU path."""
+    require_device(xs, "layernorm_backward(xs)")
+    if xs.dtype not in (torch.bfloat16, torch.float16):
+        raise TomeHipError(f"layernorm_backward: 16-bit tokens only, got {xs.dtype}")
+    C = xs.shape[-1]
+    if xs.dim() < 2 or C % 8 or C > 1024 or xs.numel() == 0:
+        raise TomeHipError(f"layernorm_backward: xs must be [..., C] with C % 8 == 0 and C <= 1024, got {tuple(xs.shape)}")
+    if skip_first:
+        if xs.dim() != 3 or xs.shape[1] < 2:
+            raise TomeHipError("layernorm_backward(skip_first): xs must be [B, N >= 2, C]")
+        groups, group_rows = xs.shape[0], xs.shape[1]
+        gy_shape = (groups, group_rows - 1, C)
+    else:
+        groups, group_rows = xs.numel() // C, 1
+        gy_shape = tuple(xs.shape)
+    if weight.numel() != C or weight.dtype != xs.dtype or weight.device != xs.device:
+        raise TomeHipError(f"layernorm_backward: weight must hold {C} values of {xs.dtype} on {xs.device}")
+    gy = _prep_grad(gy, gy_shape, xs.dtype, xs.device, "layernorm_backward(gy)")
+    if gx_in is not None:
+        gx_in = _prep_grad(gx_in, tuple(xs.shape), xs.dtype, xs.device, "layernorm_backward(gx_in)")
+    xs = xs.detach()
+    xs = xs if xs.is_contiguous() else xs.contiguous()
+    weight = weight.detach().contiguous()
+    L = lib()
+    entry = require_symbol(L, "tome_layernorm_backward")
+    gx = torch.empty_like(xs)
+    dweight = torch.empty(C, dtype=xs.dtype, device=xs.device) if want_weight else None
+    dbias = torch.empty(C, dtype=xs.dtype, device=xs.device) if want_bias else None
+    with _on_device(xs.device):
+        stream = _stream(xs.device)
+        ws = None
+        if want_weight or want_bias:
+            nbytes = require_symbol(L, "tome_layernorm_backward_workspace_bytes")(groups * group_rows, C)
+            if nbytes == 0:
+                raise TomeHipError(f"layernorm_backward: no workspace size for {groups * group_rows} rows of {C}")
+            ws = _workspace(xs.device, stream, nbytes)
+        rc = entry(gy.data_ptr(), xs.data_ptr(), _ptr(gx_in), dtype_code(xs, "xs"), groups, group_rows,
+                   int(bool(skip_first)), C, weight.data_ptr(), float(eps), gx.data_ptr(), _ptr(dweight), _ptr(dbias),
+                   _ptr(ws), stream)
+    _check(rc, "tome_layernorm_backward")
+    return gx, dweight, dbias
 
 
 def source_init(plan: MatchPlan, drop: bool = False) -> torch.Tensor:

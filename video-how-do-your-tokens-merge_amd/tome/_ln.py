@@ -1,0 +1,110 @@
+"""The LayerNorms of the patched blocks for tokens that require grad (models are patched for training,
+tools/train_net.py:727-741): forward = the inference kernels (tome_add_layernorm / tome_add_layernorm_skip_first) on the
+detached tensors, backward = tome_layernorm_backward (csrc/tome_ln_bwd.h).
+
+    add_layernorm_native(x, addend, norm, skip_first=False) -> (x + addend, norm(x + addend))
+    layernorm_native(x, norm, skip_first=False)             -> norm(x)
+
+skip_first (x [B, N, C]): the LayerNorm output leaves out every clip's first row, as `_abi.add_layernorm` does.
+The backward recomputes mean and rstd from the stored sum (the row the forward normalised), so the forward saves
+nothing but the tensors it returns anyway.  The gradient of the sum that arrives through the residual stream and the
+gradient through the LayerNorm are added inside the one launch and rounded once; x and addend receive the same
+tensor.  Not covered (they keep the framework's ops: DESIGN.md section 7): fp32 tokens, LayerNorms `_abi.ln_trainable`
+refuses, double backward (raises).
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _abi
+
+# False: the callers in tome/patch/_common.py take the framework's `x + a`, `norm(x)` and autograd (the behaviour before
+# the backward kernel existed) -- for A/B in tests and tools/layernorm_backward_bench.py.  Also off when
+# tome.merge.NATIVE_BACKWARD is off.  On by default; what that rests on (measured or not) is said in DESIGN.md section 1.
+NATIVE_LN_BACKWARD = True
+
+
+def enabled() -> bool:
+    from . import merge
+    return bool(NATIVE_LN_BACKWARD and merge.NATIVE_BACKWARD)
+
+
+def wants(x: torch.Tensor, norm, *others) -> bool:
+    """Do the tokens require grad, and does this LayerNorm of them run on the native Functions?"""
+    return (torch.is_grad_enabled() and (x.requires_grad or any(t is not None and t.requires_grad for t in others))
+            and enabled() and _abi.ln_trainable(x, norm))
+
+
+def ln_backward(gy, xs, gx_in, weight, eps, skip_first, want_weight, want_bias):
+    """The backward arithmetic of both Functions: (gx, dweight, dbias) from the saved tensors.  One module-level seam, so
+    that a test can put another evaluation of the same formula in its place."""
+    return _abi.layernorm_backward(gy, xs, gx_in, weight, eps, skip_first=skip_first, want_weight=want_weight,
+                                   want_bias=want_bias)
+
+
+def _backward(ctx, g_sum, g_y):
+    xs, weight = ctx.saved_tensors
+    want_x = ctx.needs_x
+    want_w, want_b = ctx.needs_input_grad[ctx.first_param], ctx.needs_input_grad[ctx.first_param + 1]
+    if g_y is None:  # nothing read the LayerNorm: the stream's gradient passes through, the parameters get zeros
+        gx = g_sum if want_x else None
+        return gx, (torch.zeros_like(weight) if want_w else None), (torch.zeros_like(weight) if want_b else None)
+    cast = lambda g: g if g is None or g.dtype == xs.dtype else g.to(xs.dtype)  # noqa: E731
+    gx, dw, db = ln_backward(cast(g_y), xs, cast(g_sum), weight, ctx.eps, ctx.skip_first, want_w, want_b)
+    return (gx if want_x else None), dw, db
+
+
+class _AddLayerNormFunction(torch.autograd.Function):
+    """(x + addend, LayerNorm(x + addend)): tome_add_layernorm[_skip_first] forward, tome_layernorm_backward backward."""
+
+    @staticmethod
+    def forward(ctx, x, addend, weight, bias, eps, skip_first):
+        x_out, y = _abi.add_layernorm(x.detach(), addend.detach(), weight.detach(), bias.detach(), eps,
+                                      skip_first=skip_first)
+        ctx.eps, ctx.skip_first, ctx.first_param = float(eps), bool(skip_first), 2
+        ctx.needs_x = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        ctx.save_for_backward(x_out, weight)
+        ctx.set_materialize_grads(False)  # an output nobody read arrives as None, not as a tensor of zeros
+        return x_out, y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_sum, g_y):
+        gx, dw, db = _backward(ctx, g_sum, g_y)
+        return (gx if ctx.needs_input_grad[0] else None), (gx if ctx.needs_input_grad[1] else None), dw, db, None, None
+
+
+class _LayerNormFunction(torch.autograd.Function):
+    """LayerNorm(x) alone: tome_add_layernorm[_skip_first] without addend forward, tome_layernorm_backward backward."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps, skip_first):
+        xs, y = _abi.add_layernorm(x.detach(), None, weight.detach(), bias.detach(), eps, skip_first=skip_first)
+        ctx.eps, ctx.skip_first, ctx.first_param = float(eps), bool(skip_first), 1
+        ctx.needs_x = ctx.needs_input_grad[0]
+        ctx.save_for_backward(xs, weight)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_y):
+        gx, dw, db = _backward(ctx, None, g_y)
+        return gx, dw, db, None, None
+
+
+def _check(x, norm, what):
+    if not _abi.ln_trainable(x, norm):
+        raise _abi.TomeHipError(f"{what}: this LayerNorm of {tuple(x.shape)} {x.dtype} tokens is not one the kernels take "
+                                "(_abi.ln_trainable)")
+
+
+def add_layernorm_native(x, addend, norm, skip_first: bool = False):
+    """`x = x + addend; y = norm(x)` (y without every clip's first row when skip_first) for tokens that require grad."""
+    _check(x, norm, "add_layernorm_native")
+    return _AddLayerNormFunction.apply(x, addend, norm.weight, norm.bias, norm.eps, bool(skip_first))
+
+
+def layernorm_native(x, norm, skip_first: bool = False):
+    """`norm(x)` (`norm(x)[:, 1:]` when skip_first) for tokens that require grad."""
+    _check(x, norm, "layernorm_native")
+    return _LayerNormFunction.apply(x, norm.weight, norm.bias, norm.eps, bool(skip_first))

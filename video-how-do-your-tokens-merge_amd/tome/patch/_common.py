@@ -12,7 +12,7 @@ from typing import Callable, Dict, Tuple
 
 import torch
 
-from .. import _overlap
+from .. import _ln, _overlap
 from ..merge import (bipartite_soft_matching, bipartite_soft_matching_drop, bipartite_soft_matching_hybrid,
                      merge_source, merge_wavg)
 from ..utils import parse_r
@@ -325,6 +325,11 @@ def first_norm(block, x, info, norm, skip_first: bool = False):
         skip = skip_first and x.dim() == 3 and x.shape[1] >= 2
         y = _abi.add_layernorm(x, None, norm.weight, norm.bias, norm.eps, skip_first=skip)[1]
         return y[:, 1:, :] if (skip_first and not skip) else y
+    if _FUSE_NEXT and _ln.wants(x, norm):
+        # tokens that require grad: the same launch as a Function with tome_layernorm_backward behind it (tome/_ln.py)
+        skip = skip_first and x.dim() == 3 and x.shape[1] >= 2
+        y = _ln.layernorm_native(x, norm, skip_first=skip)
+        return y[:, 1:, :] if (skip_first and not skip) else y
     return norm(x)[:, 1:, :] if skip_first else norm(x)
 
 
@@ -336,6 +341,12 @@ def finish_block(block, x, residual, info):
     if _FUSE_NEXT and nxt is not None and residual.dtype == x.dtype and _abi.ln_fusable(x, nxt):
         skip = bool(getattr(block, "_tome_next_skip_first", False)) and x.dim() == 3 and x.shape[1] >= 2
         x, h = _abi.add_layernorm(x, residual, nxt.weight, nxt.bias, nxt.eps, skip_first=skip)
+        info["_prenorm"] = (x, h, nxt, skip)
+        return x
+    if _FUSE_NEXT and nxt is not None and residual.dtype == x.dtype and _ln.wants(x, nxt, residual):
+        # tokens that require grad: sum and next norm in the one forward launch, one backward launch for both gradients
+        skip = bool(getattr(block, "_tome_next_skip_first", False)) and x.dim() == 3 and x.shape[1] >= 2
+        x, h = _ln.add_layernorm_native(x, residual, nxt, skip_first=skip)
         info["_prenorm"] = (x, h, nxt, skip)
         return x
     return x + residual
@@ -358,6 +369,15 @@ def finish_linear(block, x, h, linear, info):
         _, hn = _abi.add_layernorm(x, None, nxt.weight, nxt.bias, nxt.eps, skip_first=skip)
         info["_prenorm"] = (x, hn, nxt, skip)
     return x
+
+
+def _trailing_norm(x, norm):
+    """norm(x) behind a reduction step that ran on its own.  Tokens that require grad: the streaming LayerNorm kernel as
+    a Function (tome/_ln.py); the merge in front of it stays merge_wavg_native / merge_wavg_regrouped_native -- the
+    fused merge + LayerNorm launch is inference-only."""
+    if _FUSE_LN and _ln.wants(x, norm):
+        return _ln.layernorm_native(x, norm)
+    return norm(x)
 
 
 def merge_then_norm(metric, x, info, norm, reduction_function, plain_merge_fn, residual=None, fold=None):
@@ -397,7 +417,7 @@ def merge_then_norm(metric, x, info, norm, reduction_function, plain_merge_fn, r
             print(f"Merged {before} to {x.size(1)} tokens")
         return x, y
     x = reduction_function(metric, x, info)
-    return x, norm(x)
+    return x, _trailing_norm(x, norm)
 
 
 def _regrouped_by_views(reduce_grouped, metric, x_full, info, r, frames):
@@ -499,7 +519,7 @@ def merge_then_norm_regrouped(metric, x_full, info, norm, unfused_reduce, is_pla
         if residual is not None:
             x_full = x_full + residual
         x_full = unfused_reduce(x_full)
-        return x_full, norm(x_full)
+        return x_full, _trailing_norm(x_full, norm)
     if grouped is None and residual is not None and (not _FUSE_ADD or residual.dtype != x_full.dtype):
         x_full = x_full + residual
         residual = None
