@@ -341,6 +341,35 @@ int tome_layernorm_backward(const void *gy, const void *xs, const void *gx_in, i
                             int64_t group_rows, int skip_first, int64_t C, const void *weight, float eps, void *gx,
                             void *dweight, void *dbias, void *workspace, tome_stream_t stream);
 
+/*
+ * tome_prop_attention_backward  <-  what autograd derives from the proportional attention of the patched blocks when
+ *     q, k or v require grad (additions to ABI v11, no entry changed; models are patched for training,
+ *     tools/train_net.py:727-741):
+ *         attn = softmax(q k^T * scale + log(size)); x = attn @ v      tome/patch/videomae.py:55-66, vivit.py:95-113
+ *         the same with the bias on the non-class block only           tome/patch/timesformer.py:66-78  (bias_skip)
+ *     i.e. the backward of tome_prop_attention (its plain form; the segmented form has none).  With P the softmax and
+ *     O = out the forward's stored 16-bit result:
+ *         dV = P^T dO,  delta = rowsum(dO o O),  dS = P o (dO V^T - delta),  dQ = scale dS K,  dK = scale dS^T Q
+ *     size gets no gradient.  The forward saves nothing: P is recomputed with the forward's definition of the logits
+ *     (q * scale * log2 e rounded once to the 16-bit format, bias in log2 units, exp2).  fp32 softmax and accumulation,
+ *     P and dS enter the matrix products in the 16-bit format, one rounding per output.  Two launches, no atomics,
+ *     every row of dq, dk, dv written once, same bits on every run; no allocation, no synchronisation.
+ *     q, out, dout, dq: [B, H, N, 64]; k, v, dk, dv: [B, H, Nk, 64]; each with element strides {batch, head, token}
+ *     (multiples of 8, contiguous channels, 16-byte aligned base) -- the three slices of one [B, N, 3, H, 64] buffer
+ *     are a legal source and a legal target; only the 64 channels of every row are written.  log_size as in
+ *     tome_prop_attention (NULL: no bias; bias_skip needs N == Nk).  workspace: 16-byte aligned,
+ *     tome_prop_attention_backward_workspace_bytes(B, H, N, Nk) bytes (fp32 row statistics; 0 for an illegal shape);
+ *     NULL or workspace_bytes below that: TOME_EWORKSPACE.  Head dim 64 and TOME_BF16 / TOME_F16 only.
+ */
+size_t tome_prop_attention_backward_workspace_bytes(int64_t B, int64_t H, int64_t N, int64_t Nk);
+int tome_prop_attention_backward(const void *q, const void *k, const void *v, const void *out, const void *dout,
+                                 int dtype, int64_t B, int64_t H, int64_t N, int64_t Nk, int64_t D,
+                                 const int64_t *q_strides, const int64_t *k_strides, const int64_t *v_strides,
+                                 const int64_t *out_strides, const int64_t *dout_strides, const float *log_size,
+                                 int64_t log_size_stride, int bias_skip, float scale, void *dq, void *dk, void *dv,
+                                 const int64_t *dq_strides, const int64_t *dk_strides, const int64_t *dv_strides,
+                                 void *workspace, size_t workspace_bytes, tome_stream_t stream);
+
 /* tome_gelu_erf  <-  the activation of the MLP the patched block calls between merge and second residual
  * (`x = x + self.drop_path(self.mlp(self.norm2(x)))`, tome/patch/videomae.py:29, timesformer.py:56,
  * motionformer.py:29; the models' `act_layer=nn.GELU`): y = x * 0.5 * (1 + erf(x / sqrt(2))) on `elements` 16-bit

@@ -22,6 +22,9 @@
 //   k_ln_rows_bwd        gx = gx_in + rstd (gw - mean gw - xhat mean(gw xhat)), statistics recomputed from the stored
 //                        rows; per-workgroup partial rows of dweight / dbias                    (HBM bound)
 //   k_ln_param_grad      the partial rows summed in a fixed order
+// and of the proportional attention's backward (tome_prop_attention_backward), tome_attn_bwd.h:
+//   k_attn_bwd_dq        row statistics recomputed (two sweeps over the keys), dq, L and delta to the workspace
+//   k_attn_bwd_dkv       dk and dv per block of keys over all queries                          (MFMA bound)
 // The partition matchings (kth_ / random_bipartite_soft_matching: arbitrary source / destination sets, every source
 // merged) have their own sequence, written out at the top of tome_partition.h.
 //
@@ -47,6 +50,7 @@
 #include "tome_attn.h"
 #include "tome_attn_stream.h"
 #include "tome_attn_resident.h"
+#include "tome_attn_bwd.h"
 #include "tome_embed.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -1075,6 +1079,75 @@ extern "C" int tome_trajectory_mix(const void *q2, const void *k2, const void *v
                            (const f16_t *)val, rows, (int)S, (int)F, (int)H, k_row_stride, v_row_stride, scale,
                            (f16_t *)out, out_batch_stride, tattn);
     return check_launch("k_trajectory_mix");
+}
+
+// ---- backward of tome_prop_attention's plain form (tome_attn_bwd.h)
+static bool attn_bwd_shape_ok(int64_t B, int64_t H, int64_t N, int64_t Nk) {
+    return B > 0 && H > 0 && N > 0 && Nk > 0 && B * H <= 0x7fffffffLL / 64 && N <= 0x7fffffffLL / 4 &&
+           Nk <= 0x7fffffffLL / 4 && B * H * N <= (1ll << 40);
+}
+
+extern "C" size_t tome_prop_attention_backward_workspace_bytes(int64_t B, int64_t H, int64_t N, int64_t Nk) {
+    if (!attn_bwd_shape_ok(B, H, N, Nk)) return 0;
+    return align_up(2 * (size_t)(B * H * N) * sizeof(float), 256);  // L and delta, one fp32 each per query row
+}
+
+extern "C" int tome_prop_attention_backward(const void *q, const void *k, const void *v, const void *out,
+                                            const void *dout, int dtype, int64_t B, int64_t H, int64_t N, int64_t Nk,
+                                            int64_t D, const int64_t *q_strides, const int64_t *k_strides,
+                                            const int64_t *v_strides, const int64_t *out_strides,
+                                            const int64_t *dout_strides, const float *log_size,
+                                            int64_t log_size_stride, int bias_skip, float scale, void *dq, void *dk,
+                                            void *dv, const int64_t *dq_strides, const int64_t *dk_strides,
+                                            const int64_t *dv_strides, void *workspace, size_t workspace_bytes,
+                                            tome_stream_t stream) {
+    const char *const fn = "tome_prop_attention_backward";
+    if (!q || !k || !v || !out || !dout || !dq || !dk || !dv || !q_strides || !k_strides || !v_strides || !out_strides ||
+        !dout_strides || !dq_strides || !dk_strides || !dv_strides || !attn_bwd_shape_ok(B, H, N, Nk))
+        return fail(TOME_EINVAL, "%s: bad shape/pointer", fn);
+    if (D != ATT_D) return fail(TOME_EINVAL, "%s: head dim %lld (only 64)", fn, (long long)D);
+    if (dtype != TOME_BF16 && dtype != TOME_F16) return fail(TOME_EINVAL, "%s: 16-bit q/k/v only", fn);
+    if (bias_skip != 0 && bias_skip != 1) return fail(TOME_EINVAL, "%s: bias_skip %d", fn, bias_skip);
+    if (bias_skip && N != Nk) return fail(TOME_EINVAL, "%s: bias_skip needs as many keys as queries", fn);
+    const int64_t *ss[8] = {q_strides, k_strides, v_strides, out_strides, dout_strides, dq_strides, dk_strides, dv_strides};
+    const void *pp[8] = {q, k, v, out, dout, dq, dk, dv};
+    for (int i = 0; i < 8; ++i) {
+        if (!aligned16(pp[i]) || ss[i][0] % 8 || ss[i][1] % 8 || ss[i][2] % 8 || ss[i][2] < D)
+            return fail(TOME_EINVAL, "%s: rows must be 16-byte aligned (pointers, strides %% 8 == 0, token stride >= 64)", fn);
+    }
+    const size_t need = tome_prop_attention_backward_workspace_bytes(B, H, N, Nk);
+    if (!workspace || workspace_bytes < need)
+        return fail(TOME_EWORKSPACE, "%s: workspace %zu < %zu bytes", fn, workspace ? workspace_bytes : (size_t)0, need);
+    if (!aligned16(workspace)) return fail(TOME_EINVAL, "%s: workspace not 16-byte aligned", fn);
+    AttnBwdArgs a;
+    a.q = q; a.k = k; a.v = v; a.o = out; a.dout = dout; a.dq = dq; a.dk = dk; a.dv = dv;
+    a.q_sb = q_strides[0]; a.q_sh = q_strides[1]; a.q_sn = q_strides[2];
+    a.k_sb = k_strides[0]; a.k_sh = k_strides[1]; a.k_sn = k_strides[2];
+    a.v_sb = v_strides[0]; a.v_sh = v_strides[1]; a.v_sn = v_strides[2];
+    a.o_sb = out_strides[0]; a.o_sh = out_strides[1]; a.o_sn = out_strides[2];
+    a.do_sb = dout_strides[0]; a.do_sh = dout_strides[1]; a.do_sn = dout_strides[2];
+    a.dq_sb = dq_strides[0]; a.dq_sh = dq_strides[1]; a.dq_sn = dq_strides[2];
+    a.dk_sb = dk_strides[0]; a.dk_sh = dk_strides[1]; a.dk_sn = dk_strides[2];
+    a.dv_sb = dv_strides[0]; a.dv_sh = dv_strides[1]; a.dv_sn = dv_strides[2];
+    a.log_size = log_size; a.ls_sb = log_size_stride;
+    a.lse = (float *)workspace; a.delta = (float *)workspace + B * H * N;
+    a.B = (int)B; a.H = (int)H; a.N = (int)N; a.Nk = (int)Nk; a.scale = scale; a.bias_skip = bias_skip;
+    const int64_t bh8 = (B * H + 7) / 8 * 8;
+    const int64_t qblocks = (N + ATTB_BM - 1) / ATTB_BM, kblocks = (Nk + ATTB_BM - 1) / ATTB_BM;
+    if (bh8 * qblocks > 0x7fffffffLL || bh8 * kblocks > 0x7fffffffLL) return fail(TOME_EINVAL, "%s: grid too large", fn);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 qgrid((unsigned)(bh8 * qblocks)), kgrid((unsigned)(bh8 * kblocks)), block(64 * ATTB_WAVES);
+    auto go = [&](auto tx, auto bias) {
+        using TX = typename decltype(tx)::type;
+        constexpr bool BIAS = decltype(bias)::value != 0;
+        hipLaunchKernelGGL((k_attn_bwd_dq<TX, BIAS>), qgrid, block, 0, st, a);
+        if (int rc = check_launch("k_attn_bwd_dq")) return rc;
+        hipLaunchKernelGGL((k_attn_bwd_dkv<TX, BIAS>), kgrid, block, 0, st, a);
+        return check_launch("k_attn_bwd_dkv");
+    };
+    return dispatch_x<false>(dtype, [&](auto tx) {
+        return log_size ? go(tx, AttInt<1>{}) : go(tx, AttInt<0>{});
+    }, [&] { return fail(TOME_EINVAL, "%s: 16-bit q/k/v only", fn); });
 }
 
 extern "C" int tome_short_attention(const void *q, const void *k, const void *v, int dtype, int64_t B, int64_t H,

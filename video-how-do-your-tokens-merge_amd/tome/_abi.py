@@ -25,9 +25,11 @@ SYMBOLS = (
     "tome_partition_workspace_bytes", "tome_match_partition", "tome_merge_partition", "tome_merge_wavg_partition",
     "tome_unmerge_partition",
     "tome_layernorm_backward_workspace_bytes", "tome_layernorm_backward",
+    "tome_prop_attention_backward_workspace_bytes", "tome_prop_attention_backward",
 )
 # entries added to ABI v11 after its first release: a v11 library built before them binds, and says so when one is called
 _LATER_V11 = ("tome_layernorm_backward_workspace_bytes", "tome_layernorm_backward")
+_LATER_V11_ATTN = ("tome_prop_attention_backward_workspace_bytes", "tome_prop_attention_backward")
 
 ABI_VERSION = 11
 DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
@@ -139,6 +141,12 @@ def bind(path: str) -> ctypes.CDLL:
         L.tome_layernorm_backward_workspace_bytes.argtypes = [i64, i64]
         L.tome_layernorm_backward.restype = i32
         L.tome_layernorm_backward.argtypes = [vp, vp, vp, i32, i64, i64, i32, i64, vp, ctypes.c_float, vp, vp, vp, vp, vp]
+    if all(_exports(L, name) for name in _LATER_V11_ATTN):
+        L.tome_prop_attention_backward_workspace_bytes.restype = sz
+        L.tome_prop_attention_backward_workspace_bytes.argtypes = [i64, i64, i64, i64]
+        L.tome_prop_attention_backward.restype = i32
+        L.tome_prop_attention_backward.argtypes = [vp, vp, vp, vp, vp, i32, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp,
+                                                   vp, i64, i32, ctypes.c_float, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     if L.tome_abi_version() != ABI_VERSION:
         raise TomeHipError(f"{os.path.basename(path)} ABI {L.tome_abi_version()} != expected {ABI_VERSION}")
     return L
@@ -719,6 +727,81 @@ def prop_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, size: Opti
                                        out.data_ptr(), ostr, _stream(q.device))
     _check(rc, "tome_prop_attention")
     return result
+
+
+def prop_attention_trainable(q: torch.Tensor, k: Optional[torch.Tensor] = None, v: Optional[torch.Tensor] = None) -> bool:
+    """prop_attention_ok without its grad clause, for every tensor given: can tome_prop_attention run on these heads
+    with tome_prop_attention_backward behind it (tome/_attn.py) when they require grad?"""
+    return all(t is None or (t.is_cuda and t.dim() == 4 and t.shape[-1] == 64 and t.dtype in (torch.bfloat16, torch.float16)
+                             and t.stride(-1) == 1 and all(s % 8 == 0 for s in t.stride()[:3])
+                             and t.data_ptr() % 16 == 0) for t in (q, k, v))
+
+
+def _head_strides(t: torch.Tensor):
+    return (ctypes.c_int64 * 3)(*t.stride()[:3])
+
+
+def prop_attention_backward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, dout: torch.Tensor,
+                            log_bias: Optional[torch.Tensor], scale: float, bias_skip: bool = False,
+                            grads=None, workspace: Optional[torch.Tensor] = None):
+    """tome_prop_attention_backward: (dq, dk, dv) of out = prop_attention(q, k, v, ...) given dout.  q [B, H, N, 64],
+    k / v [B, H, Nk, 64] head views as the forward took them; out and dout [B, N, H*64] (out: what the forward returned;
+    rows of dout 16-byte aligned, channels contiguous -- anything else is copied once).  log_bias: the fp32 [B, Nk(-1)]
+    bias the forward used, or None.  grads: three head views to write into (the slices of one [B, N, 3, H, 64] buffer,
+    say), or None for fresh [B, H, N, 64] tensors.  workspace: a uint8 device tensor to use instead of a fresh one.
+    size gets no gradient.  No CPU path."""
+    for t, name in ((q, "q"), (k, "k"), (v, "v")):
+        require_device(t, f"prop_attention_backward({name})")
+    if not prop_attention_trainable(q, k, v):
+        raise TomeHipError("prop_attention_backward: q, k, v must be [B, H, N, 64] 16-bit views with 16-byte aligned rows")
+    if k.dtype != q.dtype or v.dtype != q.dtype or k.device != q.device or v.device != q.device:
+        raise TomeHipError("prop_attention_backward: q, k, v must share dtype and device")
+    B, H, N, D = q.shape
+    if k.shape != v.shape or k.shape[:2] != (B, H):
+        raise TomeHipError(f"prop_attention_backward: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not match")
+    Nk = k.shape[2]
+    if bias_skip and Nk != N:
+        raise TomeHipError("prop_attention_backward: bias_skip needs as many keys as queries")
+    nb = Nk - (1 if bias_skip else 0)
+    if log_bias is not None and (tuple(log_bias.shape) != (B, nb) or log_bias.dtype != torch.float32
+                                 or log_bias.stride(1) != 1 or log_bias.device != q.device):
+        raise TomeHipError(f"prop_attention_backward: log_bias must be an fp32 {(B, nb)} view with contiguous rows")
+    heads = []
+    for t, name in ((out, "out"), (dout, "dout")):
+        if tuple(t.shape) != (B, N, H * D) or t.device != q.device:
+            raise TomeHipError(f"prop_attention_backward: {name} must be {(B, N, H * D)} on {q.device}, got {tuple(t.shape)}")
+        t = t.detach()
+        if t.dtype != q.dtype:
+            t = t.to(q.dtype)
+        if t.stride(2) != 1 or t.stride(0) % 8 or t.stride(1) % 8 or t.data_ptr() % 16:
+            t = t.contiguous()
+        heads.append(t.unflatten(2, (H, D)).permute(0, 2, 1, 3))  # [B, H, N, 64] view
+    o4, g4 = heads
+    if grads is None:
+        dq = torch.empty((B, N, H, D), dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
+        dk = torch.empty((B, Nk, H, D), dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
+        dv = torch.empty((B, Nk, H, D), dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
+    else:
+        dq, dk, dv = grads
+        for t, like, name in ((dq, q, "dq"), (dk, k, "dk"), (dv, v, "dv")):
+            if t.shape != like.shape or t.dtype != q.dtype or t.device != q.device or not prop_attention_trainable(t):
+                raise TomeHipError(f"prop_attention_backward: {name} must be a {tuple(like.shape)} {q.dtype} head view with "
+                                   "16-byte aligned rows")
+    L = lib()
+    entry = require_symbol(L, "tome_prop_attention_backward")
+    with _on_device(q.device):
+        stream = _stream(q.device)
+        nbytes = require_symbol(L, "tome_prop_attention_backward_workspace_bytes")(B, H, N, Nk)
+        if nbytes == 0:
+            raise TomeHipError(f"prop_attention_backward: no workspace size for {(B, H, N, Nk)}")
+        ws = _workspace(q.device, stream, nbytes) if workspace is None else workspace
+        rc = entry(q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), g4.data_ptr(), dtype_code(q, "q"), B, H, N, Nk,
+                   D, _head_strides(q), _head_strides(k), _head_strides(v), _head_strides(o4), _head_strides(g4),
+                   _ptr(log_bias), 0 if log_bias is None else log_bias.stride(0), 1 if bias_skip else 0, float(scale),
+                   dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), _head_strides(dq), _head_strides(dk), _head_strides(dv),
+                   ws.data_ptr(), ws.numel() * ws.element_size(), stream)
+    _check(rc, "tome_prop_attention_backward")
+    return dq, dk, dv
 
 
 def prop_attention_segments(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, nseg: int, scale: float,

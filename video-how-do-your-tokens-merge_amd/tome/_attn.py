@@ -1,0 +1,119 @@
+"""The proportional attention of the patched blocks for heads that require grad (models are patched for training,
+tools/train_net.py:727-741): forward = the inference launch (tome_prop_attention) on the detached tensors, backward =
+tome_prop_attention_backward (csrc/tome_attn_bwd.h).
+
+    attention_native(q, k, v, size, scale, bias_skip=False)   -> [B, N, H*64]      q, k, v: [B, H, N, 64] head views
+    attention_qkv_native(qkv, size, scale, bias_skip=False)   -> [B, N, H*64]      qkv: the [3, B, H, N, 64] view of one
+                                                                                   [B, N, 3, H, 64] projection output
+
+The backward recomputes the softmax from q, k and the size bias (row maximum and sum included), so the forward saves
+nothing but its inputs and the tensor it returns anyway.  `size` gets no gradient.  The qkv form
+takes the projection's buffer as its single differentiable input and returns one gradient buffer of that layout, whose
+three slices the kernels write directly: autograd's three select_backward passes (zero-fill and add, three times the
+token tensor per layer) never run.  Not covered (they keep the framework's ops: DESIGN.md section 7): dropout > 0,
+fp32 heads, head dim != 64, the segmented and short forms, double backward (raises).
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _abi
+
+# False: `tome/patch/_common.py:attention` takes the framework's scaled_dot_product_attention with the bias tensor the
+# reference builds and autograd (the behaviour before the backward kernels existed) -- for A/B in tests and
+# tools/attn_backward_bench.py.  Also off when tome.merge.NATIVE_BACKWARD is off.  On by default: faster than the framework path
+# at every measured shape.
+NATIVE_ATTN_BACKWARD = True
+
+
+def enabled() -> bool:
+    from . import merge
+    return bool(NATIVE_ATTN_BACKWARD and merge.NATIVE_BACKWARD)
+
+
+def wants(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, dropout_p: float = 0.0) -> bool:
+    """Do the heads require grad, and does this attention of them run on the native Function?"""
+    return (torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad) and dropout_p == 0.0
+            and enabled() and _abi.prop_attention_trainable(q, k, v))
+
+
+def _log_bias(size, B):
+    """The fp32 [B, keys] bias both launches read (what _abi.prop_attention makes of `size`), or None."""
+    if size is None:
+        return None
+    # (asked of `size` itself: the log the merge kernel emitted travels as an attribute that a detached copy lacks)
+    with torch.no_grad():
+        return _abi.log_of_size(size).detach().reshape(B, -1).float().contiguous()
+
+
+class _AttentionFunction(torch.autograd.Function):
+    """softmax(q k^T scale + log size) v: tome_prop_attention forward, tome_prop_attention_backward backward."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, size, scale, bias_skip):
+        q, k, v = q.detach(), k.detach(), v.detach()
+        log = _log_bias(size, q.shape[0])
+        out = _abi.prop_attention(q, k, v, None, scale, bias_skip=bias_skip, log_bias=log, checked=True)
+        ctx.scale, ctx.bias_skip, ctx.has_bias = float(scale), bool(bias_skip), log is not None
+        ctx.save_for_backward(q, k, v, out, *(() if log is None else (log,)))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out):
+        q, k, v, out = ctx.saved_tensors[:4]
+        log = ctx.saved_tensors[4] if ctx.has_bias else None
+        dq, dk, dv = _abi.prop_attention_backward(q, k, v, out, g_out, log, ctx.scale, bias_skip=ctx.bias_skip)
+        need = ctx.needs_input_grad
+        return (dq if need[0] else None), (dk if need[1] else None), (dv if need[2] else None), None, None, None
+
+
+class _AttentionQKVFunction(torch.autograd.Function):
+    """The same for q, k, v = qkv[0], qkv[1], qkv[2] of one projection output: one input, one gradient buffer."""
+
+    @staticmethod
+    def forward(ctx, qkv, size, scale, bias_skip):
+        qkv = qkv.detach()
+        q, k, v = qkv[0], qkv[1], qkv[2]
+        log = _log_bias(size, q.shape[0])
+        out = _abi.prop_attention(q, k, v, None, scale, bias_skip=bias_skip, log_bias=log, checked=True)
+        ctx.scale, ctx.bias_skip, ctx.has_bias = float(scale), bool(bias_skip), log is not None
+        ctx.save_for_backward(qkv, out, *(() if log is None else (log,)))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out):
+        qkv, out = ctx.saved_tensors[:2]
+        log = ctx.saved_tensors[2] if ctx.has_bias else None
+        _, B, H, N, D = qkv.shape
+        # [B, N, 3, H, 64] like the projection's output, seen as [3, B, H, N, 64]: every element is written below
+        g = torch.empty((B, N, 3, H, D), dtype=qkv.dtype, device=qkv.device).permute(2, 0, 3, 1, 4)
+        _abi.prop_attention_backward(qkv[0], qkv[1], qkv[2], out, g_out, log, ctx.scale, bias_skip=ctx.bias_skip,
+                                     grads=(g[0], g[1], g[2]))
+        return g, None, None, None
+
+
+def _check(what, *heads):
+    if not _abi.prop_attention_trainable(*heads):
+        raise _abi.TomeHipError(f"{what}: these heads ({tuple(heads[0].shape)} {heads[0].dtype}) are not ones the kernels "
+                                "take (_abi.prop_attention_trainable)")
+
+
+def attention_native(q, k, v, size, scale: float, bias_skip: bool = False):
+    """softmax(q k^T * scale + log(size)) v for [B, H, N, 64] head views that require grad; returns [B, N, H*64]."""
+    _check("attention_native", q, k, v)
+    return _AttentionFunction.apply(q, k, v, size, float(scale), bool(bias_skip))
+
+
+def qkv_trainable(qkv: torch.Tensor) -> bool:
+    """Is `qkv` a [3, B, H, N, 64] view whose three slices the kernels take, q / k / v of equal length?"""
+    return qkv.dim() == 5 and qkv.shape[0] == 3 and _abi.prop_attention_trainable(qkv[0], qkv[1], qkv[2])
+
+
+def attention_qkv_native(qkv, size, scale: float, bias_skip: bool = False):
+    """The same for the [3, B, H, N, 64] view of one qkv projection: its gradient comes back as one buffer."""
+    if not qkv_trainable(qkv):
+        raise _abi.TomeHipError(f"attention_qkv_native: qkv {tuple(qkv.shape)} {qkv.dtype} is not a [3, B, H, N, 64] view "
+                                "the kernels take")
+    return _AttentionQKVFunction.apply(qkv, size, float(scale), bool(bias_skip))

@@ -192,16 +192,32 @@ keys_ready = _overlap.keys_ready      # the block's matching beside its attentio
 match_beside = _overlap.match_beside  # tome/_overlap.py
 
 
+def attention_qkv(qkv, size, scale: float, dropout_p: float = 0.0, bias_skip: bool = False):
+    """`attention(qkv[0], qkv[1], qkv[2], ...)` for the [3, B, H, N, hd] view of one qkv projection.  When the heads
+    require grad and the native backward takes them, the buffer is the Function's single differentiable input and its
+    gradient comes back as one buffer of that layout, written in place by the kernels -- instead of autograd's three
+    select_backward passes (zero-fill and add: three times the token tensor per layer)."""
+    from .. import _attn
+    q, k, v = qkv[0], qkv[1], qkv[2]
+    if _ATTN_KERNEL and _attn.wants(q, k, v, dropout_p):
+        return _attn.attention_qkv_native(qkv, size, scale, bias_skip=bias_skip)
+    return attention(q, k, v, size, scale, dropout_p, bias_skip)
+
+
 def attention(q, k, v, size, scale: float, dropout_p: float = 0.0, bias_skip: bool = False):
     """softmax(q k^T * scale + log(size)) v for [B, H, N, hd] head views; returns [B, N, H*hd].
     16-bit heads of width 64 without dropout go through tome_prop_attention (the size bias is one value per key
-    inside the kernel, q/k/v are read in place from the projection's output); everything else through the
+    inside the kernel, q/k/v are read in place from the projection's output) -- under grad as the Function of
+    tome/_attn.py, whose backward is tome_prop_attention_backward; everything else through the
     framework's attention with the bias tensor the reference builds (videomae.py:62-63, timesformer.py:73-74)."""
-    from .. import _abi
+    from .. import _abi, _attn
     B, H, N, hd = q.shape
     if (_ATTN_KERNEL and dropout_p == 0.0 and _abi.prop_attention_ok(q) and _abi.prop_attention_ok(k)
             and _abi.prop_attention_ok(v)):
         return _abi.prop_attention(q, k, v, size, scale, bias_skip=bias_skip, checked=True)
+    # heads that require grad: the same forward launch with tome_prop_attention_backward behind it (tome/_attn.py)
+    if _ATTN_KERNEL and _attn.wants(q, k, v, dropout_p):
+        return _attn.attention_native(q, k, v, size, scale, bias_skip=bias_skip)
     bias = None
     if size is not None:
         log = _abi.log_of_size(size)[:, None, None, :, 0].to(q.dtype)

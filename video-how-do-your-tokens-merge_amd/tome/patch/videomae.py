@@ -52,7 +52,8 @@ def _attention_forward(self, x, size: torch.Tensor = None, head_aggregation: str
     drop_p = self.attn_drop.p if self.training else 0.0
     info = getattr(self, "_tome_info", None)
     ready = C.keys_ready(k, info) if head_aggregation == "mean" else None  # the keys exist behind the qkv GEMM
-    out = C.attention(q, k, v, size, self.scale, drop_p)
+    # (the qkv buffer itself goes in: under grad its gradient comes back as one buffer the backward kernels fill)
+    out = C.attention_qkv(qkv, size, self.scale, drop_p)
     if head_aggregation == "mean":
         metric = HeadMeanKeys(k)  # k.mean(1), averaged inside the matching kernel when the layer merges
         C.match_beside(metric, ready, info)  # ... on the side stream, beside the attention and the projection
