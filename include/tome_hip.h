@@ -376,6 +376,29 @@ int tome_prop_attention_backward(const void *q, const void *k, const void *v, co
  * values (a multiple of 8), fp32 arithmetic, bit-identical to the framework's kernel.  y may alias x. */
 int tome_gelu_erf(const void *x, int dtype, int64_t elements, void *y, tome_stream_t stream);
 
+/*
+ * tome_gelu_erf_backward  <-  what autograd derives from the MLP of the patched block between its two Linear layers
+ *     when its input or its parameters require grad (additions to ABI v11, no entry changed; models are patched for
+ *     training, tools/train_net.py:727-741):
+ *         x = x + self.drop_path(self.mlp(self.norm2(x)))      tome/patch/videomae.py:29, timesformer.py:56,
+ *                                                              motionformer.py:29   (mlp = fc1, nn.GELU(), fc2)
+ *     With h = fc1's output (the saved pre-activation), ga the gradient of the activation, v = h in fp32,
+ *     Phi(v) = 0.5 (1 + erf(v / sqrt 2)), phi(v) = exp(-v^2 / 2) / sqrt(2 pi):
+ *         gh = ga * (Phi(v) + v phi(v))                        one rounding to `dtype`; gh may be ga (in place)
+ *         act = gelu(h)                 (act != NULL)          the bits tome_gelu_erf stored in the forward, for fc2's
+ *                                                              weight gradient; a buffer of its own, never h
+ *         dbias[c] = sum over rows of the ROUNDED gh[:, c]     (dbias != NULL) fc1's bias gradient: fp32 sums, one
+ *                                                              rounding to `dtype`
+ *     h, ga, gh, act: contiguous [rows, width] of `dtype` (TOME_BF16 / TOME_F16, width % 8 == 0, width <= 8192,
+ *     1 <= rows < 2^31), 16-byte aligned; dbias [width].  One streaming launch (plus the sum of the partial rows when
+ *     dbias is asked for), no atomics, same bits on every run; no allocation, no synchronisation.  Without dbias no
+ *     workspace is read.  With it: workspace of tome_gelu_erf_backward_workspace_bytes(rows, width) bytes (fp32 partial
+ *     rows [parts <= 512, width]; 0 for an illegal shape); NULL or workspace_bytes below that: TOME_EWORKSPACE.
+ */
+size_t tome_gelu_erf_backward_workspace_bytes(int64_t rows, int64_t width);
+int tome_gelu_erf_backward(const void *h, const void *ga, int dtype, int64_t rows, int64_t width, void *gh, void *act,
+                           void *dbias, void *workspace, size_t workspace_bytes, tome_stream_t stream);
+
 /* tome_tubelet_rows  <-  the models' patch embedding, a convolution whose stride equals its kernel
  * (slowfast/models/videomae_video_model_builder.py:137-166 `PatchEmbed.proj`; TimeSformer's per-frame Conv2d; Motionformer
  * `PatchEmbed3D`; ViViT's tubelet Conv3d): its input side as the [B*N, C*kt*kh*kw] matrix the weight multiplies,

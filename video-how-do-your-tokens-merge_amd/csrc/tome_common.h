@@ -30,6 +30,12 @@ template <> __device__ __forceinline__ f16_t from_f32<f16_t>(float f) {
     return r;
 }
 
+// nn.GELU() in its exact erf form, x * 0.5 * (1 + erf(x / sqrt(2))), in the framework kernel's expression and operation
+// order (k_gelu_erf stores these bits; k_gelu_bwd rebuilds them from the saved pre-activation, and its Phi(x) is half
+// of the same 1 + erf).
+__device__ __forceinline__ float gelu_erf_one_plus(float x) { return 1.0f + erff(x * 0.70710678118654752440f); }
+__device__ __forceinline__ float gelu_erf_value(float x, float one_plus_erf) { return x * 0.5f * one_plus_erf; }
+
 // A lane's slice of a row: VEC consecutive elements moved with one 16-byte (or narrower) access.
 template <typename T, int VEC> struct Pack { T e[VEC]; };
 

@@ -2,8 +2,8 @@
 // C ABI declared in include/tome_hip.h.  Built with: hipcc --offload-arch=gfx950 -O3
 // -ffp-contract=off -shared -fPIC (csrc/build.py).  No torch, no CUDA, no portability layer.
 //
-// One translation unit: tome_common.h (types), tome_match.h, tome_merge.h, tome_merge_bwd.h, tome_ln_bwd.h and
-// tome_partition.h (kernels), this file (host).
+// One translation unit: tome_common.h (types), tome_match.h, tome_merge.h, tome_merge_bwd.h, tome_ln_bwd.h,
+// tome_gelu_bwd.h and tome_partition.h (kernels), this file (host).
 //
 // Launch sequence of one matching (tome_match / tome_match_keys), kernels in tome_match.h:
 //   k_unit_rows[_heads]  keys -> fp32 unit vectors, even/odd split, MFMA-fragment order (HBM bound)
@@ -22,6 +22,9 @@
 //   k_ln_rows_bwd        gx = gx_in + rstd (gw - mean gw - xhat mean(gw xhat)), statistics recomputed from the stored
 //                        rows; per-workgroup partial rows of dweight / dbias                    (HBM bound)
 //   k_ln_param_grad      the partial rows summed in a fixed order
+// and of the MLP's backward between its two library GEMMs (tome_gelu_erf_backward), tome_gelu_bwd.h:
+//   k_gelu_bwd           gh = ga (Phi(h) + h phi(h)), the activation again with the forward's bits, per-workgroup
+//                        partial rows of fc1's bias gradient (summed by k_ln_param_grad)        (HBM bound)
 // and of the proportional attention's backward (tome_prop_attention_backward), tome_attn_bwd.h:
 //   k_attn_bwd_dq        row statistics recomputed (two sweeps over the keys), dq, L and delta to the workspace
 //   k_attn_bwd_dkv       dk and dv per block of keys over all queries                          (MFMA bound)
@@ -46,6 +49,7 @@
 #include "tome_merge.h"
 #include "tome_merge_bwd.h"
 #include "tome_ln_bwd.h"
+#include "tome_gelu_bwd.h"
 #include "tome_partition.h"
 #include "tome_attn.h"
 #include "tome_attn_stream.h"
@@ -826,8 +830,8 @@ extern "C" int tome_layernorm_backward(const void *gy, const void *xs, const voi
                                (int)cpr, eps, skip_first ? (int)group_rows : 0, (int)f.spw, (TX *)gx, (float *)workspace);
             if (int rc = check_launch("k_ln_rows_bwd")) return rc;
             hipLaunchKernelGGL((k_ln_param_grad<TX>), dim3((unsigned)((2 * C + WAVE - 1) / WAVE)),
-                               dim3(LN_PG_RUNS * WAVE), 0, st, (const float *)workspace, (int)f.parts, (int)C,
-                               (TX *)dweight, (TX *)dbias);
+                               dim3(LN_PG_RUNS * WAVE), 0, st, (const float *)workspace, (int)f.parts, (int)(2 * C),
+                               (int)C, (TX *)dweight, (TX *)dbias);
             return check_launch("k_ln_param_grad");
         }
         // frozen LayerNorm: one slab per wave, no column sums, no workspace
@@ -1194,6 +1198,82 @@ extern "C" int tome_gelu_erf(const void *x, int dtype, int64_t elements, void *y
     else
         hipLaunchKernelGGL(k_gelu_erf<f16_t>, dim3((unsigned)blocks), dim3(256), 0, st, (const f16_t *)x, (f16_t *)y, chunks);
     return check_launch("k_gelu_erf");
+}
+
+// The launch form of k_gelu_bwd with the bias gradient for `rows` rows of `width`: S column slots per thread, U passes
+// per step, RP rows per pass, and how many steps a workgroup walks (spw) so that at most GELU_BWD_MAX_PARTS workgroups
+// (= partial rows of the workspace) run: two per CU, all resident from the start.
+#define GELU_BWD_MAX_PARTS 512
+#define GELU_BWD_MAX_WIDTH 8192
+struct GeluBwdForm { int S; int U; int RP; int64_t spw; int64_t parts; };
+static GeluBwdForm gelu_bwd_form(int64_t rows, int64_t width) {
+    const int64_t cpr = width / 8;
+    const int S = (int)((cpr + 255) / 256);
+    const int U = S == 1 ? 4 : (S <= 3 ? 2 : 1);
+    const int RP = S == 1 ? (int)(256 / cpr) : 1;
+    const int64_t passes = (rows + RP - 1) / RP;
+    const int64_t steps = (passes + U - 1) / U;
+    const int64_t spw = (steps + GELU_BWD_MAX_PARTS - 1) / GELU_BWD_MAX_PARTS;
+    return GeluBwdForm{S, U, RP, spw, (steps + spw - 1) / spw};
+}
+
+static bool gelu_bwd_shape_ok(int64_t rows, int64_t width) {
+    return rows >= 1 && rows <= 0x7fffffffLL && width >= 8 && width % 8 == 0 && width <= GELU_BWD_MAX_WIDTH;
+}
+
+extern "C" size_t tome_gelu_erf_backward_workspace_bytes(int64_t rows, int64_t width) {
+    if (!gelu_bwd_shape_ok(rows, width)) return 0;
+    return align_up((size_t)gelu_bwd_form(rows, width).parts * (size_t)width * sizeof(float), 256);
+}
+
+extern "C" int tome_gelu_erf_backward(const void *h, const void *ga, int dtype, int64_t rows, int64_t width, void *gh,
+                                      void *act, void *dbias, void *workspace, size_t workspace_bytes,
+                                      tome_stream_t stream) {
+    if (!h || !ga || !gh) return fail(TOME_EINVAL, "tome_gelu_erf_backward: null buffer");
+    if (dtype != TOME_BF16 && dtype != TOME_F16) return fail(TOME_EINVAL, "tome_gelu_erf_backward: 16-bit tensors only");
+    if (!gelu_bwd_shape_ok(rows, width))
+        return fail(TOME_EINVAL, "tome_gelu_erf_backward: width %% 8 == 0, width <= 8192 and 1 .. 2^31 - 1 rows required");
+    if (!aligned16(h) || !aligned16(ga) || !aligned16(gh) || !aligned16(act) || !aligned16(dbias) ||
+        !aligned16(workspace))
+        return fail(TOME_EINVAL, "tome_gelu_erf_backward: 16-byte aligned buffers required");
+    if (act && (act == h || act == ga || act == gh))
+        return fail(TOME_EINVAL, "tome_gelu_erf_backward: the activation needs a buffer of its own");
+    if (gh == h) return fail(TOME_EINVAL, "tome_gelu_erf_backward: gh may lie over ga, not over h");
+    if (dbias && (!workspace || workspace_bytes < tome_gelu_erf_backward_workspace_bytes(rows, width)))
+        return fail(TOME_EWORKSPACE, "tome_gelu_erf_backward: the bias gradient needs a workspace of "
+                                     "tome_gelu_erf_backward_workspace_bytes()");
+    const int64_t cpr = width / 8, chunks = rows * cpr;
+    hipStream_t st = (hipStream_t)stream;
+    return dispatch_x<false>(dtype, [&](auto tx) {
+        using TX = typename decltype(tx)::type;
+        if (!dbias) {  // flat: rows of 256 chunks, four per lane, as k_gelu_erf
+            const int64_t blocks = (chunks + 1023) / 1024;
+#define GELU_BWD_FLAT(ACT)                                                                                             \
+    hipLaunchKernelGGL((k_gelu_bwd<TX, 1, false, ACT>), dim3((unsigned)blocks), dim3(256), 0, st, (const TX *)h,       \
+                       (const TX *)ga, chunks, 256, 1, 1, (TX *)gh, (TX *)act, (float *)nullptr)
+            if (act) GELU_BWD_FLAT(true); else GELU_BWD_FLAT(false);
+#undef GELU_BWD_FLAT
+            return check_launch("k_gelu_bwd");
+        }
+        const GeluBwdForm f = gelu_bwd_form(rows, width);
+#define GELU_BWD_LAUNCH_(SLOTS, ACT)                                                                                   \
+    hipLaunchKernelGGL((k_gelu_bwd<TX, SLOTS, true, ACT>), dim3((unsigned)f.parts), dim3(256), 0, st, (const TX *)h,   \
+                       (const TX *)ga, chunks, (int)cpr, f.RP, (int)f.spw, (TX *)gh, (TX *)act, (float *)workspace)
+#define GELU_BWD_LAUNCH(SLOTS) do { if (act) GELU_BWD_LAUNCH_(SLOTS, true); else GELU_BWD_LAUNCH_(SLOTS, false); } while (0)
+        switch (f.S) {
+        case 1: GELU_BWD_LAUNCH(1); break;
+        case 2: GELU_BWD_LAUNCH(2); break;
+        case 3: GELU_BWD_LAUNCH(3); break;
+        default: GELU_BWD_LAUNCH(4); break;
+        }
+#undef GELU_BWD_LAUNCH_
+#undef GELU_BWD_LAUNCH
+        if (int rc = check_launch("k_gelu_bwd")) return rc;
+        hipLaunchKernelGGL((k_ln_param_grad<TX>), dim3((unsigned)((width + WAVE - 1) / WAVE)), dim3(LN_PG_RUNS * WAVE), 0,
+                           st, (const float *)workspace, (int)f.parts, (int)width, (int)width, (TX *)dbias,
+                           (TX *)nullptr);
+        return check_launch("k_ln_param_grad");
+    }, [&] { return fail(TOME_EINVAL, "tome_gelu_erf_backward: 16-bit tensors only"); });
 }
 
 extern "C" int tome_tubelet_rows(const void *x, int elem_bytes, int64_t B, int64_t C, int64_t T, int64_t H, int64_t W,

@@ -233,34 +233,37 @@ __global__ __launch_bounds__(256) void k_ln_rows_bwd(const TX *__restrict__ gy, 
     }
 }
 
-// k_ln_param_grad: dweight / dbias from the partial rows ws [parts, 2, C] of k_ln_rows_bwd.  A thread owns one of the
-// 2C columns; the parts are summed in index order in LN_PG_RUNS contiguous runs (one per wave of the workgroup), the
-// runs combined in run order; one rounding to the parameter dtype.  The order depends on `parts` only: same bits on
-// every run.  Either output may be NULL (that parameter is frozen).
+// k_ln_param_grad: parameter gradients from fp32 partial rows ws [parts, width]: of k_ln_rows_bwd (width = 2 C, the
+// columns [dweight | dbias], split = C) and of k_gelu_bwd (width = split = Hd, fc1's bias gradient, no second output).
+// A thread owns one of the `width` columns; the parts are summed in index order in LN_PG_RUNS contiguous runs (one per
+// wave of the workgroup), the runs combined in run order; one rounding to the parameter dtype.  The order depends on
+// `parts` only: same bits on every run.  Columns below `split` go to out_lo, the others to out_hi; either may be NULL
+// (that parameter is frozen).
 #define LN_PG_RUNS 16
 template <typename TP>
-__global__ __launch_bounds__(LN_PG_RUNS * WAVE) void k_ln_param_grad(const float *__restrict__ ws, int parts, int C,
-                                                                    TP *__restrict__ dweight, TP *__restrict__ dbias) {
+__global__ __launch_bounds__(LN_PG_RUNS * WAVE) void k_ln_param_grad(const float *__restrict__ ws, int parts, int width,
+                                                                    int split, TP *__restrict__ out_lo,
+                                                                    TP *__restrict__ out_hi) {
     __shared__ float runs[LN_PG_RUNS][WAVE];
     const int lane = threadIdx.x & 63, run = threadIdx.x >> 6;
-    const int col = (int)blockIdx.x * WAVE + lane;  // over [dweight | dbias]
+    const int col = (int)blockIdx.x * WAVE + lane;
     const int per = (parts + LN_PG_RUNS - 1) / LN_PG_RUNS;
     const int lo = run * per, hi = (lo + per) < parts ? (lo + per) : parts;
     float acc = 0.0f;
-    if (col < 2 * C) {
+    if (col < width) {
         const float *src = ws + col;
 #pragma unroll 8
-        for (int p = lo; p < hi; ++p) acc += src[(int64_t)p * 2 * C];
+        for (int p = lo; p < hi; ++p) acc += src[(int64_t)p * width];
     }
     runs[run][lane] = acc;
     __syncthreads();
-    if (run != 0 || col >= 2 * C) return;
+    if (run != 0 || col >= width) return;
     float total = runs[0][lane];
 #pragma unroll
     for (int k = 1; k < LN_PG_RUNS; ++k) total += runs[k][lane];
-    if (col < C) {
-        if (dweight) dweight[col] = from_f32<TP>(total);
-    } else if (dbias) {
-        dbias[col - C] = from_f32<TP>(total);
+    if (col < split) {
+        if (out_lo) out_lo[col] = from_f32<TP>(total);
+    } else if (out_hi) {
+        out_hi[col - split] = from_f32<TP>(total);
     }
 }

@@ -1380,7 +1380,7 @@ __global__ __launch_bounds__(256) void k_gelu_erf(const TX *__restrict__ x, TX *
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
             const float v = to_f32(pk.e[e]);
-            pk.e[e] = from_f32<TX>(v * 0.5f * (1.0f + erff(v * 0.70710678118654752440f)));
+            pk.e[e] = from_f32<TX>(gelu_erf_value(v, gelu_erf_one_plus(v)));
         }
         uint4 o;
         __builtin_memcpy(&o, &pk, 16);

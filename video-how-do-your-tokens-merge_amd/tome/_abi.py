@@ -26,10 +26,12 @@ SYMBOLS = (
     "tome_unmerge_partition",
     "tome_layernorm_backward_workspace_bytes", "tome_layernorm_backward",
     "tome_prop_attention_backward_workspace_bytes", "tome_prop_attention_backward",
+    "tome_gelu_erf_backward_workspace_bytes", "tome_gelu_erf_backward",
 )
 # entries added to ABI v11 after its first release: a v11 library built before them binds, and says so when one is called
 _LATER_V11 = ("tome_layernorm_backward_workspace_bytes", "tome_layernorm_backward")
 _LATER_V11_ATTN = ("tome_prop_attention_backward_workspace_bytes", "tome_prop_attention_backward")
+_LATER_V11_MLP = ("tome_gelu_erf_backward_workspace_bytes", "tome_gelu_erf_backward")
 
 ABI_VERSION = 11
 DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
@@ -147,6 +149,11 @@ def bind(path: str) -> ctypes.CDLL:
         L.tome_prop_attention_backward.restype = i32
         L.tome_prop_attention_backward.argtypes = [vp, vp, vp, vp, vp, i32, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp,
                                                    vp, i64, i32, ctypes.c_float, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    if all(_exports(L, name) for name in _LATER_V11_MLP):
+        L.tome_gelu_erf_backward_workspace_bytes.restype = sz
+        L.tome_gelu_erf_backward_workspace_bytes.argtypes = [i64, i64]
+        L.tome_gelu_erf_backward.restype = i32
+        L.tome_gelu_erf_backward.argtypes = [vp, vp, i32, i64, i64, vp, vp, vp, vp, sz, vp]
     if L.tome_abi_version() != ABI_VERSION:
         raise TomeHipError(f"{os.path.basename(path)} ABI {L.tome_abi_version()} != expected {ABI_VERSION}")
     return L
@@ -958,6 +965,61 @@ def gelu_erf(x: torch.Tensor, inplace: bool = False) -> torch.Tensor:
         rc = lib().tome_gelu_erf(x.data_ptr(), dtype_code(x, "x"), x.numel(), y.data_ptr(), _stream(x.device))
     _check(rc, "tome_gelu_erf")
     return y
+
+
+GELU_BWD_MAX_WIDTH = 8192  # csrc/tome_kernels.hip: GELU_BWD_MAX_WIDTH
+
+
+def mlp_trainable(y: torch.Tensor, fc1, fc2, act) -> bool:
+    """Can `fc2(act(fc1(y)))` run as the Function of tome/_mlp.py (library GEMMs, tome_gelu_erf forward,
+    tome_gelu_erf_backward backward) when y or the parameters require grad?  16-bit device tokens, the stock nn.Linear /
+    exact-erf nn.GELU modules, parameters of the tokens' dtype, hidden width within the kernel's limits, 16-byte rows."""
+    from .patch._common import _stock_module
+    if not (_stock_module(fc1, torch.nn.Linear) and _stock_module(fc2, torch.nn.Linear)
+            and _stock_module(act, torch.nn.GELU) and getattr(act, "approximate", "none") == "none"):
+        return False
+    C, Hd = fc1.in_features, fc1.out_features
+    params = [fc1.weight, fc2.weight] + [b for b in (fc1.bias, fc2.bias) if b is not None]
+    return (y.is_cuda and y.dtype in (torch.bfloat16, torch.float16) and y.dim() >= 2 and y.shape[-1] == C
+            and y.numel() > 0 and fc2.in_features == Hd and Hd % 8 == 0 and Hd <= GELU_BWD_MAX_WIDTH
+            and (C * y.element_size()) % 16 == 0 and (fc2.out_features * y.element_size()) % 16 == 0
+            and all(p.dtype == y.dtype and p.device == y.device for p in params))
+
+
+def gelu_erf_backward(h: torch.Tensor, ga: torch.Tensor, *, want_act: bool, want_bias: bool, inplace: bool = True):
+    """tome_gelu_erf_backward for contiguous 16-bit h, ga [..., Hd]: (gh, act, dbias).  gh = ga * gelu'(h), written over
+    ga when `inplace`; act = gelu(h) with the forward's bits when want_act, else None; dbias [Hd] = the column sums of
+    the rounded gh when want_bias, else None (then no workspace is taken).  No CPU path."""
+    require_device(h, "gelu_erf_backward(h)")
+    if h.dtype not in (torch.bfloat16, torch.float16):
+        raise TomeHipError(f"gelu_erf_backward: 16-bit tensors only, got {h.dtype}")
+    Hd = h.shape[-1] if h.dim() >= 2 else 0
+    if Hd == 0 or Hd % 8 or Hd > GELU_BWD_MAX_WIDTH or h.numel() == 0:
+        raise TomeHipError(f"gelu_erf_backward: h must be [..., Hd] with Hd % 8 == 0 and Hd <= {GELU_BWD_MAX_WIDTH}, "
+                           f"got {tuple(h.shape)}")
+    if ga.shape != h.shape or ga.dtype != h.dtype or ga.device != h.device:
+        raise TomeHipError("gelu_erf_backward: ga must have h's shape, dtype and device")
+    if not h.is_contiguous() or not ga.is_contiguous():
+        raise TomeHipError("gelu_erf_backward: contiguous tensors required")
+    h, ga = h.detach(), ga.detach()
+    rows = h.numel() // Hd
+    L = lib()
+    entry = require_symbol(L, "tome_gelu_erf_backward")
+    gh = ga if inplace else torch.empty_like(ga)
+    act = torch.empty_like(h) if want_act else None
+    dbias = torch.empty(Hd, dtype=h.dtype, device=h.device) if want_bias else None
+    with _on_device(h.device):
+        stream = _stream(h.device)
+        ws, nbytes = None, 0
+        if want_bias:
+            nbytes = require_symbol(L, "tome_gelu_erf_backward_workspace_bytes")(rows, Hd)
+            if nbytes == 0:
+                raise TomeHipError(f"gelu_erf_backward: no workspace size for {rows} rows of {Hd}")
+            ws = _workspace(h.device, stream, nbytes)
+        rc = entry(h.data_ptr(), ga.data_ptr(), dtype_code(h, "h"), rows, Hd, gh.data_ptr(), _ptr(act), _ptr(dbias),
+                   _ptr(ws), nbytes, stream)
+    _check(rc, "tome_gelu_erf_backward")
+    return gh, act, dbias
 
 
 def tubelet_rows_ok(x: torch.Tensor, kt: int, kh: int, kw: int) -> bool:

@@ -12,7 +12,7 @@ from typing import Callable, Dict, Tuple
 
 import torch
 
-from .. import _ln, _overlap
+from .. import _ln, _mlp, _overlap
 from ..merge import (bipartite_soft_matching, bipartite_soft_matching_drop, bipartite_soft_matching_hybrid,
                      merge_source, merge_wavg)
 from ..utils import parse_r
@@ -249,6 +249,31 @@ def _plain_mlp(mlp) -> bool:
             and set(dict(mlp.named_children())) <= {"fc1", "act", "fc2", "drop", "drop1", "drop2"})
 
 
+def _trainable_mlp(mlp) -> bool:
+    """_plain_mlp for the training path (tome/_mlp.py): the same stock modules, unhooked, the same set of children -- and
+    a module in `.train()` mode as well, when every nn.Dropout child has p == 0 (then the dropouts are the identity).
+    A dropout is live by its OWN `.training` flag, the one its forward reads, whatever mode the MLP itself is in."""
+    act = getattr(mlp, "act", None)
+    fc1, fc2 = getattr(mlp, "fc1", None), getattr(mlp, "fc2", None)
+    children = dict(mlp.named_children())
+    return (act is not None and _stock_module(act, torch.nn.GELU) and getattr(act, "approximate", "none") == "none"
+            and fc1 is not None and _stock_module(fc1, torch.nn.Linear)
+            and fc2 is not None and _stock_module(fc2, torch.nn.Linear)
+            and not mlp._forward_hooks and not mlp._forward_pre_hooks
+            and set(children) <= {"fc1", "act", "fc2", "drop", "drop1", "drop2"}
+            and all(_stock_module(m, torch.nn.Dropout) and (m.p == 0 or not m.training)
+                    for k, m in children.items() if k.startswith("drop")))
+
+
+def _native_mlp(mlp, x, y, info) -> bool:
+    """Does `mlp(y)` run as the native Function (tome/_mlp.py)?  Tokens or parameters that require grad, an MLP the
+    kernels take, and no folded bias waiting in the residual stream x (that one belongs to finish_linear)."""
+    if not (_GELU_KERNEL and torch.is_grad_enabled() and _trainable_mlp(mlp) and _mlp.wants(mlp, y)):
+        return False
+    folded = None if info is None else info.get("_folded")
+    return folded is None or folded[0] is not x
+
+
 def mlp_hidden(mlp, y):
     """fc1 and the activation of a plain MLP: the tensor its fc2 reads.  The activation runs on tome_gelu_erf (same
     bits as the framework's kernel, non-temporal streaming: 394 -> ~350 us at batch 128)."""
@@ -261,6 +286,8 @@ def mlp_hidden(mlp, y):
 
 def run_mlp(mlp, y):
     """`self.mlp(y)` of the patched block (tome/patch/videomae.py:29); anything but a plain MLP is called as it is."""
+    if _native_mlp(mlp, None, y, None):
+        return _mlp.mlp_native(mlp, y)
     if _plain_mlp(mlp):
         return mlp.fc2(mlp_hidden(mlp, y))
     return mlp(y)
@@ -279,6 +306,12 @@ def foldable(linear, eval_mode: bool = True):
 def mlp_residual(block, mlp, x, y, info, scale=None, drop_path=None):
     """`x + drop_path(scale * mlp(y))` at the end of a patched block (tome/patch/videomae.py:28-29,
     timesformer.py:57, motionformer.py:30), with the next block's first norm handed over (finish_block)."""
+    if _native_mlp(mlp, x, y, info):
+        # tokens or parameters that require grad: the MLP as one Function with tome_gelu_erf_backward between its GEMMs
+        y = _mlp.mlp_native(mlp, y)
+        if scale is not None:
+            y = scale * y
+        return finish_block(block, x, y if drop_path is None else drop_path(y), info)
     if _plain_mlp(mlp) and scale is None and (drop_path is None or not block.training):
         return finish_linear(block, x, mlp_hidden(mlp, y), mlp.fc2, info)
     if info.get("_folded") is not None and info["_folded"][0] is x:
