@@ -342,6 +342,26 @@ int tome_layernorm_backward(const void *gy, const void *xs, const void *gx_in, i
                             void *dweight, void *dbias, void *workspace, tome_stream_t stream);
 
 /*
+ * tome_layernorm_backward_regrouped  <-  what autograd derives from the middle of TimeSformer's divided space-time
+ *     ToMeBlock.forward (tome/patch/timesformer.py:24-38) when the tokens require grad (additions to ABI v11, no entry
+ *     changed; models are patched for training, tools/train_net.py:727-741): the backward of
+ *     tome_add_layernorm_regrouped.  xs is that entry's x_out [B, 1 + P*F, C], the stored rows it normalised; gx_in (or
+ *     NULL) and gx have the same layout; gy [B*F, 1 + P, C] is the gradient of the regrouped, normalised tensor.
+ *         token row 1 + p*F + t of clip b reads row (b*F + t)(1 + P) + 1 + p of gy;
+ *         a clip's class row, which the forward stored F times, takes the fp32 sum of rows (b*F + t)(1 + P) of gy in
+ *         frame order t = 0 .. F-1, not rounded (what `expand`'s backward computes, with F - 1 fewer roundings), and
+ *         enters gx, dweight and dbias once;
+ *     then tome_layernorm_backward's formula, statistics recomputed from xs, one rounding.  The gradient of the addend
+ *     is the view gx[:, 1:], that of x is gx: no pass of its own.  Parameter gradients, workspace
+ *     (tome_layernorm_backward_regrouped_workspace_bytes(B, F, P, C); 0 for an illegal shape), frozen LayerNorm, limits
+ *     on C and alignment as in tome_layernorm_backward; at most 2^31 - 1 rows on either side.
+ */
+size_t tome_layernorm_backward_regrouped_workspace_bytes(int64_t B, int64_t F, int64_t P, int64_t C);
+int tome_layernorm_backward_regrouped(const void *gy, const void *xs, const void *gx_in, int dtype, int64_t B, int64_t F,
+                                      int64_t P, int64_t C, const void *weight, float eps, void *gx, void *dweight,
+                                      void *dbias, void *workspace, tome_stream_t stream);
+
+/*
  * tome_prop_attention_backward  <-  what autograd derives from the proportional attention of the patched blocks when
  *     q, k or v require grad (additions to ABI v11, no entry changed; models are patched for training,
  *     tools/train_net.py:727-741):
@@ -369,6 +389,28 @@ int tome_prop_attention_backward(const void *q, const void *k, const void *v, co
                                  int64_t log_size_stride, int bias_skip, float scale, void *dq, void *dk, void *dv,
                                  const int64_t *dq_strides, const int64_t *dk_strides, const int64_t *dv_strides,
                                  void *workspace, size_t workspace_bytes, tome_stream_t stream);
+
+/*
+ * tome_short_attention_backward  <-  what autograd derives from `self.temporal_attn(...)` in ToMeBlock.forward of the
+ *     TimeSformer patch (tome/patch/timesformer.py:25-27) when the qkv projection requires grad (additions to ABI v11,
+ *     no entry changed; models are patched for training, tools/train_net.py:727-741): the backward of
+ *     tome_short_attention.  With P = softmax(q k^T * scale) recomputed with the forward's definition of the logits
+ *     (packed 2-element dot products, scale * log2 e, exp2):
+ *         dP = dO V^T,  delta_i = sum_j P_ij dP_ij,  dS = P o (dP - delta),  dQ = scale dS K,  dK = scale dS^T Q,
+ *         dV = P^T dO
+ *     fp32 throughout, one rounding per output; delta comes from the recomputed P, so the forward's output is not read
+ *     and the forward saves nothing.  One launch, no workspace, no atomics, same bits on every run.
+ *     q, k, v: as in tome_short_attention ([B, H, N <= 8, 64] views, head stride 64, 16-byte aligned rows); dout
+ *     [B, N, H*64] contiguous, the layout the forward writes; dq, dk, dv: views with the same kind of strides -- the
+ *     three slices of one [B, N, 3, H, 64] buffer are a legal target.  Every one of the 64 channels of every row is
+ *     written exactly once and nothing else is, so the targets need no initialisation; their rows must not overlap.
+ *     TOME_BF16 / TOME_F16 and D = 64 only; anything else is TOME_EINVAL with a message.
+ */
+int tome_short_attention_backward(const void *q, const void *k, const void *v, const void *dout, int dtype, int64_t B,
+                                  int64_t H, int64_t N, int64_t D, const int64_t *q_strides, const int64_t *k_strides,
+                                  const int64_t *v_strides, float scale, void *dq, void *dk, void *dv,
+                                  const int64_t *dq_strides, const int64_t *dk_strides, const int64_t *dv_strides,
+                                  tome_stream_t stream);
 
 /* tome_gelu_erf  <-  the activation of the MLP the patched block calls between merge and second residual
  * (`x = x + self.drop_path(self.mlp(self.norm2(x)))`, tome/patch/videomae.py:29, timesformer.py:56,

@@ -3,7 +3,7 @@
 // -ffp-contract=off -shared -fPIC (csrc/build.py).  No torch, no CUDA, no portability layer.
 //
 // One translation unit: tome_common.h (types), tome_match.h, tome_merge.h, tome_merge_bwd.h, tome_ln_bwd.h,
-// tome_gelu_bwd.h and tome_partition.h (kernels), this file (host).
+// tome_gelu_bwd.h, tome_short_attn_bwd.h and tome_partition.h (kernels), this file (host).
 //
 // Launch sequence of one matching (tome_match / tome_match_keys), kernels in tome_match.h:
 //   k_unit_rows[_heads]  keys -> fp32 unit vectors, even/odd split, MFMA-fragment order (HBM bound)
@@ -22,6 +22,11 @@
 //   k_ln_rows_bwd        gx = gx_in + rstd (gw - mean gw - xhat mean(gw xhat)), statistics recomputed from the stored
 //                        rows; per-workgroup partial rows of dweight / dbias                    (HBM bound)
 //   k_ln_param_grad      the partial rows summed in a fixed order
+//   k_ln_rows_bwd<REGROUP>  the same behind TimeSformer's mid-block regrouping (tome_layernorm_backward_regrouped): the
+//                        row map in front of gy, a class row's F gradients summed in fp32              (HBM bound)
+// and of TimeSformer's temporal attention (tome_short_attention_backward), tome_short_attn_bwd.h:
+//   k_short_attention_bwd  P recomputed, dq / dk / dv of sequences of <= 8 tokens in one pass, eight lanes per
+//                        (sequence, head), dk / dv accumulated in registers                           (HBM bound)
 // and of the MLP's backward between its two library GEMMs (tome_gelu_erf_backward), tome_gelu_bwd.h:
 //   k_gelu_bwd           gh = ga (Phi(h) + h phi(h)), the activation again with the forward's bits, per-workgroup
 //                        partial rows of fc1's bias gradient (summed by k_ln_param_grad)        (HBM bound)
@@ -55,6 +60,7 @@
 #include "tome_attn_stream.h"
 #include "tome_attn_resident.h"
 #include "tome_attn_bwd.h"
+#include "tome_short_attn_bwd.h"
 #include "tome_embed.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -842,6 +848,61 @@ extern "C" int tome_layernorm_backward(const void *gy, const void *xs, const voi
     }, [&] { return fail(TOME_EINVAL, "tome_layernorm_backward: 16-bit tokens only"); });
 }
 
+// tome_layernorm_backward_regrouped: the same kernel and launch form over the B (1 + P F) token rows, with the row map of
+// tome_add_layernorm_regrouped in front of gy (k_ln_rows_bwd<.., REGROUP>).
+static bool ln_bwd_regrouped_shape_ok(int64_t B, int64_t F, int64_t P, int64_t C) {
+    if (B <= 0 || F <= 0 || P <= 0 || B > 0x7fffffffLL || F > 0x7fffffffLL || P > 0x7fffffffLL) return false;
+    if (P * F >= 0x7fffffffLL) return false;
+    const int64_t rows = B * (1 + P * F), gy_rows = B * F * (1 + P);
+    return gy_rows <= 0x7fffffffLL && ln_bwd_shape_ok(rows, C);
+}
+
+extern "C" size_t tome_layernorm_backward_regrouped_workspace_bytes(int64_t B, int64_t F, int64_t P, int64_t C) {
+    if (!ln_bwd_regrouped_shape_ok(B, F, P, C)) return 0;
+    return align_up((size_t)ln_bwd_form(B * (1 + P * F), C).parts * 2 * (size_t)C * sizeof(float), 256);
+}
+
+extern "C" int tome_layernorm_backward_regrouped(const void *gy, const void *xs, const void *gx_in, int dtype, int64_t B,
+                                                 int64_t F, int64_t P, int64_t C, const void *weight, float eps,
+                                                 void *gx, void *dweight, void *dbias, void *workspace,
+                                                 tome_stream_t stream) {
+    if (!gy || !xs || !weight || !gx) return fail(TOME_EINVAL, "tome_layernorm_backward_regrouped: null buffer");
+    if (dtype != TOME_BF16 && dtype != TOME_F16)
+        return fail(TOME_EINVAL, "tome_layernorm_backward_regrouped: 16-bit tokens only");
+    if (!ln_bwd_regrouped_shape_ok(B, F, P, C))
+        return fail(TOME_EINVAL, "tome_layernorm_backward_regrouped: C %% 8 == 0, C <= 1024, B, F, P >= 1 and at most "
+                                 "2^31 - 1 rows on either side required");
+    if (!aligned16(gy) || !aligned16(xs) || !aligned16(gx_in) || !aligned16(weight) || !aligned16(gx) ||
+        !aligned16(workspace))
+        return fail(TOME_EINVAL, "tome_layernorm_backward_regrouped: 16-byte aligned buffers required");
+    const bool params = dweight || dbias;
+    if (params && !workspace)
+        return fail(TOME_EWORKSPACE, "tome_layernorm_backward_regrouped: parameter gradients need a workspace of "
+                                     "tome_layernorm_backward_regrouped_workspace_bytes()");
+    const int64_t rows = B * (1 + P * F), gy_rows = B * F * (1 + P), cpr = C / 8;
+    const LnBwdForm f = ln_bwd_form(rows, C);
+    hipStream_t st = (hipStream_t)stream;
+    return dispatch_x<false>(dtype, [&](auto tx) {
+        using TX = typename decltype(tx)::type;
+        if (params) {
+            hipLaunchKernelGGL((k_ln_rows_bwd<TX, 3, true, true>), dim3((unsigned)f.parts), dim3(256), 0, st,
+                               (const TX *)gy, (const TX *)xs, (const TX *)gx_in, (const TX *)weight, (int)rows,
+                               (int)gy_rows, (int)C, f.R, (int)cpr, eps, 0, (int)f.spw, (TX *)gx, (float *)workspace,
+                               (int)F, (int)P);
+            if (int rc = check_launch("k_ln_rows_bwd")) return rc;
+            hipLaunchKernelGGL((k_ln_param_grad<TX>), dim3((unsigned)((2 * C + WAVE - 1) / WAVE)),
+                               dim3(LN_PG_RUNS * WAVE), 0, st, (const float *)workspace, (int)f.parts, (int)(2 * C),
+                               (int)C, (TX *)dweight, (TX *)dbias);
+            return check_launch("k_ln_param_grad");
+        }
+        // frozen LayerNorm: one slab per wave, no column sums, no workspace
+        hipLaunchKernelGGL((k_ln_rows_bwd<TX, 3, false, true>), dim3((unsigned)f.wgs), dim3(256), 0, st, (const TX *)gy,
+                           (const TX *)xs, (const TX *)gx_in, (const TX *)weight, (int)rows, (int)gy_rows, (int)C, f.R,
+                           (int)cpr, eps, 0, 1, (TX *)gx, (float *)nullptr, (int)F, (int)P);
+        return check_launch("k_ln_rows_bwd");
+    }, [&] { return fail(TOME_EINVAL, "tome_layernorm_backward_regrouped: 16-bit tokens only"); });
+}
+
 extern "C" int tome_merge(const void *x, int dtype, int64_t n, int64_t T, int64_t C, int64_t r,
                           const int64_t *src_idx, const int64_t *dst_idx, const int64_t *unm_idx, int distill_token,
                           int mode, const uint8_t *edge_keep, void *out, tome_stream_t stream) {
@@ -1182,6 +1243,49 @@ extern "C" int tome_short_attention(const void *q, const void *k, const void *v,
                            (const f16_t *)k, (const f16_t *)v, q_strides[0], q_strides[2], k_strides[0], k_strides[2],
                            v_strides[0], v_strides[2], units, (int)H, (int)N, scale, (f16_t *)out);
     return check_launch("k_short_attention");
+}
+
+extern "C" int tome_short_attention_backward(const void *q, const void *k, const void *v, const void *dout, int dtype,
+                                             int64_t B, int64_t H, int64_t N, int64_t D, const int64_t *q_strides,
+                                             const int64_t *k_strides, const int64_t *v_strides, float scale, void *dq,
+                                             void *dk, void *dv, const int64_t *dq_strides, const int64_t *dk_strides,
+                                             const int64_t *dv_strides, tome_stream_t stream) {
+    if (!q || !k || !v || !dout || !dq || !dk || !dv || !q_strides || !k_strides || !v_strides || !dq_strides ||
+        !dk_strides || !dv_strides || B <= 0 || H <= 0 || N <= 0)
+        return fail(TOME_EINVAL, "tome_short_attention_backward: bad shape/pointer");
+    if (D != 64 || N > SHORT_MAXN)
+        return fail(TOME_EINVAL, "tome_short_attention_backward: head dim 64 and at most %d tokens per sequence",
+                    SHORT_MAXN);
+    if (dtype != TOME_BF16 && dtype != TOME_F16)
+        return fail(TOME_EINVAL, "tome_short_attention_backward: 16-bit tensors only");
+    // {batch, head, token} element strides; the heads of a token lie side by side (head stride 64), rows 16-byte aligned
+    const int64_t *strides[6] = {q_strides, k_strides, v_strides, dq_strides, dk_strides, dv_strides};
+    for (int i = 0; i < 6; ++i)
+        if (strides[i][1] != 64 || strides[i][0] % 8 || strides[i][2] % 8)
+            return fail(TOME_EINVAL,
+                        "tome_short_attention_backward: head stride must be 64, batch / token strides multiples of 8");
+    // a target's rows must not lie on top of each other: a token's H heads fill H * 64 elements
+    for (int i = 3; i < 6; ++i)
+        if ((B > 1 && strides[i][0] < H * 64) || (N > 1 && strides[i][2] < H * 64))
+            return fail(TOME_EINVAL, "tome_short_attention_backward: rows of dq / dk / dv overlap");
+    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(dout) || !aligned16(dq) || !aligned16(dk) ||
+        !aligned16(dv))
+        return fail(TOME_EINVAL, "tome_short_attention_backward: rows must be 16-byte aligned");
+    const int64_t units = B * H;  // (sequence, head) pairs, eight lanes each
+    const int64_t blocks = (units + 31) / 32;
+    if (blocks > 0x7fffffffLL) return fail(TOME_EINVAL, "tome_short_attention_backward: too many sequences");
+    const ShortBwdStrides s{q_strides[0],  q_strides[2],  k_strides[0],  k_strides[2],  v_strides[0],  v_strides[2],
+                            dq_strides[0], dq_strides[2], dk_strides[0], dk_strides[2], dv_strides[0], dv_strides[2]};
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == TOME_BF16)
+        hipLaunchKernelGGL(k_short_attention_bwd<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, st, (const bf16_t *)q,
+                           (const bf16_t *)k, (const bf16_t *)v, (const bf16_t *)dout, s, units, (int)H, (int)N, scale,
+                           (bf16_t *)dq, (bf16_t *)dk, (bf16_t *)dv);
+    else
+        hipLaunchKernelGGL(k_short_attention_bwd<f16_t>, dim3((unsigned)blocks), dim3(256), 0, st, (const f16_t *)q,
+                           (const f16_t *)k, (const f16_t *)v, (const f16_t *)dout, s, units, (int)H, (int)N, scale,
+                           (f16_t *)dq, (f16_t *)dk, (f16_t *)dv);
+    return check_launch("k_short_attention_bwd");
 }
 
 extern "C" int tome_gelu_erf(const void *x, int dtype, int64_t elements, void *y, tome_stream_t stream) {

@@ -20,13 +20,20 @@
 // same channels in every slab, so the column sums live in registers.  At the end the four waves' slots are combined
 // through LDS in the order wave 0..3, row-in-wave 0..R-1, and the workgroup writes ONE partial row [2, C] of fp32 to
 // ws[blockIdx.x].  k_ln_param_grad sums the partial rows.  Same bits on every run.
+// REGROUP (backward of tome_add_layernorm_regrouped, the middle of TimeSformer's divided space-time block,
+// tome/patch/timesformer.py:24-38): xs / gx_in / gx are token rows [B, 1 + P*F, C], gy is the gradient of the regrouped
+// tensor [B*F, 1 + P, C].  Only the row map differs: token row 1 + p*F + t of clip b reads row (b*F + t)(1 + P) + 1 + p
+// of gy; a clip's class row, which the forward stored F times, takes the fp32 sum of rows (b*F + t)(1 + P) in frame
+// order t = 0 .. F-1 (what autograd's `expand` backward computes, without its F - 1 roundings) and enters the formula
+// and the parameter gradients once.  The gradient is carried as fp32 (gyf) from the loads on; everything else is the
+// arithmetic above.  The other instantiations do not see any of it.
 // ------------------------------------------------------------------------------------------------
-template <typename TX, int NIT, bool PARAMS>
+template <typename TX, int NIT, bool PARAMS, bool REGROUP = false>
 __global__ __launch_bounds__(256) void k_ln_rows_bwd(const TX *__restrict__ gy, const TX *__restrict__ xs,
                                                      const TX *__restrict__ gx_in, const TX *__restrict__ weight,
                                                      int rows, int gy_rows, int C, int R, int cpr, float eps,
                                                      int group_rows, int spw, TX *__restrict__ gx,
-                                                     float *__restrict__ ws) {
+                                                     float *__restrict__ ws, int F = 0, int P = 0) {
     constexpr int VEC = 8;
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -63,17 +70,34 @@ __global__ __launch_bounds__(256) void k_ln_rows_bwd(const TX *__restrict__ gy, 
 
         // row of gy for each of the wave's rows, -1 for a class row: lanes 0..3, then wave-uniform scalars
         int my_g = row0 + (lane & 3);
-        if (group_rows > 0) {
+        int my_c = 0;  // REGROUP: 1 for a class row, whose gy is the sum of F rows (1 + P) apart, my_g the first
+        if (REGROUP) {
+            const unsigned ntok = 1u + (unsigned)P * (unsigned)F;
+            const unsigned cb = (unsigned)my_g / ntok, ck = (unsigned)my_g - cb * ntok;
+            if (ck == 0u) {
+                my_c = 1;
+                my_g = (int)(cb * (unsigned)F * (1u + (unsigned)P));
+            } else {
+                const unsigned cp = (ck - 1u) / (unsigned)F, ct = (ck - 1u) - cp * (unsigned)F;
+                my_g = (int)((cb * (unsigned)F + ct) * (1u + (unsigned)P) + 1u + cp);
+            }
+        } else if (group_rows > 0) {
             const unsigned gb = (unsigned)my_g / (unsigned)group_rows;
             my_g = ((unsigned)my_g - gb * (unsigned)group_rows == 0u) ? -1 : my_g - (int)gb - 1;
         }
         const int g0 = __builtin_amdgcn_readlane(my_g, 0), g1 = __builtin_amdgcn_readlane(my_g, 1),
                   g2 = __builtin_amdgcn_readlane(my_g, 2), g3 = __builtin_amdgcn_readlane(my_g, 3);
+        int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+        if (REGROUP) {
+            c0 = __builtin_amdgcn_readlane(my_c, 0), c1 = __builtin_amdgcn_readlane(my_c, 1);
+            c2 = __builtin_amdgcn_readlane(my_c, 2), c3 = __builtin_amdgcn_readlane(my_c, 3);
+        }
 
         const uint4 *xsl = reinterpret_cast<const uint4 *>(xs) + (int64_t)row0 * cpr;
         const uint4 *gil = reinterpret_cast<const uint4 *>(has_in ? gx_in : xs) + (int64_t)row0 * cpr;
         uint4 xraw[NIT], graw[NIT], iraw[NIT];
         int rowof[NIT];  // row-in-wave of a live chunk, -1: no chunk; bit 2 set: chunk of a class row
+        float gyf[REGROUP ? NIT : 1][VEC];  // REGROUP: the chunk's gradient in fp32 (a class row's is a sum)
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             const int q = it * WAVE + lane;
@@ -88,6 +112,22 @@ __global__ __launch_bounds__(256) void k_ln_rows_bwd(const TX *__restrict__ gy, 
             graw[it] = ld16(reinterpret_cast<const uint4 *>(gy) + (int64_t)gr * cpr + cc_of[it]);
             if (has_in) iraw[it] = ld16(gil + (live ? q : 0));
             rowof[it] = live ? (g < 0 ? (rr | 4) : rr) : -1;
+            if (REGROUP) {
+                Pack<TX, VEC> pg;
+                __builtin_memcpy(&pg, &graw[it], 16);
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) gyf[it][e] = to_f32(pg.e[e]);
+                const int c = rr == 0 ? c0 : (rr == 1 ? c1 : (rr == 2 ? c2 : c3));
+                if (live && c) {  // class row: frames 1 .. F-1 added in frame order, fp32, nothing rounded
+                    const uint4 *gsrc = reinterpret_cast<const uint4 *>(gy) + (int64_t)gr * cpr + cc_of[it];
+                    for (int t = 1; t < F; ++t) {
+                        const uint4 more = ld16(gsrc + (int64_t)t * (1 + P) * cpr);
+                        __builtin_memcpy(&pg, &more, 16);
+#pragma unroll
+                        for (int e = 0; e < VEC; ++e) gyf[it][e] += to_f32(pg.e[e]);
+                    }
+                }
+            }
         }
 
         // round 1: mean of every row (as ln_rows)
@@ -129,7 +169,7 @@ __global__ __launch_bounds__(256) void k_ln_rows_bwd(const TX *__restrict__ gy, 
 #pragma unroll
             for (int e = 0; e < VEC; ++e) {
                 d[it][e] = to_f32(px.e[e]) - m;
-                const float gwe = to_f32(pg.e[e]) * to_f32(pw.e[e]);
+                const float gwe = (REGROUP ? gyf[it][e] : to_f32(pg.e[e])) * to_f32(pw.e[e]);
                 u = __fmaf_rn(d[it][e], d[it][e], u);
                 sa += gwe;
                 sb = __fmaf_rn(gwe, d[it][e], sb);
@@ -190,7 +230,7 @@ __global__ __launch_bounds__(256) void k_ln_rows_bwd(const TX *__restrict__ gy, 
             __builtin_memcpy(&pw, &wraw[it], 16);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) {
-                const float gyv = to_f32(pg.e[e]);
+                const float gyv = REGROUP ? gyf[it][e] : to_f32(pg.e[e]);
                 const float t = __fmaf_rn(-d[it][e], kk, gyv * to_f32(pw.e[e]) - mg);
                 po.e[e] = from_f32<TX>(has_in ? __fmaf_rn(rs, t, to_f32(pi.e[e])) : rs * t);
                 if (PARAMS) {

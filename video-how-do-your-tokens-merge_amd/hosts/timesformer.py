@@ -10,7 +10,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ._patchify import frame_patch_tokens, patch_tokens, tubelet_tokens  # noqa: F401
-from tome import _abi
+from tome import _abi, _attn
 
 _SHORT_KERNEL = os.environ.get("TOME_SHORT_ATTN", "1") != "0"  # 0 = the framework's attention for the temporal stage
 
@@ -41,11 +41,18 @@ class Attention(nn.Module):
 
     def forward(self, x):
         B, N, C = x.shape
+        live_drop = self.training and self.attn_drop.p > 0.0
         if self.with_qkv:
-            q, k, v = self.qkv(x).reshape(B, N, 3, self.num_heads, C // self.num_heads).permute(2, 0, 3, 1, 4)
+            qkv5 = self.qkv(x).reshape(B, N, 3, self.num_heads, C // self.num_heads)
+            if N <= 8 and _SHORT_KERNEL and torch.is_grad_enabled() and qkv5.requires_grad and not live_drop \
+                    and _attn.short_enabled() and _attn.short_qkv_trainable(qkv5):
+                # the temporal attention under grad: the same launch forward, tome_short_attention_backward behind it
+                # (one launch that fills the qkv gradient buffer: no head transpose, no select_backward passes)
+                return self.proj_drop(self.proj(_attn.short_attention_native(qkv5, self.scale)))
+            q, k, v = qkv5.permute(2, 0, 3, 1, 4)
         else:
             q = k = v = x.reshape(B, N, self.num_heads, C // self.num_heads).permute(0, 2, 1, 3)
-        if N <= 8 and _SHORT_KERNEL and q.is_cuda and not (self.training and self.attn_drop.p > 0.0) \
+        if N <= 8 and _SHORT_KERNEL and q.is_cuda and not live_drop \
                 and _abi.short_attention_ok(q, k, v):
             # the temporal attention: thousands of sequences of T <= 8 tokens -- one streaming pass over q, k, v
             # (tome_short_attention: 5 TB/s; the framework's fused attention + the head transpose run at 2.8)

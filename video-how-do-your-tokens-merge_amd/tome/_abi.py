@@ -27,11 +27,15 @@ SYMBOLS = (
     "tome_layernorm_backward_workspace_bytes", "tome_layernorm_backward",
     "tome_prop_attention_backward_workspace_bytes", "tome_prop_attention_backward",
     "tome_gelu_erf_backward_workspace_bytes", "tome_gelu_erf_backward",
+    "tome_short_attention_backward",
+    "tome_layernorm_backward_regrouped_workspace_bytes", "tome_layernorm_backward_regrouped",
 )
 # entries added to ABI v11 after its first release: a v11 library built before them binds, and says so when one is called
 _LATER_V11 = ("tome_layernorm_backward_workspace_bytes", "tome_layernorm_backward")
 _LATER_V11_ATTN = ("tome_prop_attention_backward_workspace_bytes", "tome_prop_attention_backward")
 _LATER_V11_MLP = ("tome_gelu_erf_backward_workspace_bytes", "tome_gelu_erf_backward")
+_LATER_V11_TIMESFORMER = ("tome_short_attention_backward", "tome_layernorm_backward_regrouped_workspace_bytes",
+                          "tome_layernorm_backward_regrouped")
 
 ABI_VERSION = 11
 DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
@@ -154,6 +158,15 @@ def bind(path: str) -> ctypes.CDLL:
         L.tome_gelu_erf_backward_workspace_bytes.argtypes = [i64, i64]
         L.tome_gelu_erf_backward.restype = i32
         L.tome_gelu_erf_backward.argtypes = [vp, vp, i32, i64, i64, vp, vp, vp, vp, sz, vp]
+    if all(_exports(L, name) for name in _LATER_V11_TIMESFORMER):
+        L.tome_short_attention_backward.restype = i32
+        L.tome_short_attention_backward.argtypes = [vp, vp, vp, vp, i32, i64, i64, i64, i64, vp, vp, vp, ctypes.c_float,
+                                                    vp, vp, vp, vp, vp, vp, vp]
+        L.tome_layernorm_backward_regrouped_workspace_bytes.restype = sz
+        L.tome_layernorm_backward_regrouped_workspace_bytes.argtypes = [i64, i64, i64, i64]
+        L.tome_layernorm_backward_regrouped.restype = i32
+        L.tome_layernorm_backward_regrouped.argtypes = [vp, vp, vp, i32, i64, i64, i64, i64, vp, ctypes.c_float, vp, vp,
+                                                        vp, vp, vp]
     if L.tome_abi_version() != ABI_VERSION:
         raise TomeHipError(f"{os.path.basename(path)} ABI {L.tome_abi_version()} != expected {ABI_VERSION}")
     return L
@@ -442,6 +455,12 @@ def ln_fusable(x: torch.Tensor, norm) -> bool:
             and tuple(norm.normalized_shape) == (C,) and x.dtype in (torch.bfloat16, torch.float16)
             and norm.weight.dtype == x.dtype and C % 8 == 0 and C <= 1024 and x.is_cuda
             and not (torch.is_grad_enabled() and (x.requires_grad or norm.weight.requires_grad)))
+
+
+def ln_regrouped_trainable(x: torch.Tensor, norm) -> bool:
+    """Can tome_add_layernorm_regrouped run on x with tome_layernorm_backward_regrouped behind it (tome/_ln.py) when x
+    or the LayerNorm's parameters require grad?  ln_trainable and nothing more."""
+    return ln_trainable(x, norm)
 
 
 def ln_trainable(x: torch.Tensor, norm) -> bool:
@@ -876,6 +895,55 @@ def short_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: fl
     return out
 
 
+def short_attention_trainable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> bool:
+    """short_attention_ok without its grad clause: can tome_short_attention run on these heads with
+    tome_short_attention_backward behind it (tome/_attn.py) when they require grad?  q, k, v that alias one tensor
+    (with_qkv=False) are refused: their three gradients would have to be summed."""
+    def ok(t):
+        return (t.is_cuda and t.dim() == 4 and t.shape == q.shape and t.dtype == q.dtype and t.device == q.device
+                and t.stride(3) == 1 and t.stride(1) == 64 and t.stride(0) % 8 == 0 and t.stride(2) % 8 == 0
+                and t.data_ptr() % 16 == 0)
+    return (q.dim() == 4 and q.dtype in (torch.bfloat16, torch.float16) and q.shape[-1] == 64 and 1 <= q.shape[2] <= 8
+            and ok(q) and ok(k) and ok(v)
+            and len({q.data_ptr(), k.data_ptr(), v.data_ptr()}) == 3)
+
+
+def short_attention_backward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, dout: torch.Tensor, scale: float,
+                             grads=None):
+    """tome_short_attention_backward: (dq, dk, dv) of out = short_attention(q, k, v, scale) given dout [B, N, H*64].
+    q, k, v: the [B, H, N <= 8, 64] head views the forward took.  grads: three head views to write into (the slices of
+    one [B, N, 3, H, 64] buffer, say; every element of them is written), or None for fresh tensors.  No CPU path."""
+    for t, name in ((q, "q"), (k, "k"), (v, "v")):
+        require_device(t, f"short_attention_backward({name})")
+    if not short_attention_trainable(q, k, v):
+        raise TomeHipError(f"short_attention_backward: q, k, v must be three distinct [B, H, N <= 8, 64] 16-bit views with "
+                           f"head stride 64 and 16-byte aligned rows, got {tuple(q.shape)} {q.dtype} strides {q.stride()}")
+    B, H, N, D = q.shape
+    if tuple(dout.shape) != (B, N, H * D) or dout.device != q.device:
+        raise TomeHipError(f"short_attention_backward: dout must be {(B, N, H * D)} on {q.device}, got {tuple(dout.shape)}")
+    dout = dout.detach()
+    if dout.dtype != q.dtype:
+        dout = dout.to(q.dtype)
+    if not dout.is_contiguous() or dout.data_ptr() % 16:
+        dout = dout.contiguous()
+    if grads is None:
+        dq, dk, dv = (torch.empty((B, N, H, D), dtype=q.dtype, device=q.device).permute(0, 2, 1, 3) for _ in range(3))
+    else:
+        dq, dk, dv = grads
+        for t, name in ((dq, "dq"), (dk, "dk"), (dv, "dv")):
+            if (t.shape != q.shape or t.dtype != q.dtype or t.device != q.device or t.stride(3) != 1 or t.stride(1) != 64
+                    or t.stride(0) % 8 or t.stride(2) % 8 or t.data_ptr() % 16):
+                raise TomeHipError(f"short_attention_backward: {name} must be a {tuple(q.shape)} {q.dtype} head view with "
+                                   "head stride 64 and 16-byte aligned rows")
+    entry = require_symbol(lib(), "tome_short_attention_backward")
+    with _on_device(q.device):
+        rc = entry(q.data_ptr(), k.data_ptr(), v.data_ptr(), dout.data_ptr(), dtype_code(q, "q"), B, H, N, D,
+                   _head_strides(q), _head_strides(k), _head_strides(v), float(scale), dq.data_ptr(), dk.data_ptr(),
+                   dv.data_ptr(), _head_strides(dq), _head_strides(dk), _head_strides(dv), _stream(q.device))
+    _check(rc, "tome_short_attention_backward")
+    return dq, dk, dv
+
+
 def trajectory_mix_ok(q2: torch.Tensor, k2: torch.Tensor, val: torch.Tensor, heads: int) -> bool:
     """Can tome_trajectory_mix take these?  q2 [B, S, C], k2 / val [B, S, F, C] views (rows contiguous over C,
     (b, s, f) rows evenly spaced), 16-bit, head dim 64, at most 16 heads and 8 frames."""
@@ -1190,6 +1258,50 @@ def layernorm_backward(gy: torch.Tensor, xs: torch.Tensor, gx_in: Optional[torch
                    int(bool(skip_first)), C, weight.data_ptr(), float(eps), gx.data_ptr(), _ptr(dweight), _ptr(dbias),
                    _ptr(ws), stream)
     _check(rc, "tome_layernorm_backward")
+    return gx, dweight, dbias
+
+
+def layernorm_backward_regrouped(gy: torch.Tensor, xs: torch.Tensor, gx_in: Optional[torch.Tensor], frames: int,
+                                 weight: torch.Tensor, eps: float, want_weight: bool = True, want_bias: bool = True):
+    """tome_layernorm_backward_regrouped: the backward of add_layernorm_regrouped.  xs [B, 1 + P*F, C]: the x1 that
+    call returned (the stored rows it normalised); gy [B*F, 1 + P, C]: the gradient of its regrouped, normalised output;
+    gx_in: optional gradient that reaches xs directly, xs's shape.  Returns (gx, dweight, dbias), gx of xs's shape (the
+    addend's gradient is gx[:, 1:]); a gradient that is not wanted is None.  No CPU path."""
+    require_device(xs, "layernorm_backward_regrouped(xs)")
+    if xs.dtype not in (torch.bfloat16, torch.float16):
+        raise TomeHipError(f"layernorm_backward_regrouped: 16-bit tokens only, got {xs.dtype}")
+    F = int(frames)
+    if xs.dim() != 3 or F < 1 or xs.shape[1] < 1 + F or (xs.shape[1] - 1) % F or xs.shape[0] < 1:
+        raise TomeHipError(f"layernorm_backward_regrouped: xs {tuple(xs.shape)} does not hold a class token and {F} "
+                           "frames of tokens")
+    B, N, C = xs.shape
+    P = (N - 1) // F
+    if C % 8 or C > 1024:
+        raise TomeHipError(f"layernorm_backward_regrouped: C % 8 == 0 and C <= 1024 required, got {C}")
+    if weight.numel() != C or weight.dtype != xs.dtype or weight.device != xs.device:
+        raise TomeHipError(f"layernorm_backward_regrouped: weight must hold {C} values of {xs.dtype} on {xs.device}")
+    gy = _prep_grad(gy, (B * F, 1 + P, C), xs.dtype, xs.device, "layernorm_backward_regrouped(gy)")
+    if gx_in is not None:
+        gx_in = _prep_grad(gx_in, tuple(xs.shape), xs.dtype, xs.device, "layernorm_backward_regrouped(gx_in)")
+    xs = xs.detach()
+    xs = xs if xs.is_contiguous() else xs.contiguous()
+    weight = weight.detach().contiguous()
+    L = lib()
+    entry = require_symbol(L, "tome_layernorm_backward_regrouped")
+    gx = torch.empty_like(xs)
+    dweight = torch.empty(C, dtype=xs.dtype, device=xs.device) if want_weight else None
+    dbias = torch.empty(C, dtype=xs.dtype, device=xs.device) if want_bias else None
+    with _on_device(xs.device):
+        stream = _stream(xs.device)
+        ws = None
+        if want_weight or want_bias:
+            nbytes = require_symbol(L, "tome_layernorm_backward_regrouped_workspace_bytes")(B, F, P, C)
+            if nbytes == 0:
+                raise TomeHipError(f"layernorm_backward_regrouped: no workspace size for {(B, F, P, C)}")
+            ws = _workspace(xs.device, stream, nbytes)
+        rc = entry(gy.data_ptr(), xs.data_ptr(), _ptr(gx_in), dtype_code(xs, "xs"), B, F, P, C, weight.data_ptr(),
+                   float(eps), gx.data_ptr(), _ptr(dweight), _ptr(dbias), _ptr(ws), stream)
+    _check(rc, "tome_layernorm_backward_regrouped")
     return gx, dweight, dbias
 
 

@@ -5,13 +5,18 @@ tome_prop_attention_backward (csrc/tome_attn_bwd.h).
     attention_native(q, k, v, size, scale, bias_skip=False)   -> [B, N, H*64]      q, k, v: [B, H, N, 64] head views
     attention_qkv_native(qkv, size, scale, bias_skip=False)   -> [B, N, H*64]      qkv: the [3, B, H, N, 64] view of one
                                                                                    [B, N, 3, H, 64] projection output
+    short_attention_native(qkv5, scale)                       -> [B, N, H*64]      qkv5: the [B, N <= 8, 3, H, 64] projection
+                                                                                   output itself (TimeSformer's temporal
+                                                                                   attention, no size bias)
 
 The backward recomputes the softmax from q, k and the size bias (row maximum and sum included), so the forward saves
 nothing but its inputs and the tensor it returns anyway.  `size` gets no gradient.  The qkv form
 takes the projection's buffer as its single differentiable input and returns one gradient buffer of that layout, whose
 three slices the kernels write directly: autograd's three select_backward passes (zero-fill and add, three times the
 token tensor per layer) never run.  Not covered (they keep the framework's ops: DESIGN.md section 7): dropout > 0,
-fp32 heads, head dim != 64, the segmented and short forms, double backward (raises).
+fp32 heads, head dim != 64, the segmented form, double backward (raises).  The short form (sequences of at most 8
+tokens) has a backward of its own, tome_short_attention_backward (csrc/tome_short_attn_bwd.h): one launch that
+recomputes the softmax and writes the three slices of one gradient buffer.
 """
 from __future__ import annotations
 
@@ -24,6 +29,17 @@ from . import _abi
 # tools/attn_backward_bench.py.  Also off when tome.merge.NATIVE_BACKWARD is off.  On by default: faster than the framework path
 # at every measured shape.
 NATIVE_ATTN_BACKWARD = True
+
+
+# False: `hosts/timesformer.py::Attention.forward` keeps the framework's scaled_dot_product_attention and autograd for a
+# temporal attention that requires grad (the behaviour before tome_short_attention_backward existed) -- for A/B in tests
+# and tools/timesformer_backward_bench.py.  Effective only while enabled() below holds too, so that the two older
+# switches still restore the framework path as a whole.  What the default rests on is said in DESIGN.md section 1.
+NATIVE_SHORT_ATTN_BACKWARD = True
+
+
+def short_enabled() -> bool:
+    return bool(NATIVE_SHORT_ATTN_BACKWARD and enabled())
 
 
 def enabled() -> bool:
@@ -117,3 +133,43 @@ def attention_qkv_native(qkv, size, scale: float, bias_skip: bool = False):
         raise _abi.TomeHipError(f"attention_qkv_native: qkv {tuple(qkv.shape)} {qkv.dtype} is not a [3, B, H, N, 64] view "
                                 "the kernels take")
     return _AttentionQKVFunction.apply(qkv, size, float(scale), bool(bias_skip))
+
+
+class _ShortAttentionFunction(torch.autograd.Function):
+    """softmax(q k^T scale) v over sequences of at most 8 tokens, q, k, v the slices of one [B, N, 3, H, 64] projection
+    output: tome_short_attention forward, tome_short_attention_backward backward.  One input, one gradient buffer."""
+
+    @staticmethod
+    def forward(ctx, qkv5, scale):
+        qkv5 = qkv5.detach()
+        q, k, v = qkv5.permute(2, 0, 3, 1, 4).unbind(0)
+        out = _abi.short_attention(q, k, v, scale)
+        ctx.scale = float(scale)
+        ctx.save_for_backward(qkv5)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out):
+        (qkv5,) = ctx.saved_tensors
+        q, k, v = qkv5.permute(2, 0, 3, 1, 4).unbind(0)
+        g = torch.empty_like(qkv5)  # every element is written by the launch below
+        _abi.short_attention_backward(q, k, v, g_out, ctx.scale, grads=tuple(g.permute(2, 0, 3, 1, 4).unbind(0)))
+        return g, None
+
+
+def short_qkv_trainable(qkv5: torch.Tensor) -> bool:
+    """Is `qkv5` a [B, N <= 8, 3, H, 64] projection output whose three slices the short kernels take?"""
+    if qkv5.dim() != 5 or qkv5.shape[2] != 3 or not qkv5.is_contiguous():
+        return False
+    q, k, v = qkv5.permute(2, 0, 3, 1, 4).unbind(0)
+    return _abi.short_attention_trainable(q, k, v)
+
+
+def short_attention_native(qkv5, scale: float):
+    """softmax(q k^T * scale) v for the [B, N <= 8, 3, H, 64] output of a qkv projection that requires grad; returns
+    [B, N, H*64].  The gradient of the buffer comes back as one tensor of its layout."""
+    if not short_qkv_trainable(qkv5):
+        raise _abi.TomeHipError(f"short_attention_native: qkv {tuple(qkv5.shape)} {qkv5.dtype} is not a contiguous "
+                                "[B, N <= 8, 3, H, 64] buffer the kernels take (_abi.short_attention_trainable)")
+    return _ShortAttentionFunction.apply(qkv5, float(scale))

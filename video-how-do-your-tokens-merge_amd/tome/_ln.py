@@ -4,6 +4,7 @@ detached tensors, backward = tome_layernorm_backward (csrc/tome_ln_bwd.h).
 
     add_layernorm_native(x, addend, norm, skip_first=False) -> (x + addend, norm(x + addend))
     layernorm_native(x, norm, skip_first=False)             -> norm(x)
+    add_layernorm_regrouped_native(x, addend, T, norm)      -> (cat(cls, x[:, 1:] + addend), norm of the regrouped tokens)
 
 skip_first (x [B, N, C]): the LayerNorm output leaves out every clip's first row, as `_abi.add_layernorm` does.
 The backward recomputes mean and rstd from the stored sum (the row the forward normalised), so the forward saves
@@ -11,6 +12,8 @@ nothing but the tensors it returns anyway.  The gradient of the sum that arrives
 gradient through the LayerNorm are added inside the one launch and rounded once; x and addend receive the same
 tensor.  Not covered (they keep the framework's ops: DESIGN.md section 7): fp32 tokens, LayerNorms `_abi.ln_trainable`
 refuses, double backward (raises).
+The regrouped form is the middle of TimeSformer's divided space-time block (tome_add_layernorm_regrouped forward,
+tome_layernorm_backward_regrouped backward): x [B, 1 + P*T, C] and addend [B, P*T, C] receive gx and its view gx[:, 1:].
 """
 from __future__ import annotations
 
@@ -22,6 +25,17 @@ from . import _abi
 # the backward kernel existed) -- for A/B in tests and tools/layernorm_backward_bench.py.  Also off when
 # tome.merge.NATIVE_BACKWARD is off.  On by default; what that rests on (measured or not) is said in DESIGN.md section 1.
 NATIVE_LN_BACKWARD = True
+
+
+# False: `tome/patch/timesformer.py::_block_forward` keeps the reference's op sequence (add, transpose, three cats,
+# norm1) and autograd for tokens that require grad (the behaviour before tome_layernorm_backward_regrouped existed) -- for
+# A/B in tests and tools/timesformer_backward_bench.py.  Effective only while enabled() below holds too.  What the default
+# rests on is said in DESIGN.md section 1.
+NATIVE_LN_REGROUPED_BACKWARD = True
+
+
+def regrouped_enabled() -> bool:
+    return bool(NATIVE_LN_REGROUPED_BACKWARD and enabled())
 
 
 def enabled() -> bool:
@@ -40,6 +54,12 @@ def ln_backward(gy, xs, gx_in, weight, eps, skip_first, want_weight, want_bias):
     that a test can put another evaluation of the same formula in its place."""
     return _abi.layernorm_backward(gy, xs, gx_in, weight, eps, skip_first=skip_first, want_weight=want_weight,
                                    want_bias=want_bias)
+
+
+def ln_backward_regrouped(gy, xs, gx_in, frames, weight, eps, want_weight, want_bias):
+    """The backward arithmetic of the regrouped Function: (gx, dweight, dbias).  A seam of its own, like ln_backward."""
+    return _abi.layernorm_backward_regrouped(gy, xs, gx_in, frames, weight, eps, want_weight=want_weight,
+                                             want_bias=want_bias)
 
 
 def _backward(ctx, g_sum, g_y):
@@ -92,6 +112,34 @@ class _LayerNormFunction(torch.autograd.Function):
         return gx, dw, db, None, None
 
 
+class _AddLayerNormRegroupedFunction(torch.autograd.Function):
+    """(cat(cls, x[:, 1:] + addend), LayerNorm of the tokens regrouped 'b (p t) m -> (b t) p m' behind a class token per
+    frame): tome_add_layernorm_regrouped forward, tome_layernorm_backward_regrouped backward."""
+
+    @staticmethod
+    def forward(ctx, x, addend, weight, bias, eps, frames):
+        x1, y = _abi.add_layernorm_regrouped(x.detach(), addend.detach(), frames, weight.detach(), bias.detach(), eps)
+        ctx.eps, ctx.frames = float(eps), int(frames)
+        ctx.save_for_backward(x1, weight)
+        ctx.set_materialize_grads(False)  # an output nobody read arrives as None, not as a tensor of zeros
+        return x1, y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_x1, g_y):
+        x1, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        want_w, want_b = need[2], need[3]
+        if g_y is None:  # nothing read the LayerNorm: the stream's gradient passes through, the parameters get zeros
+            gx, dw, db = g_x1, (torch.zeros_like(weight) if want_w else None), (torch.zeros_like(weight) if want_b else None)
+        else:
+            cast = lambda g: g if g is None or g.dtype == x1.dtype else g.to(x1.dtype)  # noqa: E731
+            gx, dw, db = ln_backward_regrouped(cast(g_y), x1, cast(g_x1), ctx.frames, weight, ctx.eps, want_w, want_b)
+        # x1 = cat(cls, x[:, 1:] + addend): x receives gx, the addend the view behind the class row
+        return ((gx if need[0] and gx is not None else None), (gx[:, 1:] if need[1] and gx is not None else None), dw, db,
+                None, None)
+
+
 def _check(x, norm, what):
     if not _abi.ln_trainable(x, norm):
         raise _abi.TomeHipError(f"{what}: this LayerNorm of {tuple(x.shape)} {x.dtype} tokens is not one the kernels take "
@@ -108,3 +156,13 @@ def layernorm_native(x, norm, skip_first: bool = False):
     """`norm(x)` (`norm(x)[:, 1:]` when skip_first) for tokens that require grad."""
     _check(x, norm, "layernorm_native")
     return _LayerNormFunction.apply(x, norm.weight, norm.bias, norm.eps, bool(skip_first))
+
+
+def add_layernorm_regrouped_native(x, addend, T: int, norm):
+    """TimeSformer's mid-block step for tokens that require grad: x [B, 1 + P*T, C], addend [B, P*T, C] ->
+    (x1, xs_normed) with x1 = cat(cls, x[:, 1:] + addend) and xs_normed = norm of the tokens regrouped
+    'b (p t) m -> (b t) p m' with the class token in front of every frame, [B*T, 1 + P, C]."""
+    if not _abi.ln_regrouped_trainable(x, norm):
+        raise _abi.TomeHipError(f"add_layernorm_regrouped_native: this LayerNorm of {tuple(x.shape)} {x.dtype} tokens is not "
+                                "one the kernels take (_abi.ln_regrouped_trainable)")
+    return _AddLayerNormRegroupedFunction.apply(x, addend, norm.weight, norm.bias, norm.eps, int(T))

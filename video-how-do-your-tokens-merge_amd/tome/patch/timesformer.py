@@ -1,12 +1,17 @@
 """ToMe patch for TimeSformer (reference: tome/patch/timesformer.py).  Divided space-time attention: the
 merge runs per frame on the spatial tokens ('b (p t) m -> (b t) p m'), the class token is kept aside, every
-frame loses the same r tokens so the frame groups stay rectangular."""
+frame loses the same r tokens so the frame groups stay rectangular.
+
+Under grad (models are patched for training, tools/train_net.py:727-741) a divided space-time block stays on the kernels
+from its first LayerNorm to its MLP: temporal_norm1 and norm2 through tome/_ln.py, the temporal attention through
+tome/_attn.py::short_attention_native (hosts/timesformer.py), the middle of the block through
+tome/_ln.py::add_layernorm_regrouped_native, the spatial attention, the merge and the MLP as in the other models."""
 from __future__ import annotations
 
 import torch
 
 from . import _common as C
-from .. import _abi
+from .. import _abi, _ln
 from ..merge import HeadMeanKeys
 
 
@@ -32,6 +37,11 @@ def _block_forward(self, x, B, T, W):
         # and the spatial attention's norm1 -- one pass (tome_add_layernorm_regrouped); the regrouped
         # un-normalised tokens never exist
         x1, xs_normed = _abi.add_layernorm_regrouped(x, rt, T, self.norm1.weight, self.norm1.bias, self.norm1.eps)
+    elif (C._FUSE_NEXT and rt.dtype == x.dtype and torch.is_grad_enabled() and _ln.regrouped_enabled()
+          and _abi.ln_regrouped_trainable(x, self.norm1)):
+        # the same launch under grad (ln_fusable refuses tensors that require grad), with
+        # tome_layernorm_backward_regrouped behind it: x and rt receive gx and its view gx[:, 1:]
+        x1, xs_normed = _ln.add_layernorm_regrouped_native(x, rt, T, self.norm1)
     else:
         if torch.is_grad_enabled() and x.requires_grad:
             # the reference's op sequence (differentiable): add, transpose, three cats
