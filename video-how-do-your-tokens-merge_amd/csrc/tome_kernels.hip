@@ -702,6 +702,20 @@ extern "C" int tome_merge_wavg_regrouped_ln(const void *x, int x_dtype, const vo
                                      has_cls, src_idx, dst_idx, unm_idx, edge_keep, x_out, size_out, log_size_out, &ln, stream);
 }
 
+// Rows per wave of the LayerNorm kernels: `nit` 16-byte chunks per lane, rows of `cpr` chunks, at most FAST_MAXR rows.
+// The backward (ln_bwd_form) recomputes the statistics of the rows the forward normalised and must pick the forward's
+// packing to reproduce its bits: every one of them asks here.
+static inline int ln_rows_per_wave(int64_t cpr, int nit) {
+    const int64_t R = (nit * WAVE) / cpr;
+    return R > FAST_MAXR ? FAST_MAXR : (int)R;
+}
+
+// The dtype test of the entries without an fp32 form: 0 for bf16 / f16, otherwise the error "<who>: 16-bit <what> only"
+static int not_16bit(const char *who, int dtype, const char *what = "tokens") {
+    if (dtype == TOME_BF16 || dtype == TOME_F16) return 0;
+    return fail(TOME_EINVAL, "%s: 16-bit %s only", who, what);
+}
+
 static int add_layernorm_impl(const void *x, const void *addend, int dtype, int64_t rows, int64_t C,
                               const void *ln_weight, const void *ln_bias, float eps, void *x_out, void *y_out,
                               int64_t y_group, tome_stream_t stream);
@@ -728,14 +742,13 @@ static int add_layernorm_impl(const void *x, const void *addend, int dtype, int6
     // addend == NULL: LayerNorm only (y_out = LN(x)); x_out is then neither read nor written and may be NULL
     if (!x || !ln_weight || !ln_bias || (addend && !x_out) || !y_out || rows <= 0 || C <= 0)
         return fail(TOME_EINVAL, "tome_add_layernorm: bad shape/pointer");
-    if (dtype != TOME_BF16 && dtype != TOME_F16) return fail(TOME_EINVAL, "tome_add_layernorm: 16-bit tokens only");
+    if (int rc = not_16bit("tome_add_layernorm", dtype)) return rc;
     const int64_t cpr = C / 8;
     if (C % 8 || cpr > 2 * WAVE || !aligned16(x) || !aligned16(addend) || (addend && !aligned16(x_out)) ||
         !aligned16(y_out) || !aligned16(ln_weight) || !aligned16(ln_bias))
         return fail(TOME_EINVAL, "tome_add_layernorm: C %% 8 == 0, C <= 1024 and 16-byte aligned buffers required");
     const int nit = (cpr <= 3 * WAVE) ? 3 : FAST_NIT;  // 3 chunks per lane: 100.6 us vs 105 us with 6 (batch 64)
-    int R = (int)((nit * WAVE) / cpr);
-    if (R > FAST_MAXR) R = FAST_MAXR;
+    const int R = ln_rows_per_wave(cpr, nit);
     const int64_t waves = (rows + R - 1) / R;
     const LnArgs ln{ln_weight, ln_bias, y_out, eps, nullptr, 0, TokLayout{0, 0, 0, 0, 1}, nullptr, (int)y_group, nullptr};
     const dim3 grid((unsigned)((waves + 3) / 4));
@@ -749,7 +762,7 @@ static int add_layernorm_impl(const void *x, const void *addend, int dtype, int6
             hipLaunchKernelGGL((k_add_ln_rows<TX, FAST_NIT>), grid, dim3(256), 0, st, (const TX *)x, (const TX *)addend,
                                rows, (int)C, R, (int)cpr, ln, (TX *)x_out);
         return check_launch("k_add_ln_rows");
-    }, [&] { return fail(TOME_EINVAL, "tome_add_layernorm: 16-bit tokens only"); });
+    }, [&] { return not_16bit("tome_add_layernorm", dtype); });
 }
 
 extern "C" int tome_add_layernorm_regrouped(const void *x, const void *addend, int dtype, int64_t B, int64_t F, int64_t P,
@@ -757,17 +770,14 @@ extern "C" int tome_add_layernorm_regrouped(const void *x, const void *addend, i
                                             void *x_out, void *y_out, tome_stream_t stream) {
     if (!x || !addend || !x_out || !y_out || !ln_weight || !ln_bias || B <= 0 || F <= 0 || P <= 0 || C <= 0)
         return fail(TOME_EINVAL, "tome_add_layernorm_regrouped: bad shape/pointer");
-    if (dtype != TOME_BF16 && dtype != TOME_F16)
-        return fail(TOME_EINVAL, "tome_add_layernorm_regrouped: 16-bit tokens only");
+    if (int rc = not_16bit("tome_add_layernorm_regrouped", dtype)) return rc;
     const int64_t cpr = C / 8;
     if (C % 8 || cpr > 2 * WAVE || !aligned16(x) || !aligned16(addend) || !aligned16(x_out) || !aligned16(y_out) ||
         !aligned16(ln_weight) || !aligned16(ln_bias))
         return fail(TOME_EINVAL, "tome_add_layernorm_regrouped: C %% 8 == 0, C <= 1024 and 16-byte aligned buffers required");
     const int64_t rows = B * (1 + P * F);
     if (rows > 0x7fffffffLL) return fail(TOME_EINVAL, "tome_add_layernorm_regrouped: too many rows");
-    const int nit = 3;
-    int R = (int)((nit * WAVE) / cpr);
-    if (R > FAST_MAXR) R = FAST_MAXR;
+    const int R = ln_rows_per_wave(cpr, 3);
     if (R < 1) return fail(TOME_EINVAL, "tome_add_layernorm_regrouped: row too wide");
     const int64_t waves = (rows + R - 1) / R;
     const LnArgs ln{ln_weight, ln_bias, y_out, eps, nullptr, 0, TokLayout{0, 0, 0, 0, 1}, nullptr, 0, nullptr};
@@ -778,7 +788,7 @@ extern "C" int tome_add_layernorm_regrouped(const void *x, const void *addend, i
         hipLaunchKernelGGL((k_add_ln_regroup<TX, 3>), grid, dim3(256), 0, st, (const TX *)x, (const TX *)addend, (int)B,
                            (int)F, (int)P, (int)C, R, (int)cpr, ln, (TX *)x_out);
         return check_launch("k_add_ln_regroup");
-    }, [&] { return fail(TOME_EINVAL, "tome_add_layernorm_regrouped: 16-bit tokens only"); });
+    }, [&] { return not_16bit("tome_add_layernorm_regrouped", dtype); });
 }
 
 // The launch form of k_ln_rows_bwd for `rows` rows of C channels: R rows per wave as add_layernorm_impl picks them,
@@ -789,13 +799,20 @@ extern "C" int tome_add_layernorm_regrouped(const void *x, const void *addend, i
 #define LN_BWD_MAX_PARTS 512
 struct LnBwdForm { int R; int64_t wgs; int64_t spw; int64_t parts; };
 static LnBwdForm ln_bwd_form(int64_t rows, int64_t C) {
-    const int64_t cpr = C / 8;
-    int R = (int)((3 * WAVE) / cpr);
-    if (R > FAST_MAXR) R = FAST_MAXR;
+    const int R = ln_rows_per_wave(C / 8, 3);
     const int64_t waves = (rows + R - 1) / R;
     const int64_t wgs = (waves + 3) / 4;
     const int64_t spw = (wgs + LN_BWD_MAX_PARTS - 1) / LN_BWD_MAX_PARTS;
     return LnBwdForm{R, wgs, spw, (wgs + spw - 1) / spw};
+}
+
+// k_ln_param_grad over the `parts` fp32 partial rows [width] of a workspace: columns below `split` to lo, the others to hi
+template <typename TX>
+static int launch_param_grad(const void *ws, int64_t parts, int64_t width, int64_t split, void *lo, void *hi,
+                             hipStream_t st) {
+    hipLaunchKernelGGL((k_ln_param_grad<TX>), dim3((unsigned)((width + WAVE - 1) / WAVE)), dim3(LN_PG_RUNS * WAVE), 0, st,
+                       (const float *)ws, (int)parts, (int)width, (int)split, (TX *)lo, (TX *)hi);
+    return check_launch("k_ln_param_grad");
 }
 
 static bool ln_bwd_shape_ok(int64_t rows, int64_t C) {
@@ -807,45 +824,54 @@ extern "C" size_t tome_layernorm_backward_workspace_bytes(int64_t rows, int64_t 
     return align_up((size_t)ln_bwd_form(rows, C).parts * 2 * (size_t)C * sizeof(float), 256);
 }
 
-extern "C" int tome_layernorm_backward(const void *gy, const void *xs, const void *gx_in, int dtype, int64_t groups,
-                                       int64_t group_rows, int skip_first, int64_t C, const void *weight, float eps,
-                                       void *gx, void *dweight, void *dbias, void *workspace, tome_stream_t stream) {
-    if (!gy || !xs || !weight || !gx) return fail(TOME_EINVAL, "tome_layernorm_backward: null buffer");
-    if (dtype != TOME_BF16 && dtype != TOME_F16) return fail(TOME_EINVAL, "tome_layernorm_backward: 16-bit tokens only");
-    if (groups <= 0 || group_rows <= 0 || group_rows > 0x7fffffffLL || groups > 0x7fffffffLL ||
-        !ln_bwd_shape_ok(groups * group_rows, C))
-        return fail(TOME_EINVAL, "tome_layernorm_backward: C %% 8 == 0, C <= 1024 and 1 .. 2^31 - 1 rows required");
-    if (skip_first && group_rows < 2)
-        return fail(TOME_EINVAL, "tome_layernorm_backward: skip_first needs groups of at least two rows");
+// What the two backward entries share once their shapes are validated: `rows` token rows, `gy_rows` rows of gy, and the
+// row map between them -- group_rows (skip_first, else 0) or REGROUP with F and P.
+template <int REGROUP>
+static int layernorm_backward_impl(Op<REGROUP>, const char *who, const void *gy, const void *xs, const void *gx_in,
+                                   int dtype, int64_t rows, int64_t gy_rows, int64_t group_rows, int64_t F, int64_t P,
+                                   int64_t C, const void *weight, float eps, void *gx, void *dweight, void *dbias,
+                                   void *workspace, tome_stream_t stream) {
     if (!aligned16(gy) || !aligned16(xs) || !aligned16(gx_in) || !aligned16(weight) || !aligned16(gx) ||
         !aligned16(workspace))
-        return fail(TOME_EINVAL, "tome_layernorm_backward: 16-byte aligned buffers required");
+        return fail(TOME_EINVAL, "%s: 16-byte aligned buffers required", who);
     const bool params = dweight || dbias;
     if (params && !workspace)
-        return fail(TOME_EWORKSPACE, "tome_layernorm_backward: parameter gradients need a workspace of "
-                                     "tome_layernorm_backward_workspace_bytes()");
-    const int64_t rows = groups * group_rows, cpr = C / 8;
-    const int64_t gy_rows = skip_first ? groups * (group_rows - 1) : rows;
+        return fail(TOME_EWORKSPACE, "%s: parameter gradients need a workspace of %s_workspace_bytes()", who, who);
+    const int64_t cpr = C / 8;
     const LnBwdForm f = ln_bwd_form(rows, C);
     hipStream_t st = (hipStream_t)stream;
     return dispatch_x<false>(dtype, [&](auto tx) {
         using TX = typename decltype(tx)::type;
         if (params) {
-            hipLaunchKernelGGL((k_ln_rows_bwd<TX, 3, true>), dim3((unsigned)f.parts), dim3(256), 0, st, (const TX *)gy,
-                               (const TX *)xs, (const TX *)gx_in, (const TX *)weight, (int)rows, (int)gy_rows, (int)C, f.R,
-                               (int)cpr, eps, skip_first ? (int)group_rows : 0, (int)f.spw, (TX *)gx, (float *)workspace);
+            hipLaunchKernelGGL((k_ln_rows_bwd<TX, 3, true, REGROUP != 0>), dim3((unsigned)f.parts), dim3(256), 0, st,
+                               (const TX *)gy, (const TX *)xs, (const TX *)gx_in, (const TX *)weight, (int)rows,
+                               (int)gy_rows, (int)C, f.R, (int)cpr, eps, (int)group_rows, (int)f.spw, (TX *)gx,
+                               (float *)workspace, (int)F, (int)P);
             if (int rc = check_launch("k_ln_rows_bwd")) return rc;
-            hipLaunchKernelGGL((k_ln_param_grad<TX>), dim3((unsigned)((2 * C + WAVE - 1) / WAVE)),
-                               dim3(LN_PG_RUNS * WAVE), 0, st, (const float *)workspace, (int)f.parts, (int)(2 * C),
-                               (int)C, (TX *)dweight, (TX *)dbias);
-            return check_launch("k_ln_param_grad");
+            return launch_param_grad<TX>(workspace, f.parts, 2 * C, C, dweight, dbias, st);
         }
         // frozen LayerNorm: one slab per wave, no column sums, no workspace
-        hipLaunchKernelGGL((k_ln_rows_bwd<TX, 3, false>), dim3((unsigned)f.wgs), dim3(256), 0, st, (const TX *)gy,
-                           (const TX *)xs, (const TX *)gx_in, (const TX *)weight, (int)rows, (int)gy_rows, (int)C, f.R,
-                           (int)cpr, eps, skip_first ? (int)group_rows : 0, 1, (TX *)gx, (float *)nullptr);
+        hipLaunchKernelGGL((k_ln_rows_bwd<TX, 3, false, REGROUP != 0>), dim3((unsigned)f.wgs), dim3(256), 0, st,
+                           (const TX *)gy, (const TX *)xs, (const TX *)gx_in, (const TX *)weight, (int)rows, (int)gy_rows,
+                           (int)C, f.R, (int)cpr, eps, (int)group_rows, 1, (TX *)gx, (float *)nullptr, (int)F, (int)P);
         return check_launch("k_ln_rows_bwd");
-    }, [&] { return fail(TOME_EINVAL, "tome_layernorm_backward: 16-bit tokens only"); });
+    }, [&] { return not_16bit(who, dtype); });
+}
+
+extern "C" int tome_layernorm_backward(const void *gy, const void *xs, const void *gx_in, int dtype, int64_t groups,
+                                       int64_t group_rows, int skip_first, int64_t C, const void *weight, float eps,
+                                       void *gx, void *dweight, void *dbias, void *workspace, tome_stream_t stream) {
+    if (!gy || !xs || !weight || !gx) return fail(TOME_EINVAL, "tome_layernorm_backward: null buffer");
+    if (int rc = not_16bit("tome_layernorm_backward", dtype)) return rc;
+    if (groups <= 0 || group_rows <= 0 || group_rows > 0x7fffffffLL || groups > 0x7fffffffLL ||
+        !ln_bwd_shape_ok(groups * group_rows, C))
+        return fail(TOME_EINVAL, "tome_layernorm_backward: C %% 8 == 0, C <= 1024 and 1 .. 2^31 - 1 rows required");
+    if (skip_first && group_rows < 2)
+        return fail(TOME_EINVAL, "tome_layernorm_backward: skip_first needs groups of at least two rows");
+    const int64_t rows = groups * group_rows;
+    return layernorm_backward_impl(Op<0>{}, "tome_layernorm_backward", gy, xs, gx_in, dtype, rows,
+                                   skip_first ? groups * (group_rows - 1) : rows, skip_first ? group_rows : 0, 0, 0, C,
+                                   weight, eps, gx, dweight, dbias, workspace, stream);
 }
 
 // tome_layernorm_backward_regrouped: the same kernel and launch form over the B (1 + P F) token rows, with the row map of
@@ -859,7 +885,7 @@ static bool ln_bwd_regrouped_shape_ok(int64_t B, int64_t F, int64_t P, int64_t C
 
 extern "C" size_t tome_layernorm_backward_regrouped_workspace_bytes(int64_t B, int64_t F, int64_t P, int64_t C) {
     if (!ln_bwd_regrouped_shape_ok(B, F, P, C)) return 0;
-    return align_up((size_t)ln_bwd_form(B * (1 + P * F), C).parts * 2 * (size_t)C * sizeof(float), 256);
+    return tome_layernorm_backward_workspace_bytes(B * (1 + P * F), C);
 }
 
 extern "C" int tome_layernorm_backward_regrouped(const void *gy, const void *xs, const void *gx_in, int dtype, int64_t B,
@@ -867,40 +893,12 @@ extern "C" int tome_layernorm_backward_regrouped(const void *gy, const void *xs,
                                                  void *gx, void *dweight, void *dbias, void *workspace,
                                                  tome_stream_t stream) {
     if (!gy || !xs || !weight || !gx) return fail(TOME_EINVAL, "tome_layernorm_backward_regrouped: null buffer");
-    if (dtype != TOME_BF16 && dtype != TOME_F16)
-        return fail(TOME_EINVAL, "tome_layernorm_backward_regrouped: 16-bit tokens only");
+    if (int rc = not_16bit("tome_layernorm_backward_regrouped", dtype)) return rc;
     if (!ln_bwd_regrouped_shape_ok(B, F, P, C))
         return fail(TOME_EINVAL, "tome_layernorm_backward_regrouped: C %% 8 == 0, C <= 1024, B, F, P >= 1 and at most "
                                  "2^31 - 1 rows on either side required");
-    if (!aligned16(gy) || !aligned16(xs) || !aligned16(gx_in) || !aligned16(weight) || !aligned16(gx) ||
-        !aligned16(workspace))
-        return fail(TOME_EINVAL, "tome_layernorm_backward_regrouped: 16-byte aligned buffers required");
-    const bool params = dweight || dbias;
-    if (params && !workspace)
-        return fail(TOME_EWORKSPACE, "tome_layernorm_backward_regrouped: parameter gradients need a workspace of "
-                                     "tome_layernorm_backward_regrouped_workspace_bytes()");
-    const int64_t rows = B * (1 + P * F), gy_rows = B * F * (1 + P), cpr = C / 8;
-    const LnBwdForm f = ln_bwd_form(rows, C);
-    hipStream_t st = (hipStream_t)stream;
-    return dispatch_x<false>(dtype, [&](auto tx) {
-        using TX = typename decltype(tx)::type;
-        if (params) {
-            hipLaunchKernelGGL((k_ln_rows_bwd<TX, 3, true, true>), dim3((unsigned)f.parts), dim3(256), 0, st,
-                               (const TX *)gy, (const TX *)xs, (const TX *)gx_in, (const TX *)weight, (int)rows,
-                               (int)gy_rows, (int)C, f.R, (int)cpr, eps, 0, (int)f.spw, (TX *)gx, (float *)workspace,
-                               (int)F, (int)P);
-            if (int rc = check_launch("k_ln_rows_bwd")) return rc;
-            hipLaunchKernelGGL((k_ln_param_grad<TX>), dim3((unsigned)((2 * C + WAVE - 1) / WAVE)),
-                               dim3(LN_PG_RUNS * WAVE), 0, st, (const float *)workspace, (int)f.parts, (int)(2 * C),
-                               (int)C, (TX *)dweight, (TX *)dbias);
-            return check_launch("k_ln_param_grad");
-        }
-        // frozen LayerNorm: one slab per wave, no column sums, no workspace
-        hipLaunchKernelGGL((k_ln_rows_bwd<TX, 3, false, true>), dim3((unsigned)f.wgs), dim3(256), 0, st, (const TX *)gy,
-                           (const TX *)xs, (const TX *)gx_in, (const TX *)weight, (int)rows, (int)gy_rows, (int)C, f.R,
-                           (int)cpr, eps, 0, 1, (TX *)gx, (float *)nullptr, (int)F, (int)P);
-        return check_launch("k_ln_rows_bwd");
-    }, [&] { return fail(TOME_EINVAL, "tome_layernorm_backward_regrouped: 16-bit tokens only"); });
+    return layernorm_backward_impl(Op<1>{}, "tome_layernorm_backward_regrouped", gy, xs, gx_in, dtype, B * (1 + P * F),
+                                   B * F * (1 + P), 0, F, P, C, weight, eps, gx, dweight, dbias, workspace, stream);
 }
 
 extern "C" int tome_merge(const void *x, int dtype, int64_t n, int64_t T, int64_t C, int64_t r,
@@ -1124,7 +1122,7 @@ extern "C" int tome_trajectory_mix(const void *q2, const void *k2, const void *v
         return fail(TOME_EINVAL, "tome_trajectory_mix: bad shape/pointer");
     if (D != 64 || H > 16 || F > TRAJ_MAXF)
         return fail(TOME_EINVAL, "tome_trajectory_mix: head dim 64, at most 16 heads and %d frames", TRAJ_MAXF);
-    if (dtype != TOME_BF16 && dtype != TOME_F16) return fail(TOME_EINVAL, "tome_trajectory_mix: 16-bit tensors only");
+    if (int rc = not_16bit("tome_trajectory_mix", dtype, "tensors")) return rc;
     if (k_row_stride % 8 || v_row_stride % 8 || k_row_stride < H * D || v_row_stride < H * D || !aligned16(q2) ||
         !aligned16(k2) || !aligned16(val) || !aligned16(out))
         return fail(TOME_EINVAL, "tome_trajectory_mix: rows must be 16-byte aligned");
@@ -1135,15 +1133,13 @@ extern "C" int tome_trajectory_mix(const void *q2, const void *k2, const void *v
     if (rows > 0x7fffffffLL) return fail(TOME_EINVAL, "tome_trajectory_mix: too many tokens");
     const dim3 grid((unsigned)((rows + 3) / 4));
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == TOME_BF16)
-        hipLaunchKernelGGL(k_trajectory_mix<bf16_t>, grid, dim3(256), 0, st, (const bf16_t *)q2, (const bf16_t *)k2,
-                           (const bf16_t *)val, rows, (int)S, (int)F, (int)H, k_row_stride, v_row_stride, scale,
-                           (bf16_t *)out, out_batch_stride, tattn);
-    else
-        hipLaunchKernelGGL(k_trajectory_mix<f16_t>, grid, dim3(256), 0, st, (const f16_t *)q2, (const f16_t *)k2,
-                           (const f16_t *)val, rows, (int)S, (int)F, (int)H, k_row_stride, v_row_stride, scale,
-                           (f16_t *)out, out_batch_stride, tattn);
-    return check_launch("k_trajectory_mix");
+    return dispatch_x<false>(dtype, [&](auto tx) {
+        using TX = typename decltype(tx)::type;
+        hipLaunchKernelGGL(k_trajectory_mix<TX>, grid, dim3(256), 0, st, (const TX *)q2, (const TX *)k2, (const TX *)val,
+                           rows, (int)S, (int)F, (int)H, k_row_stride, v_row_stride, scale, (TX *)out, out_batch_stride,
+                           tattn);
+        return check_launch("k_trajectory_mix");
+    }, [&] { return not_16bit("tome_trajectory_mix", dtype, "tensors"); });
 }
 
 // ---- backward of tome_prop_attention's plain form (tome_attn_bwd.h)
@@ -1171,7 +1167,7 @@ extern "C" int tome_prop_attention_backward(const void *q, const void *k, const 
         !dout_strides || !dq_strides || !dk_strides || !dv_strides || !attn_bwd_shape_ok(B, H, N, Nk))
         return fail(TOME_EINVAL, "%s: bad shape/pointer", fn);
     if (D != ATT_D) return fail(TOME_EINVAL, "%s: head dim %lld (only 64)", fn, (long long)D);
-    if (dtype != TOME_BF16 && dtype != TOME_F16) return fail(TOME_EINVAL, "%s: 16-bit q/k/v only", fn);
+    if (int rc = not_16bit(fn, dtype, "q/k/v")) return rc;
     if (bias_skip != 0 && bias_skip != 1) return fail(TOME_EINVAL, "%s: bias_skip %d", fn, bias_skip);
     if (bias_skip && N != Nk) return fail(TOME_EINVAL, "%s: bias_skip needs as many keys as queries", fn);
     const int64_t *ss[8] = {q_strides, k_strides, v_strides, out_strides, dout_strides, dq_strides, dk_strides, dv_strides};
@@ -1212,7 +1208,19 @@ extern "C" int tome_prop_attention_backward(const void *q, const void *k, const 
     };
     return dispatch_x<false>(dtype, [&](auto tx) {
         return log_size ? go(tx, AttInt<1>{}) : go(tx, AttInt<0>{});
-    }, [&] { return fail(TOME_EINVAL, "%s: 16-bit q/k/v only", fn); });
+    }, [&] { return not_16bit(fn, dtype, "q/k/v"); });
+}
+
+// The rows tome_short_attention and its backward can walk: {batch, head, token} element strides with the heads of a
+// token side by side (head stride 64), rows 16-byte aligned
+static int check_short_rows(const char *who, const int64_t *const *strides, int nstrides, const void *const *ptrs,
+                            int nptrs) {
+    for (int i = 0; i < nstrides; ++i)
+        if (strides[i][1] != 64 || strides[i][0] % 8 || strides[i][2] % 8)
+            return fail(TOME_EINVAL, "%s: head stride must be 64, batch / token strides multiples of 8", who);
+    for (int i = 0; i < nptrs; ++i)
+        if (!aligned16(ptrs[i])) return fail(TOME_EINVAL, "%s: rows must be 16-byte aligned", who);
+    return TOME_OK;
 }
 
 extern "C" int tome_short_attention(const void *q, const void *k, const void *v, int dtype, int64_t B, int64_t H,
@@ -1222,27 +1230,21 @@ extern "C" int tome_short_attention(const void *q, const void *k, const void *v,
         return fail(TOME_EINVAL, "tome_short_attention: bad shape/pointer");
     if (D != 64 || N > SHORT_MAXN)
         return fail(TOME_EINVAL, "tome_short_attention: head dim 64 and at most %d tokens per sequence", SHORT_MAXN);
-    if (dtype != TOME_BF16 && dtype != TOME_F16) return fail(TOME_EINVAL, "tome_short_attention: 16-bit tensors only");
-    // {batch, head, token} element strides; the heads of a token lie side by side (head stride 64), rows 16-byte aligned
+    if (int rc = not_16bit("tome_short_attention", dtype, "tensors")) return rc;
     const int64_t *strides[3] = {q_strides, k_strides, v_strides};
-    for (int i = 0; i < 3; ++i)
-        if (strides[i][1] != 64 || strides[i][0] % 8 || strides[i][2] % 8)
-            return fail(TOME_EINVAL, "tome_short_attention: head stride must be 64, batch / token strides multiples of 8");
-    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out))
-        return fail(TOME_EINVAL, "tome_short_attention: rows must be 16-byte aligned");
+    const void *ptrs[4] = {q, k, v, out};
+    if (int rc = check_short_rows("tome_short_attention", strides, 3, ptrs, 4)) return rc;
     const int64_t units = B * H;  // (sequence, head) pairs, eight lanes each
     const int64_t blocks = (units + 31) / 32;
     if (blocks > 0x7fffffffLL) return fail(TOME_EINVAL, "tome_short_attention: too many sequences");
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == TOME_BF16)
-        hipLaunchKernelGGL(k_short_attention<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, st, (const bf16_t *)q,
-                           (const bf16_t *)k, (const bf16_t *)v, q_strides[0], q_strides[2], k_strides[0], k_strides[2],
-                           v_strides[0], v_strides[2], units, (int)H, (int)N, scale, (bf16_t *)out);
-    else
-        hipLaunchKernelGGL(k_short_attention<f16_t>, dim3((unsigned)blocks), dim3(256), 0, st, (const f16_t *)q,
-                           (const f16_t *)k, (const f16_t *)v, q_strides[0], q_strides[2], k_strides[0], k_strides[2],
-                           v_strides[0], v_strides[2], units, (int)H, (int)N, scale, (f16_t *)out);
-    return check_launch("k_short_attention");
+    return dispatch_x<false>(dtype, [&](auto tx) {
+        using TX = typename decltype(tx)::type;
+        hipLaunchKernelGGL(k_short_attention<TX>, dim3((unsigned)blocks), dim3(256), 0, st, (const TX *)q, (const TX *)k,
+                           (const TX *)v, q_strides[0], q_strides[2], k_strides[0], k_strides[2], v_strides[0],
+                           v_strides[2], units, (int)H, (int)N, scale, (TX *)out);
+        return check_launch("k_short_attention");
+    }, [&] { return not_16bit("tome_short_attention", dtype, "tensors"); });
 }
 
 extern "C" int tome_short_attention_backward(const void *q, const void *k, const void *v, const void *dout, int dtype,
@@ -1256,52 +1258,43 @@ extern "C" int tome_short_attention_backward(const void *q, const void *k, const
     if (D != 64 || N > SHORT_MAXN)
         return fail(TOME_EINVAL, "tome_short_attention_backward: head dim 64 and at most %d tokens per sequence",
                     SHORT_MAXN);
-    if (dtype != TOME_BF16 && dtype != TOME_F16)
-        return fail(TOME_EINVAL, "tome_short_attention_backward: 16-bit tensors only");
-    // {batch, head, token} element strides; the heads of a token lie side by side (head stride 64), rows 16-byte aligned
+    if (int rc = not_16bit("tome_short_attention_backward", dtype, "tensors")) return rc;
     const int64_t *strides[6] = {q_strides, k_strides, v_strides, dq_strides, dk_strides, dv_strides};
-    for (int i = 0; i < 6; ++i)
-        if (strides[i][1] != 64 || strides[i][0] % 8 || strides[i][2] % 8)
-            return fail(TOME_EINVAL,
-                        "tome_short_attention_backward: head stride must be 64, batch / token strides multiples of 8");
+    const void *ptrs[7] = {q, k, v, dout, dq, dk, dv};
+    if (int rc = check_short_rows("tome_short_attention_backward", strides, 6, ptrs, 7)) return rc;
     // a target's rows must not lie on top of each other: a token's H heads fill H * 64 elements
     for (int i = 3; i < 6; ++i)
         if ((B > 1 && strides[i][0] < H * 64) || (N > 1 && strides[i][2] < H * 64))
             return fail(TOME_EINVAL, "tome_short_attention_backward: rows of dq / dk / dv overlap");
-    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(dout) || !aligned16(dq) || !aligned16(dk) ||
-        !aligned16(dv))
-        return fail(TOME_EINVAL, "tome_short_attention_backward: rows must be 16-byte aligned");
     const int64_t units = B * H;  // (sequence, head) pairs, eight lanes each
     const int64_t blocks = (units + 31) / 32;
     if (blocks > 0x7fffffffLL) return fail(TOME_EINVAL, "tome_short_attention_backward: too many sequences");
     const ShortBwdStrides s{q_strides[0],  q_strides[2],  k_strides[0],  k_strides[2],  v_strides[0],  v_strides[2],
                             dq_strides[0], dq_strides[2], dk_strides[0], dk_strides[2], dv_strides[0], dv_strides[2]};
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == TOME_BF16)
-        hipLaunchKernelGGL(k_short_attention_bwd<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, st, (const bf16_t *)q,
-                           (const bf16_t *)k, (const bf16_t *)v, (const bf16_t *)dout, s, units, (int)H, (int)N, scale,
-                           (bf16_t *)dq, (bf16_t *)dk, (bf16_t *)dv);
-    else
-        hipLaunchKernelGGL(k_short_attention_bwd<f16_t>, dim3((unsigned)blocks), dim3(256), 0, st, (const f16_t *)q,
-                           (const f16_t *)k, (const f16_t *)v, (const f16_t *)dout, s, units, (int)H, (int)N, scale,
-                           (f16_t *)dq, (f16_t *)dk, (f16_t *)dv);
-    return check_launch("k_short_attention_bwd");
+    return dispatch_x<false>(dtype, [&](auto tx) {
+        using TX = typename decltype(tx)::type;
+        hipLaunchKernelGGL(k_short_attention_bwd<TX>, dim3((unsigned)blocks), dim3(256), 0, st, (const TX *)q,
+                           (const TX *)k, (const TX *)v, (const TX *)dout, s, units, (int)H, (int)N, scale, (TX *)dq,
+                           (TX *)dk, (TX *)dv);
+        return check_launch("k_short_attention_bwd");
+    }, [&] { return not_16bit("tome_short_attention_backward", dtype, "tensors"); });
 }
 
 extern "C" int tome_gelu_erf(const void *x, int dtype, int64_t elements, void *y, tome_stream_t stream) {
     if (!x || !y || elements <= 0) return fail(TOME_EINVAL, "tome_gelu_erf: bad shape/pointer");
-    if (dtype != TOME_BF16 && dtype != TOME_F16) return fail(TOME_EINVAL, "tome_gelu_erf: 16-bit tensors only");
+    if (int rc = not_16bit("tome_gelu_erf", dtype, "tensors")) return rc;
     if (elements % 8 || !aligned16(x) || !aligned16(y))
         return fail(TOME_EINVAL, "tome_gelu_erf: a multiple of 8 elements in 16-byte aligned buffers required");
     const int64_t chunks = elements / 8;
     const int64_t blocks = (chunks + 1023) / 1024;  // 256 threads x 4 chunks
     if (blocks > 0x7fffffffLL) return fail(TOME_EINVAL, "tome_gelu_erf: too large");
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == TOME_BF16)
-        hipLaunchKernelGGL(k_gelu_erf<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, st, (const bf16_t *)x, (bf16_t *)y, chunks);
-    else
-        hipLaunchKernelGGL(k_gelu_erf<f16_t>, dim3((unsigned)blocks), dim3(256), 0, st, (const f16_t *)x, (f16_t *)y, chunks);
-    return check_launch("k_gelu_erf");
+    return dispatch_x<false>(dtype, [&](auto tx) {
+        using TX = typename decltype(tx)::type;
+        hipLaunchKernelGGL(k_gelu_erf<TX>, dim3((unsigned)blocks), dim3(256), 0, st, (const TX *)x, (TX *)y, chunks);
+        return check_launch("k_gelu_erf");
+    }, [&] { return not_16bit("tome_gelu_erf", dtype, "tensors"); });
 }
 
 // The launch form of k_gelu_bwd with the bias gradient for `rows` rows of `width`: S column slots per thread, U passes
@@ -1334,7 +1327,7 @@ extern "C" int tome_gelu_erf_backward(const void *h, const void *ga, int dtype, 
                                       void *act, void *dbias, void *workspace, size_t workspace_bytes,
                                       tome_stream_t stream) {
     if (!h || !ga || !gh) return fail(TOME_EINVAL, "tome_gelu_erf_backward: null buffer");
-    if (dtype != TOME_BF16 && dtype != TOME_F16) return fail(TOME_EINVAL, "tome_gelu_erf_backward: 16-bit tensors only");
+    if (int rc = not_16bit("tome_gelu_erf_backward", dtype, "tensors")) return rc;
     if (!gelu_bwd_shape_ok(rows, width))
         return fail(TOME_EINVAL, "tome_gelu_erf_backward: width %% 8 == 0, width <= 8192 and 1 .. 2^31 - 1 rows required");
     if (!aligned16(h) || !aligned16(ga) || !aligned16(gh) || !aligned16(act) || !aligned16(dbias) ||
@@ -1373,11 +1366,8 @@ extern "C" int tome_gelu_erf_backward(const void *h, const void *ga, int dtype, 
 #undef GELU_BWD_LAUNCH_
 #undef GELU_BWD_LAUNCH
         if (int rc = check_launch("k_gelu_bwd")) return rc;
-        hipLaunchKernelGGL((k_ln_param_grad<TX>), dim3((unsigned)((width + WAVE - 1) / WAVE)), dim3(LN_PG_RUNS * WAVE), 0,
-                           st, (const float *)workspace, (int)f.parts, (int)width, (int)width, (TX *)dbias,
-                           (TX *)nullptr);
-        return check_launch("k_ln_param_grad");
-    }, [&] { return fail(TOME_EINVAL, "tome_gelu_erf_backward: 16-bit tensors only"); });
+        return launch_param_grad<TX>(workspace, f.parts, width, width, dbias, nullptr, st);
+    }, [&] { return not_16bit("tome_gelu_erf_backward", dtype, "tensors"); });
 }
 
 extern "C" int tome_tubelet_rows(const void *x, int elem_bytes, int64_t B, int64_t C, int64_t T, int64_t H, int64_t W,

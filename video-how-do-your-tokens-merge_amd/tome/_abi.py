@@ -14,28 +14,68 @@ import torch
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("TOME_HIP_LIB", os.path.join(_PKG, "lib", "libtome_hip.so"))
 
-SYMBOLS = (
-    "tome_abi_version", "tome_last_error", "tome_effective_r", "tome_match_workspace_bytes", "tome_match",
-    "tome_match_keys",
-    "tome_match_scores", "tome_edge_keep", "tome_merge_wavg", "tome_merge_wavg_ln", "tome_merge_wavg_regrouped",
-    "tome_merge_wavg_regrouped_ln", "tome_add_layernorm", "tome_add_layernorm_skip_first", "tome_add_layernorm_regrouped", "tome_prop_attention", "tome_prop_attention_segments", "tome_trajectory_mix", "tome_short_attention", "tome_merge",
-    "tome_drop",
-    "tome_drop_regrouped",
-    "tome_unmerge", "tome_merge_backward", "tome_merge_backward_regrouped", "tome_row_map", "tome_source_init", "tome_gelu_erf", "tome_tubelet_rows",
-    "tome_partition_workspace_bytes", "tome_match_partition", "tome_merge_partition", "tome_merge_wavg_partition",
-    "tome_unmerge_partition",
-    "tome_layernorm_backward_workspace_bytes", "tome_layernorm_backward",
-    "tome_prop_attention_backward_workspace_bytes", "tome_prop_attention_backward",
-    "tome_gelu_erf_backward_workspace_bytes", "tome_gelu_erf_backward",
-    "tome_short_attention_backward",
-    "tome_layernorm_backward_regrouped_workspace_bytes", "tome_layernorm_backward_regrouped",
-)
-# entries added to ABI v11 after its first release: a v11 library built before them binds, and says so when one is called
-_LATER_V11 = ("tome_layernorm_backward_workspace_bytes", "tome_layernorm_backward")
-_LATER_V11_ATTN = ("tome_prop_attention_backward_workspace_bytes", "tome_prop_attention_backward")
-_LATER_V11_MLP = ("tome_gelu_erf_backward_workspace_bytes", "tome_gelu_erf_backward")
-_LATER_V11_TIMESFORMER = ("tome_short_attention_backward", "tome_layernorm_backward_regrouped_workspace_bytes",
-                          "tome_layernorm_backward_regrouped")
+i64, i32, vp, sz, f32 = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_float
+# The C ABI of include/tome_hip.h, name -> (restype, argtypes, later); tests/test_abi_cpu.py holds every row to the header's
+# prototype.  later: the entry was added to ABI v11 after its first release -- a v11 library built before it still binds,
+# and require_symbol says so when the entry is called.  Every other name must be exported.
+SIGNATURES = {
+    "tome_abi_version": (i32, [], False),
+    "tome_last_error": (ctypes.c_char_p, [], False),
+    "tome_effective_r": (i64, [i64, i64, i32, i32], False),
+    "tome_match_workspace_bytes": (sz, [i64, i64, i64], False),
+    "tome_match": (i32, [vp, i32, i64, i64, i64, i64, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp], False),
+    "tome_match_keys": (i32, [vp, i32, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i32, i32, vp, vp, vp, vp, vp,
+                             vp, sz, vp], False),
+    "tome_match_scores": (i32, [vp, i64, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp], False),
+    "tome_edge_keep": (i32, [vp, vp, i64, i64, i64, f32, vp, vp], False),
+    "tome_merge_wavg": (i32, [vp, i32, vp, i32, i64, i64, i64, i64, vp, vp, vp, i32, vp, vp, vp, vp, vp], False),
+    "tome_merge_wavg_ln": (i32, [vp, i32, vp, i32, i64, i64, i64, i64, vp, vp, vp, i32, vp, vp, vp, f32, vp, vp, vp, vp,
+                                vp, vp, vp], False),
+    "tome_merge_wavg_regrouped": (i32, [vp, i32, vp, i32, i64, i64, i64, i64, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+                                       False),
+    "tome_merge_wavg_regrouped_ln": (i32, [vp, i32, vp, i32, i64, i64, i64, i64, i64, i32, vp, vp, vp, vp, vp, vp, f32,
+                                          vp, i32, vp, vp, vp, vp, vp, vp, vp], False),
+    "tome_add_layernorm": (i32, [vp, vp, i32, i64, i64, vp, vp, f32, vp, vp, vp], False),
+    "tome_add_layernorm_skip_first": (i32, [vp, vp, i32, i64, i64, i64, vp, vp, f32, vp, vp, vp], False),
+    "tome_add_layernorm_regrouped": (i32, [vp, vp, i32, i64, i64, i64, i64, vp, vp, f32, vp, vp, vp], False),
+    "tome_prop_attention": (i32, [vp, vp, vp, i32, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, i32, f32, vp, vp, vp],
+                                 False),
+    "tome_prop_attention_segments": (i32, [vp, vp, vp, i32, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, f32, vp, vp,
+                                          i64, vp, vp], False),
+    "tome_trajectory_mix": (i32, [vp, vp, vp, i32, i64, i64, i64, i64, i64, i64, i64, f32, vp, i64, vp, vp], False),
+    "tome_short_attention": (i32, [vp, vp, vp, i32, i64, i64, i64, i64, vp, vp, vp, f32, vp, vp], False),
+    "tome_merge": (i32, [vp, i32, i64, i64, i64, i64, vp, vp, vp, i32, i32, vp, vp, vp], False),
+    "tome_drop": (i32, [vp, i32, i64, i64, i64, i64, vp, i32, vp, vp], False),
+    "tome_drop_regrouped": (i32, [vp, i32, i64, i64, i64, i64, i64, i32, vp, vp, vp], False),
+    "tome_unmerge": (i32, [vp, i32, i64, i64, i64, i64, vp, vp, vp, vp, vp], False),
+    "tome_merge_backward": (i32, [vp, i32, vp, vp, i32, i64, i64, i64, i64, vp, i32, i32, vp, vp], False),
+    "tome_merge_backward_regrouped": (i32, [vp, i32, vp, vp, i32, i64, i64, i64, i64, i64, i32, vp, i32, vp, vp],
+                                           False),
+    "tome_row_map": (i32, [i64, i64, i64, i32, vp, vp, vp, vp, vp], False),
+    "tome_source_init": (i32, [i64, i64, i64, i32, i32, vp, vp, vp], False),
+    "tome_gelu_erf": (i32, [vp, i32, i64, vp, vp], False),
+    "tome_tubelet_rows": (i32, [vp, i32, i64, i64, i64, i64, i64, vp, i64, i64, i64, vp, vp], False),
+    "tome_partition_workspace_bytes": (sz, [i64, i64, i64, i64], False),
+    "tome_match_partition": (i32, [vp, i32, i64, i64, i64, i64, i64, i64, vp, vp, i64, i64, vp, vp, vp, vp, sz, vp],
+                                  False),
+    "tome_merge_partition": (i32, [vp, i32, i64, i64, i64, i64, vp, vp, i64, i64, vp, vp, i32, vp, vp], False),
+    "tome_merge_wavg_partition": (i32, [vp, i32, vp, i32, i64, i64, i64, i64, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp],
+                                       False),
+    "tome_unmerge_partition": (i32, [vp, i32, i64, i64, i64, i64, vp, vp, i64, i64, vp, vp, vp], False),
+    "tome_layernorm_backward_workspace_bytes": (sz, [i64, i64], True),
+    "tome_layernorm_backward": (i32, [vp, vp, vp, i32, i64, i64, i32, i64, vp, f32, vp, vp, vp, vp, vp], True),
+    "tome_prop_attention_backward_workspace_bytes": (sz, [i64, i64, i64, i64], True),
+    "tome_prop_attention_backward": (i32, [vp, vp, vp, vp, vp, i32, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp,
+                                          i64, i32, f32, vp, vp, vp, vp, vp, vp, vp, sz, vp], True),
+    "tome_gelu_erf_backward_workspace_bytes": (sz, [i64, i64], True),
+    "tome_gelu_erf_backward": (i32, [vp, vp, i32, i64, i64, vp, vp, vp, vp, sz, vp], True),
+    "tome_short_attention_backward": (i32, [vp, vp, vp, vp, i32, i64, i64, i64, i64, vp, vp, vp, f32, vp, vp, vp, vp,
+                                           vp, vp, vp], True),
+    "tome_layernorm_backward_regrouped_workspace_bytes": (sz, [i64, i64, i64, i64], True),
+    "tome_layernorm_backward_regrouped": (i32, [vp, vp, vp, i32, i64, i64, i64, i64, vp, f32, vp, vp, vp, vp, vp],
+                                               True),
+}
+SYMBOLS = tuple(SIGNATURES)
 
 ABI_VERSION = 11
 DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
@@ -66,107 +106,11 @@ def bind(path: str) -> ctypes.CDLL:
             f"HIP extension not found at {path}: the MI355X merge path has no fallback. "
             "Build it with `python video-how-do-your-tokens-merge_amd/csrc/build.py` (needs hipcc).")
     L = ctypes.CDLL(path)
-    i64, i32, vp, sz = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t
-    L.tome_abi_version.restype = i32
-    L.tome_abi_version.argtypes = []
-    L.tome_last_error.restype = ctypes.c_char_p
-    L.tome_last_error.argtypes = []
-    L.tome_effective_r.restype = i64
-    L.tome_effective_r.argtypes = [i64, i64, i32, i32]
-    L.tome_match_workspace_bytes.restype = sz
-    L.tome_match_workspace_bytes.argtypes = [i64, i64, i64]
-    L.tome_match.restype = i32
-    L.tome_match.argtypes = [vp, i32, i64, i64, i64, i64, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.tome_match_keys.restype = i32
-    L.tome_match_keys.argtypes = [vp, i32, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i32, i32, vp, vp, vp, vp,
-                                  vp, vp, sz, vp]
-    L.tome_match_scores.restype = i32
-    L.tome_match_scores.argtypes = [vp, i64, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.tome_edge_keep.restype = i32
-    L.tome_edge_keep.argtypes = [vp, vp, i64, i64, i64, ctypes.c_float, vp, vp]
-    L.tome_merge_wavg.restype = i32
-    L.tome_merge_wavg.argtypes = [vp, i32, vp, i32, i64, i64, i64, i64, vp, vp, vp, i32, vp, vp, vp, vp, vp]
-    L.tome_merge_wavg_ln.restype = i32
-    L.tome_merge_wavg_ln.argtypes = [vp, i32, vp, i32, i64, i64, i64, i64, vp, vp, vp, i32, vp, vp, vp, ctypes.c_float,
-                                     vp, vp, vp, vp, vp, vp, vp]
-    L.tome_merge_wavg_regrouped.restype = i32
-    L.tome_merge_wavg_regrouped.argtypes = [vp, i32, vp, i32, i64, i64, i64, i64, i64, i32, vp, vp, vp, vp, vp, vp, vp,
-                                            vp]
-    L.tome_merge_wavg_regrouped_ln.restype = i32
-    L.tome_merge_wavg_regrouped_ln.argtypes = [vp, i32, vp, i32, i64, i64, i64, i64, i64, i32, vp, vp, vp, vp, vp, vp,
-                                               ctypes.c_float, vp, i32, vp, vp, vp, vp, vp, vp, vp]
-    L.tome_add_layernorm.restype = i32
-    L.tome_add_layernorm.argtypes = [vp, vp, i32, i64, i64, vp, vp, ctypes.c_float, vp, vp, vp]
-    L.tome_add_layernorm_skip_first.restype = i32
-    L.tome_add_layernorm_skip_first.argtypes = [vp, vp, i32, i64, i64, i64, vp, vp, ctypes.c_float, vp, vp, vp]
-    L.tome_add_layernorm_regrouped.restype = i32
-    L.tome_add_layernorm_regrouped.argtypes = [vp, vp, i32, i64, i64, i64, i64, vp, vp, ctypes.c_float, vp, vp, vp]
-    L.tome_merge.restype = i32
-    L.tome_merge.argtypes = [vp, i32, i64, i64, i64, i64, vp, vp, vp, i32, i32, vp, vp, vp]
-    L.tome_prop_attention.restype = i32
-    L.tome_prop_attention.argtypes = [vp, vp, vp, i32, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, i32, ctypes.c_float,
-                                      vp, vp, vp]
-    L.tome_prop_attention_segments.restype = i32
-    L.tome_prop_attention_segments.argtypes = [vp, vp, vp, i32, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64,
-                                               ctypes.c_float, vp, vp, i64, vp, vp]
-    L.tome_short_attention.restype = i32
-    L.tome_short_attention.argtypes = [vp, vp, vp, i32, i64, i64, i64, i64, vp, vp, vp, ctypes.c_float, vp, vp]
-    L.tome_trajectory_mix.restype = i32
-    L.tome_trajectory_mix.argtypes = [vp, vp, vp, i32, i64, i64, i64, i64, i64, i64, i64, ctypes.c_float, vp, i64, vp, vp]
-    L.tome_drop_regrouped.restype = i32
-    L.tome_drop_regrouped.argtypes = [vp, i32, i64, i64, i64, i64, i64, i32, vp, vp, vp]
-    L.tome_drop.restype = i32
-    L.tome_drop.argtypes = [vp, i32, i64, i64, i64, i64, vp, i32, vp, vp]
-    L.tome_unmerge.restype = i32
-    L.tome_unmerge.argtypes = [vp, i32, i64, i64, i64, i64, vp, vp, vp, vp, vp]
-    L.tome_merge_backward.restype = i32
-    L.tome_merge_backward.argtypes = [vp, i32, vp, vp, i32, i64, i64, i64, i64, vp, i32, i32, vp, vp]
-    L.tome_merge_backward_regrouped.restype = i32
-    L.tome_merge_backward_regrouped.argtypes = [vp, i32, vp, vp, i32, i64, i64, i64, i64, i64, i32, vp, i32, vp, vp]
-    L.tome_gelu_erf.restype = i32
-    L.tome_gelu_erf.argtypes = [vp, i32, i64, vp, vp]
-    L.tome_tubelet_rows.restype = i32
-    L.tome_tubelet_rows.argtypes = [vp, i32, i64, i64, i64, i64, i64, vp, i64, i64, i64, vp, vp]
-    L.tome_row_map.restype = i32
-    L.tome_row_map.argtypes = [i64, i64, i64, i32, vp, vp, vp, vp, vp]
-    L.tome_source_init.restype = i32
-    L.tome_source_init.argtypes = [i64, i64, i64, i32, i32, vp, vp, vp]
-    L.tome_partition_workspace_bytes.restype = sz
-    L.tome_partition_workspace_bytes.argtypes = [i64, i64, i64, i64]
-    L.tome_match_partition.restype = i32
-    L.tome_match_partition.argtypes = [vp, i32, i64, i64, i64, i64, i64, i64, vp, vp, i64, i64, vp, vp, vp, vp, sz, vp]
-    L.tome_merge_partition.restype = i32
-    L.tome_merge_partition.argtypes = [vp, i32, i64, i64, i64, i64, vp, vp, i64, i64, vp, vp, i32, vp, vp]
-    L.tome_merge_wavg_partition.restype = i32
-    L.tome_merge_wavg_partition.argtypes = [vp, i32, vp, i32, i64, i64, i64, i64, vp, vp, i64, i64, vp, vp, vp, vp, vp,
-                                            vp]
-    L.tome_unmerge_partition.restype = i32
-    L.tome_unmerge_partition.argtypes = [vp, i32, i64, i64, i64, i64, vp, vp, i64, i64, vp, vp, vp]
-    if all(_exports(L, name) for name in _LATER_V11):
-        L.tome_layernorm_backward_workspace_bytes.restype = sz
-        L.tome_layernorm_backward_workspace_bytes.argtypes = [i64, i64]
-        L.tome_layernorm_backward.restype = i32
-        L.tome_layernorm_backward.argtypes = [vp, vp, vp, i32, i64, i64, i32, i64, vp, ctypes.c_float, vp, vp, vp, vp, vp]
-    if all(_exports(L, name) for name in _LATER_V11_ATTN):
-        L.tome_prop_attention_backward_workspace_bytes.restype = sz
-        L.tome_prop_attention_backward_workspace_bytes.argtypes = [i64, i64, i64, i64]
-        L.tome_prop_attention_backward.restype = i32
-        L.tome_prop_attention_backward.argtypes = [vp, vp, vp, vp, vp, i32, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp,
-                                                   vp, i64, i32, ctypes.c_float, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-    if all(_exports(L, name) for name in _LATER_V11_MLP):
-        L.tome_gelu_erf_backward_workspace_bytes.restype = sz
-        L.tome_gelu_erf_backward_workspace_bytes.argtypes = [i64, i64]
-        L.tome_gelu_erf_backward.restype = i32
-        L.tome_gelu_erf_backward.argtypes = [vp, vp, i32, i64, i64, vp, vp, vp, vp, sz, vp]
-    if all(_exports(L, name) for name in _LATER_V11_TIMESFORMER):
-        L.tome_short_attention_backward.restype = i32
-        L.tome_short_attention_backward.argtypes = [vp, vp, vp, vp, i32, i64, i64, i64, i64, vp, vp, vp, ctypes.c_float,
-                                                    vp, vp, vp, vp, vp, vp, vp]
-        L.tome_layernorm_backward_regrouped_workspace_bytes.restype = sz
-        L.tome_layernorm_backward_regrouped_workspace_bytes.argtypes = [i64, i64, i64, i64]
-        L.tome_layernorm_backward_regrouped.restype = i32
-        L.tome_layernorm_backward_regrouped.argtypes = [vp, vp, vp, i32, i64, i64, i64, i64, vp, ctypes.c_float, vp, vp,
-                                                        vp, vp, vp]
+    for name, (restype, argtypes, later) in SIGNATURES.items():
+        if later and not _exports(L, name):
+            continue
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if L.tome_abi_version() != ABI_VERSION:
         raise TomeHipError(f"{os.path.basename(path)} ABI {L.tome_abi_version()} != expected {ABI_VERSION}")
     return L
@@ -246,6 +190,14 @@ def _workspace(device, stream: int, nbytes: int) -> torch.Tensor:
     so the kernels still in flight when this tensor is released can never share it with another stream's or
     another graph's matching -- which a process-wide cache keyed by stream handle could not guarantee."""
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+
+
+def _sized_workspace(L, entry_name: str, dims, device, stream: int, what: str) -> torch.Tensor:
+    """A workspace of the size `L.<entry_name>(*dims)` asks for; an entry that answers 0 has refused the shape."""
+    nbytes = require_symbol(L, entry_name)(*dims)
+    if nbytes == 0:
+        raise TomeHipError(f"{what}: no workspace size for {tuple(dims)}")
+    return _workspace(device, stream, nbytes)
 
 
 def effective_r(T: int, r: int, class_token: bool, distill_token: bool) -> int:
@@ -421,20 +373,27 @@ def log_of_size(size: torch.Tensor) -> torch.Tensor:
     return log if log is not None else size.log()
 
 
+def _prep_size(size: Optional[torch.Tensor], n: int, rows: int, x: torch.Tensor):
+    """The token sizes as the weighted merges take them, and the dtype of the sizes they return: `size` [n, rows, 1] on
+    x's device, contiguous, in x's dtype or fp32 (anything else is cast to x's) -- or None, which stands for ones of x's
+    dtype (torch.ones_like(x[..., 0, None]), merge.py:362-363)."""
+    if size is None:
+        return None, x.dtype
+    if size.device != x.device:  # (x is on a HIP device: every caller has asked require_device of it)
+        raise TomeHipError(f"merge_wavg(size): tensor on {size.device}, tokens on {x.device}")
+    if size.shape != (n, rows, 1):
+        raise TomeHipError(f"size must be [{n}, {rows}, 1], got {tuple(size.shape)}")
+    if size.dtype not in (x.dtype, torch.float32):
+        size = size.to(x.dtype)
+    size = size.contiguous()
+    return size, size.dtype
+
+
 def merge_wavg(plan: MatchPlan, x: torch.Tensor, size: Optional[torch.Tensor], log_size: bool = False):
     x = _prep_x(plan, x, "merge_wavg(x)", plan.T)
     n, T, C = x.shape
     xcode = dtype_code(x, "x")
-    if size is not None:
-        require_device(size, "merge_wavg(size)")
-        if size.shape != (n, T, 1):
-            raise TomeHipError(f"size must be [{n}, {T}, 1], got {tuple(size.shape)}")
-        if size.dtype not in (x.dtype, torch.float32):
-            size = size.to(x.dtype)
-        size = size.contiguous()
-        sdtype = size.dtype
-    else:
-        sdtype = x.dtype  # torch.ones_like(x[..., 0, None]) -- merge.py:362-363
+    size, sdtype = _prep_size(size, n, T, x)
     scode = DTYPES[sdtype]
     x_out = torch.empty((n, T - plan.r, C), dtype=x.dtype, device=x.device)
     s_out = torch.empty((n, T - plan.r, 1), dtype=sdtype, device=x.device)
@@ -448,29 +407,28 @@ def merge_wavg(plan: MatchPlan, x: torch.Tensor, size: Optional[torch.Tensor], l
     return x_out, s_out
 
 
-def ln_fusable(x: torch.Tensor, norm) -> bool:
-    """Can tome_merge_wavg_ln produce norm(x') for this LayerNorm module?"""
+_HALF = (torch.bfloat16, torch.float16)
+
+
+def _ln_of(x: torch.Tensor, norm) -> bool:
+    """The LayerNorm kind the kernels take, for a `norm` that is an nn.LayerNorm: affine with a bias, over the C <= 1024
+    (C % 8 == 0) channels of 16-bit device tokens x, weight of x's dtype."""
     C = x.shape[-1]
-    return (isinstance(norm, torch.nn.LayerNorm) and norm.elementwise_affine and norm.bias is not None
-            and tuple(norm.normalized_shape) == (C,) and x.dtype in (torch.bfloat16, torch.float16)
-            and norm.weight.dtype == x.dtype and C % 8 == 0 and C <= 1024 and x.is_cuda
+    return (norm.elementwise_affine and norm.bias is not None and tuple(norm.normalized_shape) == (C,)
+            and x.dtype in _HALF and norm.weight.dtype == x.dtype and C % 8 == 0 and C <= 1024 and x.is_cuda)
+
+
+def ln_fusable(x: torch.Tensor, norm) -> bool:
+    """Can tome_merge_wavg_ln produce norm(x') for this LayerNorm module (a subclass included), no gradient wanted?"""
+    return (isinstance(norm, torch.nn.LayerNorm) and _ln_of(x, norm)
             and not (torch.is_grad_enabled() and (x.requires_grad or norm.weight.requires_grad)))
 
 
-def ln_regrouped_trainable(x: torch.Tensor, norm) -> bool:
-    """Can tome_add_layernorm_regrouped run on x with tome_layernorm_backward_regrouped behind it (tome/_ln.py) when x
-    or the LayerNorm's parameters require grad?  ln_trainable and nothing more."""
-    return ln_trainable(x, norm)
-
-
 def ln_trainable(x: torch.Tensor, norm) -> bool:
-    """ln_fusable without its grad clause: can this LayerNorm of x run on the add + LayerNorm kernels with
-    tome_layernorm_backward behind them (tome/_ln.py) when x or its parameters require grad?  The stock module only: a
-    subclass may carry a forward of its own, which a training run must keep."""
-    C = x.shape[-1]
-    return (type(norm) is torch.nn.LayerNorm and norm.elementwise_affine and norm.bias is not None
-            and tuple(norm.normalized_shape) == (C,) and x.dtype in (torch.bfloat16, torch.float16)
-            and norm.weight.dtype == x.dtype and norm.bias.dtype == x.dtype and C % 8 == 0 and C <= 1024 and x.is_cuda)
+    """Can this LayerNorm of x run on the add + LayerNorm kernels (the regrouped one included) with
+    tome_layernorm_backward[_regrouped] behind them (tome/_ln.py) when x or its parameters require grad?  The stock
+    module only: a subclass may carry a forward of its own, which a training run must keep; and a bias of x's dtype."""
+    return type(norm) is torch.nn.LayerNorm and _ln_of(x, norm) and norm.bias.dtype == x.dtype
 
 
 def _out_bias(out_bias, x, C):
@@ -496,15 +454,7 @@ def merge_wavg_ln(plan: MatchPlan, x: torch.Tensor, size: Optional[torch.Tensor]
             raise TomeHipError("merge_wavg_ln: addend must match x in shape, dtype and device")
         addend = addend if addend.is_contiguous() else addend.contiguous()
     xcode = dtype_code(x, "x")
-    if size is not None:
-        if size.shape != (n, T, 1):
-            raise TomeHipError(f"size must be [{n}, {T}, 1], got {tuple(size.shape)}")
-        if size.dtype not in (x.dtype, torch.float32):
-            size = size.to(x.dtype)
-        size = size.contiguous()
-        sdtype = size.dtype
-    else:
-        sdtype = x.dtype
+    size, sdtype = _prep_size(size, n, T, x)
     x_out = torch.empty((n, T - plan.r, C), dtype=x.dtype, device=x.device)
     y_out = torch.empty_like(x_out)
     s_out = torch.empty((n, T - plan.r, 1), dtype=sdtype, device=x.device)
@@ -527,44 +477,28 @@ def add_layernorm(x: torch.Tensor, addend: Optional[torch.Tensor], weight: torch
     require_device(x, "add_layernorm(x)")
     x = x if x.is_contiguous() else x.contiguous()
     C = x.shape[-1]
-    if addend is None:
-        # LayerNorm only: x holds the finished sum already (returned as it is)
-        if skip_first and (x.dim() != 3 or x.shape[1] < 2):
-            raise TomeHipError("add_layernorm(skip_first): x must be [B, N >= 2, C]")
-        y_out = (torch.empty((x.shape[0], x.shape[1] - 1, C), dtype=x.dtype, device=x.device) if skip_first
-                 else torch.empty_like(x))
-        with _on_device(x.device):
-            if skip_first:
-                rc = lib().tome_add_layernorm_skip_first(x.data_ptr(), None, dtype_code(x, "x"), x.shape[0], x.shape[1],
-                                                         C, weight.data_ptr(), bias.data_ptr(), float(eps), None,
-                                                         y_out.data_ptr(), _stream(x.device))
-            else:
-                rc = lib().tome_add_layernorm(x.data_ptr(), None, dtype_code(x, "x"), x.numel() // C, C,
-                                              weight.data_ptr(), bias.data_ptr(), float(eps), None, y_out.data_ptr(),
-                                              _stream(x.device))
-        _check(rc, "tome_add_layernorm")
-        return x, y_out
-    if addend.shape != x.shape or addend.dtype != x.dtype or addend.device != x.device:
-        raise TomeHipError("add_layernorm: addend must match x in shape, dtype and device")
-    addend = addend if addend.is_contiguous() else addend.contiguous()
-    x_out = torch.empty_like(x)
-    if skip_first:
-        if x.dim() != 3 or x.shape[1] < 2:
-            raise TomeHipError("add_layernorm(skip_first): x must be [B, N >= 2, C]")
-        y_out = torch.empty((x.shape[0], x.shape[1] - 1, C), dtype=x.dtype, device=x.device)
-        with _on_device(x.device):
-            rc = lib().tome_add_layernorm_skip_first(x.data_ptr(), addend.data_ptr(), dtype_code(x, "x"), x.shape[0],
-                                                     x.shape[1], C, weight.data_ptr(), bias.data_ptr(), float(eps),
-                                                     x_out.data_ptr(), y_out.data_ptr(), _stream(x.device))
-        _check(rc, "tome_add_layernorm_skip_first")
-        return x_out, y_out
-    y_out = torch.empty_like(x)
+    if addend is not None:
+        if addend.shape != x.shape or addend.dtype != x.dtype or addend.device != x.device:
+            raise TomeHipError("add_layernorm: addend must match x in shape, dtype and device")
+        addend = addend if addend.is_contiguous() else addend.contiguous()
+    if skip_first and (x.dim() != 3 or x.shape[1] < 2):
+        raise TomeHipError("add_layernorm(skip_first): x must be [B, N >= 2, C]")
+    # without addend: LayerNorm only, x holds the finished sum already (returned as it is)
+    x_out = None if addend is None else torch.empty_like(x)
+    y_out = (torch.empty((x.shape[0], x.shape[1] - 1, C), dtype=x.dtype, device=x.device) if skip_first
+             else torch.empty_like(x))
     with _on_device(x.device):
-        rc = lib().tome_add_layernorm(x.data_ptr(), addend.data_ptr(), dtype_code(x, "x"), x.numel() // C, C,
-                                      weight.data_ptr(), bias.data_ptr(), float(eps), x_out.data_ptr(),
-                                      y_out.data_ptr(), _stream(x.device))
-    _check(rc, "tome_add_layernorm")
-    return x_out, y_out
+        if skip_first:
+            rc = lib().tome_add_layernorm_skip_first(x.data_ptr(), _ptr(addend), dtype_code(x, "x"), x.shape[0],
+                                                     x.shape[1], C, weight.data_ptr(), bias.data_ptr(), float(eps),
+                                                     _ptr(x_out), y_out.data_ptr(), _stream(x.device))
+        else:
+            rc = lib().tome_add_layernorm(x.data_ptr(), _ptr(addend), dtype_code(x, "x"), x.numel() // C, C,
+                                          weight.data_ptr(), bias.data_ptr(), float(eps), _ptr(x_out), y_out.data_ptr(),
+                                          _stream(x.device))
+    # (the name without an addend has always been the plain entry's)
+    _check(rc, "tome_add_layernorm_skip_first" if skip_first and addend is not None else "tome_add_layernorm")
+    return (x if addend is None else x_out), y_out
 
 
 def add_layernorm_regrouped(x: torch.Tensor, addend: torch.Tensor, frames: int, weight: torch.Tensor,
@@ -615,15 +549,7 @@ def merge_wavg_regrouped(plan: MatchPlan, x_full: torch.Tensor, size: Optional[t
         raise TomeHipError("merge_wavg_regrouped: autograd through the HIP merge kernels is not implemented")
     x_full = x_full if x_full.is_contiguous() else x_full.contiguous()
     xcode = dtype_code(x_full, "x")
-    if size is not None:
-        if size.shape != (plan.n, P, 1):
-            raise TomeHipError(f"size must be [{plan.n}, {P}, 1], got {tuple(size.shape)}")
-        if size.dtype not in (x_full.dtype, torch.float32):
-            size = size.to(x_full.dtype)
-        size = size.contiguous()
-        sdtype = size.dtype
-    else:
-        sdtype = x_full.dtype
+    size, sdtype = _prep_size(size, plan.n, P, x_full)
     x_out = torch.empty((B, cls + (P - plan.r) * F, C), dtype=x_full.dtype, device=x_full.device)
     s_out = torch.empty((plan.n, P - plan.r, 1), dtype=sdtype, device=x_full.device)
     log = _log_size_like(s_out, log_size)
@@ -695,11 +621,15 @@ def drop(plan: MatchPlan, x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _head_view(t: torch.Tensor) -> bool:
+    """A [B, H, N, 64] view of a 16-bit device tensor with contiguous channels and 16-byte aligned rows."""
+    return (t.is_cuda and t.dim() == 4 and t.shape[-1] == 64 and t.dtype in _HALF and t.stride(-1) == 1
+            and all(s % 8 == 0 for s in t.stride()[:3]) and t.data_ptr() % 16 == 0)
+
+
 def prop_attention_ok(q: torch.Tensor) -> bool:
-    """Can tome_prop_attention take these heads?  ([B, H, N, 64] views of 16-bit device tensors, rows 16-byte aligned.)"""
-    return (q.is_cuda and q.dim() == 4 and q.shape[-1] == 64 and q.dtype in (torch.bfloat16, torch.float16)
-            and q.stride(-1) == 1 and all(s % 8 == 0 for s in q.stride()[:3]) and q.data_ptr() % 16 == 0
-            and not (torch.is_grad_enabled() and q.requires_grad))
+    """Can tome_prop_attention take these heads (_head_view), no gradient wanted?"""
+    return _head_view(q) and not (torch.is_grad_enabled() and q.requires_grad)
 
 
 def prop_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, size: Optional[torch.Tensor], scale: float,
@@ -745,10 +675,9 @@ def prop_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, size: Opti
             raise TomeHipError(f"prop_attention: out must be a {(B, N, H, D)} view of the q dtype with contiguous channels")
         ostr = (ctypes.c_int64 * 3)(out.stride(0), out.stride(2), out.stride(1))
         result = out
-    strides = [(ctypes.c_int64 * 3)(*t.stride()[:3]) for t in (q, k, v)]
     with _on_device(q.device):
         rc = lib().tome_prop_attention(q.data_ptr(), k.data_ptr(), v.data_ptr(), dtype_code(q, "q"), B, H, N, Nk, D,
-                                       strides[0], strides[1], strides[2], _ptr(log),
+                                       _head_strides(q), _head_strides(k), _head_strides(v), _ptr(log),
                                        0 if log is None else log.stride(0), 1 if bias_skip else 0, float(scale),
                                        out.data_ptr(), ostr, _stream(q.device))
     _check(rc, "tome_prop_attention")
@@ -756,11 +685,9 @@ def prop_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, size: Opti
 
 
 def prop_attention_trainable(q: torch.Tensor, k: Optional[torch.Tensor] = None, v: Optional[torch.Tensor] = None) -> bool:
-    """prop_attention_ok without its grad clause, for every tensor given: can tome_prop_attention run on these heads
-    with tome_prop_attention_backward behind it (tome/_attn.py) when they require grad?"""
-    return all(t is None or (t.is_cuda and t.dim() == 4 and t.shape[-1] == 64 and t.dtype in (torch.bfloat16, torch.float16)
-                             and t.stride(-1) == 1 and all(s % 8 == 0 for s in t.stride()[:3])
-                             and t.data_ptr() % 16 == 0) for t in (q, k, v))
+    """_head_view of every tensor given: can tome_prop_attention run on these heads with tome_prop_attention_backward
+    behind it (tome/_attn.py) when they require grad?"""
+    return all(t is None or _head_view(t) for t in (q, k, v))
 
 
 def _head_strides(t: torch.Tensor):
@@ -817,10 +744,8 @@ def prop_attention_backward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o
     entry = require_symbol(L, "tome_prop_attention_backward")
     with _on_device(q.device):
         stream = _stream(q.device)
-        nbytes = require_symbol(L, "tome_prop_attention_backward_workspace_bytes")(B, H, N, Nk)
-        if nbytes == 0:
-            raise TomeHipError(f"prop_attention_backward: no workspace size for {(B, H, N, Nk)}")
-        ws = _workspace(q.device, stream, nbytes) if workspace is None else workspace
+        ws = workspace if workspace is not None else _sized_workspace(
+            L, "tome_prop_attention_backward_workspace_bytes", (B, H, N, Nk), q.device, stream, "prop_attention_backward")
         rc = entry(q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), g4.data_ptr(), dtype_code(q, "q"), B, H, N, Nk,
                    D, _head_strides(q), _head_strides(k), _head_strides(v), _head_strides(o4), _head_strides(g4),
                    _ptr(log_bias), 0 if log_bias is None else log_bias.stride(0), 1 if bias_skip else 0, float(scale),
@@ -851,27 +776,32 @@ def prop_attention_segments(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, n
                                  or log_bias.stride(1) != 1 or log_bias.device != q.device):
         raise TomeHipError(f"prop_attention_segments: log_bias must be an fp32 {(B, nseg * P)} view with contiguous rows")
     y = torch.empty((B, N, nseg, H * D), dtype=q.dtype, device=q.device)
-    strides = [(ctypes.c_int64 * 3)(*t.stride()[:3]) for t in (q, k, v)]
     ostr = (ctypes.c_int64 * 3)(y.stride(0), D, y.stride(1))  # {batch, head, token}
     seg = (ctypes.c_int64 * 4)(P * k.stride(2), P * v.stride(2), y.stride(2), P)
     with _on_device(q.device):
         rc = lib().tome_prop_attention_segments(q.data_ptr(), k.data_ptr(), v.data_ptr(), dtype_code(q, "q"), B, H, N, P,
-                                                D, strides[0], strides[1], strides[2], _ptr(log_bias),
+                                                D, _head_strides(q), _head_strides(k), _head_strides(v), _ptr(log_bias),
                                                 0 if log_bias is None else log_bias.stride(0), float(scale),
                                                 y.data_ptr(), ostr, nseg, seg, _stream(q.device))
     _check(rc, "tome_prop_attention_segments")
     return y
 
 
-def short_attention_ok(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> bool:
-    """Can tome_short_attention take these?  [B, H, N <= 8, 64] views of 16-bit device tensors whose heads lie side
-    by side in a token's row (head stride 64), rows 16-byte aligned, no gradient wanted."""
+def _short_heads(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> bool:
+    """[B, H, N <= 8, 64] views of 16-bit tensors on one device whose heads lie side by side in a token's row (head
+    stride 64), rows 16-byte aligned."""
     def ok(t):
         return (t.is_cuda and t.dim() == 4 and t.shape == q.shape and t.dtype == q.dtype and t.device == q.device
                 and t.stride(3) == 1 and t.stride(1) == 64 and t.stride(0) % 8 == 0 and t.stride(2) % 8 == 0
-                and t.data_ptr() % 16 == 0 and not (torch.is_grad_enabled() and t.requires_grad))
-    return (q.dim() == 4 and q.dtype in (torch.bfloat16, torch.float16) and q.shape[-1] == 64 and 1 <= q.shape[2] <= 8
+                and t.data_ptr() % 16 == 0)
+    return (q.dim() == 4 and q.dtype in _HALF and q.shape[-1] == 64 and 1 <= q.shape[2] <= 8
             and ok(q) and ok(k) and ok(v))
+
+
+def short_attention_ok(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> bool:
+    """Can tome_short_attention take these (_short_heads), no gradient wanted?"""
+    return _short_heads(q, k, v) and not (torch.is_grad_enabled()
+                                          and (q.requires_grad or k.requires_grad or v.requires_grad))
 
 
 def short_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, checked: bool = False
@@ -886,26 +816,19 @@ def short_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: fl
                            f"16-byte aligned rows, got {tuple(q.shape)} {q.dtype} strides {q.stride()}")
     B, H, N, D = q.shape
     out = torch.empty((B, N, H * D), dtype=q.dtype, device=q.device)
-    strides = [(ctypes.c_int64 * 3)(*t.stride()[:3]) for t in (q, k, v)]
     with _on_device(q.device):
         rc = lib().tome_short_attention(q.data_ptr(), k.data_ptr(), v.data_ptr(), dtype_code(q, "q"), B, H, N, D,
-                                        strides[0], strides[1], strides[2], float(scale), out.data_ptr(),
-                                        _stream(q.device))
+                                        _head_strides(q), _head_strides(k), _head_strides(v), float(scale),
+                                        out.data_ptr(), _stream(q.device))
     _check(rc, "tome_short_attention")
     return out
 
 
 def short_attention_trainable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> bool:
-    """short_attention_ok without its grad clause: can tome_short_attention run on these heads with
-    tome_short_attention_backward behind it (tome/_attn.py) when they require grad?  q, k, v that alias one tensor
-    (with_qkv=False) are refused: their three gradients would have to be summed."""
-    def ok(t):
-        return (t.is_cuda and t.dim() == 4 and t.shape == q.shape and t.dtype == q.dtype and t.device == q.device
-                and t.stride(3) == 1 and t.stride(1) == 64 and t.stride(0) % 8 == 0 and t.stride(2) % 8 == 0
-                and t.data_ptr() % 16 == 0)
-    return (q.dim() == 4 and q.dtype in (torch.bfloat16, torch.float16) and q.shape[-1] == 64 and 1 <= q.shape[2] <= 8
-            and ok(q) and ok(k) and ok(v)
-            and len({q.data_ptr(), k.data_ptr(), v.data_ptr()}) == 3)
+    """Can tome_short_attention run on these heads (_short_heads) with tome_short_attention_backward behind it
+    (tome/_attn.py) when they require grad?  q, k, v that alias one tensor (with_qkv=False) are refused: their three
+    gradients would have to be summed."""
+    return _short_heads(q, k, v) and len({q.data_ptr(), k.data_ptr(), v.data_ptr()}) == 3
 
 
 def short_attention_backward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, dout: torch.Tensor, scale: float,
@@ -1078,14 +1001,10 @@ def gelu_erf_backward(h: torch.Tensor, ga: torch.Tensor, *, want_act: bool, want
     dbias = torch.empty(Hd, dtype=h.dtype, device=h.device) if want_bias else None
     with _on_device(h.device):
         stream = _stream(h.device)
-        ws, nbytes = None, 0
-        if want_bias:
-            nbytes = require_symbol(L, "tome_gelu_erf_backward_workspace_bytes")(rows, Hd)
-            if nbytes == 0:
-                raise TomeHipError(f"gelu_erf_backward: no workspace size for {rows} rows of {Hd}")
-            ws = _workspace(h.device, stream, nbytes)
+        ws = _sized_workspace(L, "tome_gelu_erf_backward_workspace_bytes", (rows, Hd), h.device, stream,
+                              "gelu_erf_backward") if want_bias else None
         rc = entry(h.data_ptr(), ga.data_ptr(), dtype_code(h, "h"), rows, Hd, gh.data_ptr(), _ptr(act), _ptr(dbias),
-                   _ptr(ws), nbytes, stream)
+                   _ptr(ws), 0 if ws is None else ws.numel(), stream)
     _check(rc, "tome_gelu_erf_backward")
     return gh, act, dbias
 
@@ -1213,6 +1132,35 @@ def merge_backward_regrouped(plan: MatchPlan, grad_out: torch.Tensor, frames: in
     return gx
 
 
+def _layernorm_backward_call(what: str, gy, gy_shape, xs, gx_in, weight, eps, want_weight, want_bias, dims, ws_dims):
+    """What tome_layernorm_backward and its regrouped form share behind their shape checks: the gradients prepared,
+    gx / dweight / dbias allocated, the workspace taken when a parameter gradient is wanted, and the call of entry
+    tome_<what>(gy, xs, gx_in, dtype, *dims, C, weight, eps, gx, dweight, dbias, workspace, stream) with a workspace of
+    tome_<what>_workspace_bytes(*ws_dims).  Returns (gx, dweight, dbias)."""
+    C = xs.shape[-1]
+    if weight.numel() != C or weight.dtype != xs.dtype or weight.device != xs.device:
+        raise TomeHipError(f"{what}: weight must hold {C} values of {xs.dtype} on {xs.device}")
+    gy = _prep_grad(gy, gy_shape, xs.dtype, xs.device, f"{what}(gy)")
+    if gx_in is not None:
+        gx_in = _prep_grad(gx_in, tuple(xs.shape), xs.dtype, xs.device, f"{what}(gx_in)")
+    xs = xs.detach()
+    xs = xs if xs.is_contiguous() else xs.contiguous()
+    weight = weight.detach().contiguous()
+    L = lib()
+    entry = require_symbol(L, f"tome_{what}")
+    gx = torch.empty_like(xs)
+    dweight = torch.empty(C, dtype=xs.dtype, device=xs.device) if want_weight else None
+    dbias = torch.empty(C, dtype=xs.dtype, device=xs.device) if want_bias else None
+    with _on_device(xs.device):
+        stream = _stream(xs.device)
+        ws = _sized_workspace(L, f"tome_{what}_workspace_bytes", ws_dims, xs.device, stream,
+                              what) if want_weight or want_bias else None
+        rc = entry(gy.data_ptr(), xs.data_ptr(), _ptr(gx_in), dtype_code(xs, "xs"), *dims, C, weight.data_ptr(), float(eps),
+                   gx.data_ptr(), _ptr(dweight), _ptr(dbias), _ptr(ws), stream)
+    _check(rc, f"tome_{what}")
+    return gx, dweight, dbias
+
+
 def layernorm_backward(gy: torch.Tensor, xs: torch.Tensor, gx_in: Optional[torch.Tensor], weight: torch.Tensor,
                        eps: float, skip_first: bool = False, want_weight: bool = True, want_bias: bool = True):
     """tome_layernorm_backward: the gradient of y = LayerNorm(xs) (and of the residual stream through xs) for the
@@ -1220,7 +1168,7 @@ def layernorm_backward(gy: torch.Tensor, xs: torch.Tensor, gx_in: Optional[torch
     (xs [B, N, C]), [B, N-1, C]: every clip's first row has no row in y.  gx_in: optional gradient that reaches xs
     directly, xs's shape.  Returns (gx, dweight, dbias); a gradient that is not wanted is None.  No CPU path."""
     require_device(xs, "layernorm_backward(xs)")
-    if xs.dtype not in (torch.bfloat16, torch.float16):
+    if xs.dtype not in _HALF:
         raise TomeHipError(f"layernorm_backward: 16-bit tokens only, got {xs.dtype}")
     C = xs.shape[-1]
     if xs.dim() < 2 or C % 8 or C > 1024 or xs.numel() == 0:
@@ -1233,32 +1181,8 @@ def layernorm_backward(gy: torch.Tensor, xs: torch.Tensor, gx_in: Optional[torch
     else:
         groups, group_rows = xs.numel() // C, 1
         gy_shape = tuple(xs.shape)
-    if weight.numel() != C or weight.dtype != xs.dtype or weight.device != xs.device:
-        raise TomeHipError(f"layernorm_backward: weight must hold {C} values of {xs.dtype} on {xs.device}")
-    gy = _prep_grad(gy, gy_shape, xs.dtype, xs.device, "layernorm_backward(gy)")
-    if gx_in is not None:
-        gx_in = _prep_grad(gx_in, tuple(xs.shape), xs.dtype, xs.device, "layernorm_backward(gx_in)")
-    xs = xs.detach()
-    xs = xs if xs.is_contiguous() else xs.contiguous()
-    weight = weight.detach().contiguous()
-    L = lib()
-    entry = require_symbol(L, "tome_layernorm_backward")
-    gx = torch.empty_like(xs)
-    dweight = torch.empty(C, dtype=xs.dtype, device=xs.device) if want_weight else None
-    dbias = torch.empty(C, dtype=xs.dtype, device=xs.device) if want_bias else None
-    with _on_device(xs.device):
-        stream = _stream(xs.device)
-        ws = None
-        if want_weight or want_bias:
-            nbytes = require_symbol(L, "tome_layernorm_backward_workspace_bytes")(groups * group_rows, C)
-            if nbytes == 0:
-                raise TomeHipError(f"layernorm_backward: no workspace size for {groups * group_rows} rows of {C}")
-            ws = _workspace(xs.device, stream, nbytes)
-        rc = entry(gy.data_ptr(), xs.data_ptr(), _ptr(gx_in), dtype_code(xs, "xs"), groups, group_rows,
-                   int(bool(skip_first)), C, weight.data_ptr(), float(eps), gx.data_ptr(), _ptr(dweight), _ptr(dbias),
-                   _ptr(ws), stream)
-    _check(rc, "tome_layernorm_backward")
-    return gx, dweight, dbias
+    return _layernorm_backward_call("layernorm_backward", gy, gy_shape, xs, gx_in, weight, eps, want_weight, want_bias,
+                                    (groups, group_rows, int(bool(skip_first))), (groups * group_rows, C))
 
 
 def layernorm_backward_regrouped(gy: torch.Tensor, xs: torch.Tensor, gx_in: Optional[torch.Tensor], frames: int,
@@ -1268,7 +1192,7 @@ def layernorm_backward_regrouped(gy: torch.Tensor, xs: torch.Tensor, gx_in: Opti
     gx_in: optional gradient that reaches xs directly, xs's shape.  Returns (gx, dweight, dbias), gx of xs's shape (the
     addend's gradient is gx[:, 1:]); a gradient that is not wanted is None.  No CPU path."""
     require_device(xs, "layernorm_backward_regrouped(xs)")
-    if xs.dtype not in (torch.bfloat16, torch.float16):
+    if xs.dtype not in _HALF:
         raise TomeHipError(f"layernorm_backward_regrouped: 16-bit tokens only, got {xs.dtype}")
     F = int(frames)
     if xs.dim() != 3 or F < 1 or xs.shape[1] < 1 + F or (xs.shape[1] - 1) % F or xs.shape[0] < 1:
@@ -1278,31 +1202,8 @@ def layernorm_backward_regrouped(gy: torch.Tensor, xs: torch.Tensor, gx_in: Opti
     P = (N - 1) // F
     if C % 8 or C > 1024:
         raise TomeHipError(f"layernorm_backward_regrouped: C % 8 == 0 and C <= 1024 required, got {C}")
-    if weight.numel() != C or weight.dtype != xs.dtype or weight.device != xs.device:
-        raise TomeHipError(f"layernorm_backward_regrouped: weight must hold {C} values of {xs.dtype} on {xs.device}")
-    gy = _prep_grad(gy, (B * F, 1 + P, C), xs.dtype, xs.device, "layernorm_backward_regrouped(gy)")
-    if gx_in is not None:
-        gx_in = _prep_grad(gx_in, tuple(xs.shape), xs.dtype, xs.device, "layernorm_backward_regrouped(gx_in)")
-    xs = xs.detach()
-    xs = xs if xs.is_contiguous() else xs.contiguous()
-    weight = weight.detach().contiguous()
-    L = lib()
-    entry = require_symbol(L, "tome_layernorm_backward_regrouped")
-    gx = torch.empty_like(xs)
-    dweight = torch.empty(C, dtype=xs.dtype, device=xs.device) if want_weight else None
-    dbias = torch.empty(C, dtype=xs.dtype, device=xs.device) if want_bias else None
-    with _on_device(xs.device):
-        stream = _stream(xs.device)
-        ws = None
-        if want_weight or want_bias:
-            nbytes = require_symbol(L, "tome_layernorm_backward_regrouped_workspace_bytes")(B, F, P, C)
-            if nbytes == 0:
-                raise TomeHipError(f"layernorm_backward_regrouped: no workspace size for {(B, F, P, C)}")
-            ws = _workspace(xs.device, stream, nbytes)
-        rc = entry(gy.data_ptr(), xs.data_ptr(), _ptr(gx_in), dtype_code(xs, "xs"), B, F, P, C, weight.data_ptr(),
-                   float(eps), gx.data_ptr(), _ptr(dweight), _ptr(dbias), _ptr(ws), stream)
-    _check(rc, "tome_layernorm_backward_regrouped")
-    return gx, dweight, dbias
+    return _layernorm_backward_call("layernorm_backward_regrouped", gy, (B * F, 1 + P, C), xs, gx_in, weight, eps,
+                                    want_weight, want_bias, (B, F, P), (B, F, P, C))
 
 
 def source_init(plan: MatchPlan, drop: bool = False) -> torch.Tensor:
@@ -1407,16 +1308,7 @@ def merge_wavg_partition(plan: PartitionPlan, x: torch.Tensor, size: Optional[to
     x = _prep_x(plan, x, "merge_wavg(x)", plan.T)
     n, T, C = x.shape
     xcode = dtype_code(x, "x")
-    if size is not None:
-        require_device(size, "merge_wavg(size)")
-        if size.shape != (n, T, 1):
-            raise TomeHipError(f"size must be [{n}, {T}, 1], got {tuple(size.shape)}")
-        if size.dtype not in (x.dtype, torch.float32):
-            size = size.to(x.dtype)
-        size = size.contiguous()
-        sdtype = size.dtype
-    else:
-        sdtype = x.dtype  # torch.ones_like(x[..., 0, None]) -- merge.py:362-363
+    size, sdtype = _prep_size(size, n, T, x)
     x_out = torch.empty((n, plan.Nb, C), dtype=x.dtype, device=x.device)
     s_out = torch.empty((n, plan.Nb, 1), dtype=sdtype, device=x.device)
     log = _log_size_like(s_out, log_size)

@@ -62,17 +62,22 @@ def _log_bias(size, B):
         return _abi.log_of_size(size).detach().reshape(B, -1).float().contiguous()
 
 
+def _forward(ctx, saved, q, k, v, size, scale, bias_skip):
+    """Both Functions' forward on detached heads; `saved`: the inputs kept for backward, ahead of the output and the bias."""
+    log = _log_bias(size, q.shape[0])
+    out = _abi.prop_attention(q, k, v, None, scale, bias_skip=bias_skip, log_bias=log, checked=True)
+    ctx.scale, ctx.bias_skip, ctx.has_bias = float(scale), bool(bias_skip), log is not None
+    ctx.save_for_backward(*saved, out, *(() if log is None else (log,)))
+    return out
+
+
 class _AttentionFunction(torch.autograd.Function):
     """softmax(q k^T scale + log size) v: tome_prop_attention forward, tome_prop_attention_backward backward."""
 
     @staticmethod
     def forward(ctx, q, k, v, size, scale, bias_skip):
         q, k, v = q.detach(), k.detach(), v.detach()
-        log = _log_bias(size, q.shape[0])
-        out = _abi.prop_attention(q, k, v, None, scale, bias_skip=bias_skip, log_bias=log, checked=True)
-        ctx.scale, ctx.bias_skip, ctx.has_bias = float(scale), bool(bias_skip), log is not None
-        ctx.save_for_backward(q, k, v, out, *(() if log is None else (log,)))
-        return out
+        return _forward(ctx, (q, k, v), q, k, v, size, scale, bias_skip)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -90,12 +95,7 @@ class _AttentionQKVFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, size, scale, bias_skip):
         qkv = qkv.detach()
-        q, k, v = qkv[0], qkv[1], qkv[2]
-        log = _log_bias(size, q.shape[0])
-        out = _abi.prop_attention(q, k, v, None, scale, bias_skip=bias_skip, log_bias=log, checked=True)
-        ctx.scale, ctx.bias_skip, ctx.has_bias = float(scale), bool(bias_skip), log is not None
-        ctx.save_for_backward(qkv, out, *(() if log is None else (log,)))
-        return out
+        return _forward(ctx, (qkv,), qkv[0], qkv[1], qkv[2], size, scale, bias_skip)
 
     @staticmethod
     @torch.autograd.function.once_differentiable

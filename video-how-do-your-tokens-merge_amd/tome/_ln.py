@@ -62,7 +62,9 @@ def ln_backward_regrouped(gy, xs, gx_in, frames, weight, eps, want_weight, want_
                                              want_bias=want_bias)
 
 
-def _backward(ctx, g_sum, g_y):
+def _backward(ctx, g_sum, g_y, seam=None):
+    """(gx, dweight, dbias) of every Function here.  seam(gy, xs, gx_in, weight, want_weight, want_bias): the backward
+    launch, ln_backward unless the Function has another."""
     xs, weight = ctx.saved_tensors
     want_x = ctx.needs_x
     want_w, want_b = ctx.needs_input_grad[ctx.first_param], ctx.needs_input_grad[ctx.first_param + 1]
@@ -70,7 +72,10 @@ def _backward(ctx, g_sum, g_y):
         gx = g_sum if want_x else None
         return gx, (torch.zeros_like(weight) if want_w else None), (torch.zeros_like(weight) if want_b else None)
     cast = lambda g: g if g is None or g.dtype == xs.dtype else g.to(xs.dtype)  # noqa: E731
-    gx, dw, db = ln_backward(cast(g_y), xs, cast(g_sum), weight, ctx.eps, ctx.skip_first, want_w, want_b)
+    if seam is None:
+        gx, dw, db = ln_backward(cast(g_y), xs, cast(g_sum), weight, ctx.eps, ctx.skip_first, want_w, want_b)
+    else:
+        gx, dw, db = seam(cast(g_y), xs, cast(g_sum), weight, want_w, want_b)
     return (gx if want_x else None), dw, db
 
 
@@ -119,7 +124,8 @@ class _AddLayerNormRegroupedFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, addend, weight, bias, eps, frames):
         x1, y = _abi.add_layernorm_regrouped(x.detach(), addend.detach(), frames, weight.detach(), bias.detach(), eps)
-        ctx.eps, ctx.frames = float(eps), int(frames)
+        ctx.eps, ctx.frames, ctx.first_param = float(eps), int(frames), 2
+        ctx.needs_x = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         ctx.save_for_backward(x1, weight)
         ctx.set_materialize_grads(False)  # an output nobody read arrives as None, not as a tensor of zeros
         return x1, y
@@ -127,15 +133,10 @@ class _AddLayerNormRegroupedFunction(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_x1, g_y):
-        x1, weight = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        want_w, want_b = need[2], need[3]
-        if g_y is None:  # nothing read the LayerNorm: the stream's gradient passes through, the parameters get zeros
-            gx, dw, db = g_x1, (torch.zeros_like(weight) if want_w else None), (torch.zeros_like(weight) if want_b else None)
-        else:
-            cast = lambda g: g if g is None or g.dtype == x1.dtype else g.to(x1.dtype)  # noqa: E731
-            gx, dw, db = ln_backward_regrouped(cast(g_y), x1, cast(g_x1), ctx.frames, weight, ctx.eps, want_w, want_b)
+        gx, dw, db = _backward(ctx, g_x1, g_y, lambda gy, xs, gx_in, weight, want_w, want_b: ln_backward_regrouped(
+            gy, xs, gx_in, ctx.frames, weight, ctx.eps, want_w, want_b))
         # x1 = cat(cls, x[:, 1:] + addend): x receives gx, the addend the view behind the class row
+        need = ctx.needs_input_grad
         return ((gx if need[0] and gx is not None else None), (gx[:, 1:] if need[1] and gx is not None else None), dw, db,
                 None, None)
 
@@ -162,7 +163,5 @@ def add_layernorm_regrouped_native(x, addend, T: int, norm):
     """TimeSformer's mid-block step for tokens that require grad: x [B, 1 + P*T, C], addend [B, P*T, C] ->
     (x1, xs_normed) with x1 = cat(cls, x[:, 1:] + addend) and xs_normed = norm of the tokens regrouped
     'b (p t) m -> (b t) p m' with the class token in front of every frame, [B*T, 1 + P, C]."""
-    if not _abi.ln_regrouped_trainable(x, norm):
-        raise _abi.TomeHipError(f"add_layernorm_regrouped_native: this LayerNorm of {tuple(x.shape)} {x.dtype} tokens is not "
-                                "one the kernels take (_abi.ln_regrouped_trainable)")
+    _check(x, norm, "add_layernorm_regrouped_native")
     return _AddLayerNormRegroupedFunction.apply(x, addend, norm.weight, norm.bias, norm.eps, int(T))

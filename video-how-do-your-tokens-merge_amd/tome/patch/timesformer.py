@@ -38,7 +38,7 @@ def _block_forward(self, x, B, T, W):
         # un-normalised tokens never exist
         x1, xs_normed = _abi.add_layernorm_regrouped(x, rt, T, self.norm1.weight, self.norm1.bias, self.norm1.eps)
     elif (C._FUSE_NEXT and rt.dtype == x.dtype and torch.is_grad_enabled() and _ln.regrouped_enabled()
-          and _abi.ln_regrouped_trainable(x, self.norm1)):
+          and _abi.ln_trainable(x, self.norm1)):
         # the same launch under grad (ln_fusable refuses tensors that require grad), with
         # tome_layernorm_backward_regrouped behind it: x and rt receive gx and its view gx[:, 1:]
         x1, xs_normed = _ln.add_layernorm_regrouped_native(x, rt, T, self.norm1)
