@@ -367,7 +367,8 @@ int tome_layernorm_backward_regrouped(const void *gy, const void *xs, const void
  *     tools/train_net.py:727-741):
  *         attn = softmax(q k^T * scale + log(size)); x = attn @ v      tome/patch/videomae.py:55-66, vivit.py:95-113
  *         the same with the bias on the non-class block only           tome/patch/timesformer.py:66-78  (bias_skip)
- *     i.e. the backward of tome_prop_attention (its plain form; the segmented form has none).  With P the softmax and
+ *     i.e. the backward of tome_prop_attention (its plain form; the segmented form's is
+ *     tome_prop_attention_segments_backward below).  With P the softmax and
  *     O = out the forward's stored 16-bit result:
  *         dV = P^T dO,  delta = rowsum(dO o O),  dS = P o (dO V^T - delta),  dQ = scale dS K,  dK = scale dS^T Q
  *     size gets no gradient.  The forward saves nothing: P is recomputed with the forward's definition of the logits
@@ -389,6 +390,59 @@ int tome_prop_attention_backward(const void *q, const void *k, const void *v, co
                                  int64_t log_size_stride, int bias_skip, float scale, void *dq, void *dk, void *dv,
                                  const int64_t *dq_strides, const int64_t *dk_strides, const int64_t *dv_strides,
                                  void *workspace, size_t workspace_bytes, tome_stream_t stream);
+
+/*
+ * tome_prop_attention_segments_backward  <-  what autograd derives from the per-frame stage of
+ *     ToMeTrajectoryAttention.forward (tome/patch/motionformer.py:98-121) when q, k or v require grad (additions to ABI
+ *     v11, no entry changed): the backward of tome_prop_attention_segments.  For every segment s, with P_s its own softmax
+ *     recomputed with the forward's definition of the logits (as in tome_prop_attention_backward) and O_s the forward's
+ *     stored 16-bit result:
+ *         dV_s = P_s^T dO_s,  delta_s = rowsum(dO_s o O_s),  dS_s = P_s o (dO_s V_s^T - delta_s),  dK_s = scale dS_s^T Q,
+ *         dQ = scale * sum_s dS_s K_s
+ *     The sum over the segments is taken in fp32 inside the workgroup that owns the query rows and rounded once when dq
+ *     is stored.  Two launches, no atomics, every row of dq, dk, dv written exactly once and nothing beside its 64
+ *     channels, same bits on every run; no allocation, no synchronisation.  size gets no gradient.
+ *     q, k, v, log_size, nseg and seg_strides = {k, v, out, log_size}: the forward's arguments (Nk keys per segment).
+ *     out and dout: the [B, N, nseg, H*64] layout the forward writes, each as {batch, head, token} element strides;
+ *     segment s of out lies seg_strides[2] elements, of dout grad_seg_strides[0] elements behind segment s-1.
+ *     dq [B, H, N, 64]; dk, dv [B, H, Nk, 64] per segment, each with strides of its own; segment s of dk / dv lies
+ *     grad_seg_strides[1] / [2] elements behind segment s-1 (grad_seg_strides = {dout, dk, dv}) -- rows 1 .. of the
+ *     three slices of one [B, N, 3, H, 64] gradient buffer are a legal target.  All strides and offsets multiples of 8,
+ *     bases 16-byte aligned.  workspace: 16-byte aligned, tome_prop_attention_segments_backward_workspace_bytes(B, H, N,
+ *     Nk, nseg) bytes (fp32 L and delta per segment and query row; 0 for an illegal shape); NULL or workspace_bytes
+ *     below that: TOME_EWORKSPACE; anything else wrong: TOME_EINVAL with a message.  Head dim 64, TOME_BF16 / TOME_F16.
+ */
+size_t tome_prop_attention_segments_backward_workspace_bytes(int64_t B, int64_t H, int64_t N, int64_t Nk, int64_t nseg);
+int tome_prop_attention_segments_backward(const void *q, const void *k, const void *v, const void *out, const void *dout,
+                                          int dtype, int64_t B, int64_t H, int64_t N, int64_t Nk, int64_t D,
+                                          const int64_t *q_strides, const int64_t *k_strides, const int64_t *v_strides,
+                                          const int64_t *out_strides, const int64_t *dout_strides, const float *log_size,
+                                          int64_t log_size_stride, float scale, int64_t nseg, const int64_t *seg_strides,
+                                          const int64_t *grad_seg_strides, void *dq, void *dk, void *dv,
+                                          const int64_t *dq_strides, const int64_t *dk_strides, const int64_t *dv_strides,
+                                          void *workspace, size_t workspace_bytes, tome_stream_t stream);
+
+/*
+ * tome_trajectory_mix_backward  <-  what autograd derives from the temporal stage of ToMeTrajectoryAttention.forward
+ *     (tome/patch/motionformer.py:122-139) when q2, k2 or val require grad (additions to ABI v11, no entry changed): the
+ *     backward of tome_trajectory_mix.  Per (batch, token, head), with p = softmax_f(scale * q2 . k2[f]) recomputed as
+ *     the forward computes it:
+ *         dval[f] = p_f dout,  dp_f = dout . val[f],  delta = sum_f p_f dp_f,  ds_f = p_f (dp_f - delta),
+ *         dq2 = scale sum_f ds_f k2[f],  dk2[f] = scale ds_f q2
+ *     fp32 throughout, one rounding per output element; one streaming launch, no workspace, no atomics, same bits on
+ *     every run.  The forward's `tattn` output gets NO gradient: the patched block never consumes the map; a caller that
+ *     wants it under grad keeps the framework's ops.
+ *     q2 [B, S, H*64] contiguous; k2, val [B, S, F, H*64] views with their row strides as in the forward (val may be
+ *     the trajectory tokens themselves); dout [B, S, H*64] rows, batch b starting dout_batch_stride elements behind
+ *     batch b-1 (0 = contiguous; larger: rows 1 .. of the [B, 1+S, C] gradient of the joined buffer); dq2 [B, S, H*64]
+ *     contiguous; dk2, dval [B, S, F, H*64] with row strides of their own -- the two halves of one [B, S, F, 2C] buffer
+ *     are a legal target -- each NULL when that gradient is not wanted.  Only the H*64 channels of every row are written.
+ *     16-bit tensors, head dim 64, H <= 16, F <= 8, rows 16-byte aligned; anything else is TOME_EINVAL with a message.
+ */
+int tome_trajectory_mix_backward(const void *q2, const void *k2, const void *val, const void *dout, int dtype, int64_t B,
+                                 int64_t S, int64_t F, int64_t H, int64_t D, int64_t k_row_stride, int64_t v_row_stride,
+                                 int64_t dout_batch_stride, float scale, void *dq2, void *dk2, void *dval,
+                                 int64_t dk_row_stride, int64_t dv_row_stride, tome_stream_t stream);
 
 /*
  * tome_short_attention_backward  <-  what autograd derives from `self.temporal_attn(...)` in ToMeBlock.forward of the

@@ -30,6 +30,15 @@
 // images (row stride 144 B for the ds_read_b128 rows, 192 B for the transposed reads: the forward's conflict-free
 // strides).  32 matrix instructions (32x32x16) per wave and tile in each kernel: eight tile products where the forward
 // does two.
+//
+// The segmented form (SEG = true: the backward of tome_prop_attention_segments, Motionformer's per-frame stage,
+// tome/patch/motionformer.py:98-121) shares every line of the two kernels.  Segment s has keys, values, bias, O, dO, dK
+// and dV of its own and the queries in common, so dQ = scale * sum_s dS_s K_s:
+//   k_attn_bwd_dq   walks its two sweeps once per segment with the dQ accumulators kept in registers across the segments
+//                   (one fp32 sum, one rounding when dq is stored); dO and delta are per segment, L and delta go to the
+//                   workspace per (segment, batch*head, row).
+//   k_attn_bwd_dkv  takes the segment as one more grid factor: (segment, batch*head) in the place of batch*head.
+// The plain instantiations (SEG = false) never read the segment fields and keep their code.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -52,6 +61,9 @@ struct AttnBwdArgs {
     int B, H, N, Nk;
     float scale;
     int bias_skip;
+    // the segmented form only (SEG = true): element offsets from one segment to the next; lse / delta [nseg, B*H, N]
+    int nseg;
+    int64_t k_seg, v_seg, o_seg, do_seg, dk_seg, dv_seg, ls_seg;
 };
 
 // A 16-byte chunk of 16-bit values times a fp32 factor, rounded once to the format (q -> q~)
@@ -153,7 +165,7 @@ __device__ __forceinline__ bool attb_item(int blocks, int BH, int &bh, int &blk)
     return bh < BH;
 }
 
-template <typename TX, bool BIAS>
+template <typename TX, bool BIAS, bool SEG = false>
 __global__ __launch_bounds__(64 * ATTB_WAVES, 2) void k_attn_bwd_dq(AttnBwdArgs a) {
     __shared__ __attribute__((aligned(16))) short lds_kr[ATT_BN * ATT_KS];  // K, rows      (S^T)
     __shared__ __attribute__((aligned(16))) short lds_kt[ATT_BN * ATT_VS];  // K, transposed reads (dQ^T)
@@ -166,6 +178,7 @@ __global__ __launch_bounds__(64 * ATTB_WAVES, 2) void k_attn_bwd_dq(AttnBwdArgs 
     if (!attb_item((a.N + ATTB_BM - 1) / ATTB_BM, a.B * a.H, bh, qb)) return;
     const int b = bh / a.H, h = bh % a.H;
     const short *qp = reinterpret_cast<const short *>(a.q) + b * a.q_sb + h * a.q_sh;
+    // (SEG: the five below move on by a segment offset at the end of every pass of the segment loop)
     const short *kp = reinterpret_cast<const short *>(a.k) + b * a.k_sb + h * a.k_sh;
     const short *vp = reinterpret_cast<const short *>(a.v) + b * a.v_sb + h * a.v_sh;
     const short *op = reinterpret_cast<const short *>(a.o) + b * a.o_sb + h * a.o_sh;
@@ -176,7 +189,8 @@ __global__ __launch_bounds__(64 * ATTB_WAVES, 2) void k_attn_bwd_dq(AttnBwdArgs 
     const bool qon = qrow < a.N;
     const int qload = qon ? qrow : a.N - 1;  // (a lane past the end repeats the last query and stores nothing)
     const float LOG2E = 1.4426950408889634f;
-    const float bfac = (a.bias_skip && qrow == 0) ? 0.0f : 1.0f;  // the class query carries no bias
+    const int skip = SEG ? 0 : a.bias_skip;                  // (the segmented form has no skip form)
+    const float bfac = (skip && qrow == 0) ? 0.0f : 1.0f;  // the class query carries no bias
     const float sl = a.scale * LOG2E;
     att_s16x8 qf[4], gf[4];  // q~ and dO of this lane's query: channels 16ks + 8hf .. +7
     float delta = 0.0f;
@@ -196,6 +210,24 @@ __global__ __launch_bounds__(64 * ATTB_WAVES, 2) void k_attn_bwd_dq(AttnBwdArgs 
         }
     }
     delta += __shfl_xor(delta, 32);  // the partner lane holds the other 32 channels
+    // SEG: dO and delta of the next segment (the loop above without q~; gp and op have moved on)
+    auto next_rows = [&]() __attribute__((always_inline)) {
+        delta = 0.0f;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            gf[ks] = *reinterpret_cast<const att_s16x8 *>(gp + (int64_t)qload * a.do_sn + 16 * ks + 8 * hf);
+            const att_s16x8 of = *reinterpret_cast<const att_s16x8 *>(op + (int64_t)qload * a.o_sn + 16 * ks + 8 * hf);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                TX x, y;
+                const short sx = gf[ks][e], sy = of[e];
+                __builtin_memcpy(&x, &sx, 2);
+                __builtin_memcpy(&y, &sy, 2);
+                delta = __builtin_fmaf(to_f32(x), to_f32(y), delta);
+            }
+        }
+        delta += __shfl_xor(delta, 32);
+    };
 
     const int ntiles = (a.Nk + ATT_BN - 1) / ATT_BN;
     // staging through registers: thread -> rows r0 and r0 + 32, 16-byte column c0 of the 64 x 64 K and V tiles
@@ -217,7 +249,7 @@ __global__ __launch_bounds__(64 * ATTB_WAVES, 2) void k_attn_bwd_dq(AttnBwdArgs 
         if (BIAS && tid < ATT_BN) {
             const int key = t * ATT_BN + tid;
             const int kl = key < a.Nk ? key : a.Nk - 1;
-            breg = kl >= a.bias_skip ? lsp[kl - a.bias_skip] * LOG2E : 0.0f;
+            breg = kl >= skip ? lsp[kl - skip] * LOG2E : 0.0f;
         }
     };
     auto stage_write = [&](bool with_v) __attribute__((always_inline)) {
@@ -249,78 +281,90 @@ __global__ __launch_bounds__(64 * ATTB_WAVES, 2) void k_attn_bwd_dq(AttnBwdArgs 
         }
     };
 
-    // ---- sweep 1: row maximum and sum (log2 units), plain online softmax over this lane's half of every tile's keys
-    float m_run = -INFINITY, l_run = 0.0f;
-    stage_load(0, false);
-    for (int t = 0; t < ntiles; ++t) {
-        __syncthreads();  // every wave has left tile t-1
-        stage_write(false);
-        if (t + 1 < ntiles) stage_load(t + 1, false);
-        __syncthreads();
-        att_f32x16 s0, s1;
-        start(0.0f, s0, s1);
-        attb_rows_product<TX>(lds_kr, col, hf, qf, s0, s1);
-        const int key0 = t * ATT_BN + 4 * hf;
-        float mt = -INFINITY;
+    att_f32x16 dq0, dq1;  // dQ^T of this lane's query, summed over the key tiles (SEG: of every segment)
+    const int nseg = SEG ? a.nseg : 1;
+#pragma unroll 1
+    for (int seg = 0; seg < nseg; ++seg) {
+        if (SEG && seg > 0) next_rows();
+        // ---- sweep 1: row maximum and sum (log2 units), plain online softmax over this lane's half of every tile's keys
+        float m_run = -INFINITY, l_run = 0.0f;
+        stage_load(0, false);
+        for (int t = 0; t < ntiles; ++t) {
+            __syncthreads();  // every wave has left tile t-1
+            stage_write(false);
+            if (t + 1 < ntiles) stage_load(t + 1, false);
+            __syncthreads();
+            att_f32x16 s0, s1;
+            start(0.0f, s0, s1);
+            attb_rows_product<TX>(lds_kr, col, hf, qf, s0, s1);
+            const int key0 = t * ATT_BN + 4 * hf;
+            float mt = -INFINITY;
 #pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int key = key0 + (v & 3) + 8 * (v >> 2);
-            s0[v] = key < a.Nk ? s0[v] : -INFINITY;
-            s1[v] = key + 32 < a.Nk ? s1[v] : -INFINITY;
-            mt = fmaxf(mt, fmaxf(s0[v], s1[v]));
-        }
-        {
-            const unsigned mb = __float_as_uint(mt);
-            const auto sw = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);
-            mt = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-        }
-        const float m_new = fmaxf(m_run, mt);  // finite: every tile holds at least one key in range
-        float lsum = 0.0f;
+            for (int v = 0; v < 16; ++v) {
+                const int key = key0 + (v & 3) + 8 * (v >> 2);
+                s0[v] = key < a.Nk ? s0[v] : -INFINITY;
+                s1[v] = key + 32 < a.Nk ? s1[v] : -INFINITY;
+                mt = fmaxf(mt, fmaxf(s0[v], s1[v]));
+            }
+            {
+                const unsigned mb = __float_as_uint(mt);
+                const auto sw = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);
+                mt = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
+            }
+            const float m_new = fmaxf(m_run, mt);  // finite: every tile holds at least one key in range
+            float lsum = 0.0f;
 #pragma unroll
-        for (int v = 0; v < 16; ++v)
-            lsum += __builtin_amdgcn_exp2f(s0[v] - m_new) + __builtin_amdgcn_exp2f(s1[v] - m_new);
-        l_run = l_run * __builtin_amdgcn_exp2f(m_run - m_new) + lsum;
-        m_run = m_new;
-    }
-    const float l_tot = l_run + __shfl_xor(l_run, 32);
-    const float lse = m_run + __builtin_log2f(l_tot);
-    if (qon && hf == 0) {
-        a.lse[(int64_t)bh * a.N + qrow] = lse;
-        a.delta[(int64_t)bh * a.N + qrow] = delta;
-    }
+            for (int v = 0; v < 16; ++v)
+                lsum += __builtin_amdgcn_exp2f(s0[v] - m_new) + __builtin_amdgcn_exp2f(s1[v] - m_new);
+            l_run = l_run * __builtin_amdgcn_exp2f(m_run - m_new) + lsum;
+            m_run = m_new;
+        }
+        const float l_tot = l_run + __shfl_xor(l_run, 32);
+        const float lse = m_run + __builtin_log2f(l_tot);
+        if (qon && hf == 0) {  // (SEG: the workspace rows of segment `seg` lie seg * B*H*N further on)
+            const int64_t wrow = ((int64_t)(SEG ? seg * (a.B * a.H) : 0) + bh) * a.N + qrow;
+            a.lse[wrow] = lse;
+            a.delta[wrow] = delta;
+        }
 
-    // ---- sweep 2: dQ^T += K^T (P o (dP - delta))^T
-    att_f32x16 dq0, dq1;
+        // ---- sweep 2: dQ^T += K^T (P o (dP - delta))^T
+        if (!SEG || seg == 0) {
 #pragma unroll
-    for (int v = 0; v < 16; ++v) dq0[v] = dq1[v] = 0.0f;
-    stage_load(0, true);
-    for (int t = 0; t < ntiles; ++t) {
-        __syncthreads();
-        stage_write(true);
-        if (t + 1 < ntiles) stage_load(t + 1, true);
-        __syncthreads();
-        att_f32x16 s0, s1, p0, p1;
-        start(-lse, s0, s1);
-        attb_rows_product<TX>(lds_kr, col, hf, qf, s0, s1);
-#pragma unroll
-        for (int v = 0; v < 16; ++v) p0[v] = p1[v] = -delta;
-        attb_rows_product<TX>(lds_vr, col, hf, gf, p0, p1);
-        const int key0 = t * ATT_BN + 4 * hf;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int key = key0 + (v & 3) + 8 * (v >> 2);
-            const float w0 = key < a.Nk ? __builtin_amdgcn_exp2f(s0[v]) : 0.0f;  // out-of-range keys weigh exactly zero
-            const float w1 = key + 32 < a.Nk ? __builtin_amdgcn_exp2f(s1[v]) : 0.0f;
-            s0[v] = w0 * p0[v];
-            s1[v] = w1 * p1[v];
+            for (int v = 0; v < 16; ++v) dq0[v] = dq1[v] = 0.0f;
         }
-        attb_tr_product<TX>(lds_kt, lane, s0, s1, dq0, dq1);
-    }
+        stage_load(0, true);
+        for (int t = 0; t < ntiles; ++t) {
+            __syncthreads();
+            stage_write(true);
+            if (t + 1 < ntiles) stage_load(t + 1, true);
+            __syncthreads();
+            att_f32x16 s0, s1, p0, p1;
+            start(-lse, s0, s1);
+            attb_rows_product<TX>(lds_kr, col, hf, qf, s0, s1);
+#pragma unroll
+            for (int v = 0; v < 16; ++v) p0[v] = p1[v] = -delta;
+            attb_rows_product<TX>(lds_vr, col, hf, gf, p0, p1);
+            const int key0 = t * ATT_BN + 4 * hf;
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const int key = key0 + (v & 3) + 8 * (v >> 2);
+                const float w0 = key < a.Nk ? __builtin_amdgcn_exp2f(s0[v]) : 0.0f;  // out-of-range keys weigh exactly zero
+                const float w1 = key + 32 < a.Nk ? __builtin_amdgcn_exp2f(s1[v]) : 0.0f;
+                s0[v] = w0 * p0[v];
+                s1[v] = w1 * p1[v];
+            }
+            attb_tr_product<TX>(lds_kt, lane, s0, s1, dq0, dq1);
+        }
+        if (SEG) {  // the next segment's keys, values, bias, O and dO
+            kp += a.k_seg; vp += a.v_seg; op += a.o_seg; gp += a.do_seg;
+            if (BIAS) lsp += a.ls_seg;
+        }
+    }  // segments
     short *dqp = reinterpret_cast<short *>(a.dq) + b * a.dq_sb + h * a.dq_sh + (int64_t)(qon ? qrow : 0) * a.dq_sn;
     attb_store_row<TX>(dqp, hf, qon, dq0, dq1, a.scale);
 }
 
-template <typename TX, bool BIAS>
+template <typename TX, bool BIAS, bool SEG = false>
 __global__ __launch_bounds__(64 * ATTB_WAVES, 2) void k_attn_bwd_dkv(AttnBwdArgs a) {
     __shared__ __attribute__((aligned(16))) short lds_qr[ATT_BN * ATT_KS];  // Q~, rows     (S)
     __shared__ __attribute__((aligned(16))) short lds_qt[ATT_BN * ATT_VS];  // Q, transposed reads (dK^T)
@@ -331,13 +375,17 @@ __global__ __launch_bounds__(64 * ATTB_WAVES, 2) void k_attn_bwd_dkv(AttnBwdArgs
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int col = lane & 31, hf = lane >> 5;
     int bh, kb;
-    if (!attb_item((a.Nk + ATTB_BM - 1) / ATTB_BM, a.B * a.H, bh, kb)) return;
+    const int BH = a.B * a.H;
+    if (!attb_item((a.Nk + ATTB_BM - 1) / ATTB_BM, SEG ? BH * a.nseg : BH, bh, kb)) return;
+    const int seg = SEG ? bh / BH : 0;  // (SEG: the items are (segment, batch*head) pairs)
+    if (SEG) bh -= seg * BH;
     const int b = bh / a.H, h = bh % a.H;
     const short *qp = reinterpret_cast<const short *>(a.q) + b * a.q_sb + h * a.q_sh;
-    const short *kp = reinterpret_cast<const short *>(a.k) + b * a.k_sb + h * a.k_sh;
-    const short *vp = reinterpret_cast<const short *>(a.v) + b * a.v_sb + h * a.v_sh;
-    const short *gp = reinterpret_cast<const short *>(a.dout) + b * a.do_sb + h * a.do_sh;
-    const float *lsep = a.lse + (int64_t)bh * a.N, *dlp = a.delta + (int64_t)bh * a.N;
+    const short *kp = reinterpret_cast<const short *>(a.k) + b * a.k_sb + h * a.k_sh + (SEG ? seg * a.k_seg : 0);
+    const short *vp = reinterpret_cast<const short *>(a.v) + b * a.v_sb + h * a.v_sh + (SEG ? seg * a.v_seg : 0);
+    const short *gp = reinterpret_cast<const short *>(a.dout) + b * a.do_sb + h * a.do_sh + (SEG ? seg * a.do_seg : 0);
+    const int64_t wrow = ((int64_t)(SEG ? seg * BH : 0) + bh) * a.N;
+    const float *lsep = a.lse + wrow, *dlp = a.delta + wrow;
 
     const int krow = kb * ATTB_BM + wave * 32 + col;
     const bool kon = krow < a.Nk;
@@ -345,7 +393,9 @@ __global__ __launch_bounds__(64 * ATTB_WAVES, 2) void k_attn_bwd_dkv(AttnBwdArgs
     const float LOG2E = 1.4426950408889634f;
     const float sl = a.scale * LOG2E;
     float beta = 0.0f;  // this lane's key: log(size) * log2(e); key 0 of the skip form carries none
-    if (BIAS) beta = kload >= a.bias_skip ? a.log_size[b * a.ls_sb + kload - a.bias_skip] * LOG2E : 0.0f;
+    if (BIAS)
+        beta = kload >= a.bias_skip ? a.log_size[b * a.ls_sb + (SEG ? seg * a.ls_seg : 0) + kload - a.bias_skip] * LOG2E
+                                    : 0.0f;
     att_s16x8 kf[4], vf[4];  // K and V rows of this lane's key: channels 16ks + 8hf .. +7
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
@@ -427,8 +477,8 @@ __global__ __launch_bounds__(64 * ATTB_WAVES, 2) void k_attn_bwd_dkv(AttnBwdArgs
         }
     }
     const int64_t kst = kon ? krow : 0;
-    short *dkp = reinterpret_cast<short *>(a.dk) + b * a.dk_sb + h * a.dk_sh + kst * a.dk_sn;
-    short *dvp = reinterpret_cast<short *>(a.dv) + b * a.dv_sb + h * a.dv_sh + kst * a.dv_sn;
+    short *dkp = reinterpret_cast<short *>(a.dk) + b * a.dk_sb + h * a.dk_sh + kst * a.dk_sn + (SEG ? seg * a.dk_seg : 0);
+    short *dvp = reinterpret_cast<short *>(a.dv) + b * a.dv_sb + h * a.dv_sh + kst * a.dv_sn + (SEG ? seg * a.dv_seg : 0);
     attb_store_row<TX>(dkp, hf, kon, dk0, dk1, a.scale);
     attb_store_row<TX>(dvp, hf, kon, dv0, dv1, 1.0f);
 }

@@ -3,7 +3,7 @@
 // -ffp-contract=off -shared -fPIC (csrc/build.py).  No torch, no CUDA, no portability layer.
 //
 // One translation unit: tome_common.h (types), tome_match.h, tome_merge.h, tome_merge_bwd.h, tome_ln_bwd.h,
-// tome_gelu_bwd.h, tome_short_attn_bwd.h and tome_partition.h (kernels), this file (host).
+// tome_gelu_bwd.h, tome_short_attn_bwd.h, tome_traj_bwd.h and tome_partition.h (kernels), this file (host).
 //
 // Launch sequence of one matching (tome_match / tome_match_keys), kernels in tome_match.h:
 //   k_unit_rows[_heads]  keys -> fp32 unit vectors, even/odd split, MFMA-fragment order (HBM bound)
@@ -33,6 +33,10 @@
 // and of the proportional attention's backward (tome_prop_attention_backward), tome_attn_bwd.h:
 //   k_attn_bwd_dq        row statistics recomputed (two sweeps over the keys), dq, L and delta to the workspace
 //   k_attn_bwd_dkv       dk and dv per block of keys over all queries                          (MFMA bound)
+// the same two with a segment dimension for Motionformer's per-frame stage (tome_prop_attention_segments_backward): dq
+// summed over the segments in registers, the segment one more grid factor of dk / dv;
+// and of its temporal stage (tome_trajectory_mix_backward), tome_traj_bwd.h:
+//   k_trajectory_mix_bwd   the F weights of a (token, head) recomputed, dq2 / dk2 / dval in one pass   (HBM bound)
 // The partition matchings (kth_ / random_bipartite_soft_matching: arbitrary source / destination sets, every source
 // merged) have their own sequence, written out at the top of tome_partition.h.
 //
@@ -61,6 +65,7 @@
 #include "tome_attn_resident.h"
 #include "tome_attn_bwd.h"
 #include "tome_short_attn_bwd.h"
+#include "tome_traj_bwd.h"
 #include "tome_embed.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -1142,10 +1147,11 @@ extern "C" int tome_trajectory_mix(const void *q2, const void *k2, const void *v
     }, [&] { return not_16bit("tome_trajectory_mix", dtype, "tensors"); });
 }
 
-// ---- backward of tome_prop_attention's plain form (tome_attn_bwd.h)
-static bool attn_bwd_shape_ok(int64_t B, int64_t H, int64_t N, int64_t Nk) {
-    return B > 0 && H > 0 && N > 0 && Nk > 0 && B * H <= 0x7fffffffLL / 64 && N <= 0x7fffffffLL / 4 &&
-           Nk <= 0x7fffffffLL / 4 && B * H * N <= (1ll << 40);
+// ---- backward of tome_prop_attention (plain form) and of tome_prop_attention_segments (tome_attn_bwd.h)
+static bool attn_bwd_shape_ok(int64_t B, int64_t H, int64_t N, int64_t Nk, int64_t nseg = 1) {
+    return B > 0 && H > 0 && N > 0 && Nk > 0 && nseg > 0 && nseg <= 0x7fffffffLL / 64 &&
+           B * H * nseg <= 0x7fffffffLL / 64 && N <= 0x7fffffffLL / 4 && Nk <= 0x7fffffffLL / 4 &&
+           B * H * nseg * N <= (1ll << 40);
 }
 
 extern "C" size_t tome_prop_attention_backward_workspace_bytes(int64_t B, int64_t H, int64_t N, int64_t Nk) {
@@ -1153,18 +1159,26 @@ extern "C" size_t tome_prop_attention_backward_workspace_bytes(int64_t B, int64_
     return align_up(2 * (size_t)(B * H * N) * sizeof(float), 256);  // L and delta, one fp32 each per query row
 }
 
-extern "C" int tome_prop_attention_backward(const void *q, const void *k, const void *v, const void *out,
-                                            const void *dout, int dtype, int64_t B, int64_t H, int64_t N, int64_t Nk,
-                                            int64_t D, const int64_t *q_strides, const int64_t *k_strides,
-                                            const int64_t *v_strides, const int64_t *out_strides,
-                                            const int64_t *dout_strides, const float *log_size,
-                                            int64_t log_size_stride, int bias_skip, float scale, void *dq, void *dk,
-                                            void *dv, const int64_t *dq_strides, const int64_t *dk_strides,
-                                            const int64_t *dv_strides, void *workspace, size_t workspace_bytes,
-                                            tome_stream_t stream) {
-    const char *const fn = "tome_prop_attention_backward";
+extern "C" size_t tome_prop_attention_segments_backward_workspace_bytes(int64_t B, int64_t H, int64_t N, int64_t Nk,
+                                                                        int64_t nseg) {
+    if (!attn_bwd_shape_ok(B, H, N, Nk, nseg)) return 0;
+    return align_up(2 * (size_t)(nseg * B * H * N) * sizeof(float), 256);  // L and delta per (segment, query row)
+}
+
+// Both entries: nseg == 0 is the plain form (seg_strides / grad_seg_strides unused), nseg >= 1 the segmented one with
+// seg_strides = {k, v, out, log_size} and grad_seg_strides = {dout, dk, dv} element offsets between segments.
+static int attn_backward_impl(const char *fn, const void *q, const void *k, const void *v, const void *out,
+                              const void *dout, int dtype, int64_t B, int64_t H, int64_t N, int64_t Nk, int64_t D,
+                              const int64_t *q_strides, const int64_t *k_strides, const int64_t *v_strides,
+                              const int64_t *out_strides, const int64_t *dout_strides, const float *log_size,
+                              int64_t log_size_stride, int bias_skip, float scale, int64_t nseg,
+                              const int64_t *seg_strides, const int64_t *grad_seg_strides, void *dq, void *dk, void *dv,
+                              const int64_t *dq_strides, const int64_t *dk_strides, const int64_t *dv_strides,
+                              void *workspace, size_t workspace_bytes, tome_stream_t stream) {
+    const bool seg = nseg > 0;
+    const int64_t ns = seg ? nseg : 1;
     if (!q || !k || !v || !out || !dout || !dq || !dk || !dv || !q_strides || !k_strides || !v_strides || !out_strides ||
-        !dout_strides || !dq_strides || !dk_strides || !dv_strides || !attn_bwd_shape_ok(B, H, N, Nk))
+        !dout_strides || !dq_strides || !dk_strides || !dv_strides || !attn_bwd_shape_ok(B, H, N, Nk, ns))
         return fail(TOME_EINVAL, "%s: bad shape/pointer", fn);
     if (D != ATT_D) return fail(TOME_EINVAL, "%s: head dim %lld (only 64)", fn, (long long)D);
     if (int rc = not_16bit(fn, dtype, "q/k/v")) return rc;
@@ -1176,7 +1190,14 @@ extern "C" int tome_prop_attention_backward(const void *q, const void *k, const 
         if (!aligned16(pp[i]) || ss[i][0] % 8 || ss[i][1] % 8 || ss[i][2] % 8 || ss[i][2] < D)
             return fail(TOME_EINVAL, "%s: rows must be 16-byte aligned (pointers, strides %% 8 == 0, token stride >= 64)", fn);
     }
-    const size_t need = tome_prop_attention_backward_workspace_bytes(B, H, N, Nk);
+    if (seg) {
+        if (!seg_strides || !grad_seg_strides) return fail(TOME_EINVAL, "%s: segment offsets required", fn);
+        if (seg_strides[0] % 8 || seg_strides[1] % 8 || seg_strides[2] % 8 || grad_seg_strides[0] % 8 ||
+            grad_seg_strides[1] % 8 || grad_seg_strides[2] % 8)
+            return fail(TOME_EINVAL, "%s: segment offsets must keep rows 16-byte aligned", fn);
+    }
+    const size_t need = seg ? tome_prop_attention_segments_backward_workspace_bytes(B, H, N, Nk, nseg)
+                            : tome_prop_attention_backward_workspace_bytes(B, H, N, Nk);
     if (!workspace || workspace_bytes < need)
         return fail(TOME_EWORKSPACE, "%s: workspace %zu < %zu bytes", fn, workspace ? workspace_bytes : (size_t)0, need);
     if (!aligned16(workspace)) return fail(TOME_EINVAL, "%s: workspace not 16-byte aligned", fn);
@@ -1191,24 +1212,99 @@ extern "C" int tome_prop_attention_backward(const void *q, const void *k, const 
     a.dk_sb = dk_strides[0]; a.dk_sh = dk_strides[1]; a.dk_sn = dk_strides[2];
     a.dv_sb = dv_strides[0]; a.dv_sh = dv_strides[1]; a.dv_sn = dv_strides[2];
     a.log_size = log_size; a.ls_sb = log_size_stride;
-    a.lse = (float *)workspace; a.delta = (float *)workspace + B * H * N;
+    a.lse = (float *)workspace; a.delta = (float *)workspace + ns * B * H * N;
     a.B = (int)B; a.H = (int)H; a.N = (int)N; a.Nk = (int)Nk; a.scale = scale; a.bias_skip = bias_skip;
-    const int64_t bh8 = (B * H + 7) / 8 * 8;
+    a.nseg = (int)ns;
+    a.k_seg = a.v_seg = a.o_seg = a.do_seg = a.dk_seg = a.dv_seg = a.ls_seg = 0;
+    if (seg) {
+        a.k_seg = seg_strides[0]; a.v_seg = seg_strides[1]; a.o_seg = seg_strides[2]; a.ls_seg = seg_strides[3];
+        a.do_seg = grad_seg_strides[0]; a.dk_seg = grad_seg_strides[1]; a.dv_seg = grad_seg_strides[2];
+    }
+    // dq: one workgroup per 128 queries of a (batch, head), every segment inside it; dk / dv: per (segment, batch, head)
+    const int64_t bh8 = (B * H + 7) / 8 * 8, sbh8 = (ns * B * H + 7) / 8 * 8;
     const int64_t qblocks = (N + ATTB_BM - 1) / ATTB_BM, kblocks = (Nk + ATTB_BM - 1) / ATTB_BM;
-    if (bh8 * qblocks > 0x7fffffffLL || bh8 * kblocks > 0x7fffffffLL) return fail(TOME_EINVAL, "%s: grid too large", fn);
+    if (bh8 * qblocks > 0x7fffffffLL || sbh8 * kblocks > 0x7fffffffLL) return fail(TOME_EINVAL, "%s: grid too large", fn);
     hipStream_t st = (hipStream_t)stream;
-    const dim3 qgrid((unsigned)(bh8 * qblocks)), kgrid((unsigned)(bh8 * kblocks)), block(64 * ATTB_WAVES);
-    auto go = [&](auto tx, auto bias) {
+    const dim3 qgrid((unsigned)(bh8 * qblocks)), kgrid((unsigned)(sbh8 * kblocks)), block(64 * ATTB_WAVES);
+    auto go = [&](auto tx, auto bias, auto segf) {
         using TX = typename decltype(tx)::type;
         constexpr bool BIAS = decltype(bias)::value != 0;
-        hipLaunchKernelGGL((k_attn_bwd_dq<TX, BIAS>), qgrid, block, 0, st, a);
+        constexpr bool SEG = decltype(segf)::value != 0;
+        hipLaunchKernelGGL((k_attn_bwd_dq<TX, BIAS, SEG>), qgrid, block, 0, st, a);
         if (int rc = check_launch("k_attn_bwd_dq")) return rc;
-        hipLaunchKernelGGL((k_attn_bwd_dkv<TX, BIAS>), kgrid, block, 0, st, a);
+        hipLaunchKernelGGL((k_attn_bwd_dkv<TX, BIAS, SEG>), kgrid, block, 0, st, a);
         return check_launch("k_attn_bwd_dkv");
     };
     return dispatch_x<false>(dtype, [&](auto tx) {
-        return log_size ? go(tx, AttInt<1>{}) : go(tx, AttInt<0>{});
+        if (seg) return log_size ? go(tx, AttInt<1>{}, AttInt<1>{}) : go(tx, AttInt<0>{}, AttInt<1>{});
+        return log_size ? go(tx, AttInt<1>{}, AttInt<0>{}) : go(tx, AttInt<0>{}, AttInt<0>{});
     }, [&] { return not_16bit(fn, dtype, "q/k/v"); });
+}
+
+extern "C" int tome_prop_attention_backward(const void *q, const void *k, const void *v, const void *out,
+                                            const void *dout, int dtype, int64_t B, int64_t H, int64_t N, int64_t Nk,
+                                            int64_t D, const int64_t *q_strides, const int64_t *k_strides,
+                                            const int64_t *v_strides, const int64_t *out_strides,
+                                            const int64_t *dout_strides, const float *log_size,
+                                            int64_t log_size_stride, int bias_skip, float scale, void *dq, void *dk,
+                                            void *dv, const int64_t *dq_strides, const int64_t *dk_strides,
+                                            const int64_t *dv_strides, void *workspace, size_t workspace_bytes,
+                                            tome_stream_t stream) {
+    return attn_backward_impl("tome_prop_attention_backward", q, k, v, out, dout, dtype, B, H, N, Nk, D, q_strides,
+                              k_strides, v_strides, out_strides, dout_strides, log_size, log_size_stride, bias_skip, scale,
+                              0, nullptr, nullptr, dq, dk, dv, dq_strides, dk_strides, dv_strides, workspace,
+                              workspace_bytes, stream);
+}
+
+extern "C" int tome_prop_attention_segments_backward(
+    const void *q, const void *k, const void *v, const void *out, const void *dout, int dtype, int64_t B, int64_t H,
+    int64_t N, int64_t Nk, int64_t D, const int64_t *q_strides, const int64_t *k_strides, const int64_t *v_strides,
+    const int64_t *out_strides, const int64_t *dout_strides, const float *log_size, int64_t log_size_stride, float scale,
+    int64_t nseg, const int64_t *seg_strides, const int64_t *grad_seg_strides, void *dq, void *dk, void *dv,
+    const int64_t *dq_strides, const int64_t *dk_strides, const int64_t *dv_strides, void *workspace,
+    size_t workspace_bytes, tome_stream_t stream) {
+    const char *const fn = "tome_prop_attention_segments_backward";
+    if (nseg < 1) return fail(TOME_EINVAL, "%s: nseg >= 1 required", fn);
+    return attn_backward_impl(fn, q, k, v, out, dout, dtype, B, H, N, Nk, D, q_strides, k_strides, v_strides, out_strides,
+                              dout_strides, log_size, log_size_stride, 0, scale, nseg, seg_strides, grad_seg_strides, dq,
+                              dk, dv, dq_strides, dk_strides, dv_strides, workspace, workspace_bytes, stream);
+}
+
+// ---- backward of tome_trajectory_mix (tome_traj_bwd.h)
+extern "C" int tome_trajectory_mix_backward(const void *q2, const void *k2, const void *val, const void *dout, int dtype,
+                                            int64_t B, int64_t S, int64_t F, int64_t H, int64_t D, int64_t k_row_stride,
+                                            int64_t v_row_stride, int64_t dout_batch_stride, float scale, void *dq2,
+                                            void *dk2, void *dval, int64_t dk_row_stride, int64_t dv_row_stride,
+                                            tome_stream_t stream) {
+    const char *const fn = "tome_trajectory_mix_backward";
+    if (!q2 || !k2 || !val || !dout || !dq2 || B <= 0 || S <= 0 || F <= 0 || H <= 0)
+        return fail(TOME_EINVAL, "%s: bad shape/pointer", fn);
+    if (D != 64 || H > 16 || F > TRAJ_MAXF)
+        return fail(TOME_EINVAL, "%s: head dim 64, at most 16 heads and %d frames", fn, TRAJ_MAXF);
+    if (int rc = not_16bit(fn, dtype, "tensors")) return rc;
+    const int64_t C = H * D;
+    if (k_row_stride % 8 || v_row_stride % 8 || k_row_stride < C || v_row_stride < C || !aligned16(q2) || !aligned16(k2) ||
+        !aligned16(val) || !aligned16(dout) || !aligned16(dq2))
+        return fail(TOME_EINVAL, "%s: rows must be 16-byte aligned", fn);
+    if ((dk2 && (dk_row_stride % 8 || dk_row_stride < C || !aligned16(dk2))) ||
+        (dval && (dv_row_stride % 8 || dv_row_stride < C || !aligned16(dval))))
+        return fail(TOME_EINVAL, "%s: rows of dk2 / dval must be 16-byte aligned and at least H*64 elements apart", fn);
+    if (dout_batch_stride == 0) dout_batch_stride = S * C;
+    if (dout_batch_stride < S * C || dout_batch_stride % 8)
+        return fail(TOME_EINVAL, "%s: dout_batch_stride must be 0 or a multiple of 8 >= S*H*D", fn);
+    const int64_t rows = B * S;
+    if (rows > 0x7fffffffLL) return fail(TOME_EINVAL, "%s: too many tokens", fn);
+    TrajBwdArgs a;
+    a.q2 = q2; a.k2 = k2; a.val = val; a.dout = dout; a.dq2 = dq2; a.dk2 = dk2; a.dval = dval;
+    a.rows = rows; a.k_row = k_row_stride; a.v_row = v_row_stride; a.dk_row = dk_row_stride; a.dv_row = dv_row_stride;
+    a.do_sb = dout_batch_stride; a.S = (int)S; a.F = (int)F; a.H = (int)H; a.scale = scale;
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    hipStream_t st = (hipStream_t)stream;
+    return dispatch_x<false>(dtype, [&](auto tx) {
+        using TX = typename decltype(tx)::type;
+        hipLaunchKernelGGL(k_trajectory_mix_bwd<TX>, grid, dim3(256), 0, st, a);
+        return check_launch("k_trajectory_mix_bwd");
+    }, [&] { return not_16bit(fn, dtype, "tensors"); });
 }
 
 // The rows tome_short_attention and its backward can walk: {batch, head, token} element strides with the heads of a

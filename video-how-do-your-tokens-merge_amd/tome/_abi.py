@@ -74,6 +74,11 @@ SIGNATURES = {
     "tome_layernorm_backward_regrouped_workspace_bytes": (sz, [i64, i64, i64, i64], True),
     "tome_layernorm_backward_regrouped": (i32, [vp, vp, vp, i32, i64, i64, i64, i64, vp, f32, vp, vp, vp, vp, vp],
                                                True),
+    "tome_prop_attention_segments_backward_workspace_bytes": (sz, [i64, i64, i64, i64, i64], True),
+    "tome_prop_attention_segments_backward": (i32, [vp, vp, vp, vp, vp, i32, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp,
+                                                   vp, i64, f32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp], True),
+    "tome_trajectory_mix_backward": (i32, [vp, vp, vp, vp, i32, i64, i64, i64, i64, i64, i64, i64, i64, f32, vp, vp, vp,
+                                          i64, i64, vp], True),
 }
 SYMBOLS = tuple(SIGNATURES)
 
@@ -787,6 +792,76 @@ def prop_attention_segments(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, n
     return y
 
 
+def prop_attention_segments_trainable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, nseg: int) -> bool:
+    """Can tome_prop_attention_segments run on these heads (_head_view each, one dtype and device, the keys a whole number
+    of segments) with tome_prop_attention_segments_backward behind it (tome/_attn.py) when they require grad?"""
+    return (all(_head_view(t) and t.dtype == q.dtype and t.device == q.device for t in (q, k, v))
+            and k.shape == v.shape and k.shape[:2] == q.shape[:2] and int(nseg) >= 1 and k.shape[2] >= int(nseg)
+            and k.shape[2] % int(nseg) == 0)
+
+
+def prop_attention_segments_backward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, y: torch.Tensor, dy: torch.Tensor,
+                                     nseg: int, scale: float, log_bias: Optional[torch.Tensor] = None, grads=None,
+                                     workspace: Optional[torch.Tensor] = None):
+    """tome_prop_attention_segments_backward: (dq, dk, dv) of y = prop_attention_segments(q, k, v, nseg, scale, log_bias)
+    given dy.  q [B, H, N, 64], k / v [B, H, nseg*P, 64] head views as the forward took them; y and dy [B, N, nseg, H*64]
+    (y: what the forward returned; dy is copied once unless its rows are 16-byte aligned with contiguous channels).
+    grads: three head views to write into, of q's and k's shapes (rows of the slices of one [B, N, 3, H, 64] buffer,
+    say), or None for fresh tensors.  dq is the sum over the segments, taken in fp32 and rounded once.  No CPU path."""
+    for t, name in ((q, "q"), (k, "k"), (v, "v")):
+        require_device(t, f"prop_attention_segments_backward({name})")
+    nseg = int(nseg)
+    if not prop_attention_segments_trainable(q, k, v, nseg):
+        raise TomeHipError(f"prop_attention_segments_backward: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} "
+                           f"must be [B, H, N, 64] 16-bit views of one dtype with 16-byte aligned rows, the keys {nseg} "
+                           "segments of equal length")
+    B, H, N, D = q.shape
+    P = k.shape[2] // nseg
+    if log_bias is not None and (tuple(log_bias.shape) != (B, nseg * P) or log_bias.dtype != torch.float32
+                                 or log_bias.stride(1) != 1 or log_bias.device != q.device):
+        raise TomeHipError(f"prop_attention_segments_backward: log_bias must be an fp32 {(B, nseg * P)} view with "
+                           "contiguous rows")
+    rows = []
+    for t, name in ((y, "y"), (dy, "dy")):
+        if tuple(t.shape) != (B, N, nseg, H * D) or t.device != q.device:
+            raise TomeHipError(f"prop_attention_segments_backward: {name} must be {(B, N, nseg, H * D)} on {q.device}, "
+                               f"got {tuple(t.shape)}")
+        t = t.detach()
+        if t.dtype != q.dtype:
+            t = t.to(q.dtype)
+        if t.stride(3) != 1 or any(s % 8 for s in t.stride()[:3]) or t.data_ptr() % 16:
+            t = t.contiguous()
+        rows.append(t)
+    y, dy = rows
+    if grads is None:
+        dq = torch.empty((B, N, H, D), dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
+        dk = torch.empty((B, nseg * P, H, D), dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
+        dv = torch.empty((B, nseg * P, H, D), dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
+    else:
+        dq, dk, dv = grads
+        for t, like, name in ((dq, q, "dq"), (dk, k, "dk"), (dv, v, "dv")):
+            if t.shape != like.shape or t.dtype != q.dtype or t.device != q.device or not _head_view(t):
+                raise TomeHipError(f"prop_attention_segments_backward: {name} must be a {tuple(like.shape)} {q.dtype} head "
+                                   "view with 16-byte aligned rows")
+    L = lib()
+    entry = require_symbol(L, "tome_prop_attention_segments_backward")
+    i64x3 = ctypes.c_int64 * 3
+    seg = (ctypes.c_int64 * 4)(P * k.stride(2), P * v.stride(2), y.stride(2), P)
+    gseg = i64x3(dy.stride(2), P * dk.stride(2), P * dv.stride(2))
+    with _on_device(q.device):
+        stream = _stream(q.device)
+        ws = workspace if workspace is not None else _sized_workspace(
+            L, "tome_prop_attention_segments_backward_workspace_bytes", (B, H, N, P, nseg), q.device, stream,
+            "prop_attention_segments_backward")
+        rc = entry(q.data_ptr(), k.data_ptr(), v.data_ptr(), y.data_ptr(), dy.data_ptr(), dtype_code(q, "q"), B, H, N, P, D,
+                   _head_strides(q), _head_strides(k), _head_strides(v), i64x3(y.stride(0), D, y.stride(1)),
+                   i64x3(dy.stride(0), D, dy.stride(1)), _ptr(log_bias), 0 if log_bias is None else log_bias.stride(0),
+                   float(scale), nseg, seg, gseg, dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), _head_strides(dq),
+                   _head_strides(dk), _head_strides(dv), ws.data_ptr(), ws.numel() * ws.element_size(), stream)
+    _check(rc, "tome_prop_attention_segments_backward")
+    return dq, dk, dv
+
+
 def _short_heads(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> bool:
     """[B, H, N <= 8, 64] views of 16-bit tensors on one device whose heads lie side by side in a token's row (head
     stride 64), rows 16-byte aligned."""
@@ -867,9 +942,9 @@ def short_attention_backward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, 
     return dq, dk, dv
 
 
-def trajectory_mix_ok(q2: torch.Tensor, k2: torch.Tensor, val: torch.Tensor, heads: int) -> bool:
-    """Can tome_trajectory_mix take these?  q2 [B, S, C], k2 / val [B, S, F, C] views (rows contiguous over C,
-    (b, s, f) rows evenly spaced), 16-bit, head dim 64, at most 16 heads and 8 frames."""
+def _trajectory_rows(q2: torch.Tensor, k2: torch.Tensor, val: torch.Tensor, heads: int) -> bool:
+    """q2 [B, S, C], k2 / val [B, S, F, C] views (rows contiguous over C, (b, s, f) rows evenly spaced), 16-bit, head
+    dim 64, at most 16 heads and 8 frames."""
     if not (q2.is_cuda and q2.dtype in (torch.bfloat16, torch.float16) and q2.dim() == 3 and k2.dim() == 4):
         return False
     B, S, C = q2.shape
@@ -878,7 +953,19 @@ def trajectory_mix_ok(q2: torch.Tensor, k2: torch.Tensor, val: torch.Tensor, hea
         return (t.shape == (B, S, F, C) and t.dtype == q2.dtype and t.stride(3) == 1 and t.stride(2) % 8 == 0
                 and t.stride(1) == F * t.stride(2) and t.stride(0) == S * t.stride(1) and t.data_ptr() % 16 == 0)
     return (C == heads * 64 and heads <= 16 and F <= 8 and q2.is_contiguous() and q2.data_ptr() % 16 == 0
-            and rows_ok(k2) and rows_ok(val) and not (torch.is_grad_enabled() and (q2.requires_grad or k2.requires_grad)))
+            and rows_ok(k2) and rows_ok(val))
+
+
+def trajectory_mix_ok(q2: torch.Tensor, k2: torch.Tensor, val: torch.Tensor, heads: int) -> bool:
+    """Can tome_trajectory_mix take these (_trajectory_rows), no gradient wanted?"""
+    return (_trajectory_rows(q2, k2, val, heads)
+            and not (torch.is_grad_enabled() and (q2.requires_grad or k2.requires_grad)))
+
+
+def trajectory_mix_trainable(q2: torch.Tensor, k2: torch.Tensor, val: torch.Tensor, heads: int) -> bool:
+    """Can tome_trajectory_mix run on these (_trajectory_rows) with tome_trajectory_mix_backward behind it (tome/_attn.py)
+    when they require grad?"""
+    return _trajectory_rows(q2, k2, val, heads)
 
 
 def trajectory_mix(q2: torch.Tensor, k2: torch.Tensor, val: torch.Tensor, heads: int, scale: float,
@@ -904,6 +991,51 @@ def trajectory_mix(q2: torch.Tensor, k2: torch.Tensor, val: torch.Tensor, heads:
                                        _ptr(attn), _stream(q2.device))
     _check(rc, "tome_trajectory_mix")
     return out, attn
+
+
+def trajectory_mix_backward(q2: torch.Tensor, k2: torch.Tensor, val: torch.Tensor, dout: torch.Tensor, heads: int,
+                            scale: float, want_k2: bool = True, want_val: bool = True, grads=None):
+    """tome_trajectory_mix_backward: (dq2, dk2, dval) of out = trajectory_mix(q2, k2, val, heads, scale)[0] given dout
+    [B, S, C] (rows contiguous, any batch stride: a slice of the [B, 1+S, C] gradient is read in place; anything else is
+    copied once).  want_k2 / want_val False: that gradient is not computed and comes back as None.  grads: (dq2, dk2,
+    dval) targets -- dq2 [B, S, C] contiguous, dk2 / dval [B, S, F, C] views with evenly spaced rows (the two halves of
+    one [B, S, F, 2C] buffer, say), None for an unwanted one -- or None for fresh tensors.  The attention map of the
+    forward gets no gradient.  No CPU path."""
+    require_device(q2, "trajectory_mix_backward(q2)")
+    if not trajectory_mix_trainable(q2, k2, val, heads):
+        raise TomeHipError("trajectory_mix_backward: unsupported tensors (16-bit, head dim 64, <= 16 heads, <= 8 frames, "
+                           "evenly spaced 16-byte aligned rows)")
+    B, S, C = q2.shape
+    F = k2.shape[2]
+    if tuple(dout.shape) != (B, S, C) or dout.device != q2.device:
+        raise TomeHipError(f"trajectory_mix_backward: dout must be {(B, S, C)} on {q2.device}, got {tuple(dout.shape)}")
+    dout = dout.detach()
+    if dout.dtype != q2.dtype:
+        dout = dout.to(q2.dtype)
+    if (dout.stride(2) != 1 or dout.stride(1) != C or (B > 1 and (dout.stride(0) % 8 or dout.stride(0) < S * C))
+            or dout.data_ptr() % 16):
+        dout = dout.contiguous()
+    if grads is None:
+        dq2 = torch.empty((B, S, C), dtype=q2.dtype, device=q2.device)
+        dk2 = torch.empty((B, S, F, C), dtype=q2.dtype, device=q2.device) if want_k2 else None
+        dval = torch.empty((B, S, F, C), dtype=q2.dtype, device=q2.device) if want_val else None
+    else:
+        dq2, dk2, dval = grads
+        if (tuple(dq2.shape) != (B, S, C) or dq2.dtype != q2.dtype or dq2.device != q2.device or not dq2.is_contiguous()
+                or dq2.data_ptr() % 16):
+            raise TomeHipError(f"trajectory_mix_backward: dq2 must be a contiguous {(B, S, C)} {q2.dtype} tensor")
+        for t, name, want in ((dk2, "dk2", want_k2), (dval, "dval", want_val)):
+            if (t is None) == want or (t is not None and not _trajectory_rows(q2, t, t, heads)):
+                raise TomeHipError(f"trajectory_mix_backward: {name} must be a {(B, S, F, C)} {q2.dtype} view with evenly "
+                                   "spaced 16-byte aligned rows when wanted, None when not")
+    entry = require_symbol(lib(), "tome_trajectory_mix_backward")
+    with _on_device(q2.device):
+        rc = entry(q2.data_ptr(), k2.data_ptr(), val.data_ptr(), dout.data_ptr(), dtype_code(q2, "q2"), B, S, F, heads, 64,
+                   k2.stride(2), val.stride(2), dout.stride(0) if B > 1 else 0, float(scale), dq2.data_ptr(), _ptr(dk2),
+                   _ptr(dval), 0 if dk2 is None else dk2.stride(2), 0 if dval is None else dval.stride(2),
+                   _stream(q2.device))
+    _check(rc, "tome_trajectory_mix_backward")
+    return dq2, dk2, dval
 
 
 def drop_regrouped(plan: MatchPlan, x_full: torch.Tensor, frames: int, has_cls: bool = True) -> torch.Tensor:

@@ -14,9 +14,23 @@ nothing but its inputs and the tensor it returns anyway.  `size` gets no gradien
 takes the projection's buffer as its single differentiable input and returns one gradient buffer of that layout, whose
 three slices the kernels write directly: autograd's three select_backward passes (zero-fill and add, three times the
 token tensor per layer) never run.  Not covered (they keep the framework's ops: DESIGN.md section 7): dropout > 0,
-fp32 heads, head dim != 64, the segmented form, double backward (raises).  The short form (sequences of at most 8
+fp32 heads, head dim != 64, double backward (raises).  The short form (sequences of at most 8
 tokens) has a backward of its own, tome_short_attention_backward (csrc/tome_short_attn_bwd.h): one launch that
 recomputes the softmax and writes the three slices of one gradient buffer.
+
+Motionformer's trajectory attention (tome/patch/motionformer.py) has two more:
+
+    segment_attention_native(q, k, v, nseg, log_bias, scale)   -> [B, N, nseg, H*64]   tome_prop_attention_segments,
+    segment_attention_qkv_native(qkv, nseg, log_bias, scale)      backward tome_prop_attention_segments_backward; the qkv
+                                                                  form: q = qkv[0][:, :, 1:], k / v = rows 1 .. 1 + nseg*P
+                                                                  of qkv[1] / qkv[2], one gradient buffer
+    trajectory_mix_native(q2, k2, val, heads, scale)           -> [B, S, C]            tome_trajectory_mix without the map,
+                                                                  backward tome_trajectory_mix_backward
+
+The class token's attention over all keys is NOT part of the segment Function: the patch runs it through
+attention_native with one query, and autograd adds its dq (row 0) and dk / dv (all rows) to the buffer the qkv form
+returns -- two Functions summed by autograd, no read-modify-write of a shared buffer (DESIGN.md section 1 says what
+that costs).
 """
 from __future__ import annotations
 
@@ -36,6 +50,17 @@ NATIVE_ATTN_BACKWARD = True
 # and tools/timesformer_backward_bench.py.  Effective only while enabled() below holds too, so that the two older
 # switches still restore the framework path as a whole.  What the default rests on is said in DESIGN.md section 1.
 NATIVE_SHORT_ATTN_BACKWARD = True
+
+
+# False: `tome/patch/motionformer.py::_trajectory_forward` keeps the reference's op sequence and autograd for a trajectory
+# attention that requires grad (the behaviour before tome_prop_attention_segments_backward and
+# tome_trajectory_mix_backward existed) -- for A/B in tests and tools/motionformer_backward_bench.py.  Effective only
+# while enabled() below holds too.  What the default rests on is said in DESIGN.md section 1.
+NATIVE_TRAJECTORY_BACKWARD = True
+
+
+def trajectory_enabled() -> bool:
+    return bool(NATIVE_TRAJECTORY_BACKWARD and enabled())
 
 
 def short_enabled() -> bool:
@@ -173,3 +198,125 @@ def short_attention_native(qkv5, scale: float):
         raise _abi.TomeHipError(f"short_attention_native: qkv {tuple(qkv5.shape)} {qkv5.dtype} is not a contiguous "
                                 "[B, N <= 8, 3, H, 64] buffer the kernels take (_abi.short_attention_trainable)")
     return _ShortAttentionFunction.apply(qkv5, float(scale))
+
+
+def _segments_backward(ctx, q, k, v, y, g_y, log, grads=None):
+    return _abi.prop_attention_segments_backward(q, k, v, y, g_y, ctx.nseg, ctx.scale, log_bias=log, grads=grads)
+
+
+class _SegmentAttentionFunction(torch.autograd.Function):
+    """Every query against the keys of one segment at a time, a softmax per segment: tome_prop_attention_segments
+    forward, tome_prop_attention_segments_backward backward.  Saves its inputs, y and the bias."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, nseg, log_bias, scale):
+        q, k, v = q.detach(), k.detach(), v.detach()
+        y = _abi.prop_attention_segments(q, k, v, nseg, scale, log_bias=log_bias)
+        ctx.nseg, ctx.scale, ctx.has_bias = int(nseg), float(scale), log_bias is not None
+        ctx.save_for_backward(q, k, v, y, *(() if log_bias is None else (log_bias,)))
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_y):
+        q, k, v, y = ctx.saved_tensors[:4]
+        dq, dk, dv = _segments_backward(ctx, q, k, v, y, g_y, ctx.saved_tensors[4] if ctx.has_bias else None)
+        need = ctx.needs_input_grad
+        return (dq if need[0] else None), (dk if need[1] else None), (dv if need[2] else None), None, None, None
+
+
+def _segment_slices(qkv, nseg):
+    """q, k, v of the trajectory attention inside the [3, B, H, N, 64] view of one projection: every token but the class
+    token asks, the nseg * P tokens behind the class token are the keys."""
+    N = qkv.shape[3]
+    P = (N - 1) // nseg
+    return qkv[0][:, :, 1:], qkv[1][:, :, 1:1 + nseg * P], qkv[2][:, :, 1:1 + nseg * P]
+
+
+class _SegmentAttentionQKVFunction(torch.autograd.Function):
+    """The same for the slices of one projection output ([3, B, H, N, 64] view, class token in row 0): one input, one
+    gradient buffer of its layout whose rows the kernels write; the rows no segment touches (the class token's, and
+    tokens past the last whole segment) are zeros."""
+
+    @staticmethod
+    def forward(ctx, qkv, nseg, log_bias, scale):
+        qkv = qkv.detach()
+        q, k, v = _segment_slices(qkv, nseg)
+        y = _abi.prop_attention_segments(q, k, v, nseg, scale, log_bias=log_bias)
+        ctx.nseg, ctx.scale, ctx.has_bias = int(nseg), float(scale), log_bias is not None
+        ctx.save_for_backward(qkv, y, *(() if log_bias is None else (log_bias,)))
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_y):
+        qkv, y = ctx.saved_tensors[:2]
+        _, B, H, N, D = qkv.shape
+        g = torch.empty((B, N, 3, H, D), dtype=qkv.dtype, device=qkv.device).permute(2, 0, 3, 1, 4)
+        q, k, v = _segment_slices(qkv, ctx.nseg)
+        keys = k.shape[2]
+        g[:, :, :, :1].zero_()          # the class token asks and is asked elsewhere (attention_native, one query)
+        g[1:, :, :, 1 + keys:].zero_()  # (N - 1 not a multiple of nseg: tokens that are queries only)
+        _segments_backward(ctx, q, k, v, y, g_y, ctx.saved_tensors[2] if ctx.has_bias else None,
+                           grads=_segment_slices(g, ctx.nseg))
+        return g, None, None, None
+
+
+def _segment_bias(log_bias):
+    return None if log_bias is None else log_bias.detach().float().contiguous()
+
+
+def segment_attention_native(q, k, v, nseg: int, log_bias, scale: float):
+    """Per-segment attention (see _abi.prop_attention_segments) for head views that require grad; log_bias: the
+    [B, nseg*P] bias in natural-log units or None (no gradient).  Returns y [B, N, nseg, H*64]."""
+    if not _abi.prop_attention_segments_trainable(q, k, v, nseg):
+        raise _abi.TomeHipError(f"segment_attention_native: these heads ({tuple(q.shape)} / {tuple(k.shape)} {q.dtype}, "
+                                f"{nseg} segments) are not ones the kernels take "
+                                "(_abi.prop_attention_segments_trainable)")
+    return _SegmentAttentionFunction.apply(q, k, v, int(nseg), _segment_bias(log_bias), float(scale))
+
+
+def segments_qkv_trainable(qkv: torch.Tensor, nseg: int) -> bool:
+    """Is `qkv` a [3, B, H, N, 64] view whose trajectory slices (_segment_slices) the segment kernels take?"""
+    if qkv.dim() != 5 or qkv.shape[0] != 3 or int(nseg) < 1 or qkv.shape[3] - 1 < int(nseg):
+        return False
+    return _abi.prop_attention_segments_trainable(*_segment_slices(qkv, nseg), nseg)
+
+
+def segment_attention_qkv_native(qkv, nseg: int, log_bias, scale: float):
+    """The same for the [3, B, H, N, 64] view of one qkv projection (class token in row 0): its gradient comes back as
+    one buffer.  The class token's own attention is not part of it."""
+    if not segments_qkv_trainable(qkv, nseg):
+        raise _abi.TomeHipError(f"segment_attention_qkv_native: qkv {tuple(qkv.shape)} {qkv.dtype} is not a "
+                                f"[3, B, H, N, 64] view the kernels take with {nseg} segments")
+    return _SegmentAttentionQKVFunction.apply(qkv, int(nseg), _segment_bias(log_bias), float(scale))
+
+
+class _TrajectoryMixFunction(torch.autograd.Function):
+    """softmax over the F frames of (q2 * scale . k2[f]), weighted sum of val[f]: tome_trajectory_mix (no map) forward,
+    tome_trajectory_mix_backward backward.  The map is not returned, so it gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, q2, k2, val, heads, scale):
+        q2, k2, val = q2.detach(), k2.detach(), val.detach()
+        out, _ = _abi.trajectory_mix(q2, k2, val, heads, scale, want_attn=False)
+        ctx.heads, ctx.scale = int(heads), float(scale)
+        ctx.save_for_backward(q2, k2, val)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out):
+        q2, k2, val = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dq2, dk2, dval = _abi.trajectory_mix_backward(q2, k2, val, g_out, ctx.heads, ctx.scale, want_k2=need[1],
+                                                      want_val=need[2])
+        return (dq2 if need[0] else None), dk2, dval, None, None
+
+
+def trajectory_mix_native(q2, k2, val, heads: int, scale: float):
+    """The temporal stage of the trajectory attention for tensors that require grad (see _abi.trajectory_mix); returns
+    out [B, S, C] only.  A caller that wants the attention map under grad keeps the framework's ops."""
+    if not _abi.trajectory_mix_trainable(q2, k2, val, heads):
+        raise _abi.TomeHipError("trajectory_mix_native: unsupported tensors (_abi.trajectory_mix_trainable)")
+    return _TrajectoryMixFunction.apply(q2, k2, val, int(heads), float(scale))

@@ -10,7 +10,7 @@ import torch
 from einops import rearrange
 
 from . import _common as C
-from .. import _abi
+from .. import _abi, _attn
 from ..merge import HeadMeanKeys
 
 _KEYS_ONLY = os.environ.get("TOME_TRAJ_KEYS_ONLY", "1") != "0"  # 0 = evaluate all of proj_kv even when v2 is unused
@@ -58,6 +58,11 @@ def _trajectory_forward(self, x, seq_len=196, num_frames=8, approx="none", num_l
     info = getattr(self, "_tome_info", None)
     ready = C.keys_ready(metric.keys, info, capture_only=True)  # the keys exist behind the qkv GEMM
     fused = (C._ATTN_KERNEL and not (self.training and self.attn_drop.p > 0.0) and all(_abi.prop_attention_ok(t) for t in heads))
+    # under grad, a stage whose inputs require grad runs the same launch as an autograd Function with the native
+    # backward behind it (tome/_attn.py) -- unless the caller wants the attention map, which has no gradient there
+    train = (C._ATTN_KERNEL and torch.is_grad_enabled() and not _want_attn and _attn.trajectory_enabled()
+             and not (self.training and self.attn_drop.p > 0.0))
+    train_seg = train and not fused and qkv.requires_grad and _attn.segments_qkv_trainable(heads, F)
     # flat per-key bias in the reference's '(s f)' order (motionformer.py:107-111): key j of the (f n)-ordered
     # sequence gets log(size) of (s = j // F, f = j % F)
     log_flat = None
@@ -76,6 +81,11 @@ def _trajectory_forward(self, x, seq_len=196, num_frames=8, approx="none", num_l
         lf = None if log_flat is None else log_flat.float().contiguous()
         y = _abi.prop_attention_segments(heads[0][:, :, 1:], heads[1][:, :, 1:1 + P * F], heads[2][:, :, 1:1 + P * F], F,
                                          self.scale, log_bias=lf)
+    elif train_seg:
+        # the class token's single query through the plain Function, the per-frame stage through the segment Function
+        # with the projection's buffer as its one input; autograd adds the two gradients of qkv
+        cls_out = _attn.attention_native(heads[0][:, :, :1], heads[1], heads[2], None, self.scale)
+        y = _attn.segment_attention_qkv_native(heads, F, log_flat, self.scale)
     else:
         q, k, v = (rearrange(t, "b n (h d) -> (b h) n d", h=h) for t in qkv.chunk(3, dim=-1))
         (cls_q, q_), (cls_k, k_), (cls_v, v_) = ((t[:, 0:1], t[:, 1:]) for t in (q, k, v))
@@ -115,6 +125,12 @@ def _trajectory_forward(self, x, seq_len=196, num_frames=8, approx="none", num_l
             tattn = tattn.to(x.dtype)
         # class row + trajectory rows, already side by side
         out = joined if _JOIN else torch.cat((cls_out.reshape(B, 1, -1), out), dim=1)
+    elif (train and (q2p.requires_grad or k2_tok.requires_grad or val_tok.requires_grad)
+          and _abi.trajectory_mix_trainable(q2p, k2_tok, val_tok, h)):
+        # (under grad the class row and the trajectory rows meet in torch.cat: no writes into a shared buffer)
+        out = _attn.trajectory_mix_native(q2p, k2_tok, val_tok, h, self.scale)
+        tattn = None
+        out = torch.cat((cls_out.reshape(B, 1, -1), out), dim=1)
     else:
         q2 = rearrange(q2p, "b s (h d) -> b h s d", h=h) * self.scale
         k2 = rearrange(k2_tok, "b s f (h d) -> b h s f d", f=F, h=h)
