@@ -148,6 +148,23 @@ def check(label, gx, dw, db, ref, dtype):
     assert not fails, (label, fails)
 
 
+def residual_gradient_survives(run, x, residual, dev):
+    """`run(x, residual)` -> the tokens a block step returns, with x WITHOUT grad, its LayerNorm frozen and the residual
+    alone requiring grad (the first block behind a frozen embedding when only the attention trains): every returned
+    tensor has a grad_fn, and residual.grad after a backward with fixed cotangents is, bit for bit, the one of the same
+    call with x requiring grad as well -- which takes the Functions whoever else requires grad (deterministic kernels)."""
+    grads = []
+    for x_grad in (False, True):
+        xi, ri = x.clone().requires_grad_(x_grad), residual.clone().requires_grad_(True)
+        tokens = run(xi, ri)
+        assert all(t.grad_fn is not None for t in tokens), f"x.requires_grad={x_grad}: a returned tensor has no grad_fn"
+        gen = torch.Generator().manual_seed(11)
+        torch.autograd.backward(tokens, [torch.randn(t.shape, generator=gen).to(t.dtype).to(dev) for t in tokens])
+        assert ri.grad is not None, f"x.requires_grad={x_grad}: grad is None"
+        grads.append(ri.grad)
+    assert torch.equal(grads[0], grads[1])
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # inputs
 # ---------------------------------------------------------------------------------------------------------------------

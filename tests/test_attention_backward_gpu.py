@@ -200,7 +200,8 @@ def _train_hosts():
                      tome.patch.timesformer, 6))
 
 
-@pytest.mark.parametrize("name", ["videomae", "vivit", "timesformer"])
+@pytest.mark.parametrize("name", ["videomae", "vivit", "timesformer", "videomae/attention only", "vivit/attention only",
+                                  "timesformer/attention only"])
 def test_patched_model_gradients_native_framework_fp32(name, monkeypatch):
     """Reduced-width model, bf16, prop_attn=True, merging in every block (r = 6), three runs on the same weights:
     (a) native attention backward, (b) the framework path (switch off: the parent commit's behaviour), (c) the framework
@@ -213,8 +214,12 @@ def test_patched_model_gradients_native_framework_fp32(name, monkeypatch):
     (the rounding noise of 16-bit sums, not a gradient).  The measured pairs are in DESIGN.md section 2.  What this test
     can and cannot see: the bf16 and fp32 runs may merge different tokens, an error both 16-bit runs share -- VideoMAE's
     pair is equal to four digits for that reason -- so the op-level tests above, not this one, are what holds the
-    kernels to their arithmetic."""
+    kernels to their arithmetic.
+    ".../attention only": embedding, LayerNorms, MLPs and head frozen, the attention projections alone train (LoRA-style
+    fine-tuning) -- block 0 then reads tokens without grad and adds a residual that requires grad to them; every trainable
+    parameter of block 0 must get a gradient, under the same bound."""
     _, _abi, _attn, M, _ = _mods()
+    name, _, freeze = name.partition("/")
     make, clip_shape, patch, r = _train_hosts()[name]
     torch.manual_seed(0)
     model32 = make().to(DEV).train()
@@ -226,6 +231,10 @@ def test_patched_model_gradients_native_framework_fp32(name, monkeypatch):
     with torch.no_grad():  # the fp32 run starts from the bf16 weights
         for p32, p16 in zip(model32.parameters(), model16.parameters()):
             p32.copy_(p16.float())
+    if freeze:
+        for model in (model32, model16):
+            for k, prm in model.named_parameters():
+                prm.requires_grad_("attn." in k or ".attention." in k)
     patch(model16, prop_attn=True)
     patch(model32, prop_attn=True)
     clip = torch.rand(*clip_shape, generator=torch.Generator().manual_seed(3)).to(DEV)
@@ -247,6 +256,9 @@ def test_patched_model_gradients_native_framework_fp32(name, monkeypatch):
     assert len(launches) == 3
     gc = run(model32, clip)
     assert ga.keys() == gb.keys() == gc.keys()
+    if freeze:
+        first = [k for k, prm in model16.named_parameters() if prm.requires_grad and (".blocks.0." in k or ".layer.0." in k)]
+        assert len(first) >= 4 and not [k for k in first if k not in ga], [k for k in first if k not in ga]
     worst_a = worst_b = 0.0
     top = max(g.abs().max().item() for g in gc.values())
     for k in gc:
@@ -257,5 +269,5 @@ def test_patched_model_gradients_native_framework_fp32(name, monkeypatch):
             continue
         worst_a = max(worst_a, (ga[k] - gc[k]).abs().max().item() / scale)
         worst_b = max(worst_b, (gb[k] - gc[k]).abs().max().item() / scale)
-    print(f"{name}: worst scaled gradient error native vs fp32 {worst_a:.3e}, framework vs fp32 {worst_b:.3e}")
+    print(f"{name} {freeze}: worst scaled gradient error native vs fp32 {worst_a:.3e}, framework vs fp32 {worst_b:.3e}")
     assert worst_a <= 2 * worst_b, (name, worst_a, worst_b)

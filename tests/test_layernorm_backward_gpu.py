@@ -195,6 +195,83 @@ def test_routing(monkeypatch):
         assert common.first_norm(blk, x96.to(bf), {}, norm).grad_fn is None
 
 
+def test_finish_block_keeps_the_gradient_of_a_residual_that_alone_requires_grad():
+    _, _, _, common = _mods()
+    bf = torch.bfloat16
+    norm = _norm(96, bf).requires_grad_(False)
+
+    class Blk:
+        training = True
+    blk = Blk()
+    object.__setattr__(blk, "_tome_next_norm", norm)
+
+    def run(x, residual):
+        info = {}
+        out = common.finish_block(blk, x, residual, info)
+        return out, common.first_norm(blk, out, info, norm)
+
+    gen = torch.Generator().manual_seed(5)
+    bo.residual_gradient_survives(run, torch.randn(2, 9, 96, generator=gen).to(bf).to(DEV),
+                                  torch.randn(2, 9, 96, generator=gen).to(bf).to(DEV), DEV)
+
+
+def test_merge_then_norm_keeps_the_gradient_of_a_residual_that_alone_requires_grad():
+    """[2, 8, 96], r = 2, the VideoMAE patch's merge function: the fused merge + LayerNorm launch is inference-only, a
+    residual that requires grad takes the unfused steps (add, merge_wavg as a Function, the trailing norm)."""
+    _, _, _, common = _mods()
+    from tome.patch.videomae import videomae_merge
+    bf = torch.bfloat16
+    norm = _norm(96, bf).requires_grad_(False)
+    gen = torch.Generator().manual_seed(6)
+    metric = torch.randn(2, 8, 32, generator=gen).to(DEV)
+
+    def run(x, residual):
+        info = common.new_tome_info(False, True, "merge", "mean", 0.0, False, False)
+        info["r"] = [2]
+        out, y = common.merge_then_norm(metric, x, info, norm, videomae_merge, videomae_merge, residual=residual)
+        assert out.shape == (2, 6, 96) and not info["r"]
+        return out, y
+
+    bo.residual_gradient_survives(run, torch.randn(2, 8, 96, generator=gen).to(bf).to(DEV),
+                                  torch.randn(2, 8, 96, generator=gen).to(bf).to(DEV), DEV)
+
+
+def test_a_bias_that_alone_requires_grad_gets_its_gradient():
+    """x without grad, the weight frozen, norm.bias alone requires grad (bias-only fine-tuning): first_norm takes the
+    Function, and dbias is inside the bound ln_bwd_oracle.check applies to it."""
+    _, _, _, common = _mods()
+    bf = torch.bfloat16
+    gy, xs, _, _ = bo.make_inputs((2, 9, 96), bf, 17, with_in=False)
+    norm = _norm(96, bf)
+    norm.weight.requires_grad_(False)
+    y = common.first_norm(None, xs.to(DEV), {}, norm)
+    assert type(y.grad_fn).__name__ == "_LayerNormFunctionBackward", y.grad_fn
+    y.backward(gy.to(DEV))
+    assert norm.bias.grad is not None and norm.weight.grad is None
+    ref = bo.reference(gy, xs, None, norm.weight, EPS)
+    bad, worst = bo.outside_param(norm.bias.grad, ref, "db", bf)
+    print(f"bias alone: dbias worst err/bound {worst:.3f}")
+    assert not bool(bad.any()), (int(bad.sum()), worst)
+
+
+def test_a_weight_that_alone_requires_grad_gets_its_gradient():
+    """The twin: x without grad, the bias frozen, norm.weight alone requires grad.  The parent took the framework's
+    LayerNorm here; asking every participant once gives the Function, and dweight is inside ln_bwd_oracle's bound."""
+    _, _, _, common = _mods()
+    bf = torch.bfloat16
+    gy, xs, _, _ = bo.make_inputs((2, 9, 96), bf, 19, with_in=False)
+    norm = _norm(96, bf)
+    norm.bias.requires_grad_(False)
+    y = common.first_norm(None, xs.to(DEV), {}, norm)
+    assert type(y.grad_fn).__name__ == "_LayerNormFunctionBackward", y.grad_fn
+    y.backward(gy.to(DEV))
+    assert norm.weight.grad is not None and norm.bias.grad is None
+    ref = bo.reference(gy, xs, None, norm.weight, EPS)
+    bad, worst = bo.outside_param(norm.weight.grad, ref, "dw", bf)
+    print(f"weight alone: dweight worst err/bound {worst:.3f}")
+    assert not bool(bad.any()), (int(bad.sum()), worst)
+
+
 def _train_hosts():
     import tome
     from hosts import timesformer, videomae

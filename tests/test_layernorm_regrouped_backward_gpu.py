@@ -6,6 +6,7 @@ in tests/test_short_attention_backward_gpu.py."""
 import pytest
 import torch
 
+import ln_bwd_oracle as bo
 import ln_oracle as lo
 import ln_regrouped_bwd_oracle as ro
 
@@ -192,3 +193,56 @@ def test_routing_in_the_block(monkeypatch):
     m.zero_grad(set_to_none=True)
     m([clip.to(torch.bfloat16)]).float().sum().backward()
     assert not seen, "a LayerNorm subclass keeps its own forward"
+
+
+def test_merge_then_norm_regrouped_keeps_the_gradient_of_a_residual_that_alone_requires_grad():
+    """B = 2, F = 2, P = 4, r = 1, TimeSformer's merge function: the fused regrouped merge + LayerNorm launch is
+    inference-only, a residual that requires grad takes the unfused steps."""
+    _, _, _, common = _mods()
+    from tome.patch.timesformer import timesformer_merge
+    B, F, P, C = 2, 2, 4, 96
+    dtype = torch.bfloat16
+    norm = _norm(C, dtype).requires_grad_(False)
+    gen = torch.Generator().manual_seed(7)
+    metric = torch.randn(B * F, P, 32, generator=gen).to(DEV)
+
+    def run(x, residual):
+        info = common.new_tome_info(False, True, "merge", "mean", 0.0, False, False)
+        info["r"] = [1]
+        out, y = common.merge_then_norm_regrouped(metric, x, info, norm,
+                                                  lambda z: timesformer_merge(metric, z, info, B, F, P), True, F,
+                                                  residual=residual)
+        assert out.shape == (B, 1 + (P - 1) * F, C) and not info["r"]
+        return out, y
+
+    bo.residual_gradient_survives(run, torch.randn(B, 1 + P * F, C, generator=gen).to(dtype).to(DEV),
+                                  torch.randn(B, 1 + P * F, C, generator=gen).to(dtype).to(DEV), DEV)
+
+
+def test_mid_block_step_keeps_the_gradient_of_an_addend_that_alone_requires_grad():
+    """TimeSformer's mid-block step as the patched block calls it (tome/patch/timesformer.py::_block_forward, r = 1):
+    the tokens without grad, every parameter frozen, and a tensor that requires grad added to temporal_fc's output -- so
+    the temporal residual alone requires grad where the block adds it."""
+    import tome
+    from hosts import timesformer
+    B, F, P, C = 2, 2, 4, 96
+    torch.manual_seed(0)
+    model = timesformer.TimeSformer(num_frames=F, img_size=16, patch_size=8, embed_dim=C, depth=1, num_heads=1,
+                                    num_classes=3).to(DEV).to(torch.bfloat16).eval()
+    tome.patch.timesformer(model)
+    block = model.model.blocks[0]
+    model.requires_grad_(False)
+
+    def run(x, rt_offset):
+        model._tome_info.update(r=[1], size=None, source=None)
+        model._tome_info.pop("_prenorm", None)
+        model._tome_info.pop("_folded", None)
+        hook = block.temporal_fc.register_forward_hook(lambda m, i, o: o + rt_offset.reshape(B, P * F, C))
+        try:
+            return (block(x, B, F, 2),)
+        finally:
+            hook.remove()
+
+    gen = torch.Generator().manual_seed(8)
+    bo.residual_gradient_survives(run, torch.randn(B, 1 + P * F, C, generator=gen).to(torch.bfloat16).to(DEV),
+                                  torch.zeros(B, P * F, C, dtype=torch.bfloat16, device=DEV), DEV)

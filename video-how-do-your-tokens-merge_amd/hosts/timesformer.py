@@ -10,7 +10,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ._patchify import frame_patch_tokens, patch_tokens, tubelet_tokens  # noqa: F401
-from tome import _abi, _attn
+from tome import _attn
 
 _SHORT_KERNEL = os.environ.get("TOME_SHORT_ATTN", "1") != "0"  # 0 = the framework's attention for the temporal stage
 
@@ -42,24 +42,18 @@ class Attention(nn.Module):
     def forward(self, x):
         B, N, C = x.shape
         live_drop = self.training and self.attn_drop.p > 0.0
+        qkv5 = None
         if self.with_qkv:
             qkv5 = self.qkv(x).reshape(B, N, 3, self.num_heads, C // self.num_heads)
-            if N <= 8 and _SHORT_KERNEL and torch.is_grad_enabled() and qkv5.requires_grad and not live_drop \
-                    and _attn.short_enabled() and _attn.short_qkv_trainable(qkv5):
-                # the temporal attention under grad: the same launch forward, tome_short_attention_backward behind it
-                # (one launch that fills the qkv gradient buffer: no head transpose, no select_backward passes)
-                return self.proj_drop(self.proj(_attn.short_attention_native(qkv5, self.scale)))
             q, k, v = qkv5.permute(2, 0, 3, 1, 4)
         else:
             q = k = v = x.reshape(B, N, self.num_heads, C // self.num_heads).permute(0, 2, 1, 3)
-        if N <= 8 and _SHORT_KERNEL and q.is_cuda and not live_drop \
-                and _abi.short_attention_ok(q, k, v):
-            # the temporal attention: thousands of sequences of T <= 8 tokens -- one streaming pass over q, k, v
-            # (tome_short_attention: 5 TB/s; the framework's fused attention + the head transpose run at 2.8)
-            x = _abi.short_attention(q, k, v, self.scale, checked=True)
-        else:
-            x = F.scaled_dot_product_attention(q, k, v, scale=self.scale).transpose(1, 2).reshape(B, N, C)
-        return self.proj_drop(self.proj(x)) if self.with_qkv else x
+        # the temporal attention: thousands of sequences of T <= 8 tokens -- one streaming pass over q, k, v
+        # (tome_short_attention: 5 TB/s; the framework's fused attention + the head transpose run at 2.8; tome/_attn.py)
+        out = _attn.short_attention(q, k, v, self.scale, live_drop, qkv5) if N <= 8 and _SHORT_KERNEL else None
+        if out is None:
+            out = F.scaled_dot_product_attention(q, k, v, scale=self.scale).transpose(1, 2).reshape(B, N, C)
+        return self.proj_drop(self.proj(out)) if self.with_qkv else out
 
 
 class Block(nn.Module):

@@ -415,6 +415,18 @@ def merge_wavg(plan: MatchPlan, x: torch.Tensor, size: Optional[torch.Tensor], l
 _HALF = (torch.bfloat16, torch.float16)
 
 
+def needs_grad(*tensors) -> bool:
+    """Is a gradient wanted of any of these tensors (None: an absent one)?  Asked of every differentiable tensor of an
+    operation at once: by every `*_ok` / `ln_fusable` below and by the `route` functions of tome/_ln.py, _attn.py, _mlp.py.
+    Those sit on the host-bound no-grad forward and test grad mode in front of the call: that spares the frame and the
+    look-up of the arguments (`norm.weight` is a Python-level `__getattr__`)."""
+    if torch.is_grad_enabled():
+        for t in tensors:
+            if t is not None and t.requires_grad:
+                return True
+    return False
+
+
 def _ln_of(x: torch.Tensor, norm) -> bool:
     """The LayerNorm kind the kernels take, for a `norm` that is an nn.LayerNorm: affine with a bias, over the C <= 1024
     (C % 8 == 0) channels of 16-bit device tokens x, weight of x's dtype."""
@@ -423,10 +435,11 @@ def _ln_of(x: torch.Tensor, norm) -> bool:
             and x.dtype in _HALF and norm.weight.dtype == x.dtype and C % 8 == 0 and C <= 1024 and x.is_cuda)
 
 
-def ln_fusable(x: torch.Tensor, norm) -> bool:
-    """Can tome_merge_wavg_ln produce norm(x') for this LayerNorm module (a subclass included), no gradient wanted?"""
+def ln_fusable(x: torch.Tensor, norm, *others) -> bool:
+    """Can tome_merge_wavg_ln produce norm(x') for this LayerNorm module (a subclass included), no gradient wanted -- of
+    x, of the norm's weight and bias, or of `others`, the residual or addend the launch reads beside x?"""
     return (isinstance(norm, torch.nn.LayerNorm) and _ln_of(x, norm)
-            and not (torch.is_grad_enabled() and (x.requires_grad or norm.weight.requires_grad)))
+            and not (torch.is_grad_enabled() and needs_grad(x, norm.weight, norm.bias, *others)))
 
 
 def ln_trainable(x: torch.Tensor, norm) -> bool:
@@ -634,7 +647,7 @@ def _head_view(t: torch.Tensor) -> bool:
 
 def prop_attention_ok(q: torch.Tensor) -> bool:
     """Can tome_prop_attention take these heads (_head_view), no gradient wanted?"""
-    return _head_view(q) and not (torch.is_grad_enabled() and q.requires_grad)
+    return _head_view(q) and not (torch.is_grad_enabled() and needs_grad(q))
 
 
 def prop_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, size: Optional[torch.Tensor], scale: float,
@@ -875,8 +888,7 @@ def _short_heads(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> bool:
 
 def short_attention_ok(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> bool:
     """Can tome_short_attention take these (_short_heads), no gradient wanted?"""
-    return _short_heads(q, k, v) and not (torch.is_grad_enabled()
-                                          and (q.requires_grad or k.requires_grad or v.requires_grad))
+    return _short_heads(q, k, v) and not (torch.is_grad_enabled() and needs_grad(q, k, v))
 
 
 def short_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, checked: bool = False
@@ -958,8 +970,7 @@ def _trajectory_rows(q2: torch.Tensor, k2: torch.Tensor, val: torch.Tensor, head
 
 def trajectory_mix_ok(q2: torch.Tensor, k2: torch.Tensor, val: torch.Tensor, heads: int) -> bool:
     """Can tome_trajectory_mix take these (_trajectory_rows), no gradient wanted?"""
-    return (_trajectory_rows(q2, k2, val, heads)
-            and not (torch.is_grad_enabled() and (q2.requires_grad or k2.requires_grad)))
+    return _trajectory_rows(q2, k2, val, heads) and not (torch.is_grad_enabled() and needs_grad(q2, k2, val))
 
 
 def trajectory_mix_trainable(q2: torch.Tensor, k2: torch.Tensor, val: torch.Tensor, heads: int) -> bool:
@@ -1076,7 +1087,7 @@ def unmerge(plan: MatchPlan, x: torch.Tensor) -> torch.Tensor:
 
 def gelu_ok(x: torch.Tensor) -> bool:
     return (x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and x.is_contiguous() and x.numel() % 8 == 0
-            and x.numel() > 0 and x.data_ptr() % 16 == 0 and not (torch.is_grad_enabled() and x.requires_grad))
+            and x.numel() > 0 and x.data_ptr() % 16 == 0 and not (torch.is_grad_enabled() and needs_grad(x)))
 
 
 def gelu_erf(x: torch.Tensor, inplace: bool = False) -> torch.Tensor:
@@ -1097,7 +1108,7 @@ def mlp_trainable(y: torch.Tensor, fc1, fc2, act) -> bool:
     """Can `fc2(act(fc1(y)))` run as the Function of tome/_mlp.py (library GEMMs, tome_gelu_erf forward,
     tome_gelu_erf_backward backward) when y or the parameters require grad?  16-bit device tokens, the stock nn.Linear /
     exact-erf nn.GELU modules, parameters of the tokens' dtype, hidden width within the kernel's limits, 16-byte rows."""
-    from .patch._common import _stock_module
+    from ._mlp import _stock_module
     if not (_stock_module(fc1, torch.nn.Linear) and _stock_module(fc2, torch.nn.Linear)
             and _stock_module(act, torch.nn.GELU) and getattr(act, "approximate", "none") == "none"):
         return False
@@ -1144,7 +1155,7 @@ def gelu_erf_backward(h: torch.Tensor, ga: torch.Tensor, *, want_act: bool, want
 def tubelet_rows_ok(x: torch.Tensor, kt: int, kh: int, kw: int) -> bool:
     """x [B, C, T, H, W] (any view with unit stride along W) can be regrouped by tome_tubelet_rows."""
     if not (x.is_cuda and x.dim() == 5 and x.dtype in DTYPES and x.numel() > 0 and x.stride(4) == 1
-            and not (torch.is_grad_enabled() and x.requires_grad)):
+            and not (torch.is_grad_enabled() and needs_grad(x))):
         return False
     es = x.element_size()
     _, _, T, H, W = x.shape

@@ -1,5 +1,14 @@
-"""The proportional attention of the patched blocks for heads that require grad (models are patched for training,
-tools/train_net.py:727-741): forward = the inference launch (tome_prop_attention) on the detached tensors, backward =
+"""The attention kernels of the patched blocks.  One routed entry per operation: it launches the kernel directly when
+no gradient is wanted of any participant, as an autograd Function when one is (models are patched for training,
+tools/train_net.py:727-741), and answers None when the caller is to take the framework's ops.  Each `*route` is that
+decision alone, without a launch.
+
+    attention(q, k, v, size, scale, dropout_p, bias_skip, qkv=None), short_attention(q, k, v, scale, live_drop, qkv5),
+    trajectory_stage1(heads, nseg, log_flat, scale, live_drop, want_attn, join), trajectory_mix(q2p, k2, val, heads, ...)
+
+What each examines and what its Function form needs: the routing table in DESIGN.md section 1.
+
+The Functions: forward = the inference launch (tome_prop_attention) on the detached tensors, backward =
 tome_prop_attention_backward (csrc/tome_attn_bwd.h).
 
     attention_native(q, k, v, size, scale, bias_skip=False)   -> [B, N, H*64]      q, k, v: [B, H, N, 64] head views
@@ -13,8 +22,7 @@ The backward recomputes the softmax from q, k and the size bias (row maximum and
 nothing but its inputs and the tensor it returns anyway.  `size` gets no gradient.  The qkv form
 takes the projection's buffer as its single differentiable input and returns one gradient buffer of that layout, whose
 three slices the kernels write directly: autograd's three select_backward passes (zero-fill and add, three times the
-token tensor per layer) never run.  Not covered (they keep the framework's ops: DESIGN.md section 7): dropout > 0,
-fp32 heads, head dim != 64, double backward (raises).  The short form (sequences of at most 8
+token tensor per layer) never run.  Double backward raises.  The short form (sequences of at most 8
 tokens) has a backward of its own, tome_short_attention_backward (csrc/tome_short_attn_bwd.h): one launch that
 recomputes the softmax and writes the three slices of one gradient buffer.
 
@@ -72,10 +80,42 @@ def enabled() -> bool:
     return bool(NATIVE_ATTN_BACKWARD and merge.NATIVE_BACKWARD)
 
 
-def wants(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, dropout_p: float = 0.0) -> bool:
-    """Do the heads require grad, and does this attention of them run on the native Function?"""
-    return (torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad) and dropout_p == 0.0
-            and enabled() and _abi.prop_attention_trainable(q, k, v))
+def route(q, k, v, dropout_p: float = 0.0):
+    """How the proportional attention of these heads runs: None (the framework's ops: not the kind of tensors the kernel
+    takes), "direct" (the launch itself: no participant wants a gradient) or, when one does, "function" (the same launch
+    with the native backward behind it) where the switches allow, else None."""
+    if dropout_p != 0.0 or not (_abi._head_view(q) and _abi._head_view(k) and _abi._head_view(v)):
+        return None
+    if not (torch.is_grad_enabled() and _abi.needs_grad(q, k, v)):
+        return "direct"
+    return "function" if enabled() else None
+
+
+def short_route(q, k, v, live_drop: bool = False, qkv5=None):
+    """The same for the short attention; qkv5: the [B, N, 3, H, 64] buffer q, k, v are slices of (None: no Function form)."""
+    if live_drop or not _abi._short_heads(q, k, v):
+        return None
+    if not (torch.is_grad_enabled() and _abi.needs_grad(q, k, v)):
+        return "direct"
+    return "function" if qkv5 is not None and short_enabled() and short_qkv_trainable(qkv5) else None
+
+
+def trajectory_route(heads, nseg: int, live_drop: bool = False, want_attn: bool = False):
+    """The same for the first stage of the trajectory attention; the Functions return no map: None when one is wanted."""
+    if live_drop or not all(_abi._head_view(t) for t in heads):
+        return None
+    if not (torch.is_grad_enabled() and _abi.needs_grad(heads)):
+        return "direct"
+    return "function" if not want_attn and trajectory_enabled() and segments_qkv_trainable(heads, nseg) else None
+
+
+def trajectory_mix_route(q2p, k2, val, heads: int, want_attn: bool = False):
+    """The same for the second stage (tome_trajectory_mix)."""
+    if not _abi._trajectory_rows(q2p, k2, val, heads):
+        return None
+    if not (torch.is_grad_enabled() and _abi.needs_grad(q2p, k2, val)):
+        return "direct"
+    return "function" if not want_attn and trajectory_enabled() else None
 
 
 def _log_bias(size, B):
@@ -320,3 +360,55 @@ def trajectory_mix_native(q2, k2, val, heads: int, scale: float):
     if not _abi.trajectory_mix_trainable(q2, k2, val, heads):
         raise _abi.TomeHipError("trajectory_mix_native: unsupported tensors (_abi.trajectory_mix_trainable)")
     return _TrajectoryMixFunction.apply(q2, k2, val, int(heads), float(scale))
+
+
+def attention(q, k, v, size, scale: float, dropout_p: float = 0.0, bias_skip: bool = False, qkv=None):
+    """softmax(q k^T * scale + log(size)) v for [B, H, N, 64] head views: [B, N, H*64], or None.  qkv: the [3, B, H, N, 64]
+    view they are the slices of -- under grad the Function's one input, whose gradient comes back as one buffer."""
+    how = route(q, k, v, dropout_p)
+    if how == "direct":
+        return _abi.prop_attention(q, k, v, size, scale, bias_skip=bias_skip, checked=True)
+    if how is None:
+        return None
+    if qkv is None:
+        return attention_native(q, k, v, size, scale, bias_skip=bias_skip)
+    return attention_qkv_native(qkv, size, scale, bias_skip=bias_skip)
+
+
+def short_attention(q, k, v, scale: float, live_drop: bool = False, qkv5=None):
+    """softmax(q k^T * scale) v over sequences of at most 8 tokens (TimeSformer's temporal attention), or None."""
+    how = short_route(q, k, v, live_drop, qkv5)
+    if how == "direct":
+        return _abi.short_attention(q, k, v, scale, checked=True)
+    return short_attention_native(qkv5, scale) if how == "function" else None
+
+
+def trajectory_stage1(heads, nseg: int, log_flat, scale: float, live_drop: bool, want_attn: bool, join: bool):
+    """The first stage of Motionformer's trajectory attention: (cls_out, y, joined), or None.  cls_out: the class token
+    attending to every token, sizes ignored (motionformer.py:54) -- one query per head; y: every other token attending
+    to the keys of ONE frame at a time (bias log_flat) -- one launch of the segmented kernel, the [B*h, N, N] logits
+    never exist.  joined (direct form with `join`): the [B, N, H*64] buffer whose row 0 cls_out is, for the second stage
+    to fill: cat((cls_out, x), dim=1) without the copy.  Under grad autograd adds the two Functions' gradients of qkv."""
+    how = trajectory_route(heads, nseg, live_drop, want_attn)
+    if how is None:
+        return None
+    if how == "function":
+        return (attention_native(heads[0][:, :, :1], heads[1], heads[2], None, scale),
+                segment_attention_qkv_native(heads, nseg, log_flat, scale), None)
+    _, B, h, N, hd = heads.shape
+    joined = torch.empty((B, N, h * hd), dtype=heads.dtype, device=heads.device) if join else None
+    cls_out = _abi.prop_attention(heads[0][:, :, :1], heads[1], heads[2], None, scale,
+                                  out=joined[:, :1].unflatten(2, (h, hd)) if join else None)
+    q, k, v = _segment_slices(heads, nseg)
+    lf = None if log_flat is None else log_flat.float().contiguous()
+    return cls_out, _abi.prop_attention_segments(q, k, v, nseg, scale, log_bias=lf), joined
+
+
+def trajectory_mix(q2p, k2, val, heads: int, scale: float, want_attn: bool = False, out=None):
+    """The second stage (see _abi.trajectory_mix): (out [B, S, C], attention map or None, wrote), or None.  wrote: the
+    result went into `out` -- the direct form only: under grad the class row and the trajectory rows meet in torch.cat,
+    not in a shared buffer."""
+    how = trajectory_mix_route(q2p, k2, val, heads, want_attn)
+    if how == "direct":
+        return (*_abi.trajectory_mix(q2p, k2, val, heads, scale, want_attn=want_attn, out=out), out is not None)
+    return (trajectory_mix_native(q2p, k2, val, heads, scale), None, False) if how == "function" else None

@@ -1,6 +1,14 @@
-"""The LayerNorms of the patched blocks for tokens that require grad (models are patched for training,
-tools/train_net.py:727-741): forward = the inference kernels (tome_add_layernorm / tome_add_layernorm_skip_first) on the
-detached tensors, backward = tome_layernorm_backward (csrc/tome_ln_bwd.h).
+"""The LayerNorms of the patched blocks.  One routed entry per operation: it launches the add + LayerNorm kernel
+directly when no gradient is wanted of any participant -- x, the addend, the norm's weight and bias -- as an autograd
+Function when one is (models are patched for training, tools/train_net.py:727-741; needs enabled(), for the regrouped
+form regrouped_enabled(), and _abi.ln_trainable), and answers None when the caller is to take the framework's ops (not
+_abi._ln_of, not an nn.LayerNorm, an addend of another dtype).  `route` is that decision alone, without a launch.
+
+    add_layernorm(x, addend or None, norm, skip_first=False)  -> (x + addend, norm(x + addend), skipped) or None
+    add_layernorm_regrouped(x, addend, frames, norm)           -> (cat(cls, x[:, 1:] + addend), norm regrouped) or None
+
+The Functions: forward = the inference kernels (tome_add_layernorm / tome_add_layernorm_skip_first) on the detached
+tensors, backward = tome_layernorm_backward (csrc/tome_ln_bwd.h).
 
     add_layernorm_native(x, addend, norm, skip_first=False) -> (x + addend, norm(x + addend))
     layernorm_native(x, norm, skip_first=False)             -> norm(x)
@@ -10,8 +18,7 @@ skip_first (x [B, N, C]): the LayerNorm output leaves out every clip's first row
 The backward recomputes mean and rstd from the stored sum (the row the forward normalised), so the forward saves
 nothing but the tensors it returns anyway.  The gradient of the sum that arrives through the residual stream and the
 gradient through the LayerNorm are added inside the one launch and rounded once; x and addend receive the same
-tensor.  Not covered (they keep the framework's ops: DESIGN.md section 7): fp32 tokens, LayerNorms `_abi.ln_trainable`
-refuses, double backward (raises).
+tensor.  Double backward raises.
 The regrouped form is the middle of TimeSformer's divided space-time block (tome_add_layernorm_regrouped forward,
 tome_layernorm_backward_regrouped backward): x [B, 1 + P*T, C] and addend [B, P*T, C] receive gx and its view gx[:, 1:].
 """
@@ -43,10 +50,15 @@ def enabled() -> bool:
     return bool(NATIVE_LN_BACKWARD and merge.NATIVE_BACKWARD)
 
 
-def wants(x: torch.Tensor, norm, *others) -> bool:
-    """Do the tokens require grad, and does this LayerNorm of them run on the native Functions?"""
-    return (torch.is_grad_enabled() and (x.requires_grad or any(t is not None and t.requires_grad for t in others))
-            and enabled() and _abi.ln_trainable(x, norm))
+def route(x: torch.Tensor, norm, addend=None, regrouped: bool = False):
+    """How `norm(x [+ addend])` runs: None (the framework's ops: not the kind of tensors the kernel takes), "direct" (the
+    launch itself: neither x, the addend nor the norm's weight or bias wants a gradient) or, when one does, "function"
+    (the same launch with the native backward behind it) where the switches and ln_trainable allow, else None."""
+    if not (isinstance(norm, torch.nn.LayerNorm) and _abi._ln_of(x, norm) and (addend is None or addend.dtype == x.dtype)):
+        return None
+    if not (torch.is_grad_enabled() and _abi.needs_grad(x, addend, norm.weight, norm.bias)):
+        return "direct"
+    return "function" if (regrouped_enabled() if regrouped else enabled()) and _abi.ln_trainable(x, norm) else None
 
 
 def ln_backward(gy, xs, gx_in, weight, eps, skip_first, want_weight, want_bias):
@@ -165,3 +177,26 @@ def add_layernorm_regrouped_native(x, addend, T: int, norm):
     'b (p t) m -> (b t) p m' with the class token in front of every frame, [B*T, 1 + P, C]."""
     _check(x, norm, "add_layernorm_regrouped_native")
     return _AddLayerNormRegroupedFunction.apply(x, addend, norm.weight, norm.bias, norm.eps, int(T))
+
+
+def add_layernorm(x, addend, norm, skip_first: bool = False, how=False):
+    """`x = x + addend` (addend None: x as it is) and `y = norm(x)`: (x, y, skipped), or None.  skip_first: y without
+    every clip's first row where x has one to leave out; `skipped` says whether it was.  how: the route, when the caller
+    has asked it already."""
+    how = route(x, norm, addend) if how is False else how
+    if how is None:
+        return None
+    skip = bool(skip_first) and x.dim() == 3 and x.shape[1] >= 2
+    if how == "direct":
+        return (*_abi.add_layernorm(x, addend, norm.weight, norm.bias, norm.eps, skip_first=skip), skip)
+    if addend is None:
+        return x, layernorm_native(x, norm, skip_first=skip), skip
+    return (*add_layernorm_native(x, addend, norm, skip_first=skip), skip)
+
+
+def add_layernorm_regrouped(x, addend, frames: int, norm):
+    """TimeSformer's mid-block step (see _abi.add_layernorm_regrouped): (x1, xs_normed), or None."""
+    how = route(x, norm, addend, regrouped=True)
+    if how == "direct":
+        return _abi.add_layernorm_regrouped(x, addend, frames, norm.weight, norm.bias, norm.eps)
+    return add_layernorm_regrouped_native(x, addend, frames, norm) if how == "function" else None

@@ -1,6 +1,9 @@
-"""The MLP of the patched blocks, `fc2(gelu(fc1(y)))` with the exact-erf GELU, for tokens or parameters that require grad
-(models are patched for training, tools/train_net.py:727-741; `self.mlp(self.norm2(x))`, tome/patch/videomae.py:29):
-one autograd Function around the two library GEMMs.
+"""The MLP of the patched blocks, `fc2(gelu(fc1(y)))` with the exact-erf GELU (`self.mlp(self.norm2(x))`,
+tome/patch/videomae.py:29).  Participants: y and the four parameters.  None of them wants a gradient ("direct"): the
+caller's own fc1 / `hidden` / fc2, the activation on tome_gelu_erf in place.  One does ("function"; needs enabled(), a
+plain MLP whose dropouts are the identity, _abi.mlp_trainable): `mlp`, one autograd Function around the two library
+GEMMs (models are patched for training, tools/train_net.py:727-741).  Otherwise the framework's modules.  `route` is
+that decision alone, without a launch.
 
     mlp_native(mlp, y) -> mlp.fc2(gelu(mlp.fc1(y)))
 
@@ -9,8 +12,7 @@ y, the pre-activation h and the two weights; the activation is dropped (autograd
 GELU, the activation for fc2's weight gradient).  Backward: ga = g W2, then ONE launch of tome_gelu_erf_backward
 (csrc/tome_gelu_bwd.h) writes gh over ga, the activation again with the forward's bits (only when fc2's weight needs a
 gradient) and fc1's bias gradient (only when it needs one); the remaining products are library GEMMs.
-Not covered (they keep the framework's ops: DESIGN.md section 7): the tanh GELU, fp32 tokens, live dropout, hooked or
-subclassed layers, double backward (raises).
+Double backward raises; the routing table is in DESIGN.md section 1.
 """
 from __future__ import annotations
 
@@ -30,16 +32,40 @@ def enabled() -> bool:
     return bool(NATIVE_MLP_BACKWARD and merge.NATIVE_BACKWARD)
 
 
-def wants(mlp, y: torch.Tensor) -> bool:
-    """Does y or a parameter of this MLP require grad, and does the MLP run on the native Function?"""
-    if not (torch.is_grad_enabled() and enabled()):
-        return False
+def _stock_module(m, cls) -> bool:
+    """`m` is exactly `cls` (not a subclass with a forward of its own: LoRA, quantised, ... layers), carries no
+    parametrization and no forward hook -- only then may its forward be replaced by a hand-made call."""
+    return (type(m) is cls and not getattr(m, "parametrizations", None)
+            and not m._forward_hooks and not m._forward_pre_hooks)
+
+
+def _plain_mlp(mlp, training: bool = False) -> bool:
+    """An MLP of the usual shape: fc1, exact-erf nn.GELU, fc2 and dropouts -- all of them the stock modules, unhooked
+    (feature extractors / flop counters hook mlp, act, fc2: those run the module itself) -- whose dropouts are the
+    identity: the module in `.eval()` mode, or, with `training` (the native Function, tome/_mlp.py), in `.train()` mode
+    as well when every nn.Dropout child has p == 0.  There a dropout is live by its OWN `.training` flag, the one its
+    forward reads, whatever mode the MLP itself is in."""
+    act = getattr(mlp, "act", None)
+    fc1, fc2 = getattr(mlp, "fc1", None), getattr(mlp, "fc2", None)
+    children = dict(mlp.named_children())
+    return (act is not None and _stock_module(act, torch.nn.GELU) and getattr(act, "approximate", "none") == "none"
+            and fc1 is not None and _stock_module(fc1, torch.nn.Linear)
+            and fc2 is not None and _stock_module(fc2, torch.nn.Linear)
+            and not mlp._forward_hooks and not mlp._forward_pre_hooks
+            and set(children) <= {"fc1", "act", "fc2", "drop", "drop1", "drop2"}
+            and (all(_stock_module(m, torch.nn.Dropout) and (m.p == 0 or not m.training)
+                     for k, m in children.items() if k.startswith("drop")) if training else not mlp.training))
+
+
+def route(mlp, y: torch.Tensor):
+    """How `mlp(y)` runs: "direct" (neither y nor a parameter wants a gradient and the MLP is plain: the caller's own
+    fc1, `hidden`, fc2), "function" (one does, and the native Function takes this MLP) or None (the module as it is)."""
     fc1, fc2, act = getattr(mlp, "fc1", None), getattr(mlp, "fc2", None), getattr(mlp, "act", None)
     if fc1 is None or fc2 is None or act is None:
-        return False
-    params = (fc1.weight, fc1.bias, fc2.weight, fc2.bias)
-    return ((y.requires_grad or any(p is not None and p.requires_grad for p in params))
-            and _abi.mlp_trainable(y, fc1, fc2, act))
+        return None
+    if not (torch.is_grad_enabled() and _abi.needs_grad(y, fc1.weight, fc1.bias, fc2.weight, fc2.bias)):
+        return "direct" if _plain_mlp(mlp) else None
+    return "function" if enabled() and _plain_mlp(mlp, training=True) and _abi.mlp_trainable(y, fc1, fc2, act) else None
 
 
 def gelu_backward(h, ga, want_act, want_bias):
@@ -93,3 +119,20 @@ def mlp_native(mlp, y: torch.Tensor) -> torch.Tensor:
         raise _abi.TomeHipError(f"mlp_native: this MLP of {tuple(y.shape)} {y.dtype} tokens is not one the kernels take "
                                 "(_abi.mlp_trainable)")
     return _MlpFunction.apply(y, fc1.weight, fc1.bias, fc2.weight, fc2.bias)
+
+
+def hidden(mlp, y: torch.Tensor, kernel: bool = True) -> torch.Tensor:
+    """fc1 and the activation of a plain MLP: the tensor its fc2 reads.  The activation runs on tome_gelu_erf (same
+    bits as the framework's kernel, non-temporal streaming: 394 -> ~350 us at batch 128) when nothing wants a gradient
+    of fc1's output, which requires grad when y or fc1's parameters do."""
+    h = mlp.fc1(y)
+    if kernel and _abi.gelu_ok(h):
+        return _abi.gelu_erf(h, inplace=True)
+    return mlp.act(h)
+
+
+def mlp(module, y: torch.Tensor):
+    """`module(y)` as the native Function when a gradient is wanted and the Function takes this MLP; None otherwise."""
+    if not torch.is_grad_enabled():  # (no Function form: the no-grad forward is host-bound, spare it the look-ups of route)
+        return None
+    return mlp_native(module, y) if route(module, y) == "function" else None

@@ -302,6 +302,17 @@ def drop_regrouped_native(plan, x_full, frames: int, has_cls: bool = True):
     return _DropRegroupedFunction.apply(x_full, plan, int(frames), bool(has_cls))
 
 
+def merge_wavg_regrouped(plan, x_full, size, frames: int, has_cls: bool = True, log_size: bool = False):
+    """`_abi.merge_wavg_regrouped`, as the Function above when the tokens want a gradient."""
+    run = merge_wavg_regrouped_native if _wants_autograd(x_full) else _abi.merge_wavg_regrouped
+    return run(plan, x_full, size, frames, has_cls=has_cls, log_size=log_size)
+
+
+def drop_regrouped(plan, x_full, frames: int, has_cls: bool = True):
+    """The same for `_abi.drop_regrouped`."""
+    return (drop_regrouped_native if _wants_autograd(x_full) else _abi.drop_regrouped)(plan, x_full, frames, has_cls=has_cls)
+
+
 _SCATTER_MODE = {"sum": "sum", "mean": "mean", "prod": "prod", "max": "amax", "amax": "amax", "min": "amin", "amin": "amin"}
 
 

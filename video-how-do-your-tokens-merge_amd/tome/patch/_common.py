@@ -12,9 +12,10 @@ from typing import Callable, Dict, Tuple
 
 import torch
 
-from .. import _ln, _mlp, _overlap
+from .. import _abi, _attn, _ln, _mlp, _overlap
+from .._mlp import _plain_mlp, _stock_module  # (the module-kind predicates live beside the MLP's route)
 from ..merge import (bipartite_soft_matching, bipartite_soft_matching_drop, bipartite_soft_matching_hybrid,
-                     merge_source, merge_wavg)
+                     drop_regrouped, merge_source, merge_wavg, merge_wavg_regrouped)
 from ..utils import parse_r
 
 _SUBCLASSES: Dict[Tuple[type, str], type] = {}
@@ -193,31 +194,19 @@ match_beside = _overlap.match_beside  # tome/_overlap.py
 
 
 def attention_qkv(qkv, size, scale: float, dropout_p: float = 0.0, bias_skip: bool = False):
-    """`attention(qkv[0], qkv[1], qkv[2], ...)` for the [3, B, H, N, hd] view of one qkv projection.  When the heads
-    require grad and the native backward takes them, the buffer is the Function's single differentiable input and its
-    gradient comes back as one buffer of that layout, written in place by the kernels -- instead of autograd's three
-    select_backward passes (zero-fill and add: three times the token tensor per layer)."""
-    from .. import _attn
-    q, k, v = qkv[0], qkv[1], qkv[2]
-    if _ATTN_KERNEL and _attn.wants(q, k, v, dropout_p):
-        return _attn.attention_qkv_native(qkv, size, scale, bias_skip=bias_skip)
-    return attention(q, k, v, size, scale, dropout_p, bias_skip)
+    """`attention(qkv[0], qkv[1], qkv[2], ...)` for the [3, B, H, N, hd] view of one qkv projection."""
+    return attention(qkv[0], qkv[1], qkv[2], size, scale, dropout_p, bias_skip, qkv)
 
 
-def attention(q, k, v, size, scale: float, dropout_p: float = 0.0, bias_skip: bool = False):
+def attention(q, k, v, size, scale: float, dropout_p: float = 0.0, bias_skip: bool = False, qkv=None):
     """softmax(q k^T * scale + log(size)) v for [B, H, N, hd] head views; returns [B, N, H*hd].
-    16-bit heads of width 64 without dropout go through tome_prop_attention (the size bias is one value per key
-    inside the kernel, q/k/v are read in place from the projection's output) -- under grad as the Function of
-    tome/_attn.py, whose backward is tome_prop_attention_backward; everything else through the
-    framework's attention with the bias tensor the reference builds (videomae.py:62-63, timesformer.py:73-74)."""
-    from .. import _abi, _attn
+    16-bit heads of width 64 without dropout go through tome_prop_attention (the size bias is one value per key inside
+    the kernel, q/k/v are read in place from the projection's output; under grad as a Function: tome/_attn.py), everything
+    else through the framework's attention with the bias tensor the reference builds (videomae.py:62-63, timesformer.py:73-74)."""
+    out = _attn.attention(q, k, v, size, scale, dropout_p, bias_skip, qkv) if _ATTN_KERNEL else None
+    if out is not None:
+        return out
     B, H, N, hd = q.shape
-    if (_ATTN_KERNEL and dropout_p == 0.0 and _abi.prop_attention_ok(q) and _abi.prop_attention_ok(k)
-            and _abi.prop_attention_ok(v)):
-        return _abi.prop_attention(q, k, v, size, scale, bias_skip=bias_skip, checked=True)
-    # heads that require grad: the same forward launch with tome_prop_attention_backward behind it (tome/_attn.py)
-    if _ATTN_KERNEL and _attn.wants(q, k, v, dropout_p):
-        return _attn.attention_native(q, k, v, size, scale, bias_skip=bias_skip)
     bias = None
     if size is not None:
         log = _abi.log_of_size(size)[:, None, None, :, 0].to(q.dtype)
@@ -230,67 +219,15 @@ def attention(q, k, v, size, scale: float, dropout_p: float = 0.0, bias_skip: bo
     return out.transpose(1, 2).reshape(B, N, H * hd)
 
 
-def _stock_module(m, cls) -> bool:
-    """`m` is exactly `cls` (not a subclass with a forward of its own: LoRA, quantised, ... layers), carries no
-    parametrization and no forward hook -- only then may its forward be replaced by a hand-made call."""
-    return (type(m) is cls and not getattr(m, "parametrizations", None)
-            and not m._forward_hooks and not m._forward_pre_hooks)
-
-
-def _plain_mlp(mlp) -> bool:
-    """An MLP of the usual shape: fc1, exact-erf nn.GELU, fc2, dropouts that are the identity in eval -- all of them
-    the stock modules, unhooked (feature extractors / flop counters hook mlp, act, fc2: those run the module itself)."""
-    act = getattr(mlp, "act", None)
-    fc1, fc2 = getattr(mlp, "fc1", None), getattr(mlp, "fc2", None)
-    return (act is not None and _stock_module(act, torch.nn.GELU) and getattr(act, "approximate", "none") == "none"
-            and fc1 is not None and _stock_module(fc1, torch.nn.Linear)
-            and fc2 is not None and _stock_module(fc2, torch.nn.Linear) and not mlp.training
-            and not mlp._forward_hooks and not mlp._forward_pre_hooks
-            and set(dict(mlp.named_children())) <= {"fc1", "act", "fc2", "drop", "drop1", "drop2"})
-
-
-def _trainable_mlp(mlp) -> bool:
-    """_plain_mlp for the training path (tome/_mlp.py): the same stock modules, unhooked, the same set of children -- and
-    a module in `.train()` mode as well, when every nn.Dropout child has p == 0 (then the dropouts are the identity).
-    A dropout is live by its OWN `.training` flag, the one its forward reads, whatever mode the MLP itself is in."""
-    act = getattr(mlp, "act", None)
-    fc1, fc2 = getattr(mlp, "fc1", None), getattr(mlp, "fc2", None)
-    children = dict(mlp.named_children())
-    return (act is not None and _stock_module(act, torch.nn.GELU) and getattr(act, "approximate", "none") == "none"
-            and fc1 is not None and _stock_module(fc1, torch.nn.Linear)
-            and fc2 is not None and _stock_module(fc2, torch.nn.Linear)
-            and not mlp._forward_hooks and not mlp._forward_pre_hooks
-            and set(children) <= {"fc1", "act", "fc2", "drop", "drop1", "drop2"}
-            and all(_stock_module(m, torch.nn.Dropout) and (m.p == 0 or not m.training)
-                    for k, m in children.items() if k.startswith("drop")))
-
-
-def _native_mlp(mlp, x, y, info) -> bool:
-    """Does `mlp(y)` run as the native Function (tome/_mlp.py)?  Tokens or parameters that require grad, an MLP the
-    kernels take, and no folded bias waiting in the residual stream x (that one belongs to finish_linear)."""
-    if not (_GELU_KERNEL and torch.is_grad_enabled() and _trainable_mlp(mlp) and _mlp.wants(mlp, y)):
-        return False
-    folded = None if info is None else info.get("_folded")
-    return folded is None or folded[0] is not x
-
-
-def mlp_hidden(mlp, y):
-    """fc1 and the activation of a plain MLP: the tensor its fc2 reads.  The activation runs on tome_gelu_erf (same
-    bits as the framework's kernel, non-temporal streaming: 394 -> ~350 us at batch 128)."""
-    from .. import _abi
-    h = mlp.fc1(y)
-    if _GELU_KERNEL and _abi.gelu_ok(h):
-        return _abi.gelu_erf(h, inplace=True)
-    return mlp.act(h)
+def _mlp_steps(mlp, y):
+    """`mlp(y)` without the native Function: a plain MLP step by step (tome/_mlp.py::hidden), anything else as it is."""
+    return mlp.fc2(_mlp.hidden(mlp, y, _GELU_KERNEL)) if _plain_mlp(mlp) else mlp(y)
 
 
 def run_mlp(mlp, y):
     """`self.mlp(y)` of the patched block (tome/patch/videomae.py:29); anything but a plain MLP is called as it is."""
-    if _native_mlp(mlp, None, y, None):
-        return _mlp.mlp_native(mlp, y)
-    if _plain_mlp(mlp):
-        return mlp.fc2(mlp_hidden(mlp, y))
-    return mlp(y)
+    out = _mlp.mlp(mlp, y) if _GELU_KERNEL else None
+    return _mlp_steps(mlp, y) if out is None else out
 
 
 def foldable(linear, eval_mode: bool = True):
@@ -298,7 +235,7 @@ def foldable(linear, eval_mode: bool = True):
     stream in place (`x.addmm_(h, Wᵀ)`, finish_linear) -- which needs the bias in the stream beforehand
     (merge_then_norm's `fold`, the merge kernel's x_out_bias); None when it may not."""
     if (_FUSE_FC2 and _FUSE_NEXT and eval_mode and _stock_module(linear, torch.nn.Linear) and linear.bias is not None
-            and not (torch.is_grad_enabled() and linear.weight.requires_grad)):
+            and not (torch.is_grad_enabled() and _abi.needs_grad(linear.weight, linear.bias))):
         return linear
     return None
 
@@ -306,20 +243,18 @@ def foldable(linear, eval_mode: bool = True):
 def mlp_residual(block, mlp, x, y, info, scale=None, drop_path=None):
     """`x + drop_path(scale * mlp(y))` at the end of a patched block (tome/patch/videomae.py:28-29,
     timesformer.py:57, motionformer.py:30), with the next block's first norm handed over (finish_block)."""
-    if _native_mlp(mlp, x, y, info):
-        # tokens or parameters that require grad: the MLP as one Function with tome_gelu_erf_backward between its GEMMs
-        y = _mlp.mlp_native(mlp, y)
-        if scale is not None:
-            y = scale * y
-        return finish_block(block, x, y if drop_path is None else drop_path(y), info)
-    if _plain_mlp(mlp) and scale is None and (drop_path is None or not block.training):
-        return finish_linear(block, x, mlp_hidden(mlp, y), mlp.fc2, info)
-    if info.get("_folded") is not None and info["_folded"][0] is x:
-        raise RuntimeError("the residual stream carries a folded bias, but the block's MLP is not the one it was folded for")
-    y = run_mlp(mlp, y)
+    folded = info.get("_folded")
+    waiting = folded is not None and folded[0] is x  # fc2's bias sits in the residual stream x: finish_linear's to finish
+    out = _mlp.mlp(mlp, y) if _GELU_KERNEL and not waiting else None
+    if out is None:
+        if _plain_mlp(mlp) and scale is None and (drop_path is None or not block.training):
+            return finish_linear(block, x, _mlp.hidden(mlp, y, _GELU_KERNEL), mlp.fc2, info)
+        if waiting:
+            raise RuntimeError("the residual stream carries a folded bias, but the block's MLP is not the one it was folded for")
+        out = _mlp_steps(mlp, y)
     if scale is not None:
-        y = scale * y
-    return finish_block(block, x, y if drop_path is None else drop_path(y), info)
+        out = scale * out
+    return finish_block(block, x, out if drop_path is None else drop_path(out), info)
 
 
 def pick_reduction(mode: str, merge_fn, drop_fn, hybrid_fn):
@@ -367,65 +302,55 @@ def first_norm(block, x, info, norm, skip_first: bool = False):
             return pre[1]
         if skip_first:  # a full hand-over for a reader of the patch rows
             return pre[1][:, 1:, :]
-    from .. import _abi
-    if _FUSE_NEXT and isinstance(norm, torch.nn.LayerNorm) and _abi.ln_fusable(x, norm):
-        # no hand-over (first block, or a block after one that could not fuse): the same streaming LayerNorm kernel,
-        # without an addend (6.4 TB/s against 2 TB/s for the framework's LayerNorm on these shapes)
-        skip = skip_first and x.dim() == 3 and x.shape[1] >= 2
-        y = _abi.add_layernorm(x, None, norm.weight, norm.bias, norm.eps, skip_first=skip)[1]
-        return y[:, 1:, :] if (skip_first and not skip) else y
-    if _FUSE_NEXT and _ln.wants(x, norm):
-        # tokens that require grad: the same launch as a Function with tome_layernorm_backward behind it (tome/_ln.py)
-        skip = skip_first and x.dim() == 3 and x.shape[1] >= 2
-        y = _ln.layernorm_native(x, norm, skip_first=skip)
-        return y[:, 1:, :] if (skip_first and not skip) else y
-    return norm(x)[:, 1:, :] if skip_first else norm(x)
+    # no hand-over (first block, or a block after one that could not fuse): the same streaming LayerNorm kernel,
+    # without an addend (6.4 TB/s against 2 TB/s for the framework's LayerNorm on these shapes)
+    out = _ln.add_layernorm(x, None, norm, skip_first) if _FUSE_NEXT else None
+    if out is None:
+        return norm(x)[:, 1:, :] if skip_first else norm(x)
+    _, y, skipped = out
+    return y[:, 1:, :] if (skip_first and not skipped) else y
+
+
+def _hand_over(block, x, addend, info):
+    """x [+ addend] and the next block's first LayerNorm of it in one launch (tome/_ln.py), left in info["_prenorm"] for
+    that block's first_norm; returns the sum, or None when nothing was launched."""
+    nxt = getattr(block, "_tome_next_norm", None)
+    out = None if nxt is None else _ln.add_layernorm(x, addend, nxt, getattr(block, "_tome_next_skip_first", False))
+    if out is None:
+        return None
+    x, h, skipped = out
+    info["_prenorm"] = (x, h, nxt, skipped)
+    return x
 
 
 def finish_block(block, x, residual, info):
     """x + residual at the end of a block; when the next block's first LayerNorm is known and the tokens are
     16-bit, tome_add_layernorm produces the sum and that norm's output together."""
-    from .. import _abi
-    nxt = getattr(block, "_tome_next_norm", None)
-    if _FUSE_NEXT and nxt is not None and residual.dtype == x.dtype and _abi.ln_fusable(x, nxt):
-        skip = bool(getattr(block, "_tome_next_skip_first", False)) and x.dim() == 3 and x.shape[1] >= 2
-        x, h = _abi.add_layernorm(x, residual, nxt.weight, nxt.bias, nxt.eps, skip_first=skip)
-        info["_prenorm"] = (x, h, nxt, skip)
-        return x
-    if _FUSE_NEXT and nxt is not None and residual.dtype == x.dtype and _ln.wants(x, nxt, residual):
-        # tokens that require grad: sum and next norm in the one forward launch, one backward launch for both gradients
-        skip = bool(getattr(block, "_tome_next_skip_first", False)) and x.dim() == 3 and x.shape[1] >= 2
-        x, h = _ln.add_layernorm_native(x, residual, nxt, skip_first=skip)
-        info["_prenorm"] = (x, h, nxt, skip)
-        return x
-    return x + residual
+    out = _hand_over(block, x, residual, info) if _FUSE_NEXT else None
+    return x + residual if out is None else out
 
 
 def finish_linear(block, x, h, linear, info):
     """`x + linear(h)` at the end of a block.  When the merge kernel has put linear's bias into x already (`fold`),
     the GEMM accumulates onto x in place (beta = 1: no tensor for the GEMM's result, no add pass) and the next block's
     first LayerNorm reads the finished sum once (tome_add_layernorm without addend); otherwise finish_block."""
-    from .. import _abi
     folded = info.pop("_folded", None)
     if folded is None or folded[0] is not x:
         return finish_block(block, x, linear(h), info)
     if folded[1] is not linear:
         raise RuntimeError("the residual stream carries the bias of another Linear than the one that finishes the block")
     x.view(-1, x.shape[-1]).addmm_(h.view(-1, h.shape[-1]), linear.weight.t())
-    nxt = getattr(block, "_tome_next_norm", None)
-    if nxt is not None and _abi.ln_fusable(x, nxt):
-        skip = bool(getattr(block, "_tome_next_skip_first", False)) and x.dim() == 3 and x.shape[1] >= 2
-        _, hn = _abi.add_layernorm(x, None, nxt.weight, nxt.bias, nxt.eps, skip_first=skip)
-        info["_prenorm"] = (x, hn, nxt, skip)
+    _hand_over(block, x, None, info)
     return x
 
 
 def _trailing_norm(x, norm):
-    """norm(x) behind a reduction step that ran on its own.  Tokens that require grad: the streaming LayerNorm kernel as
-    a Function (tome/_ln.py); the merge in front of it stays merge_wavg_native / merge_wavg_regrouped_native -- the
-    fused merge + LayerNorm launch is inference-only."""
-    if _FUSE_LN and _ln.wants(x, norm):
-        return _ln.layernorm_native(x, norm)
+    """norm(x) behind a reduction step that ran on its own (the fused merge + LayerNorm launch is inference-only): the
+    streaming LayerNorm kernel as a Function (tome/_ln.py) when a gradient is wanted, the framework's otherwise."""
+    if _FUSE_LN and torch.is_grad_enabled():  # (the no-grad layer stops here, as it always has)
+        how = _ln.route(x, norm)
+        if how == "function":
+            return _ln.add_layernorm(x, None, norm, how=how)[1]
     return norm(x)
 
 
@@ -435,18 +360,17 @@ def merge_then_norm(metric, x, info, norm, reduction_function, plain_merge_fn, r
     plain 'merge' mode on 16-bit tokens; returns (x, y).  Anything else runs the steps as the reference does.
     fold: the Linear that finishes the block (`foldable`); when the fused kernel runs, x comes back with that bias
     added (y is the norm of x without it) and info["_folded"] says so for finish_linear."""
-    from .. import _abi
     from ..merge import do_nothing
     r_list = info["r"]
-    if residual is not None and not (_FUSE_LN and _FUSE_ADD and reduction_function is plain_merge_fn and r_list
-                                     and r_list[0] > 0 and info["mode"] == "merge" and not info["trace_source"]
-                                     and _abi.ln_fusable(x, norm) and residual.dtype == x.dtype
+    plain = _FUSE_LN and reduction_function is plain_merge_fn and r_list and r_list[0] > 0 and info["mode"] == "merge"
+    fused = plain and _abi.ln_fusable(x, norm, residual)
+    if residual is not None and not (fused and _FUSE_ADD and not info["trace_source"] and residual.dtype == x.dtype
                                      and _abi.effective_r(x.shape[1], r_list[0], info["class_token"],
                                                           info["distill_token"]) > 0):
         x = x + residual
         residual = None
-    if (_FUSE_LN and reduction_function is plain_merge_fn and r_list and r_list[0] > 0 and info["mode"] == "merge"
-            and _abi.ln_fusable(x, norm)):
+        fused = fused and _abi.ln_fusable(x, norm)  # (the sum is another tensor: of another dtype, perhaps)
+    if fused:
         r = r_list.pop(0)
         merge, _ = bipartite_soft_matching(metric, r, info["class_token"], info["distill_token"], info["mode"])
         if merge is do_nothing:
@@ -482,10 +406,6 @@ def _regrouped_by_views(reduce_grouped, metric, x_full, info, r, frames):
     return torch.cat((x_full[:, :1], body), dim=1)
 
 
-def _training_tokens(x) -> bool:
-    return torch.is_grad_enabled() and x.requires_grad
-
-
 def _native_regrouped(kind: str, x_full, size=None) -> bool:
     """Tokens that require grad: does the regrouped reduction run as a native Function (tome/merge.py: the regrouped
     kernel forward, tome_merge_backward_regrouped backward) instead of `_regrouped_by_views`?  Plain merge and drop
@@ -493,7 +413,7 @@ def _native_regrouped(kind: str, x_full, size=None) -> bool:
     from .. import merge as tm
     return (tm.native_backward_covers(kind, even_odd=True, on_device=x_full.is_cuda and x_full.dim() == 3,
                                       dtype=x_full.dtype,
-                                      size_requires_grad=size is not None and _training_tokens(size))
+                                      size_requires_grad=size is not None and _abi.needs_grad(size))
             and (x_full.shape[-1] * x_full.element_size()) % 16 == 0)
 
 
@@ -501,9 +421,8 @@ def reduce_merge_regrouped(metric, x_full, info, r, frames, hybrid=False):
     """reduce_merge / reduce_hybrid for the models whose merge groups are interleaved in the token sequence
     (TimeSformer '(p t)', Motionformer '(s f)'): x_full is [B, 1 + P*F, C] with the class token in front; the
     kernel addresses the groups in place and returns [B, 1 + (P-r)*F, C] (no permuted copies of x)."""
-    from .. import _abi
     from ..merge import do_nothing
-    training = _training_tokens(x_full)
+    training = _abi.needs_grad(x_full)
     if training and (hybrid or info["trace_source"] or not _native_regrouped("merge_wavg", x_full, info["size"])):
         return _regrouped_by_views(reduce_hybrid if hybrid else reduce_merge, metric, x_full, info, r, frames)
     if hybrid:
@@ -517,13 +436,7 @@ def reduce_merge_regrouped(metric, x_full, info, r, frames, hybrid=False):
     if info["trace_source"]:
         shape_only = x_full.new_empty((plan.n, plan.T, 0))
         info["source"] = merge_source(merge, shape_only, info["source"])
-    if training:
-        from ..merge import merge_wavg_regrouped_native
-        x_out, info["size"] = merge_wavg_regrouped_native(plan, x_full, info["size"], frames, has_cls=True,
-                                                          log_size=info["prop_attn"])
-    else:
-        x_out, info["size"] = _abi.merge_wavg_regrouped(plan, x_full, info["size"], frames, has_cls=True,
-                                                        log_size=info["prop_attn"])
+    x_out, info["size"] = merge_wavg_regrouped(plan, x_full, info["size"], frames, has_cls=True, log_size=info["prop_attn"])
     if info["verbose"]:
         print(f"Merged {plan.T} to {plan.T - plan.r} tokens")
     return x_out
@@ -555,13 +468,13 @@ def merge_then_norm_regrouped(metric, x_full, info, norm, unfused_reduce, is_pla
     """merge_then_norm for the interleaved layouts (TimeSformer '(p t)', Motionformer '(s f)'): x_full is
     [B, 1 + P*F, C]; `unfused_reduce(x)` is the model's own reduction step (it pops r itself).  `residual`: a tensor
     in x's layout, or a GroupedResidual."""
-    from .. import _abi
     from ..merge import do_nothing
     r_list = info["r"]
-    fusable = (_FUSE_LN and is_plain_merge and r_list and r_list[0] > 0 and info["mode"] == "merge"
-               and not info["trace_source"] and _abi.ln_fusable(x_full, norm)
-               and _abi.effective_r((x_full.shape[1] - 1) // frames, r_list[0], False, False) > 0)
     grouped = residual if isinstance(residual, GroupedResidual) else None
+    fusable = (_FUSE_LN and is_plain_merge and r_list and r_list[0] > 0 and info["mode"] == "merge"
+               and not info["trace_source"]
+               and _abi.ln_fusable(x_full, norm, *((residual,) if grouped is None else (grouped.rs, grouped.cls_new)))
+               and _abi.effective_r((x_full.shape[1] - 1) // frames, r_list[0], False, False) > 0)
     if grouped is not None and not (fusable and _FUSE_ADD and grouped.dtype == x_full.dtype):
         residual, grouped = grouped.materialize(), None
     if not fusable:
@@ -597,7 +510,6 @@ def merge_then_norm_regrouped(metric, x_full, info, norm, unfused_reduce, is_pla
 def _drop_source(drop, source, n, t, device):
     """`drop(source)` with `source = eye(T)` when None (tome/patch/videomae.py:112-117); the first layer's matrix
     comes straight from the row map (tome_source_init), without the identity."""
-    from .. import _abi
     plan = getattr(drop, "plan", None)
     if source is None:
         if plan is not None:
@@ -624,8 +536,7 @@ def reduce_drop_regrouped(metric, x_full, info, r, frames: int):
     """reduce_drop for the interleaved layouts: x_full [B, 1 + P*F, C] with the class token in front; the groups
     are addressed in place by the kernel (tome_drop_regrouped) instead of regrouped by permuted copies
     (timesformer.py:111-131, motionformer.py:172-193)."""
-    from .. import _abi
-    training = _training_tokens(x_full)
+    training = _abi.needs_grad(x_full)
     if training and (info["trace_source"] or not _native_regrouped("drop", x_full)):
         return _regrouped_by_views(reduce_drop, metric, x_full, info, r, frames)
     drop = bipartite_soft_matching_drop(metric, r, info["class_token"], info["distill_token"], info["mode"])
@@ -634,11 +545,7 @@ def reduce_drop_regrouped(metric, x_full, info, r, frames: int):
     plan = drop.plan
     if info["trace_source"]:
         info["source"] = _drop_source(drop, info["source"], plan.n, plan.T, x_full.device)
-    if training:
-        from ..merge import drop_regrouped_native
-        x_out = drop_regrouped_native(plan, x_full, frames, has_cls=True)
-    else:
-        x_out = _abi.drop_regrouped(plan, x_full, frames, has_cls=True)
+    x_out = drop_regrouped(plan, x_full, frames, has_cls=True)
     info["size"] = torch.ones((plan.n, plan.T - plan.r, 1), device=x_full.device)
     if info["verbose"]:
         print(f"Dropped {plan.T} to {plan.T - plan.r} tokens")

@@ -57,36 +57,20 @@ def _trajectory_forward(self, x, seq_len=196, num_frames=8, approx="none", num_l
     metric = HeadMeanKeys(heads[1][:, :, 1:1 + P * F, :].unflatten(2, (P, F)).permute(0, 3, 1, 2, 4))
     info = getattr(self, "_tome_info", None)
     ready = C.keys_ready(metric.keys, info, capture_only=True)  # the keys exist behind the qkv GEMM
-    fused = (C._ATTN_KERNEL and not (self.training and self.attn_drop.p > 0.0) and all(_abi.prop_attention_ok(t) for t in heads))
-    # under grad, a stage whose inputs require grad runs the same launch as an autograd Function with the native
-    # backward behind it (tome/_attn.py) -- unless the caller wants the attention map, which has no gradient there
-    train = (C._ATTN_KERNEL and torch.is_grad_enabled() and not _want_attn and _attn.trajectory_enabled()
-             and not (self.training and self.attn_drop.p > 0.0))
-    train_seg = train and not fused and qkv.requires_grad and _attn.segments_qkv_trainable(heads, F)
     # flat per-key bias in the reference's '(s f)' order (motionformer.py:107-111): key j of the (f n)-ordered
     # sequence gets log(size) of (s = j // F, f = j % F)
     log_flat = None
     if size is not None:
         log_flat = rearrange(_abi.log_of_size(size), "(b f) s i -> b (s f) i", f=F)[:, :, 0]
-    if fused:
-        # the class token attends to every token, sizes ignored (motionformer.py:54): the attention kernel with one
-        # query per head, read in place
-        # (its row is row 0 of the buffer the temporal stage fills below: cat((cls_out, x), dim=1) without the copy)
-        joined = torch.empty((B, N, h * hd), dtype=qkv.dtype, device=qkv.device) if _JOIN else None
-        cls_out = _abi.prop_attention(heads[0][:, :, :1], heads[1], heads[2], None, self.scale,
-                                      out=joined[:, :1].unflatten(2, (h, hd)) if _JOIN else None)
-        # every token attends to the P keys of ONE frame at a time (softmax per frame): ONE launch of the segmented
-        # attention kernel, queries and keys read in place from the qkv buffer, segment f writing its slice of
-        # y 'b s f (h d)'; the [B*h, N, N] logits, their softmax and the attn @ v product never exist
-        lf = None if log_flat is None else log_flat.float().contiguous()
-        y = _abi.prop_attention_segments(heads[0][:, :, 1:], heads[1][:, :, 1:1 + P * F], heads[2][:, :, 1:1 + P * F], F,
-                                         self.scale, log_bias=lf)
-    elif train_seg:
-        # the class token's single query through the plain Function, the per-frame stage through the segment Function
-        # with the projection's buffer as its one input; autograd adds the two gradients of qkv
-        cls_out = _attn.attention_native(heads[0][:, :, :1], heads[1], heads[2], None, self.scale)
-        y = _attn.segment_attention_qkv_native(heads, F, log_flat, self.scale)
+    # the class token's query and the per-frame attention of every other token on the kernels, read in place from the
+    # qkv buffer; under grad as Functions, unless the caller wants the attention map (tome/_attn.py)
+    live_drop = self.training and self.attn_drop.p > 0.0
+    stage1 = None if not C._ATTN_KERNEL else _attn.trajectory_stage1(heads, F, log_flat, self.scale, live_drop, _want_attn,
+                                                                    _JOIN)
+    if stage1 is not None:
+        cls_out, y, joined = stage1
     else:
+        joined = None
         q, k, v = (rearrange(t, "b n (h d) -> (b h) n d", h=h) for t in qkv.chunk(3, dim=-1))
         (cls_q, q_), (cls_k, k_), (cls_v, v_) = ((t[:, 0:1], t[:, 1:]) for t in (q, k, v))
         cls_out = rearrange(qkv_attn(cls_q * self.scale, k, v), "(b h) f d -> b f (h d)", f=1, h=h)
@@ -116,21 +100,19 @@ def _trajectory_forward(self, x, seq_len=196, num_frames=8, approx="none", num_l
         kv = self.proj_kv(y)       # [B, S, F, 2C]: keys | values
         k2_tok = kv[..., :Cc]
         val_tok = y if self.use_original_code else kv[..., Cc:]
-    if fused and _abi.trajectory_mix_ok(q2p, k2_tok, val_tok, h):
-        # F logits per (token, head), their softmax and the weighted sum of the F trajectory tokens: one streaming
-        # pass over k2 and val (tome_trajectory_mix) instead of two multiplies, two reductions and a softmax
-        out, tattn = _abi.trajectory_mix(q2p, k2_tok, val_tok, h, self.scale, want_attn=_want_attn,
-                                         out=joined[:, 1:] if _JOIN else None)
+    # F logits per (token, head), their softmax and the weighted sum of the F trajectory tokens: one streaming pass
+    # over k2 and val (tome_trajectory_mix) instead of two multiplies, two reductions and a softmax -- into rows 1.. of
+    # the first stage's joined buffer when there is one and nothing wants a gradient
+    mix = None
+    if C._ATTN_KERNEL and not live_drop:
+        mix = _attn.trajectory_mix(q2p, k2_tok, val_tok, h, self.scale, _want_attn,
+                                   out=None if joined is None else joined[:, 1:])
+    if mix is not None:
+        out, tattn, wrote = mix
         if tattn is not None:
             tattn = tattn.to(x.dtype)
-        # class row + trajectory rows, already side by side
-        out = joined if _JOIN else torch.cat((cls_out.reshape(B, 1, -1), out), dim=1)
-    elif (train and (q2p.requires_grad or k2_tok.requires_grad or val_tok.requires_grad)
-          and _abi.trajectory_mix_trainable(q2p, k2_tok, val_tok, h)):
-        # (under grad the class row and the trajectory rows meet in torch.cat: no writes into a shared buffer)
-        out = _attn.trajectory_mix_native(q2p, k2_tok, val_tok, h, self.scale)
-        tattn = None
-        out = torch.cat((cls_out.reshape(B, 1, -1), out), dim=1)
+        # class row + trajectory rows: already side by side when the launch wrote into the joined buffer
+        out = joined if wrote else torch.cat((cls_out.reshape(B, 1, -1), out), dim=1)
     else:
         q2 = rearrange(q2p, "b s (h d) -> b h s d", h=h) * self.scale
         k2 = rearrange(k2_tok, "b s f (h d) -> b h s f d", f=F, h=h)

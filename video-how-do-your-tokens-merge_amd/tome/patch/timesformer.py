@@ -32,18 +32,14 @@ def _block_forward(self, x, B, T, W):
     rt = self.drop_path(self.temporal_attn(xn.reshape(B * P, T, m))).reshape(B, P * T, m)
     cls0 = x[:, :1, :]
     rt = self.temporal_fc(rt)
-    if C._FUSE_NEXT and rt.dtype == x.dtype and _abi.ln_fusable(x, self.norm1):
-        # residual of the temporal attention, 'b (p t) -> (b t) p' with the class token in front of every frame,
-        # and the spatial attention's norm1 -- one pass (tome_add_layernorm_regrouped); the regrouped
-        # un-normalised tokens never exist
-        x1, xs_normed = _abi.add_layernorm_regrouped(x, rt, T, self.norm1.weight, self.norm1.bias, self.norm1.eps)
-    elif (C._FUSE_NEXT and rt.dtype == x.dtype and torch.is_grad_enabled() and _ln.regrouped_enabled()
-          and _abi.ln_trainable(x, self.norm1)):
-        # the same launch under grad (ln_fusable refuses tensors that require grad), with
-        # tome_layernorm_backward_regrouped behind it: x and rt receive gx and its view gx[:, 1:]
-        x1, xs_normed = _ln.add_layernorm_regrouped_native(x, rt, T, self.norm1)
+    # residual of the temporal attention, 'b (p t) -> (b t) p' with the class token in front of every frame, and the
+    # spatial attention's norm1 -- one pass (tome_add_layernorm_regrouped, under grad as a Function: tome/_ln.py); the
+    # regrouped un-normalised tokens never exist
+    mid = _ln.add_layernorm_regrouped(x, rt, T, self.norm1) if C._FUSE_NEXT else None
+    if mid is not None:
+        x1, xs_normed = mid
     else:
-        if torch.is_grad_enabled() and x.requires_grad:
+        if _abi.needs_grad(x, rt):
             # the reference's op sequence (differentiable): add, transpose, three cats
             xt = x[:, 1:, :] + rt
             x1 = torch.cat((cls0, xt), 1)
