@@ -495,6 +495,38 @@ size_t tome_gelu_erf_backward_workspace_bytes(int64_t rows, int64_t width);
 int tome_gelu_erf_backward(const void *h, const void *ga, int dtype, int64_t rows, int64_t width, void *gh, void *act,
                            void *dbias, void *workspace, size_t workspace_bytes, tome_stream_t stream);
 
+/*
+ * tome_gelu_tanh, tome_gelu_tanh_backward  <-  the MLP of ViViT's layer, forward and what autograd derives from it
+ *     (additions to ABI v11, no entry changed):
+ *         layer_output = self.layernorm_after(hidden_states)           tome/patch/vivit.py:39   the layer forward,
+ *         layer_output = self.intermediate(layer_output)               tome/patch/vivit.py:40   ToMeVivitLayer.forward
+ *         layer_output = self.output(layer_output, hidden_states)      tome/patch/vivit.py:43   (:18-47)
+ *     where HF's VivitIntermediate is dense -> "gelu_fast" -> dropout and VivitOutput dense -> dropout -> + residual;
+ *     gelu_fast (transformers.activations.FastGELUActivation) is 0.5 x (1 + tanh(0.7978845608 x (1 + 0.044715 x^2))).
+ *     Arithmetic contract.  v = the stored 16-bit pre-activation in fp32, beta = 0.7978845608028654f, kappa = 0.044715f:
+ *         u  = beta (v + kappa v^3)
+ *         s  = sigma(2u) = 1 / (1 + exp(-2u))            ( = 0.5 (1 + tanh u) )
+ *         a  = v s                                       the activation            (tome_gelu_tanh: y; backward: act)
+ *         d  = s + v s (1 - s) * 2 beta (1 + 3 kappa v^2)     its derivative
+ *         gh = round(ga * d)                             gh may be ga (in place), never h
+ *         dbias[c] = sum over rows of the ROUNDED gh[:, c]
+ *     fp32 throughout, one rounding per output.  s and 1 - s are each computed without cancellation: with
+ *     e = exp(-2|u|) (one hardware exp2 of -2 log2(e) |u|) and r = 1 / (1 + e) (one hardware reciprocal, 1 ulp) they
+ *     are r and e r, picked by the sign of u; 1 - s is never formed by subtraction and the framework's 1 + tanh(u),
+ *     which has lost every bit below v = -4, is not used.  Every result is
+ *     finite for every finite fp16 v and every bf16 v with |v| <= 2^20 (beyond that nothing is promised: the framework's
+ *     own formula gives NaN there).  The forward and the backward evaluate s through the same inline function
+ *     (csrc/tome_common.h gelu_tanh_sigmoid / gelu_tanh_value), so `act` has the bits tome_gelu_tanh stored.
+ *     tome_gelu_tanh: `elements` 16-bit values (a multiple of 8), y may alias x; as tome_gelu_erf.
+ *     tome_gelu_tanh_backward: arguments, shapes, refusals and error codes of tome_gelu_erf_backward (16-bit tensors
+ *     only, width % 8 == 0, width <= 8192, act a buffer of its own, dbias needs the workspace).  The launch form is the
+ *     erf entry's, and so is the workspace: size it with tome_gelu_erf_backward_workspace_bytes(rows, width) -- there is
+ *     no second size function.
+ */
+int tome_gelu_tanh(const void *x, int dtype, int64_t elements, void *y, tome_stream_t stream);
+int tome_gelu_tanh_backward(const void *h, const void *ga, int dtype, int64_t rows, int64_t width, void *gh, void *act,
+                            void *dbias, void *workspace, size_t workspace_bytes, tome_stream_t stream);
+
 /* tome_tubelet_rows  <-  the models' patch embedding, a convolution whose stride equals its kernel
  * (slowfast/models/videomae_video_model_builder.py:137-166 `PatchEmbed.proj`; TimeSformer's per-frame Conv2d; Motionformer
  * `PatchEmbed3D`; ViViT's tubelet Conv3d): its input side as the [B*N, C*kt*kh*kw] matrix the weight multiplies,

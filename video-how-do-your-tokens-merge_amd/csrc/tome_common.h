@@ -36,6 +36,28 @@ template <> __device__ __forceinline__ f16_t from_f32<f16_t>(float f) {
 __device__ __forceinline__ float gelu_erf_one_plus(float x) { return 1.0f + erff(x * 0.70710678118654752440f); }
 __device__ __forceinline__ float gelu_erf_value(float x, float one_plus_erf) { return x * 0.5f * one_plus_erf; }
 
+// The activation's form, a template parameter of the GELU kernels (k_gelu_erf / k_gelu_tanh, k_gelu_bwd).
+enum { GELU_ERF = 0, GELU_TANH = 1 };
+
+// The tanh GELU (HF's "gelu_fast" in ViViT's MLP, F.gelu(approximate="tanh")) in its sigmoid form (include/tome_hip.h,
+// tome_gelu_tanh): u = beta (x + kappa x^3), s = sigma(2u) = 0.5 (1 + tanh u), the activation x s.  s and 1 - s both
+// come from e = exp(-2|u|) in (0, 1] as r = 1 / (1 + e) and e r, picked by the sign of u: neither cancels, where the
+// framework's 1 + tanh(u) has lost every bit below x = -4.  e is one v_exp_f32 of -2 log2(e) |u| and r one v_rcp_f32
+// (1 ulp each; 1 + e lies in [1, 2]): with the library's expf and two IEEE divisions the backward pass was bound by
+// the vector ALU at 0.4 of the memory rate.  Returns s, leaves 1 - s in `one_minus` and x^2 in `x2` (k_gelu_tanh stores
+// x s; k_gelu_bwd rebuilds those bits from the saved pre-activation and needs all three).
+#define GELU_TANH_BETA 0.7978845608028654f
+#define GELU_TANH_KAPPA 0.044715f
+__device__ __forceinline__ float gelu_tanh_sigmoid(float x, float &one_minus, float &x2) {
+    x2 = x * x;
+    const float u = GELU_TANH_BETA * (x + GELU_TANH_KAPPA * x2 * x);
+    const float e = __builtin_amdgcn_exp2f(-2.8853900817779268f * fabsf(u));  // 2 log2(e)
+    const float big = __builtin_amdgcn_rcpf(1.0f + e), small = e * big;
+    one_minus = u >= 0.0f ? small : big;
+    return u >= 0.0f ? big : small;
+}
+__device__ __forceinline__ float gelu_tanh_value(float x, float s) { return x * s; }
+
 // A lane's slice of a row: VEC consecutive elements moved with one 16-byte (or narrower) access.
 template <typename T, int VEC> struct Pack { T e[VEC]; };
 

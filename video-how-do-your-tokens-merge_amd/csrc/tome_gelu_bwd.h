@@ -1,4 +1,4 @@
-// tome_gelu_bwd.h -- part of the single translation unit csrc/tome_kernels.hip (backward of the MLP's exact-erf GELU).
+// tome_gelu_bwd.h -- part of the single translation unit csrc/tome_kernels.hip (backward of the MLP's GELU, exact-erf and tanh form).
 #pragma once
 // ------------------------------------------------------------------------------------------------
 // k_gelu_bwd: the one pass over the hidden tensors [rows, Hd] in the backward of `fc2(gelu(fc1(y)))` (the reference
@@ -8,6 +8,10 @@
 //     a  = gelu(h)            (optional)  gelu_erf_value, the forward's expression: the bits k_gelu_erf stored
 //     db[c] = sum_rows gh     (BIAS)      of the ROUNDED gh, the values fc1's weight-gradient GEMM reads
 // fp32 arithmetic, one rounding per output.  1 + erf(v / sqrt 2) is evaluated once per element and feeds both a and gh.
+// FORM == GELU_TANH (ViViT's `layer.intermediate`, HF's gelu_fast; the contract is in include/tome_hip.h at
+// tome_gelu_tanh): with u = beta (v + kappa v^3), s = sigma(2u) and c = 1 - s from gelu_tanh_sigmoid (no cancellation),
+//     gh = round(ga * (s + v (s c) * 2 beta (1 + 3 kappa v^2))),   a = v s    gelu_tanh_value: the bits k_gelu_tanh stored
+// Everything else -- packing, loads, the fence in front of both roundings, the bias sums -- is the same code.
 // gh may be ga (every thread reads the 16 bytes it overwrites before it writes them); a never lies over h.
 // A pure streaming pass: 16-byte chunks, non-temporal both ways.  The 2 S U loads of a step (8, 8, 12, 8 for S = 1 .. 4)
 // are issued back to back, h and ga of a chunk side by side, before the first value is used: a lane without a chunk in
@@ -32,7 +36,7 @@ __device__ __forceinline__ float fp32_value(float x) {
 
 template <int S> struct GeluBwdUnroll { static constexpr int U = S == 1 ? 4 : (S <= 3 ? 2 : 1); };
 
-template <typename TX, int S, bool BIAS, bool ACT>
+template <typename TX, int S, bool BIAS, bool ACT, int FORM>
 __global__ __launch_bounds__(256) void k_gelu_bwd(const TX *h, const TX *ga, int64_t chunks, int cpr,
                                                   int RP, int spw, TX *gh, TX *__restrict__ act,
                                                   float *__restrict__ ws) {
@@ -94,14 +98,26 @@ __global__ __launch_bounds__(256) void k_gelu_bwd(const TX *h, const TX *ga, int
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) {
                     const float v = to_f32(ph.e[e]);
-                    const float e1 = gelu_erf_one_plus(v);
-                    const float pdf = expf(-0.5f * (v * v)) * 0.39894228040143267794f;
+                    // a1: what the activation is built from (sigma(2u) / 1 + erf); w: the derivative's second term
+                    // (tanh form) or phi(v) (erf form)
+                    float a1, w;
+                    if (FORM == GELU_TANH) {
+                        float c, v2;
+                        a1 = gelu_tanh_sigmoid(v, c, v2);
+                        w = v * (a1 * c) * (2.0f * GELU_TANH_BETA * (1.0f + 3.0f * GELU_TANH_KAPPA * v2));
+                    } else {
+                        a1 = gelu_erf_one_plus(v);
+                        w = expf(-0.5f * (v * v)) * 0.39894228040143267794f;
+                    }
                     // both results exist as fp32 values before they are rounded to the format: without the fence the
                     // fp16 forms that also sum the bias take v_fma_mixlo_f16 for product and rounding in one step, and
                     // gh would depend on what else the launch was asked for
-                    const TX r = from_f32<TX>(fp32_value(to_f32(pg.e[e]) * (0.5f * e1 + v * pdf)));
+                    const TX r = from_f32<TX>(fp32_value(to_f32(pg.e[e]) *
+                                                         (FORM == GELU_TANH ? a1 + w : 0.5f * a1 + v * w)));
                     pg.e[e] = r;
-                    if (ACT) pa.e[e] = from_f32<TX>(fp32_value(gelu_erf_value(v, e1)));
+                    if (ACT)
+                        pa.e[e] = from_f32<TX>(fp32_value(FORM == GELU_TANH ? gelu_tanh_value(v, a1)
+                                                                            : gelu_erf_value(v, a1)));
                     if (BIAS) acc[s][e] += to_f32(r);
                 }
                 uint4 o;

@@ -27,8 +27,9 @@
 // and of TimeSformer's temporal attention (tome_short_attention_backward), tome_short_attn_bwd.h:
 //   k_short_attention_bwd  P recomputed, dq / dk / dv of sequences of <= 8 tokens in one pass, eight lanes per
 //                        (sequence, head), dk / dv accumulated in registers                           (HBM bound)
-// and of the MLP's backward between its two library GEMMs (tome_gelu_erf_backward), tome_gelu_bwd.h:
-//   k_gelu_bwd           gh = ga (Phi(h) + h phi(h)), the activation again with the forward's bits, per-workgroup
+// and of the MLP's backward between its two library GEMMs (tome_gelu_erf_backward / tome_gelu_tanh_backward),
+// tome_gelu_bwd.h:
+//   k_gelu_bwd           gh = ga gelu'(h) (erf or tanh form), the activation again with the forward's bits, per-workgroup
 //                        partial rows of fc1's bias gradient (summed by k_ln_param_grad)        (HBM bound)
 // and of the proportional attention's backward (tome_prop_attention_backward), tome_attn_bwd.h:
 //   k_attn_bwd_dq        row statistics recomputed (two sweeps over the keys), dq, L and delta to the workspace
@@ -1377,20 +1378,34 @@ extern "C" int tome_short_attention_backward(const void *q, const void *k, const
     }, [&] { return not_16bit("tome_short_attention_backward", dtype, "tensors"); });
 }
 
-extern "C" int tome_gelu_erf(const void *x, int dtype, int64_t elements, void *y, tome_stream_t stream) {
-    if (!x || !y || elements <= 0) return fail(TOME_EINVAL, "tome_gelu_erf: bad shape/pointer");
-    if (int rc = not_16bit("tome_gelu_erf", dtype, "tensors")) return rc;
+// tome_gelu_erf / tome_gelu_tanh: one streaming launch of k_gelu_erf / k_gelu_tanh (FORM: GELU_ERF / GELU_TANH).
+template <int FORM>
+static int gelu_impl(const char *who, const void *x, int dtype, int64_t elements, void *y, tome_stream_t stream) {
+    if (!x || !y || elements <= 0) return fail(TOME_EINVAL, "%s: bad shape/pointer", who);
+    if (int rc = not_16bit(who, dtype, "tensors")) return rc;
     if (elements % 8 || !aligned16(x) || !aligned16(y))
-        return fail(TOME_EINVAL, "tome_gelu_erf: a multiple of 8 elements in 16-byte aligned buffers required");
+        return fail(TOME_EINVAL, "%s: a multiple of 8 elements in 16-byte aligned buffers required", who);
     const int64_t chunks = elements / 8;
     const int64_t blocks = (chunks + 1023) / 1024;  // 256 threads x 4 chunks
-    if (blocks > 0x7fffffffLL) return fail(TOME_EINVAL, "tome_gelu_erf: too large");
+    if (blocks > 0x7fffffffLL) return fail(TOME_EINVAL, "%s: too large", who);
     hipStream_t st = (hipStream_t)stream;
     return dispatch_x<false>(dtype, [&](auto tx) {
         using TX = typename decltype(tx)::type;
+        if (FORM == GELU_TANH) {
+            hipLaunchKernelGGL(k_gelu_tanh<TX>, dim3((unsigned)blocks), dim3(256), 0, st, (const TX *)x, (TX *)y, chunks);
+            return check_launch("k_gelu_tanh");
+        }
         hipLaunchKernelGGL(k_gelu_erf<TX>, dim3((unsigned)blocks), dim3(256), 0, st, (const TX *)x, (TX *)y, chunks);
         return check_launch("k_gelu_erf");
-    }, [&] { return not_16bit("tome_gelu_erf", dtype, "tensors"); });
+    }, [&] { return not_16bit(who, dtype, "tensors"); });
+}
+
+extern "C" int tome_gelu_erf(const void *x, int dtype, int64_t elements, void *y, tome_stream_t stream) {
+    return gelu_impl<GELU_ERF>("tome_gelu_erf", x, dtype, elements, y, stream);
+}
+
+extern "C" int tome_gelu_tanh(const void *x, int dtype, int64_t elements, void *y, tome_stream_t stream) {
+    return gelu_impl<GELU_TANH>("tome_gelu_tanh", x, dtype, elements, y, stream);
 }
 
 // The launch form of k_gelu_bwd with the bias gradient for `rows` rows of `width`: S column slots per thread, U passes
@@ -1419,22 +1434,25 @@ extern "C" size_t tome_gelu_erf_backward_workspace_bytes(int64_t rows, int64_t w
     return align_up((size_t)gelu_bwd_form(rows, width).parts * (size_t)width * sizeof(float), 256);
 }
 
-extern "C" int tome_gelu_erf_backward(const void *h, const void *ga, int dtype, int64_t rows, int64_t width, void *gh,
-                                      void *act, void *dbias, void *workspace, size_t workspace_bytes,
-                                      tome_stream_t stream) {
-    if (!h || !ga || !gh) return fail(TOME_EINVAL, "tome_gelu_erf_backward: null buffer");
-    if (int rc = not_16bit("tome_gelu_erf_backward", dtype, "tensors")) return rc;
+// tome_gelu_erf_backward / tome_gelu_tanh_backward: the same checks, launch form and workspace; FORM picks the
+// activation's formula inside k_gelu_bwd.
+template <int FORM>
+static int gelu_backward_impl(const char *who, const void *h, const void *ga, int dtype, int64_t rows, int64_t width,
+                              void *gh, void *act, void *dbias, void *workspace, size_t workspace_bytes,
+                              tome_stream_t stream) {
+    if (!h || !ga || !gh) return fail(TOME_EINVAL, "%s: null buffer", who);
+    if (int rc = not_16bit(who, dtype, "tensors")) return rc;
     if (!gelu_bwd_shape_ok(rows, width))
-        return fail(TOME_EINVAL, "tome_gelu_erf_backward: width %% 8 == 0, width <= 8192 and 1 .. 2^31 - 1 rows required");
+        return fail(TOME_EINVAL, "%s: width %% 8 == 0, width <= 8192 and 1 .. 2^31 - 1 rows required", who);
     if (!aligned16(h) || !aligned16(ga) || !aligned16(gh) || !aligned16(act) || !aligned16(dbias) ||
         !aligned16(workspace))
-        return fail(TOME_EINVAL, "tome_gelu_erf_backward: 16-byte aligned buffers required");
+        return fail(TOME_EINVAL, "%s: 16-byte aligned buffers required", who);
     if (act && (act == h || act == ga || act == gh))
-        return fail(TOME_EINVAL, "tome_gelu_erf_backward: the activation needs a buffer of its own");
-    if (gh == h) return fail(TOME_EINVAL, "tome_gelu_erf_backward: gh may lie over ga, not over h");
+        return fail(TOME_EINVAL, "%s: the activation needs a buffer of its own", who);
+    if (gh == h) return fail(TOME_EINVAL, "%s: gh may lie over ga, not over h", who);
     if (dbias && (!workspace || workspace_bytes < tome_gelu_erf_backward_workspace_bytes(rows, width)))
-        return fail(TOME_EWORKSPACE, "tome_gelu_erf_backward: the bias gradient needs a workspace of "
-                                     "tome_gelu_erf_backward_workspace_bytes()");
+        return fail(TOME_EWORKSPACE, "%s: the bias gradient needs a workspace of "
+                                     "tome_gelu_erf_backward_workspace_bytes()", who);
     const int64_t cpr = width / 8, chunks = rows * cpr;
     hipStream_t st = (hipStream_t)stream;
     return dispatch_x<false>(dtype, [&](auto tx) {
@@ -1442,16 +1460,17 @@ extern "C" int tome_gelu_erf_backward(const void *h, const void *ga, int dtype, 
         if (!dbias) {  // flat: rows of 256 chunks, four per lane, as k_gelu_erf
             const int64_t blocks = (chunks + 1023) / 1024;
 #define GELU_BWD_FLAT(ACT)                                                                                             \
-    hipLaunchKernelGGL((k_gelu_bwd<TX, 1, false, ACT>), dim3((unsigned)blocks), dim3(256), 0, st, (const TX *)h,       \
-                       (const TX *)ga, chunks, 256, 1, 1, (TX *)gh, (TX *)act, (float *)nullptr)
+    hipLaunchKernelGGL((k_gelu_bwd<TX, 1, false, ACT, FORM>), dim3((unsigned)blocks), dim3(256), 0, st,                \
+                       (const TX *)h, (const TX *)ga, chunks, 256, 1, 1, (TX *)gh, (TX *)act, (float *)nullptr)
             if (act) GELU_BWD_FLAT(true); else GELU_BWD_FLAT(false);
 #undef GELU_BWD_FLAT
             return check_launch("k_gelu_bwd");
         }
         const GeluBwdForm f = gelu_bwd_form(rows, width);
 #define GELU_BWD_LAUNCH_(SLOTS, ACT)                                                                                   \
-    hipLaunchKernelGGL((k_gelu_bwd<TX, SLOTS, true, ACT>), dim3((unsigned)f.parts), dim3(256), 0, st, (const TX *)h,   \
-                       (const TX *)ga, chunks, (int)cpr, f.RP, (int)f.spw, (TX *)gh, (TX *)act, (float *)workspace)
+    hipLaunchKernelGGL((k_gelu_bwd<TX, SLOTS, true, ACT, FORM>), dim3((unsigned)f.parts), dim3(256), 0, st,            \
+                       (const TX *)h, (const TX *)ga, chunks, (int)cpr, f.RP, (int)f.spw, (TX *)gh, (TX *)act,         \
+                       (float *)workspace)
 #define GELU_BWD_LAUNCH(SLOTS) do { if (act) GELU_BWD_LAUNCH_(SLOTS, true); else GELU_BWD_LAUNCH_(SLOTS, false); } while (0)
         switch (f.S) {
         case 1: GELU_BWD_LAUNCH(1); break;
@@ -1463,7 +1482,21 @@ extern "C" int tome_gelu_erf_backward(const void *h, const void *ga, int dtype, 
 #undef GELU_BWD_LAUNCH
         if (int rc = check_launch("k_gelu_bwd")) return rc;
         return launch_param_grad<TX>(workspace, f.parts, width, width, dbias, nullptr, st);
-    }, [&] { return not_16bit("tome_gelu_erf_backward", dtype, "tensors"); });
+    }, [&] { return not_16bit(who, dtype, "tensors"); });
+}
+
+extern "C" int tome_gelu_erf_backward(const void *h, const void *ga, int dtype, int64_t rows, int64_t width, void *gh,
+                                      void *act, void *dbias, void *workspace, size_t workspace_bytes,
+                                      tome_stream_t stream) {
+    return gelu_backward_impl<GELU_ERF>("tome_gelu_erf_backward", h, ga, dtype, rows, width, gh, act, dbias, workspace,
+                                        workspace_bytes, stream);
+}
+
+extern "C" int tome_gelu_tanh_backward(const void *h, const void *ga, int dtype, int64_t rows, int64_t width, void *gh,
+                                       void *act, void *dbias, void *workspace, size_t workspace_bytes,
+                                       tome_stream_t stream) {
+    return gelu_backward_impl<GELU_TANH>("tome_gelu_tanh_backward", h, ga, dtype, rows, width, gh, act, dbias,
+                                         workspace, workspace_bytes, stream);
 }
 
 extern "C" int tome_tubelet_rows(const void *x, int elem_bytes, int64_t B, int64_t C, int64_t T, int64_t H, int64_t W,

@@ -1360,8 +1360,10 @@ __global__ __launch_bounds__(256) void k_add_ln_regroup(const TX *__restrict__ x
 //     y = x * 0.5 * (1 + erf(x / sqrt(2)))      fp32 arithmetic on 16-bit values, one rounding -- the expression and
 // operation order of the framework's kernel, so the result is bit-identical to it.  A pure streaming pass: four
 // 16-byte chunks per lane in flight, non-temporal both ways (the [tokens, 4C] activation is 1.2 GB at batch 128).
-template <typename TX>
-__global__ __launch_bounds__(256) void k_gelu_erf(const TX *__restrict__ x, TX *__restrict__ y, int64_t chunks) {
+// k_gelu_tanh: ViViT's activation (`layer.intermediate`, tome/patch/vivit.py layer forward; HF's "gelu_fast"), the same
+// pass with the tanh form of tome_common.h: y = x * sigma(2 beta (x + kappa x^3)).
+template <typename TX, int FORM>
+__device__ __forceinline__ void gelu_stream(const TX *__restrict__ x, TX *__restrict__ y, int64_t chunks) {
     constexpr int VEC = 16 / sizeof(TX);
     constexpr int NIT = 4;
     const int64_t base = ((int64_t)blockIdx.x * blockDim.x) * NIT + threadIdx.x;
@@ -1380,10 +1382,25 @@ __global__ __launch_bounds__(256) void k_gelu_erf(const TX *__restrict__ x, TX *
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
             const float v = to_f32(pk.e[e]);
-            pk.e[e] = from_f32<TX>(gelu_erf_value(v, gelu_erf_one_plus(v)));
+            if (FORM == GELU_TANH) {
+                float c, v2;
+                pk.e[e] = from_f32<TX>(gelu_tanh_value(v, gelu_tanh_sigmoid(v, c, v2)));
+            } else {
+                pk.e[e] = from_f32<TX>(gelu_erf_value(v, gelu_erf_one_plus(v)));
+            }
         }
         uint4 o;
         __builtin_memcpy(&o, &pk, 16);
         st16(reinterpret_cast<uint4 *>(y) + q, o);
     }
+}
+
+template <typename TX>
+__global__ __launch_bounds__(256) void k_gelu_erf(const TX *__restrict__ x, TX *__restrict__ y, int64_t chunks) {
+    gelu_stream<TX, GELU_ERF>(x, y, chunks);
+}
+
+template <typename TX>
+__global__ __launch_bounds__(256) void k_gelu_tanh(const TX *__restrict__ x, TX *__restrict__ y, int64_t chunks) {
+    gelu_stream<TX, GELU_TANH>(x, y, chunks);
 }

@@ -102,6 +102,9 @@ class VivitIntermediate(nn.Module):
         super().__init__()
         self.dense = nn.Linear(cfg.hidden_size, cfg.intermediate_size)
         self.dropout = nn.Dropout(0.0)
+        # HF's `intermediate_act_fn` (gelu_fast); no parameters, the state_dict is unchanged.  The same framework kernel
+        # as gelu_fast above; the patched layer's training path recognises the pair by it (tome/_mlp.py mlp_pair)
+        self.intermediate_act_fn = nn.GELU(approximate="tanh")
 
     def forward(self, hidden_states):
         x = hidden_states
@@ -110,7 +113,7 @@ class VivitIntermediate(nn.Module):
             # and activation in one kernel (the separate activation pass over [B, 3137, 3072] disappears)
             y = torch._addmm_activation(self.dense.bias, x.reshape(-1, x.shape[-1]), self.dense.weight.t(), use_gelu=True)
             return self.dropout(y.view(*x.shape[:-1], y.shape[-1]))
-        return self.dropout(gelu_fast(self.dense(x)))
+        return self.dropout(self.intermediate_act_fn(self.dense(x)))
 
 
 class VivitOutput(nn.Module):

@@ -79,6 +79,8 @@ SIGNATURES = {
                                                    vp, i64, f32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp], True),
     "tome_trajectory_mix_backward": (i32, [vp, vp, vp, vp, i32, i64, i64, i64, i64, i64, i64, i64, i64, f32, vp, vp, vp,
                                           i64, i64, vp], True),
+    "tome_gelu_tanh": (i32, [vp, i32, i64, vp, vp], True),
+    "tome_gelu_tanh_backward": (i32, [vp, vp, i32, i64, i64, vp, vp, vp, vp, sz, vp], True),
 }
 SYMBOLS = tuple(SIGNATURES)
 
@@ -1090,15 +1092,27 @@ def gelu_ok(x: torch.Tensor) -> bool:
             and x.numel() > 0 and x.data_ptr() % 16 == 0 and not (torch.is_grad_enabled() and needs_grad(x)))
 
 
-def gelu_erf(x: torch.Tensor, inplace: bool = False) -> torch.Tensor:
-    """nn.GELU() (exact erf form) of a contiguous 16-bit tensor, bit-identical to torch's, as one streaming pass."""
+def _gelu(name: str, x: torch.Tensor, inplace: bool) -> torch.Tensor:
+    """The streaming activation launch `tome_<name>` (gelu_erf / gelu_tanh) of a contiguous 16-bit tensor."""
     if not gelu_ok(x):
-        raise TomeHipError("gelu_erf: contiguous 16-bit device tensor with a multiple of 8 elements required")
+        raise TomeHipError(f"{name}: contiguous 16-bit device tensor with a multiple of 8 elements required")
+    entry = require_symbol(lib(), "tome_" + name)
     y = x if inplace else torch.empty_like(x)
     with _on_device(x.device):
-        rc = lib().tome_gelu_erf(x.data_ptr(), dtype_code(x, "x"), x.numel(), y.data_ptr(), _stream(x.device))
-    _check(rc, "tome_gelu_erf")
+        rc = entry(x.data_ptr(), dtype_code(x, "x"), x.numel(), y.data_ptr(), _stream(x.device))
+    _check(rc, "tome_" + name)
     return y
+
+
+def gelu_erf(x: torch.Tensor, inplace: bool = False) -> torch.Tensor:
+    """nn.GELU() (exact erf form) of a contiguous 16-bit tensor, bit-identical to torch's, as one streaming pass."""
+    return _gelu("gelu_erf", x, inplace)
+
+
+def gelu_tanh(x: torch.Tensor, inplace: bool = False) -> torch.Tensor:
+    """The tanh GELU (HF's gelu_fast, F.gelu(approximate="tanh")) of a contiguous 16-bit tensor in the sigmoid form of
+    include/tome_hip.h: x * sigma(2 beta (x + kappa x^3)), no cancellation on the negative side; one streaming pass."""
+    return _gelu("gelu_tanh", x, inplace)
 
 
 GELU_BWD_MAX_WIDTH = 8192  # csrc/tome_kernels.hip: GELU_BWD_MAX_WIDTH
@@ -1112,6 +1126,12 @@ def mlp_trainable(y: torch.Tensor, fc1, fc2, act) -> bool:
     if not (_stock_module(fc1, torch.nn.Linear) and _stock_module(fc2, torch.nn.Linear)
             and _stock_module(act, torch.nn.GELU) and getattr(act, "approximate", "none") == "none"):
         return False
+    return mlp_tensors_trainable(y, fc1, fc2)
+
+
+def mlp_tensors_trainable(y: torch.Tensor, fc1, fc2) -> bool:
+    """The dtype, device and width conditions of the MLP Function for two nn.Linear layers, whatever the activation's
+    form (mlp_trainable: exact-erf; tome/_mlp.py pair_trainable: ViViT's tanh pair)."""
     C, Hd = fc1.in_features, fc1.out_features
     params = [fc1.weight, fc2.weight] + [b for b in (fc1.bias, fc2.bias) if b is not None]
     return (y.is_cuda and y.dtype in (torch.bfloat16, torch.float16) and y.dim() >= 2 and y.shape[-1] == C
@@ -1120,36 +1140,47 @@ def mlp_trainable(y: torch.Tensor, fc1, fc2, act) -> bool:
             and all(p.dtype == y.dtype and p.device == y.device for p in params))
 
 
-def gelu_erf_backward(h: torch.Tensor, ga: torch.Tensor, *, want_act: bool, want_bias: bool, inplace: bool = True):
-    """tome_gelu_erf_backward for contiguous 16-bit h, ga [..., Hd]: (gh, act, dbias).  gh = ga * gelu'(h), written over
-    ga when `inplace`; act = gelu(h) with the forward's bits when want_act, else None; dbias [Hd] = the column sums of
-    the rounded gh when want_bias, else None (then no workspace is taken).  No CPU path."""
-    require_device(h, "gelu_erf_backward(h)")
+def _gelu_backward(name: str, h: torch.Tensor, ga: torch.Tensor, want_act: bool, want_bias: bool, inplace: bool):
+    """`tome_<name>` (gelu_erf_backward / gelu_tanh_backward): the checks, buffers and workspace the two entries share
+    (the workspace is sized by tome_gelu_erf_backward_workspace_bytes for both)."""
+    require_device(h, f"{name}(h)")
     if h.dtype not in (torch.bfloat16, torch.float16):
-        raise TomeHipError(f"gelu_erf_backward: 16-bit tensors only, got {h.dtype}")
+        raise TomeHipError(f"{name}: 16-bit tensors only, got {h.dtype}")
     Hd = h.shape[-1] if h.dim() >= 2 else 0
     if Hd == 0 or Hd % 8 or Hd > GELU_BWD_MAX_WIDTH or h.numel() == 0:
-        raise TomeHipError(f"gelu_erf_backward: h must be [..., Hd] with Hd % 8 == 0 and Hd <= {GELU_BWD_MAX_WIDTH}, "
+        raise TomeHipError(f"{name}: h must be [..., Hd] with Hd % 8 == 0 and Hd <= {GELU_BWD_MAX_WIDTH}, "
                            f"got {tuple(h.shape)}")
     if ga.shape != h.shape or ga.dtype != h.dtype or ga.device != h.device:
-        raise TomeHipError("gelu_erf_backward: ga must have h's shape, dtype and device")
+        raise TomeHipError(f"{name}: ga must have h's shape, dtype and device")
     if not h.is_contiguous() or not ga.is_contiguous():
-        raise TomeHipError("gelu_erf_backward: contiguous tensors required")
+        raise TomeHipError(f"{name}: contiguous tensors required")
     h, ga = h.detach(), ga.detach()
     rows = h.numel() // Hd
     L = lib()
-    entry = require_symbol(L, "tome_gelu_erf_backward")
+    entry = require_symbol(L, "tome_" + name)
     gh = ga if inplace else torch.empty_like(ga)
     act = torch.empty_like(h) if want_act else None
     dbias = torch.empty(Hd, dtype=h.dtype, device=h.device) if want_bias else None
     with _on_device(h.device):
         stream = _stream(h.device)
         ws = _sized_workspace(L, "tome_gelu_erf_backward_workspace_bytes", (rows, Hd), h.device, stream,
-                              "gelu_erf_backward") if want_bias else None
+                              name) if want_bias else None
         rc = entry(h.data_ptr(), ga.data_ptr(), dtype_code(h, "h"), rows, Hd, gh.data_ptr(), _ptr(act), _ptr(dbias),
                    _ptr(ws), 0 if ws is None else ws.numel(), stream)
-    _check(rc, "tome_gelu_erf_backward")
+    _check(rc, "tome_" + name)
     return gh, act, dbias
+
+
+def gelu_erf_backward(h: torch.Tensor, ga: torch.Tensor, *, want_act: bool, want_bias: bool, inplace: bool = True):
+    """tome_gelu_erf_backward for contiguous 16-bit h, ga [..., Hd]: (gh, act, dbias).  gh = ga * gelu'(h), written over
+    ga when `inplace`; act = gelu(h) with the forward's bits when want_act, else None; dbias [Hd] = the column sums of
+    the rounded gh when want_bias, else None (then no workspace is taken).  No CPU path."""
+    return _gelu_backward("gelu_erf_backward", h, ga, want_act, want_bias, inplace)
+
+
+def gelu_tanh_backward(h: torch.Tensor, ga: torch.Tensor, *, want_act: bool, want_bias: bool, inplace: bool = True):
+    """tome_gelu_tanh_backward: gelu_erf_backward for the tanh form (ViViT's MLP); act has tome_gelu_tanh's bits."""
+    return _gelu_backward("gelu_tanh_backward", h, ga, want_act, want_bias, inplace)
 
 
 def tubelet_rows_ok(x: torch.Tensor, kt: int, kh: int, kw: int) -> bool:

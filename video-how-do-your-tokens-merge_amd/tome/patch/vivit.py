@@ -11,7 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _common as C
-from .. import _abi
+from .. import _abi, _mlp
 from ..merge import HeadMeanKeys
 
 _FUSE_QKV = os.environ.get("TOME_VIVIT_QKV", "1") != "0"  # 0 = three separate query / key / value GEMMs (measurement switch)
@@ -32,6 +32,19 @@ def _layer_forward(self, hidden_states, head_mask=None, output_attentions=False)
     hidden_states, normed = C.merge_then_norm(metric, hidden_states, info, self.layernorm_after,
                                               self.reduction_function, vivit_merge, residual=attention_output,
                                               fold=C.foldable(self.output.dense, eval_mode))
+    # under grad the MLP pair runs as one Function around the two GEMMs (tome/_mlp.py: tome_gelu_tanh forward,
+    # tome_gelu_tanh_backward backward; one hidden tensor saved instead of two); grad mode is tested first, so that
+    # nothing is looked up on the no-grad forward
+    out = None
+    if torch.is_grad_enabled():
+        # output.dense's bias already sits in the residual stream (`fold`: eval, grad enabled, but nothing the merge or
+        # output.dense touches wants a gradient -- intermediate.dense alone trains): finish_linear's to finish, as in
+        # C.mlp_residual
+        folded = info.get("_folded")
+        if folded is None or folded[0] is not hidden_states:
+            out = _mlp.mlp_pair(self.intermediate, self.output, normed)
+    if out is not None:
+        return (C.finish_block(self, hidden_states, out, info),) + rest
     layer_output = self.intermediate(normed)
     if eval_mode:
         layer_output = C.finish_linear(self, hidden_states, layer_output, self.output.dense, info)
