@@ -45,7 +45,7 @@ def unit_roundoff(dtype) -> float:
 
 def expected_form(N: int, Nk: int, items: int, env: Optional[dict] = None, off32: bool = True,
                   sn_ok: bool = True) -> str:
-    """Which kernel prop_attention_impl (csrc/tome_kernels.hip) launches for N queries against Nk keys per item,
+    """Which launch form attn_form (csrc/tome_kernels.hip) gives prop_attention_impl for N queries against Nk keys per item,
     items = B * H * nseg, under the switches in `env`.  off32: the resident kernel's 32-bit token offsets fit (N and
     Nk times the token strides < 2^31); sn_ok: every token stride < 2^22 (the stream kernel's 32-bit tile offsets)."""
     env = env or {}

@@ -187,7 +187,7 @@ def test_weighted_bound_floor_and_terms():
 
 
 def test_expected_form_mirrors_the_dispatcher():
-    """Points of prop_attention_impl's dispatch (csrc/tome_kernels.hip)."""
+    """Points of attn_form's rule (csrc/tome_kernels.hip), the dispatch of prop_attention_impl."""
     f = A.expected_form
     assert f(197, 197, 64 * 12) == "resident" and f(1568, 196, 2 * 12 * 8) == "resident"
     assert f(1, 225, 24) == "wave4" and f(1, 1569, 24) == "wave4"       # Motionformer's class query, > 224 keys

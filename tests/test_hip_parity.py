@@ -726,6 +726,45 @@ def test_fuzz_against_oracle(case):
     assert torch.equal(back.cpu(), torch.from_numpy(oracle.unmerge(plan, host(xo))).to(dtype)), "unmerge"
 
 
+# metric widths: the eight chunk counts (of 64 channels) the unit-vector launch has a fast form for, two it has none
+# for (five and seven chunks), rows that are not whole 16-byte chunks -- and, `strided`, 128 channels at a token
+# stride that is no multiple of 16 bytes
+_WIDTH_FORMS = [(D, False) for D in (64, 128, 192, 256, 384, 512, 768, 1024, 320, 448, 60)] + [(128, True)]
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["fp32", "bf16", "fp16"])
+@pytest.mark.parametrize("D,strided", _WIDTH_FORMS, ids=lambda v: ("strided" if v else "dense") if isinstance(v, bool) else f"D{v}")
+def test_match_at_every_channel_count_form(D, strided, dtype):
+    """Every form of the unit-vector launch of tome_match and tome_match_partition (fast at 1, 2, 3, 4, 6, 8, 12, 16
+    chunks; generic otherwise) gives the oracle's matching bit for bit.  The fuzz above stops at three chunks; a
+    selection that fell through to the generic kernel would still be right, so this pins the answers at every width the
+    selection tells apart, not the speed.  T = 11: T1 = 6, T2 = 5."""
+    tm = _tome()
+    n, T, r = 2, 11, 2
+    full = dev(synth.clustered((n, T, D + 1 if strided else D), 7100 + D), dtype)
+    m_dev = full[:, :, :D]
+    assert not strided or (m_dev.stride(1) * m_dev.element_size()) % 16 != 0
+    m_host = host(m_dev)
+    for cls in (False, True):
+        plan = oracle.match(m_host, r, cls, False)
+        merge, _ = tm.bipartite_soft_matching(m_dev, r, cls)
+        p = merge.plan
+        np.testing.assert_array_equal(p.src_idx.cpu().numpy(), plan.src_idx)
+        np.testing.assert_array_equal(p.dst_idx.cpu().numpy(), plan.dst_idx)
+        np.testing.assert_array_equal(p.unm_idx.cpu().numpy(), plan.unm_idx)
+    # kth with k = 2 reads the first (T // 2) * 2 tokens: sources the even ones, destinations the odd ones -- the
+    # even/odd matching of those tokens with every source merged names the same destinations
+    kth, _ = tm.kth_bipartite_soft_matching(m_dev, 2)
+    m2, _ = tm.bipartite_soft_matching(m_dev[:, :T // 2 * 2], T // 2)
+    cv = closure_vars(m2)
+    by_row = torch.empty(n, T // 2, dtype=torch.int64, device=DEV)
+    by_row.scatter_(1, cv["src_idx"][..., 0], cv["dst_idx"][..., 0])
+    assert torch.equal(kth.plan.dst_idx[..., 0], by_row)
+    even_odd = oracle.match(m_host[:, :T // 2 * 2], T // 2, False, False)
+    np.testing.assert_array_equal(cv["src_idx"].cpu().numpy(), even_odd.src_idx)
+    np.testing.assert_array_equal(cv["dst_idx"].cpu().numpy(), even_odd.dst_idx)
+
+
 @pytest.mark.parametrize("dtype,tol", [(torch.bfloat16, 2 ** -7), (torch.float16, 2 ** -10)])
 @pytest.mark.parametrize("n,T,C,r,cls", [(3, 197, 768, 16, True), (2, 64, 64, 30, False), (4, 392, 1024, 150, False)])
 def test_merge_wavg_ln_fused(n, T, C, r, cls, dtype, tol):

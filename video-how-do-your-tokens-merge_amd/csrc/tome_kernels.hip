@@ -100,6 +100,49 @@ extern "C" int64_t tome_effective_r(int64_t T, int64_t r, int class_token, int d
 }
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// The dtype dispatch of every family: f(Dt<TX>{}) for token dtype code `dtype` (fp32 only where F32), otherwise
+// bad() -- the entry point's own error.  Op<V>: a compile-time int handed to a launch site the same way.
+template <typename T> struct Dt { using type = T; };
+template <int V> using Op = std::integral_constant<int, V>;
+
+template <bool F32, typename F, typename Bad>
+static int dispatch_x(int dtype, F &&f, Bad &&bad) {
+    switch (dtype) {
+    case TOME_F32:
+        if constexpr (F32) return f(Dt<float>{});
+        break;
+    case TOME_BF16: return f(Dt<bf16_t>{});
+    case TOME_F16: return f(Dt<f16_t>{});
+    }
+    return bad();
+}
+
+// ... and f(Dt<TX>{}, Dt<TS>{}) for the (token, size) pairs of the weighted merges: sizes in the token dtype or fp32
+template <bool F32, typename F, typename Bad>
+static int dispatch_xs(int x_dtype, int size_dtype, F &&f, Bad &&bad) {
+    return dispatch_x<F32>(x_dtype, [&](auto tx) {
+        if (size_dtype == TOME_F32) return f(tx, Dt<float>{});
+        if (size_dtype == x_dtype) return f(tx, tx);
+        return bad();
+    }, bad);
+}
+
+// The dtype test of the entries without an fp32 form: 0 for bf16 / f16, otherwise the error "<who>: 16-bit <what> only"
+static int not_16bit(const char *who, int dtype, const char *what = "tokens") {
+    if (dtype == TOME_BF16 || dtype == TOME_F16) return 0;
+    return fail(TOME_EINVAL, "%s: 16-bit %s only", who, what);
+}
+
+// The vector width of the generic row kernels: f(Op<VEC>{}) with VEC = the elements of a 16-byte chunk when rows of C
+// elements are whole chunks and both buffers are 16-byte aligned, otherwise f(Op<1>{})
+template <typename TX, typename F>
+static int with_vec(int64_t C, const void *in, const void *out, F &&f) {
+    constexpr int VEC = 16 / sizeof(TX);
+    if (C % VEC == 0 && aligned16(in) && aligned16(out)) return f(Op<VEC>{});
+    return f(Op<1>{});
+}
 
 // Per-stage timing of tome_match for bench.py's roofline figures: MEASUREMENT BUILD ONLY (-DTOME_PROFILE_HOOKS ->
 // lib/libtome_hip_prof.so, loaded by bench.py's stage-timing leg alone; csrc/build.py).  The product library carries
@@ -178,12 +221,40 @@ extern "C" int tome_diag_clock(double *ghz, double *wave_us, int64_t *waves) {
 }
 #endif
 
-struct MatchWs {
+// What the even/odd matching and the partition matching lay out alike at the head of their workspaces: the unit
+// vectors of the two sets (Na / Nb rows in tiles of TILE_ROWS, nchunk chunks of 64 channels), the row maxima of
+// k_scores_rowmax per j-part and the bad-row flags; the even/odd matching's rank array lies between them.
+struct SetsWs {
     float *unitA, *unitB, *part_max;
     int *part_idx, *rank;
     uint8_t *badA, *badB;
     int ntA, ntB, nchunk;
     int64_t groupA_f4, groupB_f4;  // float4 per group of each unit set
+    size_t bytes;
+};
+
+static SetsWs carve_sets(void *base, int64_t n, int64_t Na, int64_t Nb, int64_t D, bool ranked) {
+    SetsWs w;
+    w.nchunk = (int)((D + 63) / 64);
+    w.ntA = (int)((Na + TILE_ROWS - 1) / TILE_ROWS);
+    w.ntB = (int)((Nb + TILE_ROWS - 1) / TILE_ROWS);
+    w.groupA_f4 = (int64_t)w.ntA * w.nchunk * 512;
+    w.groupB_f4 = (int64_t)w.ntB * w.nchunk * 512;
+    size_t off = 0;
+    char *b = (char *)base;
+    w.unitA = (float *)(b + off); off = align_up(off + 16 * (size_t)(n * w.groupA_f4), 256);
+    w.unitB = (float *)(b + off); off = align_up(off + 16 * (size_t)(n * w.groupB_f4), 256);
+    w.part_max = (float *)(b + off); off = align_up(off + sizeof(float) * (size_t)(n * MAX_WJ * Na), 256);
+    w.part_idx = (int *)(b + off); off = align_up(off + sizeof(int) * (size_t)(n * MAX_WJ * Na), 256);
+    w.rank = nullptr;
+    if (ranked) { w.rank = (int *)(b + off); off = align_up(off + sizeof(int) * (size_t)(n * Na), 256); }
+    w.badA = (uint8_t *)(b + off); off = align_up(off + (size_t)(n * Na), 256);
+    w.badB = (uint8_t *)(b + off); off = align_up(off + (size_t)(n * (Nb > 0 ? Nb : 1)), 256);
+    w.bytes = off;
+    return w;
+}
+
+struct MatchWs : SetsWs {
     // the filter path (tome_match_filter.h; D <= 64): bf16 means in MFMA fragment order, norms, candidate lists
     uint4 *vA, *vB;
     float *normA, *normB, *invB, *node_max;
@@ -191,26 +262,14 @@ struct MatchWs {
     CandEntry *cand;
     uint8_t *cand_n, *tile_flag;
     int T2p;
-    size_t bytes;
 };
 
 static MatchWs carve(void *base, int64_t n, int64_t T, int64_t D) {
     const int64_t T1 = (T + 1) / 2, T2 = T / 2;
     MatchWs w;
-    w.nchunk = (int)((D + 63) / 64);
-    w.ntA = (int)((T1 + TILE_ROWS - 1) / TILE_ROWS);
-    w.ntB = (int)((T2 + TILE_ROWS - 1) / TILE_ROWS);
-    w.groupA_f4 = (int64_t)w.ntA * w.nchunk * 512;
-    w.groupB_f4 = (int64_t)w.ntB * w.nchunk * 512;
-    size_t off = 0;
+    static_cast<SetsWs &>(w) = carve_sets(base, n, T1, T2, D, true);
+    size_t off = w.bytes;
     char *b = (char *)base;
-    w.unitA = (float *)(b + off); off = align_up(off + 16 * (size_t)(n * w.groupA_f4), 256);
-    w.unitB = (float *)(b + off); off = align_up(off + 16 * (size_t)(n * w.groupB_f4), 256);
-    w.part_max = (float *)(b + off); off = align_up(off + sizeof(float) * (size_t)(n * MAX_WJ * T1), 256);
-    w.part_idx = (int *)(b + off); off = align_up(off + sizeof(int) * (size_t)(n * MAX_WJ * T1), 256);
-    w.rank = (int *)(b + off); off = align_up(off + sizeof(int) * (size_t)(n * T1), 256);
-    w.badA = (uint8_t *)(b + off); off = align_up(off + (size_t)(n * T1), 256);
-    w.badB = (uint8_t *)(b + off); off = align_up(off + (size_t)(n * (T2 > 0 ? T2 : 1)), 256);
     w.T2p = w.ntB * TILE_ROWS;
     w.vA = w.vB = nullptr;
     if (w.nchunk == 1) {
@@ -234,7 +293,72 @@ extern "C" size_t tome_match_workspace_bytes(int64_t n, int64_t T, int64_t D) {
     return carve(nullptr, n, T, D).bytes;
 }
 
-static int launch_select(const MatchWs &w, int nparts, bool nan_flags, int64_t n, int64_t T, int64_t re, int class_token,
+// The workspace of the matching entries: at least `need` bytes, 256-byte aligned
+static int check_workspace(const char *who, const void *workspace, size_t workspace_bytes, size_t need) {
+    if (!workspace || workspace_bytes < need)
+        return fail(TOME_EWORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
+    if (((uintptr_t)workspace & 255) != 0) return fail(TOME_EINVAL, "%s: workspace not 256-byte aligned", who);
+    return TOME_OK;
+}
+
+// ... and in front of it the index buffers of an even/odd matching that merges `re` of T tokens: unm_idx may be
+// absent when every even token is a source
+static int check_match_buffers(const char *who, int64_t T, int64_t re, const int64_t *src_idx, const int64_t *dst_idx,
+                               const int64_t *unm_idx, const void *workspace, size_t workspace_bytes, size_t need) {
+    if (!src_idx || !dst_idx || (!unm_idx && (T + 1) / 2 > re)) return fail(TOME_EINVAL, "%s: null index buffer", who);
+    return check_workspace(who, workspace, workspace_bytes, need);
+}
+
+// Can the unit-vector kernels read the rows of a [n, T, D] metric in 16-byte chunks?
+static bool rows_16byte(const void *metric, int dtype, int64_t D, int64_t stride_n, int64_t stride_t) {
+    const size_t es = dtype == TOME_F32 ? 4 : 2;
+    return (D % 8 == 0) && (((uintptr_t)metric) % 16 == 0) && ((stride_n * es) % 16 == 0) && ((stride_t * es) % 16 == 0);
+}
+
+// Stage 1 of both matchings, the unit vectors: rows of whole 16-byte chunks (rows_16byte) whose chunk count of 64
+// channels has an unrolled kernel take it -- fast(Dt<TY>{}, Op<NCH>{}) --, everything else generic(Dt<TY>{}).  The
+// two callbacks launch; `who` names the entry in the error of an unknown dtype.
+template <typename Fast, typename Generic>
+static int launch_unit_rows(const char *who, int dtype, bool rows16, int nchunk, Fast &&fast, Generic &&generic) {
+    return dispatch_x<true>(dtype, [&](auto ty) {
+        switch (rows16 ? nchunk : 0) {
+        case 1: fast(ty, Op<1>{}); break;
+        case 2: fast(ty, Op<2>{}); break;
+        case 3: fast(ty, Op<3>{}); break;
+        case 4: fast(ty, Op<4>{}); break;
+        case 6: fast(ty, Op<6>{}); break;
+        case 8: fast(ty, Op<8>{}); break;
+        case 12: fast(ty, Op<12>{}); break;
+        case 16: fast(ty, Op<16>{}); break;
+        default: generic(ty); break;
+        }
+        return TOME_OK;
+    }, [&] { return fail(TOME_EINVAL, "%s: dtype %d", who, dtype); });
+}
+
+// Stage 2 of both matchings, similarity + row max / argmax of Na rows against Nb: one single-wave workgroup per
+// (group, A tile, j-part); the B tiles are split into *parts parts so that the launch has >= ~6 waves per SIMD (1024
+// SIMDs) whatever the batch (target measured on MI355X)
+static int launch_scores_rowmax(const char *who, const SetsWs &w, int64_t n, int Na, int Nb, int distill_token,
+                                hipStream_t st, int *parts) {
+    const long target_waves = 6144L;
+    int WJ = (int)((target_waves + n * w.ntA - 1) / (n * w.ntA));
+    if (WJ > MAX_WJ) WJ = MAX_WJ;
+    if (WJ > w.ntB) WJ = w.ntB;
+    if (WJ < 1) WJ = 1;
+    *parts = WJ;
+    const int64_t nb2 = ((n + 7) / 8) * 8 * w.ntA * WJ;
+    if (nb2 > 0x7fffffffLL) return fail(TOME_EINVAL, "%s: problem too large", who);
+    auto launch = [&](auto one_chunk) {
+        hipLaunchKernelGGL(k_scores_rowmax<decltype(one_chunk)::value != 0>, dim3((unsigned)nb2), dim3(64), 0, st,
+                           (const f32x4 *)w.unitA, (const f32x4 *)w.unitB, (int)n, Na, Nb, w.nchunk, w.ntA, w.ntB, WJ,
+                           w.groupA_f4, w.groupB_f4, distill_token, w.part_max, w.part_idx, nullptr);
+        return check_launch("k_scores_rowmax");
+    };
+    return w.nchunk == 1 ? launch(Op<1>{}) : launch(Op<0>{});
+}
+
+static int launch_select(const SetsWs &w, int nparts, bool nan_flags, int64_t n, int64_t T, int64_t re, int class_token,
                          int distill_token, int64_t *src_idx, int64_t *dst_idx, int64_t *unm_idx,
                          float *node_max, int32_t *row_map, hipStream_t st) {
     const int T1 = (int)((T + 1) / 2);
@@ -266,20 +390,12 @@ static bool use_filter(const MatchWs &w, int dtype, int64_t n, int64_t D) {
 }
 
 // shared tail of tome_match / tome_match_keys: stages 2 (similarity + row max) and 3 (rank + select)
-static int match_tail(const MatchWs &w, int64_t n, int64_t T, int64_t D, int64_t re, int class_token, int distill_token,
-                      int64_t *src_idx, int64_t *dst_idx, int64_t *unm_idx, float *node_max, int32_t *row_map,
-                      hipStream_t st, bool filtered) {
+static int match_tail(const char *who, const MatchWs &w, int64_t n, int64_t T, int64_t D, int64_t re, int class_token,
+                      int distill_token, int64_t *src_idx, int64_t *dst_idx, int64_t *unm_idx, float *node_max,
+                      int32_t *row_map, hipStream_t st, bool filtered) {
     const int T1 = (int)((T + 1) / 2), T2 = (int)(T / 2);
     const int prof_reps = prof_reps_now();
-    // 2. similarity + row max/argmax: one single-wave workgroup per (group, A tile, j-part); the B tiles are
-    // split into WJ parts so that the launch has >= ~6 waves per SIMD (1024 SIMDs) whatever the batch (target
-    // measured on MI355X)
-    const long target_waves = 6144L;
-    int WJ = (int)((target_waves + n * w.ntA - 1) / (n * w.ntA));
-    if (WJ > MAX_WJ) WJ = MAX_WJ;
-    if (WJ > w.ntB) WJ = w.ntB;
-    if (WJ < 1) WJ = 1;
-    const unsigned nb2 = (unsigned)(((n + 7) / 8) * 8 * w.ntA * WJ);
+    int parts = 1;
     for (int rep = 0; rep < prof_reps; ++rep) {
         if (filtered) {
             // 2a. approximate scores on the bf16 matrix pipe, candidate columns per row (tome_match_filter.h)
@@ -298,31 +414,25 @@ static int match_tail(const MatchWs &w, int64_t n, int64_t T, int64_t D, int64_t
             if (int rc = check_launch("k_exact_rows")) return rc;
             continue;
         }
-        if (w.nchunk == 1)
-            hipLaunchKernelGGL(k_scores_rowmax<true>, dim3(nb2), dim3(64), 0, st, (const f32x4 *)w.unitA,
-                               (const f32x4 *)w.unitB, (int)n, T1, T2, w.nchunk, w.ntA, w.ntB, WJ, w.groupA_f4,
-                               w.groupB_f4, distill_token, w.part_max, w.part_idx, nullptr);
-        else
-            hipLaunchKernelGGL(k_scores_rowmax<false>, dim3(nb2), dim3(64), 0, st, (const f32x4 *)w.unitA,
-                               (const f32x4 *)w.unitB, (int)n, T1, T2, w.nchunk, w.ntA, w.ntB, WJ, w.groupA_f4,
-                               w.groupB_f4, distill_token, w.part_max, w.part_idx, nullptr);
-        if (int rc = check_launch("k_scores_rowmax")) return rc;
+        // 2. similarity + row max/argmax
+        if (int rc = launch_scores_rowmax(who, w, n, T1, T2, distill_token, st, &parts)) return rc;
     }
     prof_mark(2, st);
 
     // 3. rank + select
     int rc = TOME_OK;
-    MatchWs ws = w;
+    SetsWs ws = w;
     if (filtered) {
         ws.part_max = w.node_max;
         ws.part_idx = w.node_idx;
     }
     for (int rep = 0; rep < prof_reps && rc == TOME_OK; ++rep)
-        rc = launch_select(ws, filtered ? 1 : WJ, true, n, T, re, class_token, distill_token, src_idx, dst_idx, unm_idx, node_max, row_map, st);
+        rc = launch_select(ws, parts, true, n, T, re, class_token, distill_token, src_idx, dst_idx, unm_idx, node_max, row_map, st);
     prof_mark(3, st);
     prof_done(rc);
     return rc;
 }
+
 extern "C" int tome_match(const void *metric, int dtype, int64_t n, int64_t T, int64_t D, int64_t stride_n,
                           int64_t stride_t, int64_t r, int class_token, int distill_token, int64_t *src_idx,
                           int64_t *dst_idx, int64_t *unm_idx, float *node_max, int32_t *row_map,
@@ -332,74 +442,41 @@ extern "C" int tome_match(const void *metric, int dtype, int64_t n, int64_t T, i
         return fail(TOME_EINVAL, "tome_match: problem too large");
     const int64_t re = tome_effective_r(T, r, class_token, distill_token);
     if (re <= 0) return TOME_OK;
-    if (!src_idx || !dst_idx || (!unm_idx && (T + 1) / 2 > re))
-        return fail(TOME_EINVAL, "tome_match: null index buffer");
-    if (!workspace || workspace_bytes < tome_match_workspace_bytes(n, T, D))
-        return fail(TOME_EWORKSPACE, "tome_match: workspace %zu < %zu bytes", workspace_bytes,
-                    tome_match_workspace_bytes(n, T, D));
-    if (((uintptr_t)workspace & 255) != 0) return fail(TOME_EINVAL, "tome_match: workspace not 256-byte aligned");
+    if (int rc = check_match_buffers("tome_match", T, re, src_idx, dst_idx, unm_idx, workspace, workspace_bytes,
+                                     tome_match_workspace_bytes(n, T, D)))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
     const MatchWs w = carve(workspace, n, T, D);
     // 1. unit vectors
     prof_mark(0, st);
-    const size_t es = dtype == TOME_F32 ? 4 : 2;
-    const bool fast = (D % 8 == 0) && (((uintptr_t)metric) % 16 == 0) && ((stride_n * es) % 16 == 0) &&
-                      ((stride_t * es) % 16 == 0);
-    const bool filtered = fast && use_filter(w, dtype, n, D);
-    bool launched = false;
+    const bool rows16 = rows_16byte(metric, dtype, D, stride_n, stride_t);
+    const bool filtered = rows16 && use_filter(w, dtype, n, D);
     const int prof_reps = prof_reps_now();
     for (int rep = 0; rep < prof_reps; ++rep) {
-    launched = false;
-    if (filtered) {
-        hipLaunchKernelGGL(k_unit_rows_f<false>, dim3((unsigned)((n * T + 31) / 32)), dim3(256), 0, st,
-                           (const bf16_t *)metric, stride_n, 1, (int64_t)0, (int64_t)0, stride_t, (int)n, 1, (int)T, (int)D,
-                           w.vA, w.vB, w.ntA, w.ntB, w.normA, w.normB, w.invB, w.T2p, w.badA, w.badB);
-        continue;
-    }
-#define UNIT_FAST(TY, NCH)                                                                                    \
-    hipLaunchKernelGGL((k_unit_rows<TY, NCH>), dim3((unsigned)((n * T + 31) / 32)), dim3(256), 0, st,          \
-                       (const TY *)metric, stride_n, stride_t, (int)n, (int)T, (int)D, w.unitA, w.unitB,       \
-                       w.groupA_f4, w.groupB_f4, w.badA, w.badB);                                              \
-    launched = true
-#define UNIT_NCH(TY)                                       \
-    switch (w.nchunk) {                                    \
-    case 1: UNIT_FAST(TY, 1); break;                       \
-    case 2: UNIT_FAST(TY, 2); break;                       \
-    case 3: UNIT_FAST(TY, 3); break;                       \
-    case 4: UNIT_FAST(TY, 4); break;                       \
-    case 6: UNIT_FAST(TY, 6); break;                       \
-    case 8: UNIT_FAST(TY, 8); break;                       \
-    case 12: UNIT_FAST(TY, 12); break;                     \
-    case 16: UNIT_FAST(TY, 16); break;                     \
-    default: break;                                        \
-    }
-#define UNIT_GENERIC(TY)                                                                                       \
-    hipLaunchKernelGGL((k_unit_rows_generic<TY>), dim3((unsigned)((n * T + 255) / 256)), dim3(256), 0, st,      \
-                       (const TY *)metric, stride_n, stride_t, (int)n, (int)T, (int)D, w.nchunk * 64, w.unitA,  \
-                       w.unitB, w.groupA_f4, w.groupB_f4, w.badA, w.badB)
-    switch (dtype) {
-    case TOME_F32:
-        if (fast) { UNIT_NCH(float) }
-        if (!launched) UNIT_GENERIC(float);
-        break;
-    case TOME_BF16:
-        if (fast) { UNIT_NCH(bf16_t) }
-        if (!launched) UNIT_GENERIC(bf16_t);
-        break;
-    case TOME_F16:
-        if (fast) { UNIT_NCH(f16_t) }
-        if (!launched) UNIT_GENERIC(f16_t);
-        break;
-    default: return fail(TOME_EINVAL, "tome_match: dtype %d", dtype);
-    }
-#undef UNIT_FAST
-#undef UNIT_NCH
-#undef UNIT_GENERIC
+        if (filtered) {
+            hipLaunchKernelGGL(k_unit_rows_f<false>, dim3((unsigned)((n * T + 31) / 32)), dim3(256), 0, st,
+                               (const bf16_t *)metric, stride_n, 1, (int64_t)0, (int64_t)0, stride_t, (int)n, 1, (int)T, (int)D,
+                               w.vA, w.vB, w.ntA, w.ntB, w.normA, w.normB, w.invB, w.T2p, w.badA, w.badB);
+            continue;
+        }
+        const int rc = launch_unit_rows("tome_match", dtype, rows16, w.nchunk, [&](auto ty, auto nch) {
+            using TY = typename decltype(ty)::type;
+            hipLaunchKernelGGL((k_unit_rows<TY, decltype(nch)::value>), dim3((unsigned)((n * T + 31) / 32)), dim3(256), 0,
+                               st, (const TY *)metric, stride_n, stride_t, (int)n, (int)T, (int)D, w.unitA, w.unitB,
+                               w.groupA_f4, w.groupB_f4, w.badA, w.badB);
+        }, [&](auto ty) {
+            using TY = typename decltype(ty)::type;
+            hipLaunchKernelGGL((k_unit_rows_generic<TY>), dim3((unsigned)((n * T + 255) / 256)), dim3(256), 0, st,
+                               (const TY *)metric, stride_n, stride_t, (int)n, (int)T, (int)D, w.nchunk * 64, w.unitA,
+                               w.unitB, w.groupA_f4, w.groupB_f4, w.badA, w.badB);
+        });
+        if (rc) return rc;
     }
     if (int rc = check_launch("k_unit_rows")) return rc;
     prof_mark(1, st);
 
-    return match_tail(w, n, T, D, re, class_token, distill_token, src_idx, dst_idx, unm_idx, node_max, row_map, st, filtered);
+    return match_tail("tome_match", w, n, T, D, re, class_token, distill_token, src_idx, dst_idx, unm_idx, node_max,
+                      row_map, st, filtered);
 }
 
 extern "C" int tome_match_keys(const void *keys, int dtype, int64_t n, int64_t H, int64_t T, int64_t D,
@@ -412,7 +489,8 @@ extern "C" int tome_match_keys(const void *keys, int dtype, int64_t n, int64_t H
     if (D != 64) return fail(TOME_EINVAL, "tome_match_keys: head dimension %lld (only 64 is fused)", (long long)D);
     if (n > 0x7fffffff / T) return fail(TOME_EINVAL, "tome_match_keys: problem too large");
     const size_t es = dtype == TOME_F32 ? 4 : 2;
-    if (dtype < TOME_F32 || dtype > TOME_F16) return fail(TOME_EINVAL, "tome_match_keys: dtype %d", dtype);
+    auto bad_dtype = [&] { return fail(TOME_EINVAL, "tome_match_keys: dtype %d", dtype); };
+    if (dtype < TOME_F32 || dtype > TOME_F16) return bad_dtype();
     if (((uintptr_t)keys) % 16 || (stride_n * es) % 16 || (stride_h * es) % 16 || (stride_t * es) % 16 ||
         (stride_inner * es) % 16)
         return fail(TOME_EINVAL, "tome_match_keys: keys must be 16-byte aligned in every stride");
@@ -420,12 +498,9 @@ extern "C" int tome_match_keys(const void *keys, int dtype, int64_t n, int64_t H
                                             (long long)n, (long long)inner);
     const int64_t re = tome_effective_r(T, r, class_token, distill_token);
     if (re <= 0) return TOME_OK;
-    if (!src_idx || !dst_idx || (!unm_idx && (T + 1) / 2 > re))
-        return fail(TOME_EINVAL, "tome_match_keys: null index buffer");
-    if (!workspace || workspace_bytes < tome_match_workspace_bytes(n, T, D))
-        return fail(TOME_EWORKSPACE, "tome_match_keys: workspace %zu < %zu bytes", workspace_bytes,
-                    tome_match_workspace_bytes(n, T, D));
-    if (((uintptr_t)workspace & 255) != 0) return fail(TOME_EINVAL, "tome_match_keys: workspace not 256-byte aligned");
+    if (int rc = check_match_buffers("tome_match_keys", T, re, src_idx, dst_idx, unm_idx, workspace, workspace_bytes,
+                                     tome_match_workspace_bytes(n, T, D)))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
     const MatchWs w = carve(workspace, n, T, D);
     prof_mark(0, st);
@@ -439,27 +514,19 @@ extern "C" int tome_match_keys(const void *keys, int dtype, int64_t n, int64_t H
                                w.normA, w.normB, w.invB, w.T2p, w.badA, w.badB);
             continue;
         }
-        switch (dtype) {
-        case TOME_F32:
-            hipLaunchKernelGGL(k_unit_rows_heads<float>, dim3(nb), dim3(256), 0, st, (const float *)keys, stride_n,
-                               (int)inner, stride_inner, stride_h, stride_t, (int)n, (int)H, (int)T, w.unitA, w.unitB, w.groupA_f4, w.groupB_f4,
-                               w.badA, w.badB);
-            break;
-        case TOME_BF16:
-            hipLaunchKernelGGL(k_unit_rows_heads<bf16_t>, dim3(nb), dim3(256), 0, st, (const bf16_t *)keys, stride_n,
-                               (int)inner, stride_inner, stride_h, stride_t, (int)n, (int)H, (int)T, w.unitA, w.unitB, w.groupA_f4, w.groupB_f4,
-                               w.badA, w.badB);
-            break;
-        default:
-            hipLaunchKernelGGL(k_unit_rows_heads<f16_t>, dim3(nb), dim3(256), 0, st, (const f16_t *)keys, stride_n,
-                               (int)inner, stride_inner, stride_h, stride_t, (int)n, (int)H, (int)T, w.unitA, w.unitB, w.groupA_f4, w.groupB_f4,
-                               w.badA, w.badB);
-            break;
-        }
+        const int rc = dispatch_x<true>(dtype, [&](auto ty) {
+            using TY = typename decltype(ty)::type;
+            hipLaunchKernelGGL(k_unit_rows_heads<TY>, dim3(nb), dim3(256), 0, st, (const TY *)keys, stride_n, (int)inner,
+                               stride_inner, stride_h, stride_t, (int)n, (int)H, (int)T, w.unitA, w.unitB, w.groupA_f4,
+                               w.groupB_f4, w.badA, w.badB);
+            return TOME_OK;
+        }, bad_dtype);
+        if (rc) return rc;
     }
     if (int rc = check_launch("k_unit_rows_heads")) return rc;
     prof_mark(1, st);
-    return match_tail(w, n, T, D, re, class_token, distill_token, src_idx, dst_idx, unm_idx, node_max, row_map, st, filtered);
+    return match_tail("tome_match_keys", w, n, T, D, re, class_token, distill_token, src_idx, dst_idx, unm_idx, node_max,
+                      row_map, st, filtered);
 }
 
 extern "C" int tome_match_scores(const float *scores, int64_t n, int64_t T, int64_t r, int class_token,
@@ -469,11 +536,9 @@ extern "C" int tome_match_scores(const float *scores, int64_t n, int64_t T, int6
     if (!scores || n <= 0 || T <= 0) return fail(TOME_EINVAL, "tome_match_scores: bad shape/pointer");
     const int64_t re = tome_effective_r(T, r, class_token, distill_token);
     if (re <= 0) return TOME_OK;
-    if (!src_idx || !dst_idx || (!unm_idx && (T + 1) / 2 > re))
-        return fail(TOME_EINVAL, "tome_match_scores: null index buffer");
-    if (!workspace || workspace_bytes < tome_match_workspace_bytes(n, T, 1))
-        return fail(TOME_EWORKSPACE, "tome_match_scores: workspace too small");
-    if (((uintptr_t)workspace & 255) != 0) return fail(TOME_EINVAL, "tome_match_scores: workspace alignment");
+    if (int rc = check_match_buffers("tome_match_scores", T, re, src_idx, dst_idx, unm_idx, workspace, workspace_bytes,
+                                     tome_match_workspace_bytes(n, T, 1)))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
     const MatchWs w = carve(workspace, n, T, 1);
     const int T1 = (int)((T + 1) / 2), T2 = (int)(T / 2);
@@ -495,36 +560,7 @@ extern "C" int tome_edge_keep(const float *node_max, const int64_t *src_idx, int
     return check_launch("k_edge_keep");
 }
 
-static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 static TokLayout contiguous_layout(int64_t T, int64_t C) { return TokLayout{0, T * C, 0, C, 1}; }
-
-// The dtype dispatch of the merge family: f(Dt<TX>{}) for token dtype code `dtype` (fp32 only where F32), otherwise
-// bad() -- the entry point's own error.
-template <typename T> struct Dt { using type = T; };
-template <int V> using Op = std::integral_constant<int, V>;
-
-template <bool F32, typename F, typename Bad>
-static int dispatch_x(int dtype, F &&f, Bad &&bad) {
-    switch (dtype) {
-    case TOME_F32:
-        if constexpr (F32) return f(Dt<float>{});
-        break;
-    case TOME_BF16: return f(Dt<bf16_t>{});
-    case TOME_F16: return f(Dt<f16_t>{});
-    }
-    return bad();
-}
-
-// ... and f(Dt<TX>{}, Dt<TS>{}) for the (token, size) pairs of the weighted merges: sizes in the token dtype or fp32
-template <bool F32, typename F, typename Bad>
-static int dispatch_xs(int x_dtype, int size_dtype, F &&f, Bad &&bad) {
-    return dispatch_x<F32>(x_dtype, [&](auto tx) {
-        if (size_dtype == TOME_F32) return f(tx, Dt<float>{});
-        if (size_dtype == x_dtype) return f(tx, tx);
-        return bad();
-    }, bad);
-}
 
 // XCD-aware numbering of the workgroups (MergeSched, csrc/tome_merge.h) for the launches where many destinations
 // receive sources (8 r >= T: TimeSformer / Motionformer frame groups at r = 32, late layers at r = 16) -- there the
@@ -716,32 +752,6 @@ static inline int ln_rows_per_wave(int64_t cpr, int nit) {
     return R > FAST_MAXR ? FAST_MAXR : (int)R;
 }
 
-// The dtype test of the entries without an fp32 form: 0 for bf16 / f16, otherwise the error "<who>: 16-bit <what> only"
-static int not_16bit(const char *who, int dtype, const char *what = "tokens") {
-    if (dtype == TOME_BF16 || dtype == TOME_F16) return 0;
-    return fail(TOME_EINVAL, "%s: 16-bit %s only", who, what);
-}
-
-static int add_layernorm_impl(const void *x, const void *addend, int dtype, int64_t rows, int64_t C,
-                              const void *ln_weight, const void *ln_bias, float eps, void *x_out, void *y_out,
-                              int64_t y_group, tome_stream_t stream);
-
-extern "C" int tome_add_layernorm(const void *x, const void *addend, int dtype, int64_t rows, int64_t C,
-                                  const void *ln_weight, const void *ln_bias, float eps, void *x_out, void *y_out,
-                                  tome_stream_t stream) {
-    return add_layernorm_impl(x, addend, dtype, rows, C, ln_weight, ln_bias, eps, x_out, y_out, 0, stream);
-}
-
-extern "C" int tome_add_layernorm_skip_first(const void *x, const void *addend, int dtype, int64_t groups,
-                                             int64_t group_rows, int64_t C, const void *ln_weight,
-                                             const void *ln_bias, float eps, void *x_out, void *y_out,
-                                             tome_stream_t stream) {
-    if (groups <= 0 || group_rows < 2 || group_rows > 0x7fffffffLL)
-        return fail(TOME_EINVAL, "tome_add_layernorm_skip_first: groups of at least two rows required");
-    return add_layernorm_impl(x, addend, dtype, groups * group_rows, C, ln_weight, ln_bias, eps, x_out, y_out, group_rows,
-                              stream);
-}
-
 static int add_layernorm_impl(const void *x, const void *addend, int dtype, int64_t rows, int64_t C,
                               const void *ln_weight, const void *ln_bias, float eps, void *x_out, void *y_out,
                               int64_t y_group, tome_stream_t stream) {
@@ -769,6 +779,22 @@ static int add_layernorm_impl(const void *x, const void *addend, int dtype, int6
                                rows, (int)C, R, (int)cpr, ln, (TX *)x_out);
         return check_launch("k_add_ln_rows");
     }, [&] { return not_16bit("tome_add_layernorm", dtype); });
+}
+
+extern "C" int tome_add_layernorm(const void *x, const void *addend, int dtype, int64_t rows, int64_t C,
+                                  const void *ln_weight, const void *ln_bias, float eps, void *x_out, void *y_out,
+                                  tome_stream_t stream) {
+    return add_layernorm_impl(x, addend, dtype, rows, C, ln_weight, ln_bias, eps, x_out, y_out, 0, stream);
+}
+
+extern "C" int tome_add_layernorm_skip_first(const void *x, const void *addend, int dtype, int64_t groups,
+                                             int64_t group_rows, int64_t C, const void *ln_weight,
+                                             const void *ln_bias, float eps, void *x_out, void *y_out,
+                                             tome_stream_t stream) {
+    if (groups <= 0 || group_rows < 2 || group_rows > 0x7fffffffLL)
+        return fail(TOME_EINVAL, "tome_add_layernorm_skip_first: groups of at least two rows required");
+    return add_layernorm_impl(x, addend, dtype, groups * group_rows, C, ln_weight, ln_bias, eps, x_out, y_out, group_rows,
+                              stream);
 }
 
 extern "C" int tome_add_layernorm_regrouped(const void *x, const void *addend, int dtype, int64_t B, int64_t F, int64_t P,
@@ -957,32 +983,47 @@ extern "C" int tome_drop_regrouped(const void *x, int dtype, int64_t B, int64_t 
     }, [&] { return fail(TOME_EINVAL, "tome_drop_regrouped: dtype %d", dtype); });
 }
 
-static int prop_attention_impl(const void *q, const void *k, const void *v, int dtype, int64_t B, int64_t H,
-                               int64_t N, int64_t Nk, int64_t D, const int64_t *q_strides,
-                               const int64_t *k_strides, const int64_t *v_strides, const float *log_size,
-                               int64_t log_size_stride, int bias_skip, float scale, void *out,
-                               const int64_t *out_strides, int64_t nseg, const int64_t *seg_strides,
-                               tome_stream_t stream);
-
-extern "C" int tome_prop_attention(const void *q, const void *k, const void *v, int dtype, int64_t B, int64_t H,
-                                   int64_t N, int64_t Nk, int64_t D, const int64_t *q_strides,
-                                   const int64_t *k_strides, const int64_t *v_strides, const float *log_size,
-                                   int64_t log_size_stride, int bias_skip, float scale, void *out,
-                                   const int64_t *out_strides, tome_stream_t stream) {
-    return prop_attention_impl(q, k, v, dtype, B, H, N, Nk, D, q_strides, k_strides, v_strides, log_size,
-                               log_size_stride, bias_skip, scale, out, out_strides, 1, nullptr, stream);
+// The dtype x bias dispatch of the attention kernels, forward and backward: f(Dt<TX>{}, Op<BIAS>{}) for a 16-bit
+// dtype, BIAS = 1 with a per-key bias; otherwise bad()
+template <typename F, typename Bad>
+static int dispatch_attn(int dtype, bool bias, F &&f, Bad &&bad) {
+    return dispatch_x<false>(dtype, [&](auto tx) { return bias ? f(tx, Op<1>{}) : f(tx, Op<0>{}); }, bad);
 }
 
-extern "C" int tome_prop_attention_segments(const void *q, const void *k, const void *v, int dtype, int64_t B,
-                                            int64_t H, int64_t N, int64_t Nk, int64_t D, const int64_t *q_strides,
-                                            const int64_t *k_strides, const int64_t *v_strides, const float *log_size,
-                                            int64_t log_size_stride, float scale, void *out,
-                                            const int64_t *out_strides, int64_t nseg, const int64_t *seg_strides,
-                                            tome_stream_t stream) {
-    if (nseg < 1 || !seg_strides || !out_strides)
-        return fail(TOME_EINVAL, "tome_prop_attention_segments: nseg >= 1, segment and out strides required");
-    return prop_attention_impl(q, k, v, dtype, B, H, N, Nk, D, q_strides, k_strides, v_strides, log_size,
-                               log_size_stride, 0, scale, out, out_strides, nseg, seg_strides, stream);
+// The launch form of one forward attention call.  (tests/attn_oracle.expected_form mirrors this rule.)  The three
+// TOME_ATTN_* variables are measurement switches, read per call and not cached: the tests force each form on small
+// inputs.
+enum AttnKernel { ATTN_RESIDENT, ATTN_STREAM, ATTN_PLAIN };
+struct AttnForm { AttnKernel kernel; int waves; };  // waves: per workgroup of the plain kernel, 4 or 8
+static AttnForm attn_form(const AttnArgs &a, int64_t B, int64_t H, int64_t N, int64_t Nk, int64_t nseg) {
+    const char *re = getenv("TOME_ATTN_RESIDENT"), *we = getenv("TOME_ATTN_WAVES"), *se = getenv("TOME_ATTN_STREAM");
+    // Short key sequences (TimeSformer's 1 + p <= 197 tokens per frame, Motionformer's <= 196 keys per frame segment):
+    // the whole K / V of a (batch, head, segment) resident in LDS, one workgroup per item, no per-tile barrier
+    // (tome_attn_resident.h).  TOME_ATTN_RESIDENT=0 keeps the streaming kernels.
+    // (the kernel addresses the tokens of one (batch, head) slice with 32-bit element offsets)
+    const bool off32 = N * a.q_sn < (1ll << 31) && Nk * a.k_sn < (1ll << 31) && Nk * a.v_sn < (1ll << 31) &&
+                       N * a.o_sn < (1ll << 31);
+    if (Nk <= RES_ROWS && off32 && !(re && re[0] == '0')) return AttnForm{ATTN_RESIDENT, 0};
+    // queries per workgroup: 256 (eight waves share every staged K/V tile: staging costs 18 % with four) unless the
+    // sequence is short.  (Measured: 5, 6 or 7 waves per workgroup, chosen to leave no part-empty last block, are
+    // 10-30 % slower per block than eight -- uneven staging passes and SIMD load -- and lose more than they save.)
+    const int waves_set = we ? atoi(we) : 0;
+    const int waves_env = (waves_set == 4 || waves_set == 8) ? waves_set : 0;
+    // (the pipelined plain kernel keeps two waves per SIMD either way: two 4-wave workgroups share a CU.  They lose
+    // 3-5 % on long launches -- every tile is staged twice per CU -- and win 7-13 % when the launch is short: fewer
+    // than four rounds of 8-wave workgroups over the 256 CUs)
+    const int waves = waves_env ? waves_env : ((N > 128 && B * H * nseg * ((N + 255) / 256) >= 1024) ? 8 : 4);
+    // Eight-wave launches with at least two key tiles run as persistent workgroups, one per CU, that keep the K/V
+    // pipeline going across query blocks (tome_attn_stream.h); TOME_ATTN_STREAM=0 keeps one workgroup per block
+    const int64_t sn_max = 1 << 22;  // (the stream kernel keeps token offsets inside a tile / query block in 32 bits)
+    const bool sn_ok = a.q_sn < sn_max && a.k_sn < sn_max && a.v_sn < sn_max && a.o_sn < sn_max;
+    // (Round 3: also for launches the rule above gives four waves, as long as a block has work for more than four --
+    // 8 x 12 x 1568: 597 -> 650 TFLOP/s, with the per-key bias 476 -> 537; 64 x 12 x 197: 242 -> 280 / 199 -> 240;
+    // level at 16 x 12 x 197 and below, where the launch is the cost; the 4-wave persistent form was built and
+    // measured too: 17-20 % slower than this one at 197 .. 1568 tokens, not kept)
+    const bool stream_ok = Nk > ATT_BN && sn_ok && !(se && se[0] == '0');
+    if (stream_ok && (waves == 8 || (!waves_env && N > 128))) return AttnForm{ATTN_STREAM, waves};
+    return AttnForm{ATTN_PLAIN, waves};
 }
 
 static int prop_attention_impl(const void *q, const void *k, const void *v, int dtype, int64_t B, int64_t H,
@@ -994,7 +1035,8 @@ static int prop_attention_impl(const void *q, const void *k, const void *v, int 
     if (!q || !k || !v || !out || !q_strides || !k_strides || !v_strides || B <= 0 || H <= 0 || N <= 0 || Nk <= 0)
         return fail(TOME_EINVAL, "tome_prop_attention: bad shape/pointer");
     if (D != ATT_D) return fail(TOME_EINVAL, "tome_prop_attention: head dim %lld (only 64)", (long long)D);
-    if (dtype != TOME_BF16 && dtype != TOME_F16) return fail(TOME_EINVAL, "tome_prop_attention: 16-bit q/k/v only");
+    auto bad_dtype = [] { return fail(TOME_EINVAL, "tome_prop_attention: 16-bit q/k/v only"); };
+    if (dtype != TOME_BF16 && dtype != TOME_F16) return bad_dtype();
     if (bias_skip != 0 && bias_skip != 1) return fail(TOME_EINVAL, "tome_prop_attention: bias_skip %d", bias_skip);
     if (bias_skip && N != Nk) return fail(TOME_EINVAL, "tome_prop_attention: bias_skip needs as many keys as queries");
     if (B * H * nseg > 0x7fffffffLL / 64 || N > 0x7fffffffLL / 4 || Nk > 0x7fffffffLL / 4)
@@ -1028,58 +1070,20 @@ static int prop_attention_impl(const void *q, const void *k, const void *v, int 
         a.k_seg = seg_strides[0]; a.v_seg = seg_strides[1]; a.o_seg = seg_strides[2]; a.ls_seg = seg_strides[3];
     }
     hipStream_t st = (hipStream_t)stream;
-    // Short key sequences (TimeSformer's 1 + p <= 197 tokens per frame, Motionformer's <= 196 keys per frame segment):
-    // the whole K / V of a (batch, head, segment) resident in LDS, one workgroup per item, no per-tile barrier
-    // (tome_attn_resident.h).  TOME_ATTN_RESIDENT=0 keeps the streaming kernels (measurement switch, read per call).
-    {
-        const char *re = getenv("TOME_ATTN_RESIDENT");
-        // (the kernel addresses the tokens of one (batch, head) slice with 32-bit element offsets)
-        const bool off32 = N * a.q_sn < (1ll << 31) && Nk * a.k_sn < (1ll << 31) && Nk * a.v_sn < (1ll << 31) &&
-                           N * a.o_sn < (1ll << 31);
-        if (Nk <= RES_ROWS && off32 && !(re && re[0] == '0')) {
-            const int64_t items = (B * H + 7) / 8 * 8 * nseg;
-            if (items > 0x7fffffffLL) return fail(TOME_EINVAL, "tome_prop_attention: grid too large");
-            const dim3 rgrid((unsigned)items);
-            if (dtype == TOME_BF16) {
-                if (log_size) hipLaunchKernelGGL((k_resident_attention<bf16_t, true>), rgrid, dim3(512), 0, st, a);
-                else hipLaunchKernelGGL((k_resident_attention<bf16_t, false>), rgrid, dim3(512), 0, st, a);
-            } else {
-                if (log_size) hipLaunchKernelGGL((k_resident_attention<f16_t, true>), rgrid, dim3(512), 0, st, a);
-                else hipLaunchKernelGGL((k_resident_attention<f16_t, false>), rgrid, dim3(512), 0, st, a);
-            }
+    const AttnForm form = attn_form(a, B, H, N, Nk, nseg);
+    if (form.kernel == ATTN_RESIDENT) {
+        const int64_t items = (B * H + 7) / 8 * 8 * nseg;
+        if (items > 0x7fffffffLL) return fail(TOME_EINVAL, "tome_prop_attention: grid too large");
+        return dispatch_attn(dtype, log_size != nullptr, [&](auto tx, auto bias) {
+            hipLaunchKernelGGL((k_resident_attention<typename decltype(tx)::type, decltype(bias)::value != 0>),
+                               dim3((unsigned)items), dim3(512), 0, st, a);
             return check_launch("k_resident_attention");
-        }
+        }, bad_dtype);
     }
-    // queries per workgroup: 256 (eight waves share every staged K/V tile: staging costs 18 % with four) unless the
-    // sequence is short.  (Measured: 5, 6 or 7 waves per workgroup, chosen to leave no part-empty last block, are
-    // 10-30 % slower per block than eight -- uneven staging passes and SIMD load -- and lose more than they save.)
-    // (read per call, not cached: the tests force each workgroup shape on small inputs)
-    const int waves_env = [] {
-        const char *e = getenv("TOME_ATTN_WAVES");
-        int v = e ? atoi(e) : 0;
-        return (v == 4 || v == 8) ? v : 0;
-    }();
-    // (the pipelined plain kernel keeps two waves per SIMD either way: two 4-wave workgroups share a CU.  They lose
-    // 3-5 % on long launches -- every tile is staged twice per CU -- and win 7-13 % when the launch is short: fewer
-    // than four rounds of 8-wave workgroups over the 256 CUs)
-    const int waves = waves_env ? waves_env : ((N > 128 && B * H * nseg * ((N + 255) / 256) >= 1024) ? 8 : 4);
-    const int64_t qblocks = (N + 32 * waves - 1) / (32 * waves);
     const int64_t bh8 = (B * H * nseg + 7) / 8 * 8;
+    const int64_t qblocks = (N + 32 * form.waves - 1) / (32 * form.waves);
     if (bh8 * qblocks > 0x7fffffffLL) return fail(TOME_EINVAL, "tome_prop_attention: grid too large");
-    const dim3 grid((unsigned)(bh8 * qblocks));
-    // Eight-wave launches with at least two key tiles run as persistent workgroups, one per CU, that keep the K/V
-    // pipeline going across query blocks (tome_attn_stream.h); TOME_ATTN_STREAM=0 keeps one workgroup per block
-    // (measurement switch, read per call)
-    const char *se = getenv("TOME_ATTN_STREAM");
-    const int64_t sn_max = 1 << 22;  // (the stream kernel keeps token offsets inside a tile / query block in 32 bits)
-    const bool sn_ok = a.q_sn < sn_max && a.k_sn < sn_max && a.v_sn < sn_max && a.o_sn < sn_max;
-    // (Round 3: also for launches the rule above gives four waves, as long as a block has work for more than four --
-    // 8 x 12 x 1568: 597 -> 650 TFLOP/s, with the per-key bias 476 -> 537; 64 x 12 x 197: 242 -> 280 / 199 -> 240;
-    // level at 16 x 12 x 197 and below, where the launch is the cost; the 4-wave persistent form was built and
-    // measured too: 17-20 % slower than this one at 197 .. 1568 tokens, not kept)
-    const bool stream_ok = Nk > ATT_BN && sn_ok && !(se && se[0] == '0');
-    if (stream_ok && (waves == 8 || (!waves_env && N > 128))) {
-        const int64_t qblocks = (N + 255) / 256;
+    if (form.kernel == ATTN_STREAM) {
         static const int cus = [] {
             int dev = 0, n = 0;
             if (hipGetDevice(&dev) != hipSuccess ||
@@ -1087,27 +1091,43 @@ static int prop_attention_impl(const void *q, const void *k, const void *v, int 
                 n = 256;
             return n / 8 * 8;
         }();
-        const int nitems = (int)(bh8 * qblocks);
+        const int nitems = (int)(bh8 * ((N + 255) / 256));
         const dim3 pgrid((unsigned)(nitems < cus ? nitems : cus));
-        if (dtype == TOME_BF16) {
-            if (log_size) hipLaunchKernelGGL((k_prop_attention_stream<bf16_t, true>), pgrid, dim3(512), 0, st, a, nitems);
-            else hipLaunchKernelGGL((k_prop_attention_stream<bf16_t, false>), pgrid, dim3(512), 0, st, a, nitems);
-        } else {
-            if (log_size) hipLaunchKernelGGL((k_prop_attention_stream<f16_t, true>), pgrid, dim3(512), 0, st, a, nitems);
-            else hipLaunchKernelGGL((k_prop_attention_stream<f16_t, false>), pgrid, dim3(512), 0, st, a, nitems);
-        }
-        return check_launch("k_prop_attention_stream");
+        return dispatch_attn(dtype, log_size != nullptr, [&](auto tx, auto bias) {
+            hipLaunchKernelGGL((k_prop_attention_stream<typename decltype(tx)::type, decltype(bias)::value != 0>), pgrid,
+                               dim3(512), 0, st, a, nitems);
+            return check_launch("k_prop_attention_stream");
+        }, bad_dtype);
     }
-#define ATT_LAUNCH(TX, BI)                                                                        \
-    if (waves == 8) hipLaunchKernelGGL((k_prop_attention<TX, 8, BI>), grid, dim3(512), 0, st, a); \
-    else hipLaunchKernelGGL((k_prop_attention<TX, 4, BI>), grid, dim3(256), 0, st, a);
-    if (dtype == TOME_BF16) {
-        if (log_size) { ATT_LAUNCH(bf16_t, true) } else { ATT_LAUNCH(bf16_t, false) }
-    } else {
-        if (log_size) { ATT_LAUNCH(f16_t, true) } else { ATT_LAUNCH(f16_t, false) }
-    }
-#undef ATT_LAUNCH
-    return check_launch("k_prop_attention");
+    const dim3 grid((unsigned)(bh8 * qblocks));
+    return dispatch_attn(dtype, log_size != nullptr, [&](auto tx, auto bias) {
+        using TX = typename decltype(tx)::type;
+        constexpr bool BIAS = decltype(bias)::value != 0;
+        if (form.waves == 8) hipLaunchKernelGGL((k_prop_attention<TX, 8, BIAS>), grid, dim3(512), 0, st, a);
+        else hipLaunchKernelGGL((k_prop_attention<TX, 4, BIAS>), grid, dim3(256), 0, st, a);
+        return check_launch("k_prop_attention");
+    }, bad_dtype);
+}
+
+extern "C" int tome_prop_attention(const void *q, const void *k, const void *v, int dtype, int64_t B, int64_t H,
+                                   int64_t N, int64_t Nk, int64_t D, const int64_t *q_strides,
+                                   const int64_t *k_strides, const int64_t *v_strides, const float *log_size,
+                                   int64_t log_size_stride, int bias_skip, float scale, void *out,
+                                   const int64_t *out_strides, tome_stream_t stream) {
+    return prop_attention_impl(q, k, v, dtype, B, H, N, Nk, D, q_strides, k_strides, v_strides, log_size,
+                               log_size_stride, bias_skip, scale, out, out_strides, 1, nullptr, stream);
+}
+
+extern "C" int tome_prop_attention_segments(const void *q, const void *k, const void *v, int dtype, int64_t B,
+                                            int64_t H, int64_t N, int64_t Nk, int64_t D, const int64_t *q_strides,
+                                            const int64_t *k_strides, const int64_t *v_strides, const float *log_size,
+                                            int64_t log_size_stride, float scale, void *out,
+                                            const int64_t *out_strides, int64_t nseg, const int64_t *seg_strides,
+                                            tome_stream_t stream) {
+    if (nseg < 1 || !seg_strides || !out_strides)
+        return fail(TOME_EINVAL, "tome_prop_attention_segments: nseg >= 1, segment and out strides required");
+    return prop_attention_impl(q, k, v, dtype, B, H, N, Nk, D, q_strides, k_strides, v_strides, log_size,
+                               log_size_stride, 0, scale, out, out_strides, nseg, seg_strides, stream);
 }
 
 #ifdef ATT_DIAG
@@ -1236,9 +1256,8 @@ static int attn_backward_impl(const char *fn, const void *q, const void *k, cons
         hipLaunchKernelGGL((k_attn_bwd_dkv<TX, BIAS, SEG>), kgrid, block, 0, st, a);
         return check_launch("k_attn_bwd_dkv");
     };
-    return dispatch_x<false>(dtype, [&](auto tx) {
-        if (seg) return log_size ? go(tx, AttInt<1>{}, AttInt<1>{}) : go(tx, AttInt<0>{}, AttInt<1>{});
-        return log_size ? go(tx, AttInt<1>{}, AttInt<0>{}) : go(tx, AttInt<0>{}, AttInt<0>{});
+    return dispatch_attn(dtype, log_size != nullptr, [&](auto tx, auto bias) {
+        return seg ? go(tx, bias, Op<1>{}) : go(tx, bias, Op<0>{});
     }, [&] { return not_16bit(fn, dtype, "q/k/v"); });
 }
 
@@ -1457,30 +1476,34 @@ static int gelu_backward_impl(const char *who, const void *h, const void *ga, in
     hipStream_t st = (hipStream_t)stream;
     return dispatch_x<false>(dtype, [&](auto tx) {
         using TX = typename decltype(tx)::type;
+        // k_gelu_bwd<TX, column slots, with the bias gradient, with the activation, FORM>
+        auto with_act = [&](auto launch) { return act ? launch(Op<1>{}) : launch(Op<0>{}); };
         if (!dbias) {  // flat: rows of 256 chunks, four per lane, as k_gelu_erf
             const int64_t blocks = (chunks + 1023) / 1024;
-#define GELU_BWD_FLAT(ACT)                                                                                             \
-    hipLaunchKernelGGL((k_gelu_bwd<TX, 1, false, ACT, FORM>), dim3((unsigned)blocks), dim3(256), 0, st,                \
-                       (const TX *)h, (const TX *)ga, chunks, 256, 1, 1, (TX *)gh, (TX *)act, (float *)nullptr)
-            if (act) GELU_BWD_FLAT(true); else GELU_BWD_FLAT(false);
-#undef GELU_BWD_FLAT
-            return check_launch("k_gelu_bwd");
+            return with_act([&](auto a) {
+                hipLaunchKernelGGL((k_gelu_bwd<TX, 1, false, decltype(a)::value != 0, FORM>), dim3((unsigned)blocks),
+                                   dim3(256), 0, st, (const TX *)h, (const TX *)ga, chunks, 256, 1, 1, (TX *)gh, (TX *)act,
+                                   (float *)nullptr);
+                return check_launch("k_gelu_bwd");
+            });
         }
         const GeluBwdForm f = gelu_bwd_form(rows, width);
-#define GELU_BWD_LAUNCH_(SLOTS, ACT)                                                                                   \
-    hipLaunchKernelGGL((k_gelu_bwd<TX, SLOTS, true, ACT, FORM>), dim3((unsigned)f.parts), dim3(256), 0, st,            \
-                       (const TX *)h, (const TX *)ga, chunks, (int)cpr, f.RP, (int)f.spw, (TX *)gh, (TX *)act,         \
-                       (float *)workspace)
-#define GELU_BWD_LAUNCH(SLOTS) do { if (act) GELU_BWD_LAUNCH_(SLOTS, true); else GELU_BWD_LAUNCH_(SLOTS, false); } while (0)
+        auto launch = [&](auto slots) {
+            return with_act([&](auto a) {
+                hipLaunchKernelGGL((k_gelu_bwd<TX, decltype(slots)::value, true, decltype(a)::value != 0, FORM>),
+                                   dim3((unsigned)f.parts), dim3(256), 0, st, (const TX *)h, (const TX *)ga, chunks, (int)cpr,
+                                   f.RP, (int)f.spw, (TX *)gh, (TX *)act, (float *)workspace);
+                return check_launch("k_gelu_bwd");
+            });
+        };
+        int rc;
         switch (f.S) {
-        case 1: GELU_BWD_LAUNCH(1); break;
-        case 2: GELU_BWD_LAUNCH(2); break;
-        case 3: GELU_BWD_LAUNCH(3); break;
-        default: GELU_BWD_LAUNCH(4); break;
+        case 1: rc = launch(Op<1>{}); break;
+        case 2: rc = launch(Op<2>{}); break;
+        case 3: rc = launch(Op<3>{}); break;
+        default: rc = launch(Op<4>{}); break;
         }
-#undef GELU_BWD_LAUNCH_
-#undef GELU_BWD_LAUNCH
-        if (int rc = check_launch("k_gelu_bwd")) return rc;
+        if (rc) return rc;
         return launch_param_grad<TX>(workspace, f.parts, width, width, dbias, nullptr, st);
     }, [&] { return not_16bit(who, dtype, "tensors"); });
 }
@@ -1556,16 +1579,13 @@ extern "C" int tome_source_init(int64_t n, int64_t T, int64_t r, int distill_tok
 template <typename TX>
 static int launch_unmerge(const void *x, int64_t n, int64_t T, int64_t C, int64_t r, const int64_t *src,
                           const int64_t *dst, const int64_t *unm, void *out, hipStream_t st) {
-    constexpr int VEC = 16 / sizeof(TX);
     const int64_t rows = n * (T - r);
     const unsigned nb = (unsigned)((rows + 3) / 4);
-    if ((C % VEC == 0) && aligned16(x) && aligned16(out))
-        hipLaunchKernelGGL((k_unmerge_rows<TX, VEC>), dim3(nb), dim3(256), 0, st, (const TX *)x, (int)n, (int)T,
-                           (int)C, (int)r, src, dst, unm, (TX *)out);
-    else
-        hipLaunchKernelGGL((k_unmerge_rows<TX, 1>), dim3(nb), dim3(256), 0, st, (const TX *)x, (int)n, (int)T, (int)C,
-                           (int)r, src, dst, unm, (TX *)out);
-    return check_launch("k_unmerge_rows");
+    return with_vec<TX>(C, x, out, [&](auto vec) {
+        hipLaunchKernelGGL((k_unmerge_rows<TX, decltype(vec)::value>), dim3(nb), dim3(256), 0, st, (const TX *)x, (int)n,
+                           (int)T, (int)C, (int)r, src, dst, unm, (TX *)out);
+        return check_launch("k_unmerge_rows");
+    });
 }
 
 extern "C" int tome_unmerge(const void *x, int dtype, int64_t n, int64_t T, int64_t C, int64_t r,
@@ -1608,15 +1628,12 @@ static int launch_merge_bwd(const void *gy, const void *out_div, const void *in_
     if (lgy_p || lgx_p || cls_rows)
         return fail(TOME_EINVAL, "regrouped merge backward needs rows of whole 16-byte chunks (C=%lld)", (long long)C);
     const unsigned nb = (unsigned)((n * T + 3) / 4);
-    if (vec_ok)
-        hipLaunchKernelGGL((k_merge_rows_bwd_any<TX, TS, VEC>), dim3(nb), dim3(256), 0, st, (const TX *)gy,
-                           (const TS *)out_div, (const TS *)in_mul, (int)n, (int)T, (int)C, (int)r, row_map, distill, drop,
-                           (TX *)gx);
-    else
-        hipLaunchKernelGGL((k_merge_rows_bwd_any<TX, TS, 1>), dim3(nb), dim3(256), 0, st, (const TX *)gy,
-                           (const TS *)out_div, (const TS *)in_mul, (int)n, (int)T, (int)C, (int)r, row_map, distill, drop,
-                           (TX *)gx);
-    return check_launch("k_merge_rows_bwd_any");
+    return with_vec<TX>(C, gy, gx, [&](auto vec) {
+        hipLaunchKernelGGL((k_merge_rows_bwd_any<TX, TS, decltype(vec)::value>), dim3(nb), dim3(256), 0, st,
+                           (const TX *)gy, (const TS *)out_div, (const TS *)in_mul, (int)n, (int)T, (int)C, (int)r, row_map,
+                           distill, drop, (TX *)gx);
+        return check_launch("k_merge_rows_bwd_any");
+    });
 }
 
 extern "C" int tome_merge_backward(const void *grad_out, int x_dtype, const void *out_div, const void *in_mul,
@@ -1657,37 +1674,9 @@ extern "C" int tome_merge_backward_regrouped(const void *grad_out, int x_dtype, 
 // partition matching (kernels in tome_partition.h): kth_bipartite_soft_matching (merge.py:105-158),
 // random_bipartite_soft_matching (merge.py:161-212)
 // ------------------------------------------------------------------------------------------------
-struct PartWs {
-    float *unitA, *unitB, *part_max;
-    int *part_idx;
-    uint8_t *badA, *badB;
-    int ntA, ntB, nchunk;
-    int64_t groupA_f4, groupB_f4;
-    size_t bytes;
-};
-
-static PartWs carve_part(void *base, int64_t n, int64_t Na, int64_t Nb, int64_t D) {
-    PartWs w;
-    w.nchunk = (int)((D + 63) / 64);
-    w.ntA = (int)((Na + TILE_ROWS - 1) / TILE_ROWS);
-    w.ntB = (int)((Nb + TILE_ROWS - 1) / TILE_ROWS);
-    w.groupA_f4 = (int64_t)w.ntA * w.nchunk * 512;
-    w.groupB_f4 = (int64_t)w.ntB * w.nchunk * 512;
-    size_t off = 0;
-    char *b = (char *)base;
-    w.unitA = (float *)(b + off); off = align_up(off + 16 * (size_t)(n * w.groupA_f4), 256);
-    w.unitB = (float *)(b + off); off = align_up(off + 16 * (size_t)(n * w.groupB_f4), 256);
-    w.part_max = (float *)(b + off); off = align_up(off + sizeof(float) * (size_t)(n * MAX_WJ * Na), 256);
-    w.part_idx = (int *)(b + off); off = align_up(off + sizeof(int) * (size_t)(n * MAX_WJ * Na), 256);
-    w.badA = (uint8_t *)(b + off); off = align_up(off + (size_t)(n * Na), 256);
-    w.badB = (uint8_t *)(b + off); off = align_up(off + (size_t)(n * Nb), 256);
-    w.bytes = off;
-    return w;
-}
-
 extern "C" size_t tome_partition_workspace_bytes(int64_t n, int64_t Na, int64_t Nb, int64_t D) {
     if (n <= 0 || Na <= 0 || Nb <= 0 || D <= 0) return 0;
-    return carve_part(nullptr, n, Na, Nb, D).bytes;
+    return carve_sets(nullptr, n, Na, Nb, D, false).bytes;
 }
 
 // the two sets of a partition call, checked: k > 1 (the kth rule, Na / Nb must be what it gives) or k == 0 with two
@@ -1724,77 +1713,31 @@ extern "C" int tome_match_partition(const void *metric, int dtype, int64_t n, in
     if (!dst_idx || !offsets || !sources) return fail(TOME_EINVAL, "tome_match_partition: null output buffer");
     if (((uintptr_t)dst_idx & 7) || ((uintptr_t)offsets & 3) || ((uintptr_t)sources & 3))
         return fail(TOME_EINVAL, "tome_match_partition: misaligned output buffer");
-    const size_t need = tome_partition_workspace_bytes(n, Na, Nb, D);
-    if (!workspace || workspace_bytes < need)
-        return fail(TOME_EWORKSPACE, "tome_match_partition: workspace %zu < %zu bytes", workspace_bytes, need);
-    if (((uintptr_t)workspace & 255) != 0)
-        return fail(TOME_EINVAL, "tome_match_partition: workspace not 256-byte aligned");
+    if (int rc = check_workspace("tome_match_partition", workspace, workspace_bytes,
+                                 tome_partition_workspace_bytes(n, Na, Nb, D)))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
-    const PartWs w = carve_part(workspace, n, Na, Nb, D);
+    const SetsWs w = carve_sets(workspace, n, Na, Nb, D, false);
     // 1. unit vectors of both sets
-    const size_t es = dtype == TOME_F32 ? 4 : 2;
-    const bool fast = (D % 8 == 0) && (((uintptr_t)metric) % 16 == 0) && ((stride_n * es) % 16 == 0) &&
-                      ((stride_t * es) % 16 == 0);
     const int64_t items = n * (Na + Nb);
-    bool launched = false;
-#define PUNIT_FAST(TY, NCH)                                                                                   \
-    hipLaunchKernelGGL((k_unit_rows_part<TY, NCH>), dim3((unsigned)((items + 31) / 32)), dim3(256), 0, st,     \
-                       (const TY *)metric, stride_n, stride_t, (int)n, (int)T, (int)D, S, w.unitA, w.unitB,    \
-                       w.groupA_f4, w.groupB_f4, w.badA, w.badB);                                              \
-    launched = true
-#define PUNIT_NCH(TY)                                       \
-    switch (w.nchunk) {                                     \
-    case 1: PUNIT_FAST(TY, 1); break;                       \
-    case 2: PUNIT_FAST(TY, 2); break;                       \
-    case 3: PUNIT_FAST(TY, 3); break;                       \
-    case 4: PUNIT_FAST(TY, 4); break;                       \
-    case 6: PUNIT_FAST(TY, 6); break;                       \
-    case 8: PUNIT_FAST(TY, 8); break;                       \
-    case 12: PUNIT_FAST(TY, 12); break;                     \
-    case 16: PUNIT_FAST(TY, 16); break;                     \
-    default: break;                                         \
-    }
-#define PUNIT_GENERIC(TY)                                                                                          \
-    hipLaunchKernelGGL((k_unit_rows_part_generic<TY>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st,     \
-                       (const TY *)metric, stride_n, stride_t, (int)n, (int)T, (int)D, w.nchunk * 64, S, w.unitA,   \
-                       w.unitB, w.groupA_f4, w.groupB_f4, w.badA, w.badB)
-    switch (dtype) {
-    case TOME_F32:
-        if (fast) { PUNIT_NCH(float) }
-        if (!launched) PUNIT_GENERIC(float);
-        break;
-    case TOME_BF16:
-        if (fast) { PUNIT_NCH(bf16_t) }
-        if (!launched) PUNIT_GENERIC(bf16_t);
-        break;
-    case TOME_F16:
-        if (fast) { PUNIT_NCH(f16_t) }
-        if (!launched) PUNIT_GENERIC(f16_t);
-        break;
-    default: return fail(TOME_EINVAL, "tome_match_partition: dtype %d", dtype);
-    }
-#undef PUNIT_FAST
-#undef PUNIT_NCH
-#undef PUNIT_GENERIC
+    if (int rc = launch_unit_rows("tome_match_partition", dtype, rows_16byte(metric, dtype, D, stride_n, stride_t), w.nchunk,
+                                  [&](auto ty, auto nch) {
+        using TY = typename decltype(ty)::type;
+        hipLaunchKernelGGL((k_unit_rows_part<TY, decltype(nch)::value>), dim3((unsigned)((items + 31) / 32)), dim3(256), 0,
+                           st, (const TY *)metric, stride_n, stride_t, (int)n, (int)T, (int)D, S, w.unitA, w.unitB,
+                           w.groupA_f4, w.groupB_f4, w.badA, w.badB);
+    }, [&](auto ty) {
+        using TY = typename decltype(ty)::type;
+        hipLaunchKernelGGL((k_unit_rows_part_generic<TY>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st,
+                           (const TY *)metric, stride_n, stride_t, (int)n, (int)T, (int)D, w.nchunk * 64, S, w.unitA,
+                           w.unitB, w.groupA_f4, w.groupB_f4, w.badA, w.badB);
+    }))
+        return rc;
     if (int rc = check_launch("k_unit_rows_part")) return rc;
 
-    // 2. similarity + row max / argmax: k_scores_rowmax as tome_match launches it (match_tail), T1 = Na, T2 = Nb
-    const long target_waves = 6144L;
-    int WJ = (int)((target_waves + n * w.ntA - 1) / (n * w.ntA));
-    if (WJ > MAX_WJ) WJ = MAX_WJ;
-    if (WJ > w.ntB) WJ = w.ntB;
-    if (WJ < 1) WJ = 1;
-    const int64_t nb2 = ((n + 7) / 8) * 8 * w.ntA * WJ;
-    if (nb2 > 0x7fffffffLL) return fail(TOME_EINVAL, "tome_match_partition: problem too large");
-    if (w.nchunk == 1)
-        hipLaunchKernelGGL(k_scores_rowmax<true>, dim3((unsigned)nb2), dim3(64), 0, st, (const f32x4 *)w.unitA,
-                           (const f32x4 *)w.unitB, (int)n, (int)Na, (int)Nb, w.nchunk, w.ntA, w.ntB, WJ, w.groupA_f4,
-                           w.groupB_f4, 0, w.part_max, w.part_idx, nullptr);
-    else
-        hipLaunchKernelGGL(k_scores_rowmax<false>, dim3((unsigned)nb2), dim3(64), 0, st, (const f32x4 *)w.unitA,
-                           (const f32x4 *)w.unitB, (int)n, (int)Na, (int)Nb, w.nchunk, w.ntA, w.ntB, WJ, w.groupA_f4,
-                           w.groupB_f4, 0, w.part_max, w.part_idx, nullptr);
-    if (int rc = check_launch("k_scores_rowmax")) return rc;
+    // 2. similarity + row max / argmax of the Na sources against the Nb destinations
+    int WJ = 1;
+    if (int rc = launch_scores_rowmax("tome_match_partition", w, n, (int)Na, (int)Nb, 0, st, &WJ)) return rc;
 
     // 3. fold the column parts -> dst_idx
     if (n > 65535) return fail(TOME_EINVAL, "tome_match_partition: more than 65535 groups");
@@ -1817,16 +1760,14 @@ template <typename TX, typename TS, int OP>
 static int launch_merge_part(const void *x, const void *size, int64_t n, int64_t T, int64_t C, const PartSets &S,
                              const int32_t *offsets, const int32_t *sources, void *xout, void *sout, void *lsout,
                              hipStream_t st) {
-    constexpr int VEC = 16 / sizeof(TX);
     const int64_t rows = n * S.Nb;
     const unsigned nb = (unsigned)((rows + 3) / 4);
-    if ((C % VEC == 0) && aligned16(x) && aligned16(xout))
-        hipLaunchKernelGGL((k_merge_part<TX, TS, VEC, OP>), dim3(nb), dim3(256), 0, st, (const TX *)x, (const TS *)size,
-                           (int)n, (int)T, (int)C, S, offsets, sources, (TX *)xout, (TS *)sout, (TS *)lsout);
-    else
-        hipLaunchKernelGGL((k_merge_part<TX, TS, 1, OP>), dim3(nb), dim3(256), 0, st, (const TX *)x, (const TS *)size,
-                           (int)n, (int)T, (int)C, S, offsets, sources, (TX *)xout, (TS *)sout, (TS *)lsout);
-    return check_launch("k_merge_part");
+    return with_vec<TX>(C, x, xout, [&](auto vec) {
+        hipLaunchKernelGGL((k_merge_part<TX, TS, decltype(vec)::value, OP>), dim3(nb), dim3(256), 0, st, (const TX *)x,
+                           (const TS *)size, (int)n, (int)T, (int)C, S, offsets, sources, (TX *)xout, (TS *)sout,
+                           (TS *)lsout);
+        return check_launch("k_merge_part");
+    });
 }
 
 static int check_part_merge_args(const char *who, const void *x, int64_t C, const void *out, const int32_t *offsets,
@@ -1877,16 +1818,13 @@ extern "C" int tome_merge_wavg_partition(const void *x, int x_dtype, const void 
 template <typename TX>
 static int launch_unmerge_part(const void *x, int64_t n, int64_t T, int64_t Tout, int64_t C, const PartSets &S,
                                const int64_t *dst, void *out, hipStream_t st) {
-    constexpr int VEC = 16 / sizeof(TX);
     const int64_t items = n * ((int64_t)S.Na + S.Nb);
     const unsigned nb = (unsigned)((items + 3) / 4);
-    if ((C % VEC == 0) && aligned16(x) && aligned16(out))
-        hipLaunchKernelGGL((k_unmerge_part<TX, VEC>), dim3(nb), dim3(256), 0, st, (const TX *)x, (int)n, (int)T, (int)Tout,
-                           (int)C, S, dst, (TX *)out);
-    else
-        hipLaunchKernelGGL((k_unmerge_part<TX, 1>), dim3(nb), dim3(256), 0, st, (const TX *)x, (int)n, (int)T, (int)Tout,
-                           (int)C, S, dst, (TX *)out);
-    return check_launch("k_unmerge_part");
+    return with_vec<TX>(C, x, out, [&](auto vec) {
+        hipLaunchKernelGGL((k_unmerge_part<TX, decltype(vec)::value>), dim3(nb), dim3(256), 0, st, (const TX *)x, (int)n,
+                           (int)T, (int)Tout, (int)C, S, dst, (TX *)out);
+        return check_launch("k_unmerge_part");
+    });
 }
 
 extern "C" int tome_unmerge_partition(const void *x, int dtype, int64_t n, int64_t T, int64_t C, int64_t k,

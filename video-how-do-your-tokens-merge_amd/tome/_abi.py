@@ -230,18 +230,28 @@ class MatchPlan:
         self.count = None  # [n, T-r, 1] fp32, 1 + sources of every merged row (plan_count: backward of "mean")
 
 
-def _alloc_plan(n, T, re, class_token, distill_token, device, want_node_max, want_row_map):
-    T1 = (T + 1) // 2
-    src = torch.empty((n, re, 1), dtype=torch.int64, device=device)
-    dst = torch.empty((n, re, 1), dtype=torch.int64, device=device)
-    unm = torch.empty((n, T1 - re, 1), dtype=torch.int64, device=device)
-    nmax = torch.empty((n, T1), dtype=torch.float32, device=device) if want_node_max else None
-    rmap = torch.empty((n, T1), dtype=torch.int32, device=device) if want_row_map else None
-    return MatchPlan(n, T, re, class_token, distill_token, src, dst, unm, nmax, rmap, device)
-
-
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
+
+
+def _matching(L, entry, head, n, T, D, r, re, class_token, distill_token, device, want_node_max, want_row_map):
+    """The tail of match / match_keys / match_scores behind their own checks: the workspace of a matching of n groups of T
+    tokens (D channels), the buffers of its plan (re > 0 merged per group), and the call of `entry` of the library L --
+    `head`: its arguments in front of r.  (One frame per matching, as the plan's allocation alone was: match_keys is on
+    the host-bound forward.)"""
+    T1 = (T + 1) // 2
+    with _on_device(device):
+        st = _stream(device)
+        ws = _workspace(device, st, L.tome_match_workspace_bytes(n, T, D))
+        src = torch.empty((n, re, 1), dtype=torch.int64, device=device)
+        dst = torch.empty((n, re, 1), dtype=torch.int64, device=device)
+        unm = torch.empty((n, T1 - re, 1), dtype=torch.int64, device=device)
+        nmax = torch.empty((n, T1), dtype=torch.float32, device=device) if want_node_max else None
+        rmap = torch.empty((n, T1), dtype=torch.int32, device=device) if want_row_map else None
+        rc = entry(*head, int(r), int(bool(class_token)), int(bool(distill_token)), src.data_ptr(), dst.data_ptr(),
+                   unm.data_ptr(), _ptr(nmax), _ptr(rmap), ws.data_ptr(), ws.numel(), st)
+    _check(rc, entry.__name__)
+    return MatchPlan(n, T, re, class_token, distill_token, src, dst, unm, nmax, rmap, device)
 
 
 def match(metric: torch.Tensor, r: int, class_token=False, distill_token=False, want_node_max=False,
@@ -258,18 +268,8 @@ def match(metric: torch.Tensor, r: int, class_token=False, distill_token=False, 
     if metric.stride(2) != 1:
         metric = metric.contiguous()
     L = lib()
-    dev = metric.device
-    with _on_device(dev):
-        st = _stream(dev)
-        nbytes = L.tome_match_workspace_bytes(n, T, D)
-        ws = _workspace(dev, st, nbytes)
-        plan = _alloc_plan(n, T, re, class_token, distill_token, dev, want_node_max, want_row_map)
-        rc = L.tome_match(metric.data_ptr(), code, n, T, D, metric.stride(0), metric.stride(1), int(r),
-                          int(bool(class_token)), int(bool(distill_token)), plan.src_idx.data_ptr(),
-                          plan.dst_idx.data_ptr(), plan.unm_idx.data_ptr(), _ptr(plan.node_max), _ptr(plan.row_map),
-                          ws.data_ptr(), ws.numel(), st)
-    _check(rc, "tome_match")
-    return plan
+    return _matching(L, L.tome_match, (metric.data_ptr(), code, n, T, D, metric.stride(0), metric.stride(1)), n, T, D, r, re,
+                     class_token, distill_token, metric.device, want_node_max, want_row_map)
 
 
 def keys_fusable(keys: torch.Tensor) -> bool:
@@ -302,18 +302,8 @@ def match_keys(keys: torch.Tensor, r: int, class_token=False, distill_token=Fals
     if re <= 0 or n == 0:
         return None
     L = lib()
-    dev = keys.device
-    with _on_device(dev):
-        st = _stream(dev)
-        nbytes = L.tome_match_workspace_bytes(n, T, D)
-        ws = _workspace(dev, st, nbytes)
-        plan = _alloc_plan(n, T, re, class_token, distill_token, dev, want_node_max, want_row_map)
-        rc = L.tome_match_keys(keys.data_ptr(), DTYPES[keys.dtype], n, H, T, D, s_n, inner, s_in, s_h, s_t, int(r),
-                               int(bool(class_token)), int(bool(distill_token)),
-                               plan.src_idx.data_ptr(), plan.dst_idx.data_ptr(), plan.unm_idx.data_ptr(),
-                               _ptr(plan.node_max), _ptr(plan.row_map), ws.data_ptr(), ws.numel(), st)
-    _check(rc, "tome_match_keys")
-    return plan
+    return _matching(L, L.tome_match_keys, (keys.data_ptr(), DTYPES[keys.dtype], n, H, T, D, s_n, inner, s_in, s_h, s_t), n,
+                     T, D, r, re, class_token, distill_token, keys.device, want_node_max, want_row_map)
 
 
 def match_scores(scores: torch.Tensor, T: int, r: int, class_token=False, distill_token=False,
@@ -327,17 +317,8 @@ def match_scores(scores: torch.Tensor, T: int, r: int, class_token=False, distil
         return None
     scores = scores.float().contiguous()
     L = lib()
-    dev = scores.device
-    with _on_device(dev):
-        st = _stream(dev)
-        nbytes = L.tome_match_workspace_bytes(n, T, 1)
-        ws = _workspace(dev, st, nbytes)
-        plan = _alloc_plan(n, T, re, class_token, distill_token, dev, want_node_max, want_row_map)
-        rc = L.tome_match_scores(scores.data_ptr(), n, T, int(r), int(bool(class_token)), int(bool(distill_token)),
-                                 plan.src_idx.data_ptr(), plan.dst_idx.data_ptr(), plan.unm_idx.data_ptr(),
-                                 _ptr(plan.node_max), _ptr(plan.row_map), ws.data_ptr(), ws.numel(), st)
-    _check(rc, "tome_match_scores")
-    return plan
+    return _matching(L, L.tome_match_scores, (scores.data_ptr(), n, T), n, T, 1, r, re, class_token, distill_token,
+                     scores.device, want_node_max, want_row_map)
 
 
 def edge_keep(plan: MatchPlan, threshold: float) -> torch.Tensor:
@@ -545,6 +526,27 @@ def add_layernorm_regrouped(x: torch.Tensor, addend: torch.Tensor, frames: int, 
     return x_out, y_out
 
 
+def _prep_regrouped(who: str, plan: MatchPlan, x_full: torch.Tensor, frames: int, has_cls: bool):
+    """The prologue of merge_wavg_regrouped / drop_regrouped: x_full [B, has_cls + P*F, C] on the plan's device holds the
+    plan's B*F groups of P tokens, no gradient wanted.  Returns (x_full made contiguous, B, C, cls, F, P).  (It asks the
+    device itself: one frame, as require_device was, on the host-bound forward.)"""
+    if not x_full.is_cuda:
+        require_device(x_full, f"{who}(x)")
+    if x_full.dim() != 3:
+        raise TomeHipError(f"{who}: x must be [B, tokens, C], got {tuple(x_full.shape)}")
+    B, N, C = x_full.shape
+    cls = 1 if has_cls else 0
+    F, P = int(frames), plan.T
+    if N != cls + P * F or plan.n != B * F:
+        raise TomeHipError(f"{who}: x {tuple(x_full.shape)} does not hold {plan.n} groups of {P} tokens ({F} per clip) "
+                           f"plus {cls} class token")
+    if x_full.device != plan.device:
+        raise TomeHipError(f"{who}: tensor and matching on different devices")
+    if torch.is_grad_enabled() and x_full.requires_grad:
+        raise TomeHipError(f"{who}: autograd through the HIP merge kernels is not implemented")
+    return (x_full if x_full.is_contiguous() else x_full.contiguous()), B, C, cls, F, P
+
+
 def merge_wavg_regrouped(plan: MatchPlan, x_full: torch.Tensor, size: Optional[torch.Tensor], frames: int,
                          has_cls: bool = True, ln=None, addend: Optional[torch.Tensor] = None,
                          log_size: bool = False, addend_grouped: Optional[torch.Tensor] = None,
@@ -554,20 +556,7 @@ def merge_wavg_regrouped(plan: MatchPlan, x_full: torch.Tensor, size: Optional[t
     [B*F, P-r, 1].  Replaces rearrange -> merge_wavg -> rearrange -> cat (timesformer.py:89-107).
     With ln=(weight, bias, eps) it also returns y_out = LayerNorm(x_out) (class-token rows included) between the
     two, and `addend` (same shape as x_full) is added to the tokens while they are loaded."""
-    require_device(x_full, "merge_wavg_regrouped(x)")
-    if x_full.dim() != 3:
-        raise TomeHipError(f"merge_wavg_regrouped: x must be [B, tokens, C], got {tuple(x_full.shape)}")
-    B, N, C = x_full.shape
-    cls = 1 if has_cls else 0
-    F, P = int(frames), plan.T
-    if N != cls + P * F or plan.n != B * F:
-        raise TomeHipError(f"merge_wavg_regrouped: x {tuple(x_full.shape)} does not hold {plan.n} groups of {P} "
-                           f"tokens ({F} per clip) plus {cls} class token")
-    if x_full.device != plan.device:
-        raise TomeHipError("merge_wavg_regrouped: tensor and matching on different devices")
-    if torch.is_grad_enabled() and x_full.requires_grad:
-        raise TomeHipError("merge_wavg_regrouped: autograd through the HIP merge kernels is not implemented")
-    x_full = x_full if x_full.is_contiguous() else x_full.contiguous()
+    x_full, B, C, cls, F, P = _prep_regrouped("merge_wavg_regrouped", plan, x_full, frames, has_cls)
     xcode = dtype_code(x_full, "x")
     size, sdtype = _prep_size(size, plan.n, P, x_full)
     x_out = torch.empty((B, cls + (P - plan.r) * F, C), dtype=x_full.dtype, device=x_full.device)
@@ -652,6 +641,59 @@ def prop_attention_ok(q: torch.Tensor) -> bool:
     return _head_view(q) and not (torch.is_grad_enabled() and needs_grad(q))
 
 
+def _qkv_heads(who: str, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bias_skip: bool = False):
+    """q [B, H, N, 64] and k / v [B, H, Nk, 64] head views agree (one dtype and device, k and v one shape; bias_skip: as
+    many keys as queries).  Returns B, H, N, D, Nk and the three {batch, head, token} stride arrays the entries take --
+    built here, so prop_attention(checked=True), on the host-bound forward, has two frames fewer than with _head_strides."""
+    if k.dtype != q.dtype or v.dtype != q.dtype or k.device != q.device or v.device != q.device:
+        raise TomeHipError(f"{who}: q, k, v must share dtype and device")
+    B, H, N, D = q.shape
+    if k.shape != v.shape or k.shape[:2] != (B, H):
+        raise TomeHipError(f"{who}: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not match")
+    Nk = k.shape[2]
+    if bias_skip and Nk != N:
+        raise TomeHipError(f"{who}: bias_skip needs as many keys as queries")
+    i64x3 = ctypes.c_int64 * 3
+    return B, H, N, D, Nk, i64x3(*q.stride()[:3]), i64x3(*k.stride()[:3]), i64x3(*v.stride()[:3])
+
+
+def _key_bias(who: str, log_bias: Optional[torch.Tensor], B: int, keys: int, device) -> Optional[torch.Tensor]:
+    """The per-key bias as the attention entries read it: an fp32 [B, keys] view with contiguous rows on `device`, or None."""
+    if log_bias is not None and (tuple(log_bias.shape) != (B, keys) or log_bias.dtype != torch.float32
+                                 or log_bias.stride(1) != 1 or log_bias.device != device):
+        raise TomeHipError(f"{who}: log_bias must be an fp32 {(B, keys)} view with contiguous rows")
+    return log_bias
+
+
+def _grad_rows(who: str, t: torch.Tensor, name: str, shape, q: torch.Tensor) -> torch.Tensor:
+    """An output of the forward or its gradient as the backward entries read it: `shape` on q's device, detached, in q's
+    dtype, channels contiguous and rows 16-byte aligned (anything else is copied once)."""
+    if tuple(t.shape) != shape or t.device != q.device:
+        raise TomeHipError(f"{who}: {name} must be {shape} on {q.device}, got {tuple(t.shape)}")
+    t = t.detach()
+    if t.dtype != q.dtype:
+        t = t.to(q.dtype)
+    if t.stride(-1) != 1 or any(s % 8 for s in t.stride()[:-1]) or t.data_ptr() % 16:
+        t = t.contiguous()
+    return t
+
+
+def _grad_heads(who: str, grads, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor):
+    """(dq, dk, dv) of the attention backward entries: the three head views given, validated against q, k, v -- or, grads
+    None, fresh ones laid out [B, tokens, H, 64]."""
+    if grads is None:
+        B, H, N, D = q.shape
+        dq = torch.empty((B, N, H, D), dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
+        dk = torch.empty((B, k.shape[2], H, D), dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
+        dv = torch.empty((B, k.shape[2], H, D), dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
+        return dq, dk, dv
+    for t, like, name in zip(grads, (q, k, v), ("dq", "dk", "dv")):
+        if t.shape != like.shape or t.dtype != q.dtype or t.device != q.device or not _head_view(t):
+            raise TomeHipError(f"{who}: {name} must be a {tuple(like.shape)} {q.dtype} head view with 16-byte aligned rows")
+    dq, dk, dv = grads
+    return dq, dk, dv
+
+
 def prop_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, size: Optional[torch.Tensor], scale: float,
                    bias_skip: bool = False, log_bias: Optional[torch.Tensor] = None,
                    out: Optional[torch.Tensor] = None, checked: bool = False) -> torch.Tensor:
@@ -668,14 +710,7 @@ def prop_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, size: Opti
         if not prop_attention_ok(t):
             raise TomeHipError(f"prop_attention: {name} must be a [B, H, N, 64] 16-bit view with 16-byte aligned rows, "
                                f"got {tuple(t.shape)} {t.dtype} strides {t.stride()}")
-    if k.dtype != q.dtype or v.dtype != q.dtype or k.device != q.device or v.device != q.device:
-        raise TomeHipError("prop_attention: q, k, v must share dtype and device")
-    B, H, N, D = q.shape
-    if k.shape != v.shape or k.shape[:2] != (B, H):
-        raise TomeHipError(f"prop_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not match")
-    Nk = k.shape[2]
-    if bias_skip and Nk != N:
-        raise TomeHipError("prop_attention: bias_skip needs as many keys as queries")
+    B, H, N, D, Nk, qs, ks, vs = _qkv_heads("prop_attention", q, k, v, bias_skip)
     nb = Nk - (1 if bias_skip else 0)
     log = None
     if size is not None:
@@ -683,10 +718,7 @@ def prop_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, size: Opti
             raise TomeHipError(f"prop_attention: size must be {(B, nb, 1)}, got {tuple(size.shape)}")
         log = log_of_size(size).reshape(B, -1).float().contiguous()
     elif log_bias is not None:
-        if tuple(log_bias.shape) != (B, nb) or log_bias.dtype != torch.float32 or log_bias.stride(1) != 1 \
-                or log_bias.device != q.device:
-            raise TomeHipError(f"prop_attention: log_bias must be an fp32 {(B, nb)} view with contiguous rows")
-        log = log_bias
+        log = _key_bias("prop_attention", log_bias, B, nb, q.device)
     ostr = None
     if out is None:
         result = out = torch.empty((B, N, H * D), dtype=q.dtype, device=q.device)
@@ -697,7 +729,7 @@ def prop_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, size: Opti
         result = out
     with _on_device(q.device):
         rc = lib().tome_prop_attention(q.data_ptr(), k.data_ptr(), v.data_ptr(), dtype_code(q, "q"), B, H, N, Nk, D,
-                                       _head_strides(q), _head_strides(k), _head_strides(v), _ptr(log),
+                                       qs, ks, vs, _ptr(log),
                                        0 if log is None else log.stride(0), 1 if bias_skip else 0, float(scale),
                                        out.data_ptr(), ostr, _stream(q.device))
     _check(rc, "tome_prop_attention")
@@ -727,39 +759,13 @@ def prop_attention_backward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o
         require_device(t, f"prop_attention_backward({name})")
     if not prop_attention_trainable(q, k, v):
         raise TomeHipError("prop_attention_backward: q, k, v must be [B, H, N, 64] 16-bit views with 16-byte aligned rows")
-    if k.dtype != q.dtype or v.dtype != q.dtype or k.device != q.device or v.device != q.device:
-        raise TomeHipError("prop_attention_backward: q, k, v must share dtype and device")
-    B, H, N, D = q.shape
-    if k.shape != v.shape or k.shape[:2] != (B, H):
-        raise TomeHipError(f"prop_attention_backward: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not match")
-    Nk = k.shape[2]
-    if bias_skip and Nk != N:
-        raise TomeHipError("prop_attention_backward: bias_skip needs as many keys as queries")
-    nb = Nk - (1 if bias_skip else 0)
-    if log_bias is not None and (tuple(log_bias.shape) != (B, nb) or log_bias.dtype != torch.float32
-                                 or log_bias.stride(1) != 1 or log_bias.device != q.device):
-        raise TomeHipError(f"prop_attention_backward: log_bias must be an fp32 {(B, nb)} view with contiguous rows")
-    heads = []
-    for t, name in ((out, "out"), (dout, "dout")):
-        if tuple(t.shape) != (B, N, H * D) or t.device != q.device:
-            raise TomeHipError(f"prop_attention_backward: {name} must be {(B, N, H * D)} on {q.device}, got {tuple(t.shape)}")
-        t = t.detach()
-        if t.dtype != q.dtype:
-            t = t.to(q.dtype)
-        if t.stride(2) != 1 or t.stride(0) % 8 or t.stride(1) % 8 or t.data_ptr() % 16:
-            t = t.contiguous()
-        heads.append(t.unflatten(2, (H, D)).permute(0, 2, 1, 3))  # [B, H, N, 64] view
-    o4, g4 = heads
-    if grads is None:
-        dq = torch.empty((B, N, H, D), dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
-        dk = torch.empty((B, Nk, H, D), dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
-        dv = torch.empty((B, Nk, H, D), dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
-    else:
-        dq, dk, dv = grads
-        for t, like, name in ((dq, q, "dq"), (dk, k, "dk"), (dv, v, "dv")):
-            if t.shape != like.shape or t.dtype != q.dtype or t.device != q.device or not prop_attention_trainable(t):
-                raise TomeHipError(f"prop_attention_backward: {name} must be a {tuple(like.shape)} {q.dtype} head view with "
-                                   "16-byte aligned rows")
+    who = "prop_attention_backward"
+    B, H, N, D, Nk, qs, ks, vs = _qkv_heads(who, q, k, v, bias_skip)
+    _key_bias(who, log_bias, B, Nk - (1 if bias_skip else 0), q.device)
+    # [B, H, N, 64] views of out and dout
+    o4, g4 = (_grad_rows(who, t, name, (B, N, H * D), q).unflatten(2, (H, D)).permute(0, 2, 1, 3)
+              for t, name in ((out, "out"), (dout, "dout")))
+    dq, dk, dv = _grad_heads(who, grads, q, k, v)
     L = lib()
     entry = require_symbol(L, "tome_prop_attention_backward")
     with _on_device(q.device):
@@ -767,7 +773,7 @@ def prop_attention_backward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o
         ws = workspace if workspace is not None else _sized_workspace(
             L, "tome_prop_attention_backward_workspace_bytes", (B, H, N, Nk), q.device, stream, "prop_attention_backward")
         rc = entry(q.data_ptr(), k.data_ptr(), v.data_ptr(), o4.data_ptr(), g4.data_ptr(), dtype_code(q, "q"), B, H, N, Nk,
-                   D, _head_strides(q), _head_strides(k), _head_strides(v), _head_strides(o4), _head_strides(g4),
+                   D, qs, ks, vs, _head_strides(o4), _head_strides(g4),
                    _ptr(log_bias), 0 if log_bias is None else log_bias.stride(0), 1 if bias_skip else 0, float(scale),
                    dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), _head_strides(dq), _head_strides(dk), _head_strides(dv),
                    ws.data_ptr(), ws.numel() * ws.element_size(), stream)
@@ -792,9 +798,7 @@ def prop_attention_segments(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, n
         raise TomeHipError(f"prop_attention_segments: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}, "
                            f"{nseg} segments do not match")
     P = k.shape[2] // nseg
-    if log_bias is not None and (tuple(log_bias.shape) != (B, nseg * P) or log_bias.dtype != torch.float32
-                                 or log_bias.stride(1) != 1 or log_bias.device != q.device):
-        raise TomeHipError(f"prop_attention_segments: log_bias must be an fp32 {(B, nseg * P)} view with contiguous rows")
+    _key_bias("prop_attention_segments", log_bias, B, nseg * P, q.device)
     y = torch.empty((B, N, nseg, H * D), dtype=q.dtype, device=q.device)
     ostr = (ctypes.c_int64 * 3)(y.stride(0), D, y.stride(1))  # {batch, head, token}
     seg = (ctypes.c_int64 * 4)(P * k.stride(2), P * v.stride(2), y.stride(2), P)
@@ -832,32 +836,10 @@ def prop_attention_segments_backward(q: torch.Tensor, k: torch.Tensor, v: torch.
                            "segments of equal length")
     B, H, N, D = q.shape
     P = k.shape[2] // nseg
-    if log_bias is not None and (tuple(log_bias.shape) != (B, nseg * P) or log_bias.dtype != torch.float32
-                                 or log_bias.stride(1) != 1 or log_bias.device != q.device):
-        raise TomeHipError(f"prop_attention_segments_backward: log_bias must be an fp32 {(B, nseg * P)} view with "
-                           "contiguous rows")
-    rows = []
-    for t, name in ((y, "y"), (dy, "dy")):
-        if tuple(t.shape) != (B, N, nseg, H * D) or t.device != q.device:
-            raise TomeHipError(f"prop_attention_segments_backward: {name} must be {(B, N, nseg, H * D)} on {q.device}, "
-                               f"got {tuple(t.shape)}")
-        t = t.detach()
-        if t.dtype != q.dtype:
-            t = t.to(q.dtype)
-        if t.stride(3) != 1 or any(s % 8 for s in t.stride()[:3]) or t.data_ptr() % 16:
-            t = t.contiguous()
-        rows.append(t)
-    y, dy = rows
-    if grads is None:
-        dq = torch.empty((B, N, H, D), dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
-        dk = torch.empty((B, nseg * P, H, D), dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
-        dv = torch.empty((B, nseg * P, H, D), dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
-    else:
-        dq, dk, dv = grads
-        for t, like, name in ((dq, q, "dq"), (dk, k, "dk"), (dv, v, "dv")):
-            if t.shape != like.shape or t.dtype != q.dtype or t.device != q.device or not _head_view(t):
-                raise TomeHipError(f"prop_attention_segments_backward: {name} must be a {tuple(like.shape)} {q.dtype} head "
-                                   "view with 16-byte aligned rows")
+    who = "prop_attention_segments_backward"
+    _key_bias(who, log_bias, B, nseg * P, q.device)
+    y, dy = (_grad_rows(who, t, name, (B, N, nseg, H * D), q) for t, name in ((y, "y"), (dy, "dy")))
+    dq, dk, dv = _grad_heads(who, grads, q, k, v)
     L = lib()
     entry = require_symbol(L, "tome_prop_attention_segments_backward")
     i64x3 = ctypes.c_int64 * 3
@@ -1054,20 +1036,7 @@ def trajectory_mix_backward(q2: torch.Tensor, k2: torch.Tensor, val: torch.Tenso
 def drop_regrouped(plan: MatchPlan, x_full: torch.Tensor, frames: int, has_cls: bool = True) -> torch.Tensor:
     """drop on the interleaved layout (see merge_wavg_regrouped): x_full [B, has_cls + P*F, C] ->
     [B, has_cls + (P-r)*F, C], replacing rearrange -> drop -> rearrange -> cat (timesformer.py:111-131)."""
-    require_device(x_full, "drop_regrouped(x)")
-    if x_full.dim() != 3:
-        raise TomeHipError(f"drop_regrouped: x must be [B, tokens, C], got {tuple(x_full.shape)}")
-    B, N, C = x_full.shape
-    cls = 1 if has_cls else 0
-    F, P = int(frames), plan.T
-    if N != cls + P * F or plan.n != B * F:
-        raise TomeHipError(f"drop_regrouped: x {tuple(x_full.shape)} does not hold {plan.n} groups of {P} tokens "
-                           f"({F} per clip) plus {cls} class token")
-    if x_full.device != plan.device:
-        raise TomeHipError("drop_regrouped: tensor and matching on different devices")
-    if torch.is_grad_enabled() and x_full.requires_grad:
-        raise TomeHipError("drop_regrouped: autograd through the HIP merge kernels is not implemented")
-    x_full = x_full if x_full.is_contiguous() else x_full.contiguous()
+    x_full, B, C, cls, F, P = _prep_regrouped("drop_regrouped", plan, x_full, frames, has_cls)
     out = torch.empty((B, cls + (P - plan.r) * F, C), dtype=x_full.dtype, device=x_full.device)
     with _on_device(x_full.device):
         rc = lib().tome_drop_regrouped(x_full.data_ptr(), dtype_code(x_full, "x"), B, F, P, C, plan.r, cls,
