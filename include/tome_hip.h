@@ -362,6 +362,46 @@ int tome_layernorm_backward_regrouped(const void *gy, const void *xs, const void
                                       void *dbias, void *workspace, tome_stream_t stream);
 
 /*
+ * tome_add_layernorm_amp  <-  tome_add_layernorm / tome_add_layernorm_skip_first for a model that runs under autocast
+ *     with fp32 master weights (additions to ABI v11, no entry changed):
+ *         with torch.cuda.amp.autocast(enabled=cfg.TRAIN.MIXED_PRECISION):   tools/train_net.py:123
+ *         with torch.autocast(device.type, enabled=use_fp16):               tome/utils.py:54
+ *     Under autocast the LayerNorm's weight and bias are fp32, its output feeds a 16-bit Linear, and the residual stream
+ *     is fp32 (`x + self.pos_embed` promotes it) or 16-bit (`pos_embed.type_as(x)`,
+ *     videomae_video_model_builder.py:278).  x' = x + addend (addend NULL: x' = x, x_out neither read nor written and
+ *     may be NULL), y = LayerNorm(x'):
+ *         x, x_out of x_dtype; y_out of y_dtype (16-bit); weight_f32, bias_f32 [C] fp32.
+ *         x_dtype == y_dtype:  addend of the same dtype;  x' = round16(x + addend), the bits tome_add_layernorm stores.
+ *         x_dtype == TOME_F32: addend of y_dtype or fp32; x' = the fp32 sum, one rounding (`x + addend.float()`).
+ *     The statistics are taken in fp32 from the STORED x' (two passes, centred variance), y is rounded once.
+ *     rows = groups * group_rows; skip_first != 0: y_out [groups * (group_rows - 1), C] leaves out every group's first
+ *     row (tome_add_layernorm_skip_first).  C % 8 == 0, C <= 1024, 16-byte aligned buffers.  Any other dtype
+ *     combination: TOME_EINVAL.
+ */
+int tome_add_layernorm_amp(const void *x, int x_dtype, const void *addend, int addend_dtype, int64_t groups,
+                           int64_t group_rows, int skip_first, int64_t C, const void *weight_f32, const void *bias_f32,
+                           float eps, void *x_out, void *y_out, int y_dtype, tome_stream_t stream);
+
+/*
+ * tome_layernorm_backward_amp  <-  the backward of tome_add_layernorm_amp: tome_layernorm_backward's formula for a model
+ *     that trains under autocast with a GradScaler and fp32 master weights (additions to ABI v11, no entry changed;
+ *     tools/train_net.py:123 and :680, tome/utils.py:54).
+ *         gy of gy_dtype (16-bit): [rows, C], or with skip_first [groups * (group_rows - 1), C];
+ *         xs (the stored x'), gx_in (or NULL), gx of x_dtype: gy_dtype, or TOME_F32 (gx is then the unrounded fp32 value);
+ *         weight_f32, dweight_f32, dbias_f32 [C] fp32 (either or both gradients may be NULL: a frozen LayerNorm does no
+ *         parameter work and needs no workspace; otherwise tome_layernorm_backward_amp_workspace_bytes(rows, C, x_dtype)
+ *         bytes, 0 for an illegal shape or dtype);
+ *         gx16 (x_dtype == TOME_F32 only, or NULL): [rows, C] of gy_dtype, round16(gx) from the same registers, bit-equal
+ *         to a cast of gx -- the gradient of a 16-bit addend without a pass of its own.
+ *     Statistics recomputed from xs with the forward's arithmetic; no atomics, same bits on every run.
+ */
+size_t tome_layernorm_backward_amp_workspace_bytes(int64_t rows, int64_t C, int x_dtype);
+int tome_layernorm_backward_amp(const void *gy, int gy_dtype, const void *xs, const void *gx_in, int x_dtype,
+                                int64_t groups, int64_t group_rows, int skip_first, int64_t C, const void *weight_f32,
+                                float eps, void *gx, void *gx16, void *dweight_f32, void *dbias_f32, void *workspace,
+                                tome_stream_t stream);
+
+/*
  * tome_prop_attention_backward  <-  what autograd derives from the proportional attention of the patched blocks when
  *     q, k or v require grad (additions to ABI v11, no entry changed; models are patched for training,
  *     tools/train_net.py:727-741):

@@ -24,6 +24,11 @@
 //   k_ln_param_grad      the partial rows summed in a fixed order
 //   k_ln_rows_bwd<REGROUP>  the same behind TimeSformer's mid-block regrouping (tome_layernorm_backward_regrouped): the
 //                        row map in front of gy, a class row's F gradients summed in fp32              (HBM bound)
+// and their mixed-precision forms for a model under autocast with fp32 master weights (tome_add_layernorm_amp,
+// tome_layernorm_backward_amp), tome_merge.h / tome_ln_bwd.h:
+//   k_add_ln_rows_amp    k_add_ln_rows with fp32 weight / bias, a 16-bit y and a 16-bit or fp32 residual stream
+//   k_ln_rows_bwd_amp    k_ln_rows_bwd with a 16-bit gy, the stream's dtype for xs / gx_in / gx, fp32 partial rows summed
+//                        into fp32 parameters, optionally gx rounded to 16 bits as a second output       (HBM bound)
 // and of TimeSformer's temporal attention (tome_short_attention_backward), tome_short_attn_bwd.h:
 //   k_short_attention_bwd  P recomputed, dq / dk / dv of sequences of <= 8 tokens in one pass, eight lanes per
 //                        (sequence, head), dk / dv accumulated in registers                           (HBM bound)
@@ -931,6 +936,113 @@ extern "C" int tome_layernorm_backward_regrouped(const void *gy, const void *xs,
                                  "2^31 - 1 rows on either side required");
     return layernorm_backward_impl(Op<1>{}, "tome_layernorm_backward_regrouped", gy, xs, gx_in, dtype, B * (1 + P * F),
                                    B * F * (1 + P), 0, F, P, C, weight, eps, gx, dweight, dbias, workspace, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The mixed-precision forms (a model under autocast with fp32 master weights): k_add_ln_rows_amp and
+// k_ln_rows_bwd_amp in the launch forms of the entries above (three slots per lane, ln_rows_per_wave, ln_bwd_form).
+// ------------------------------------------------------------------------------------------------
+// f(Dt<TS>{}, Dt<TA>{}, Dt<TY>{}) for the legal (stream, addend, y) dtypes: a 16-bit stream with everything of its
+// dtype, or an fp32 stream with a 16-bit y and an addend of y's dtype or fp32.  has_addend = false: TA = TY.
+template <typename F, typename Bad>
+static int dispatch_amp(int x_dtype, int a_dtype, bool has_addend, int y_dtype, F &&f, Bad &&bad) {
+    return dispatch_x<false>(y_dtype, [&](auto ty) {
+        if (x_dtype == y_dtype) return (!has_addend || a_dtype == y_dtype) ? f(ty, ty, ty) : bad();
+        if (x_dtype != TOME_F32) return bad();
+        if (!has_addend || a_dtype == y_dtype) return f(Dt<float>{}, ty, ty);
+        if (a_dtype == TOME_F32) return f(Dt<float>{}, Dt<float>{}, ty);
+        return bad();
+    }, bad);
+}
+
+extern "C" int tome_add_layernorm_amp(const void *x, int x_dtype, const void *addend, int addend_dtype, int64_t groups,
+                                      int64_t group_rows, int skip_first, int64_t C, const void *weight_f32,
+                                      const void *bias_f32, float eps, void *x_out, void *y_out, int y_dtype,
+                                      tome_stream_t stream) {
+    const char *who = "tome_add_layernorm_amp";
+    if (!x || !weight_f32 || !bias_f32 || (addend && !x_out) || !y_out || groups <= 0 || group_rows <= 0 || C <= 0 ||
+        groups > 0x7fffffffLL || group_rows > 0x7fffffffLL)
+        return fail(TOME_EINVAL, "%s: bad shape/pointer", who);
+    if (skip_first && group_rows < 2) return fail(TOME_EINVAL, "%s: skip_first needs groups of at least two rows", who);
+    const int64_t cpr = C / 8, rows = groups * group_rows;
+    if (C % 8 || cpr > 2 * WAVE || !aligned16(x) || !aligned16(addend) || (addend && !aligned16(x_out)) ||
+        !aligned16(y_out) || !aligned16(weight_f32) || !aligned16(bias_f32))
+        return fail(TOME_EINVAL, "%s: C %% 8 == 0, C <= 1024 and 16-byte aligned buffers required", who);
+    const int R = ln_rows_per_wave(cpr, 3);
+    const int64_t waves = (rows + R - 1) / R;
+    if ((waves + 3) / 4 > 0x7fffffffLL) return fail(TOME_EINVAL, "%s: too many rows", who);
+    const dim3 grid((unsigned)((waves + 3) / 4));
+    const int y_group = skip_first ? (int)group_rows : 0;
+    hipStream_t st = (hipStream_t)stream;
+    return dispatch_amp(x_dtype, addend_dtype, addend != nullptr, y_dtype, [&](auto ts, auto ta, auto ty) {
+        using TS = typename decltype(ts)::type;
+        using TA = typename decltype(ta)::type;
+        using TY = typename decltype(ty)::type;
+        hipLaunchKernelGGL((k_add_ln_rows_amp<TS, TA, TY, 3>), grid, dim3(256), 0, st, (const TS *)x, (const TA *)addend,
+                           rows, (int)C, R, (int)cpr, (const float *)weight_f32, (const float *)bias_f32, eps, y_group,
+                           (TS *)x_out, (TY *)y_out);
+        return check_launch("k_add_ln_rows_amp");
+    }, [&] {
+        return fail(TOME_EINVAL, "%s: unsupported dtypes x=%d addend=%d y=%d (a 16-bit y; x of y's dtype with an addend "
+                                 "of the same, or fp32 x with an addend of y's dtype or fp32)", who, x_dtype,
+                    addend_dtype, y_dtype);
+    });
+}
+
+static bool ln_amp_dtypes_ok(int gy_dtype, int x_dtype) {
+    return (gy_dtype == TOME_BF16 || gy_dtype == TOME_F16) && (x_dtype == gy_dtype || x_dtype == TOME_F32);
+}
+
+extern "C" size_t tome_layernorm_backward_amp_workspace_bytes(int64_t rows, int64_t C, int x_dtype) {
+    if (x_dtype != TOME_F32 && x_dtype != TOME_BF16 && x_dtype != TOME_F16) return 0;
+    return tome_layernorm_backward_workspace_bytes(rows, C);  // the same launch form for every stream dtype
+}
+
+extern "C" int tome_layernorm_backward_amp(const void *gy, int gy_dtype, const void *xs, const void *gx_in, int x_dtype,
+                                           int64_t groups, int64_t group_rows, int skip_first, int64_t C,
+                                           const void *weight_f32, float eps, void *gx, void *gx16, void *dweight_f32,
+                                           void *dbias_f32, void *workspace, tome_stream_t stream) {
+    const char *who = "tome_layernorm_backward_amp";
+    if (!gy || !xs || !weight_f32 || !gx) return fail(TOME_EINVAL, "%s: null buffer", who);
+    if (!ln_amp_dtypes_ok(gy_dtype, x_dtype))
+        return fail(TOME_EINVAL, "%s: unsupported dtypes gy=%d x=%d (16-bit gy; x of gy's dtype or fp32)", who, gy_dtype,
+                    x_dtype);
+    if (gx16 && x_dtype != TOME_F32) return fail(TOME_EINVAL, "%s: gx16 belongs to an fp32 stream", who);
+    if (groups <= 0 || group_rows <= 0 || group_rows > 0x7fffffffLL || groups > 0x7fffffffLL ||
+        !ln_bwd_shape_ok(groups * group_rows, C))
+        return fail(TOME_EINVAL, "%s: C %% 8 == 0, C <= 1024 and 1 .. 2^31 - 1 rows required", who);
+    if (skip_first && group_rows < 2) return fail(TOME_EINVAL, "%s: skip_first needs groups of at least two rows", who);
+    if (!aligned16(gy) || !aligned16(xs) || !aligned16(gx_in) || !aligned16(weight_f32) || !aligned16(gx) ||
+        !aligned16(gx16) || !aligned16(workspace))
+        return fail(TOME_EINVAL, "%s: 16-byte aligned buffers required", who);
+    const bool params = dweight_f32 || dbias_f32;
+    if (params && !workspace)
+        return fail(TOME_EWORKSPACE, "%s: parameter gradients need a workspace of %s_workspace_bytes()", who, who);
+    const int64_t rows = groups * group_rows, gy_rows = skip_first ? groups * (group_rows - 1) : rows;
+    const int64_t cpr = C / 8;
+    const LnBwdForm f = ln_bwd_form(rows, C);
+    hipStream_t st = (hipStream_t)stream;
+    return dispatch_x<false>(gy_dtype, [&](auto tg) {
+        using TG = typename decltype(tg)::type;
+        auto go = [&](auto ts) {
+            using TS = typename decltype(ts)::type;
+            if (params) {
+                hipLaunchKernelGGL((k_ln_rows_bwd_amp<TS, TG, 3, true>), dim3((unsigned)f.parts), dim3(256), 0, st,
+                                   (const TG *)gy, (const TS *)xs, (const TS *)gx_in, (const float *)weight_f32, (int)rows,
+                                   (int)gy_rows, (int)C, f.R, (int)cpr, eps, skip_first ? (int)group_rows : 0, (int)f.spw,
+                                   (TS *)gx, (TG *)gx16, (float *)workspace);
+                if (int rc = check_launch("k_ln_rows_bwd_amp")) return rc;
+                return launch_param_grad<float>(workspace, f.parts, 2 * C, C, dweight_f32, dbias_f32, st);
+            }
+            // frozen LayerNorm: one slab per wave, no column sums, no workspace
+            hipLaunchKernelGGL((k_ln_rows_bwd_amp<TS, TG, 3, false>), dim3((unsigned)f.wgs), dim3(256), 0, st,
+                               (const TG *)gy, (const TS *)xs, (const TS *)gx_in, (const float *)weight_f32, (int)rows,
+                               (int)gy_rows, (int)C, f.R, (int)cpr, eps, skip_first ? (int)group_rows : 0, 1, (TS *)gx,
+                               (TG *)gx16, (float *)nullptr);
+            return check_launch("k_ln_rows_bwd_amp");
+        };
+        return x_dtype == TOME_F32 ? go(Dt<float>{}) : go(tg);
+    }, [&] { return not_16bit(who, gy_dtype, "gy"); });
 }
 
 extern "C" int tome_merge(const void *x, int dtype, int64_t n, int64_t T, int64_t C, int64_t r,

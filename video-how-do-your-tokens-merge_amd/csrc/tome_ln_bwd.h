@@ -307,3 +307,233 @@ __global__ __launch_bounds__(LN_PG_RUNS * WAVE) void k_ln_param_grad(const float
         out_hi[col - split] = from_f32<TP>(total);
     }
 }
+
+// ------------------------------------------------------------------------------------------------
+// k_ln_rows_bwd_amp: k_ln_rows_bwd for a model that runs under autocast with fp32 master weights
+// (tome_layernorm_backward_amp; tools/train_net.py:123, tome/utils.py:54): the backward of k_add_ln_rows_amp.
+// TG: gy, the 16-bit autocast dtype; TS: the residual stream (xs, gx_in, gx), 16-bit or fp32; weight fp32; the partial
+// rows of dweight / dbias fp32 as before, summed by k_ln_param_grad<float> into fp32 parameters.  Formula, reduction
+// rounds, packing (slots of 8 channels, tome_merge.h), slab walk and the order of every sum are those of k_ln_rows_bwd;
+// mean and rstd are recomputed from the stored row with k_add_ln_rows_amp's arithmetic.  gx is rounded once to TS (not
+// at all for an fp32 stream).  gx16 (fp32 stream, optional): round16(gx) from the same registers, the gradient of a
+// 16-bit addend without a cast pass; a class row's is round16(gx_in).
+// ------------------------------------------------------------------------------------------------
+template <typename TS, typename TG, int NIT, bool PARAMS>
+__global__ __launch_bounds__(256, 2) void k_ln_rows_bwd_amp(const TG *__restrict__ gy, const TS *__restrict__ xs,
+                                                         const TS *__restrict__ gx_in, const float *__restrict__ weight,
+                                                         int rows, int gy_rows, int C, int R, int cpr, float eps,
+                                                         int group_rows, int spw, TS *__restrict__ gx,
+                                                         TG *__restrict__ gx16, float *__restrict__ ws) {
+    constexpr int VEC = 8;
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const float inv_c = __builtin_amdgcn_rcpf((float)C);
+    const bool has_in = gx_in != nullptr;
+
+    // the place of this lane's slots in a slab: the same in every slab
+    int rr_of[NIT], cc_of[NIT];
+    float wgt[NIT][VEC];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const int q = it * WAVE + lane;
+        const int rr = (q >= cpr) + (q >= 2 * cpr) + (q >= 3 * cpr);
+        const bool slot = q < R * cpr;
+        rr_of[it] = slot ? rr : -1;
+        cc_of[it] = slot ? q - rr * cpr : 0;
+        ld_param8(weight, cc_of[it], wgt[it]);
+    }
+    float aw[NIT][VEC], ab[NIT][VEC];
+    if (PARAMS) {
+#pragma unroll
+        for (int it = 0; it < NIT; ++it)
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) aw[it][e] = ab[it][e] = 0.0f;
+    }
+
+    const int64_t slab0 = (int64_t)blockIdx.x * spw * 4;
+    for (int s = 0; s < spw; ++s) {
+        const int64_t row0_64 = (slab0 + (int64_t)s * 4 + wv) * R;
+        if (row0_64 >= rows) break;  // (wave-uniform)
+        const int row0 = (int)row0_64;
+        const int nrow = (rows - row0) < R ? (rows - row0) : R;
+        const int total = nrow * cpr;
+
+        // row of gy for each of the wave's rows, -1 for a class row: lanes 0..3, then wave-uniform scalars
+        int my_g = row0 + (lane & 3);
+        if (group_rows > 0) {
+            const unsigned gb = (unsigned)my_g / (unsigned)group_rows;
+            my_g = ((unsigned)my_g - gb * (unsigned)group_rows == 0u) ? -1 : my_g - (int)gb - 1;
+        }
+        const int g0 = __builtin_amdgcn_readlane(my_g, 0), g1 = __builtin_amdgcn_readlane(my_g, 1),
+                  g2 = __builtin_amdgcn_readlane(my_g, 2), g3 = __builtin_amdgcn_readlane(my_g, 3);
+
+        const TS *xsl = xs + (int64_t)row0 * C;
+        const TS *gil = (has_in ? gx_in : xs) + (int64_t)row0 * C;
+        Slot<TS> xraw[NIT], iraw[NIT];
+        uint4 graw[NIT];
+        int rowof[NIT];  // row-in-wave of a live slot, -1: no slot; bit 2 set: slot of a class row
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int q = it * WAVE + lane;
+            const bool live = q < total;
+            const int rr = rr_of[it];
+            const int g = rr == 0 ? g0 : (rr == 1 ? g1 : (rr == 2 ? g2 : g3));
+            // unconditional loads: a lane without a slot re-reads the slab's first slot, a class row the start of
+            // some row of gy, and ignores it
+            int gr = (live && g >= 0) ? g : 0;
+            gr = gr < gy_rows ? gr : gy_rows - 1;
+            xraw[it] = ld_slot<TS>(xsl, live ? q : 0);
+            graw[it] = ld16(reinterpret_cast<const uint4 *>(gy) + (int64_t)gr * cpr + cc_of[it]);
+            if (has_in) iraw[it] = ld_slot<TS>(gil, live ? q : 0);
+            rowof[it] = live ? (g < 0 ? (rr | 4) : rr) : -1;
+        }
+
+        // round 1: mean of every row (as k_add_ln_rows_amp)
+        float p0 = 0.0f, p1 = 0.0f, p2 = 0.0f, p3 = 0.0f;
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int rr = rowof[it] < 0 ? -1 : (rowof[it] & 3);
+            const float t = rr >= 0 ? slot_sum<TS>(xraw[it]) : 0.0f;
+            p0 += rr == 0 ? t : 0.0f;
+            if (R > 1) p1 += rr == 1 ? t : 0.0f;
+            if (R > 2) {
+                p2 += rr == 2 ? t : 0.0f;
+                p3 += rr == 3 ? t : 0.0f;
+            }
+        }
+        float m0 = wave_total(p0) * inv_c, m1 = 0.0f, m2 = 0.0f, m3 = 0.0f;
+        if (R > 1) m1 = wave_total(p1) * inv_c;
+        if (R > 2) {
+            m2 = wave_total(p2) * inv_c;
+            m3 = wave_total(p3) * inv_c;
+        }
+
+        // round 2: sum d^2, sum gw, sum gw * d
+        float d[NIT][VEC];
+        float v0 = 0.0f, v1 = 0.0f, v2 = 0.0f, v3 = 0.0f;  // sum d^2
+        float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;  // sum gw
+        float b0 = 0.0f, b1 = 0.0f, b2 = 0.0f, b3 = 0.0f;  // sum gw * d
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int ro = rowof[it];
+            const int rr = ro < 0 ? -1 : (ro & 3);
+            const bool grad = ro >= 0 && ro < 4;  // a live slot of a row that has a gradient
+            const float m = pick4(rr, m0, m1, m2, m3, R);
+            Pack<TG, VEC> pg;
+            __builtin_memcpy(&pg, &graw[it], 16);
+            slot_f32<TS>(xraw[it], d[it]);
+            float u = 0.0f, sa = 0.0f, sb = 0.0f;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                d[it][e] = d[it][e] - m;
+                const float gwe = to_f32(pg.e[e]) * wgt[it][e];
+                u = __fmaf_rn(d[it][e], d[it][e], u);
+                sa += gwe;
+                sb = __fmaf_rn(gwe, d[it][e], sb);
+            }
+            u = rr >= 0 ? u : 0.0f;
+            sa = grad ? sa : 0.0f;
+            sb = grad ? sb : 0.0f;
+            v0 += rr == 0 ? u : 0.0f;
+            a0 += rr == 0 ? sa : 0.0f;
+            b0 += rr == 0 ? sb : 0.0f;
+            if (R > 1) {
+                v1 += rr == 1 ? u : 0.0f;
+                a1 += rr == 1 ? sa : 0.0f;
+                b1 += rr == 1 ? sb : 0.0f;
+            }
+            if (R > 2) {
+                v2 += rr == 2 ? u : 0.0f;
+                a2 += rr == 2 ? sa : 0.0f;
+                b2 += rr == 2 ? sb : 0.0f;
+                v3 += rr == 3 ? u : 0.0f;
+                a3 += rr == 3 ? sa : 0.0f;
+                b3 += rr == 3 ? sb : 0.0f;
+            }
+        }
+        // per row: rstd, mean(gw), k = rstd * mean(gw * xhat) = rstd^2 * sum(gw * d) / C   (xhat * mean(.) = d * k)
+        float r0 = __builtin_amdgcn_rsqf(wave_total(v0) * inv_c + eps), r1 = 0.0f, r2 = 0.0f, r3 = 0.0f;
+        float g_0 = wave_total(a0) * inv_c, g_1 = 0.0f, g_2 = 0.0f, g_3 = 0.0f;
+        float k0 = r0 * (r0 * (wave_total(b0) * inv_c)), k1 = 0.0f, k2 = 0.0f, k3 = 0.0f;
+        if (R > 1) {
+            r1 = __builtin_amdgcn_rsqf(wave_total(v1) * inv_c + eps);
+            g_1 = wave_total(a1) * inv_c;
+            k1 = r1 * (r1 * (wave_total(b1) * inv_c));
+        }
+        if (R > 2) {
+            r2 = __builtin_amdgcn_rsqf(wave_total(v2) * inv_c + eps);
+            g_2 = wave_total(a2) * inv_c;
+            k2 = r2 * (r2 * (wave_total(b2) * inv_c));
+            r3 = __builtin_amdgcn_rsqf(wave_total(v3) * inv_c + eps);
+            g_3 = wave_total(a3) * inv_c;
+            k3 = r3 * (r3 * (wave_total(b3) * inv_c));
+        }
+
+        TS *gxl = gx + (int64_t)row0 * C;
+        TG *g16l = gx16 ? gx16 + (int64_t)row0 * C : nullptr;
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int ro = rowof[it];
+            if (ro < 0) continue;
+            const int q = it * WAVE + lane;
+            float o[VEC];
+            if (ro >= 4) {  // class row: its gradient is what the residual stream brings, moved as raw bits
+                Slot<TS> z = {};
+                if (has_in) z = iraw[it];
+                st_slot<TS>(gxl, q, z);
+                if (g16l) {
+                    slot_f32<TS>(z, o);
+                    st_slot<TG>(g16l, q, f32_slot<TG>(o));
+                }
+                continue;
+            }
+            const float rs = pick4(ro, r0, r1, r2, r3, R), mg = pick4(ro, g_0, g_1, g_2, g_3, R),
+                        kk = pick4(ro, k0, k1, k2, k3, R);
+            float gi[VEC];
+            if (has_in) slot_f32<TS>(iraw[it], gi);
+            Pack<TG, VEC> pg;
+            __builtin_memcpy(&pg, &graw[it], 16);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                const float gyv = to_f32(pg.e[e]);
+                const float t = __fmaf_rn(-d[it][e], kk, gyv * wgt[it][e] - mg);
+                // one rounding to the stream's dtype (none for fp32); gx16 rounds the stored fp32 value
+                o[e] = to_f32(from_f32<TS>(has_in ? __fmaf_rn(rs, t, gi[e]) : rs * t));
+                if (PARAMS) {
+                    aw[it][e] = __fmaf_rn(gyv, d[it][e] * rs, aw[it][e]);
+                    ab[it][e] += gyv;
+                }
+            }
+            st_slot<TS>(gxl, q, f32_slot<TS>(o));
+            if (g16l) st_slot<TG>(g16l, q, f32_slot<TG>(o));
+        }
+    }
+
+    if (PARAMS) {
+        // the workgroup's partial row: slots of the four waves through LDS, summed wave 0..3, row-in-wave 0..R-1
+        __shared__ float red[4][NIT * WAVE][VEC];
+#pragma unroll
+        for (int which = 0; which < 2; ++which) {
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                if (rr_of[it] < 0) continue;
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) red[wv][it * WAVE + lane][e] = which == 0 ? aw[it][e] : ab[it][e];
+            }
+            __syncthreads();
+            float *dst = ws + ((int64_t)blockIdx.x * 2 + which) * C;
+            for (int cc = threadIdx.x; cc < cpr; cc += 256) {
+                float sum[VEC];
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) sum[e] = 0.0f;
+                for (int w = 0; w < 4; ++w)
+                    for (int rr = 0; rr < R; ++rr)
+#pragma unroll
+                        for (int e = 0; e < VEC; ++e) sum[e] += red[w][rr * cpr + cc][e];
+                *reinterpret_cast<float4 *>(dst + cc * VEC) = float4{sum[0], sum[1], sum[2], sum[3]};
+                *reinterpret_cast<float4 *>(dst + cc * VEC + 4) = float4{sum[4], sum[5], sum[6], sum[7]};
+            }
+            __syncthreads();
+        }
+    }
+}

@@ -1183,6 +1183,177 @@ __global__ __launch_bounds__(256) void k_add_ln_rows(const TX *__restrict__ x, c
                      });
 }
 
+// ------------------------------------------------------------------------------------------------
+// Mixed precision (training under torch.autocast with fp32 master weights: tools/train_net.py:123,
+// tome/utils.py:54).  A lane SLOT is the 8 channels a 16-byte chunk of 16-bit tokens holds, whatever the byte width of
+// the tensor it is taken from: 16 bytes of a 16-bit tensor, 32 bytes (two 16-byte moves) of an fp32 one.  Slot q of a
+// wave's rows sits in lane q % 64, iteration q / 64, as the chunks of k_add_ln_rows do, so the packing (rows per wave,
+// slots per lane) of the two kernels is the same.
+// ------------------------------------------------------------------------------------------------
+template <typename T> struct Slot { uint4 q[sizeof(T) / 2]; };
+
+template <typename T> __device__ __forceinline__ Slot<T> ld_slot(const T *base, int64_t slot) {
+    Slot<T> s;
+    const uint4 *p = reinterpret_cast<const uint4 *>(base) + slot * (int64_t)(sizeof(T) / 2);
+#pragma unroll
+    for (int k = 0; k < (int)(sizeof(T) / 2); ++k) s.q[k] = ld16(p + k);
+    return s;
+}
+template <typename T> __device__ __forceinline__ void st_slot(T *base, int64_t slot, const Slot<T> &s) {
+    uint4 *p = reinterpret_cast<uint4 *>(base) + slot * (int64_t)(sizeof(T) / 2);
+#pragma unroll
+    for (int k = 0; k < (int)(sizeof(T) / 2); ++k) st16(p + k, s.q[k]);
+}
+template <typename T> __device__ __forceinline__ void slot_f32(const Slot<T> &s, float (&v)[8]) {
+    Pack<T, 8> p;
+    __builtin_memcpy(&p, &s, sizeof(p));
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = to_f32(p.e[e]);
+}
+template <typename T> __device__ __forceinline__ Slot<T> f32_slot(const float (&v)[8]) {  // one rounding (none: fp32)
+    Pack<T, 8> p;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) p.e[e] = from_f32<T>(v[e]);
+    Slot<T> s;
+    __builtin_memcpy(&s, &p, sizeof(p));
+    return s;
+}
+// the sum of a slot's 8 stored values: chunk_sum's dot products for 16-bit rows (ln_rows' bits), a chain of seven fp32
+// additions in channel order for fp32 rows
+template <typename T> __device__ __forceinline__ float slot_sum(const Slot<T> &s) {
+    if constexpr (std::is_same<T, float>::value) {
+        float v[8];
+        slot_f32<T>(s, v);
+        float t = v[0];
+#pragma unroll
+        for (int e = 1; e < 8; ++e) t += v[e];
+        return t;
+    } else {
+        return chunk_sum<T>(s.q[0]);
+    }
+}
+// the 8 fp32 values of a parameter slot (weight, bias: always fp32 under autocast), plain cached loads
+__device__ __forceinline__ void ld_param8(const float *__restrict__ p, int cc, float (&v)[8]) {
+    const float4 lo = *reinterpret_cast<const float4 *>(p + cc * 8), hi = *reinterpret_cast<const float4 *>(p + cc * 8 + 4);
+    v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w;
+    v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
+}
+
+// k_add_ln_rows_amp: k_add_ln_rows for a model that runs under autocast (tome_add_layernorm_amp).  TS: the residual
+// stream (x, x'), 16-bit or fp32; TA: the addend; TY: y, the 16-bit autocast dtype; weight and bias fp32.
+//   fp32 stream:   x' = x + (float)a, the fp32 sum, one rounding -- `x + a.float()` bit for bit
+//   16-bit stream: x' = round16(x + a), the bits k_add_ln_rows stores
+// The statistics are taken from the STORED row with ln_rows' arithmetic (two passes, centred variance, wave_total,
+// v_rsq_f32, 1/C as a multiplication); y = d * (rstd * w) + b as one multiply and one fma, rounded once to TY.
+// y_group as in k_add_ln_rows.  All loads of the wave's slots are issued before any use.
+template <typename TS, typename TA, typename TY, int NIT>
+__global__ __launch_bounds__(256) void k_add_ln_rows_amp(const TS *__restrict__ x, const TA *__restrict__ a, int64_t rows,
+                                                         int C, int R, int cpr, const float *__restrict__ lw,
+                                                         const float *__restrict__ lb, float eps, int y_group,
+                                                         TS *__restrict__ xout, TY *__restrict__ y) {
+    constexpr int VEC = 8;
+    const int lane = threadIdx.x & 63;
+    const int64_t w = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t row0 = w * R;
+    if (row0 >= rows) return;
+    const int nrow = (int)((rows - row0) < R ? (rows - row0) : R);
+    const int total = nrow * cpr;
+    const bool add = a != nullptr;  // nullptr: LayerNorm only, nothing is written to xout
+    const float inv_c = __builtin_amdgcn_rcpf((float)C);
+    const TS *xs = x + row0 * C;
+    const TA *as = a + row0 * C;
+    Slot<TS> raw[NIT] = {};
+    Slot<TA> rawa[NIT] = {};
+    int rowof[NIT];
+    float wv[NIT][VEC], bv[NIT][VEC];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const int q = it * WAVE + lane;
+        const int rr = (q >= cpr) + (q >= 2 * cpr) + (q >= 3 * cpr);
+        const bool live = q < total;
+        rowof[it] = live ? rr : -1;
+        if (live) {
+            raw[it] = ld_slot<TS>(xs, q);
+            if (add) rawa[it] = ld_slot<TA>(as, q);
+        }
+        const int cc = live ? q - rr * cpr : 0;
+        ld_param8(lw, cc, wv[it]);
+        ld_param8(lb, cc, bv[it]);
+    }
+    // x' and the first pass: the sums of the stored rows
+    float d[NIT][VEC];
+    float p0 = 0.0f, p1 = 0.0f, p2 = 0.0f, p3 = 0.0f;
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const int rr = rowof[it];
+        if (add && rr >= 0) {
+            float xa[VEC], av[VEC];
+            slot_f32<TS>(raw[it], xa);
+            slot_f32<TA>(rawa[it], av);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) xa[e] = __fadd_rn(xa[e], av[e]);
+            raw[it] = f32_slot<TS>(xa);
+            st_slot<TS>(xout + row0 * C, it * WAVE + lane, raw[it]);
+        }
+        slot_f32<TS>(raw[it], d[it]);  // the stored values; centred below
+        const float t = rr >= 0 ? slot_sum<TS>(raw[it]) : 0.0f;
+        p0 += rr == 0 ? t : 0.0f;
+        if (R > 1) p1 += rr == 1 ? t : 0.0f;
+        if (R > 2) {
+            p2 += rr == 2 ? t : 0.0f;
+            p3 += rr == 3 ? t : 0.0f;
+        }
+    }
+    float m0 = wave_total(p0) * inv_c, m1 = 0.0f, m2 = 0.0f, m3 = 0.0f;
+    if (R > 1) m1 = wave_total(p1) * inv_c;
+    if (R > 2) {
+        m2 = wave_total(p2) * inv_c;
+        m3 = wave_total(p3) * inv_c;
+    }
+    p0 = p1 = p2 = p3 = 0.0f;
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const int rr = rowof[it];
+        const float m = pick4(rr, m0, m1, m2, m3, R);
+        float u = 0.0f;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            d[it][e] = d[it][e] - m;
+            u = __fmaf_rn(d[it][e], d[it][e], u);
+        }
+        u = rr >= 0 ? u : 0.0f;
+        p0 += rr == 0 ? u : 0.0f;
+        if (R > 1) p1 += rr == 1 ? u : 0.0f;
+        if (R > 2) {
+            p2 += rr == 2 ? u : 0.0f;
+            p3 += rr == 3 ? u : 0.0f;
+        }
+    }
+    float r0 = __builtin_amdgcn_rsqf(wave_total(p0) * inv_c + eps), r1 = 0.0f, r2 = 0.0f, r3 = 0.0f;
+    if (R > 1) r1 = __builtin_amdgcn_rsqf(wave_total(p1) * inv_c + eps);
+    if (R > 2) {
+        r2 = __builtin_amdgcn_rsqf(wave_total(p2) * inv_c + eps);
+        r3 = __builtin_amdgcn_rsqf(wave_total(p3) * inv_c + eps);
+    }
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const int rr = rowof[it];
+        if (rr < 0) continue;
+        const int cc = it * WAVE + lane - rr * cpr;
+        const float rs = pick4(rr, r0, r1, r2, r3, R);
+        int64_t yrow = row0 + rr;
+        if (y_group > 0) {  // (k_add_ln_rows: the first row of every group has no place in y)
+            const int64_t gb = yrow / y_group;
+            if (yrow - gb * y_group == 0) continue;
+            yrow -= gb + 1;
+        }
+        float yv[VEC];
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) yv[e] = __fmaf_rn(d[it][e], wv[it][e] * rs, bv[it][e]);
+        st_slot<TY>(y + yrow * C, cc, f32_slot<TY>(yv));
+    }
+}
+
 // k_unmerge_rows: merge.py:87-100 as a scatter from the merged sequence: one wave per INPUT row; a
 // destination row also lands on every even slot that was merged into it.  src and unm partition the
 // even slots, so every output row is written exactly once and no zero fill is needed.

@@ -108,7 +108,9 @@ class VivitIntermediate(nn.Module):
 
     def forward(self, hidden_states):
         x = hidden_states
-        if x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and not torch.is_grad_enabled():
+        if (x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and self.dense.weight.dtype == x.dtype
+                and not torch.is_grad_enabled()):
+            # (weights of x's dtype: under autocast with fp32 master weights the Linear below casts, this op does not)
             # gelu_fast IS the tanh GELU, which is what the BLAS library's GEMM epilogue computes: projection, bias
             # and activation in one kernel (the separate activation pass over [B, 3137, 3072] disappears)
             y = torch._addmm_activation(self.dense.bias, x.reshape(-1, x.shape[-1]), self.dense.weight.t(), use_gelu=True)

@@ -81,6 +81,10 @@ SIGNATURES = {
                                           i64, i64, vp], True),
     "tome_gelu_tanh": (i32, [vp, i32, i64, vp, vp], True),
     "tome_gelu_tanh_backward": (i32, [vp, vp, i32, i64, i64, vp, vp, vp, vp, sz, vp], True),
+    "tome_add_layernorm_amp": (i32, [vp, i32, vp, i32, i64, i64, i32, i64, vp, vp, f32, vp, vp, i32, vp], True),
+    "tome_layernorm_backward_amp_workspace_bytes": (sz, [i64, i64, i32], True),
+    "tome_layernorm_backward_amp": (i32, [vp, i32, vp, vp, i32, i64, i64, i32, i64, vp, f32, vp, vp, vp, vp, vp, vp],
+                                         True),
 }
 SYMBOLS = tuple(SIGNATURES)
 
@@ -432,6 +436,35 @@ def ln_trainable(x: torch.Tensor, norm) -> bool:
     return type(norm) is torch.nn.LayerNorm and _ln_of(x, norm) and norm.bias.dtype == x.dtype
 
 
+def autocast_dtype(device) -> Optional[torch.dtype]:
+    """The 16-bit dtype autocast casts to on `device`, or None: autocast is off there, its dtype is not bf16 / fp16, or the
+    device is not the kernels' kind.  The one place the patch layer asks about autocast (the reference trains and
+    benchmarks under it: tools/train_net.py:123, tome/utils.py:54)."""
+    if device.type != "cuda" or not torch.is_autocast_enabled("cuda"):
+        return None
+    dtype = torch.get_autocast_dtype("cuda")
+    return dtype if dtype in _HALF else None
+
+
+def _ln_amp_of(x: torch.Tensor, norm, addend: Optional[torch.Tensor] = None) -> bool:
+    """The LayerNorm kind the mixed-precision kernels take under autocast, for a `norm` that is an nn.LayerNorm: fp32
+    weight and bias (master weights) over the C <= 1024 (C % 8 == 0) channels of x, where x is the autocast dtype with an
+    addend of the same (VideoMAE's stream, `pos_embed.type_as(x)`), or fp32 with an addend of the autocast dtype or fp32
+    (`x + self.pos_embed` has promoted the stream).  False whenever autocast is off: nothing changes without it."""
+    half = autocast_dtype(x.device)
+    if half is None:
+        return False
+    C = x.shape[-1]
+    if not (norm.elementwise_affine and norm.bias is not None and tuple(norm.normalized_shape) == (C,)
+            and norm.weight.dtype == torch.float32 and norm.bias.dtype == torch.float32 and C % 8 == 0 and C <= 1024):
+        return False
+    if addend is not None and (addend.shape != x.shape or addend.device != x.device):
+        return False
+    if x.dtype == half:
+        return addend is None or addend.dtype == half
+    return x.dtype == torch.float32 and (addend is None or addend.dtype == half or addend.dtype == torch.float32)
+
+
 def _out_bias(out_bias, x, C):
     if out_bias is None:
         return None
@@ -499,6 +532,53 @@ def add_layernorm(x: torch.Tensor, addend: Optional[torch.Tensor], weight: torch
                                           _stream(x.device))
     # (the name without an addend has always been the plain entry's)
     _check(rc, "tome_add_layernorm_skip_first" if skip_first and addend is not None else "tome_add_layernorm")
+    return (x if addend is None else x_out), y_out
+
+
+def _f32_params(what: str, C: int, device, *params):
+    for p in params:
+        if p.numel() != C or p.dtype != torch.float32 or p.device != device:
+            raise TomeHipError(f"{what}: the LayerNorm's parameters must hold {C} values of torch.float32 on {device}")
+    return [p.detach().contiguous() for p in params]
+
+
+def _amp_rows(what: str, x: torch.Tensor, skip_first: bool):
+    """(groups, group_rows) of [..., C] tokens for the mixed-precision entries."""
+    C = x.shape[-1]
+    if x.dim() < 2 or C % 8 or C > 1024 or x.numel() == 0:
+        raise TomeHipError(f"{what}: tokens must be [..., C] with C % 8 == 0 and C <= 1024, got {tuple(x.shape)}")
+    if skip_first:
+        if x.dim() != 3 or x.shape[1] < 2:
+            raise TomeHipError(f"{what}(skip_first): tokens must be [B, N >= 2, C]")
+        return x.shape[0], x.shape[1]
+    return x.numel() // C, 1
+
+
+def add_layernorm_amp(x: torch.Tensor, addend: Optional[torch.Tensor], weight: torch.Tensor, bias: torch.Tensor,
+                      eps: float, y_dtype: torch.dtype, skip_first: bool = False):
+    """tome_add_layernorm_amp: (x + addend, LayerNorm(x + addend)) in one launch for a model under autocast -- fp32
+    weight and bias, y of the 16-bit `y_dtype`, x of y_dtype (addend of the same) or fp32 (addend of y_dtype or fp32; the
+    sum is `x + addend.float()`).  addend None: LayerNorm only, x comes back as it is.  skip_first as in add_layernorm."""
+    require_device(x, "add_layernorm_amp(x)")
+    if y_dtype not in _HALF:
+        raise TomeHipError(f"add_layernorm_amp: y_dtype must be a 16-bit dtype, got {y_dtype}")
+    x = x if x.is_contiguous() else x.contiguous()
+    C = x.shape[-1]
+    groups, group_rows = _amp_rows("add_layernorm_amp", x, skip_first)
+    weight, bias = _f32_params("add_layernorm_amp", C, x.device, weight, bias)
+    if addend is not None:
+        if addend.shape != x.shape or addend.device != x.device:
+            raise TomeHipError("add_layernorm_amp: addend must match x in shape and device")
+        addend = addend if addend.is_contiguous() else addend.contiguous()
+    L = lib()
+    entry = require_symbol(L, "tome_add_layernorm_amp")
+    x_out = None if addend is None else torch.empty_like(x)
+    y_out = torch.empty((x.shape[0], x.shape[1] - 1, C) if skip_first else x.shape, dtype=y_dtype, device=x.device)
+    with _on_device(x.device):
+        rc = entry(x.data_ptr(), dtype_code(x, "x"), _ptr(addend), 0 if addend is None else dtype_code(addend, "addend"),
+                   groups, group_rows, int(bool(skip_first)), C, weight.data_ptr(), bias.data_ptr(), float(eps),
+                   _ptr(x_out), y_out.data_ptr(), DTYPES[y_dtype], _stream(x.device))
+    _check(rc, "tome_add_layernorm_amp")
     return (x if addend is None else x_out), y_out
 
 
@@ -1326,6 +1406,45 @@ def layernorm_backward(gy: torch.Tensor, xs: torch.Tensor, gx_in: Optional[torch
         gy_shape = tuple(xs.shape)
     return _layernorm_backward_call("layernorm_backward", gy, gy_shape, xs, gx_in, weight, eps, want_weight, want_bias,
                                     (groups, group_rows, int(bool(skip_first))), (groups * group_rows, C))
+
+
+def layernorm_backward_amp(gy: torch.Tensor, xs: torch.Tensor, gx_in: Optional[torch.Tensor], weight: torch.Tensor,
+                           eps: float, skip_first: bool = False, want_weight: bool = True, want_bias: bool = True,
+                           want_gx16: bool = False):
+    """tome_layernorm_backward_amp: layernorm_backward for the rows add_layernorm_amp stored.  gy: 16-bit gradient of y
+    (xs's shape; skip_first: [B, N-1, C]); xs, gx_in (optional) and the returned gx of gy's dtype or fp32; weight fp32;
+    dweight / dbias fp32.  want_gx16 (fp32 xs only): also gx rounded to gy's dtype, bit-equal to `gx.to(gy.dtype)`.
+    Returns (gx, gx16, dweight, dbias); what is not wanted is None.  No CPU path."""
+    what = "layernorm_backward_amp"
+    require_device(xs, f"{what}(xs)")
+    if gy.dtype not in _HALF or xs.dtype not in (gy.dtype, torch.float32):
+        raise TomeHipError(f"{what}: a 16-bit gy and xs of its dtype or fp32 required, got {gy.dtype} / {xs.dtype}")
+    if want_gx16 and xs.dtype != torch.float32:
+        raise TomeHipError(f"{what}: gx16 belongs to an fp32 stream")
+    C = xs.shape[-1]
+    groups, group_rows = _amp_rows(what, xs, skip_first)
+    gy_shape = (groups, group_rows - 1, C) if skip_first else tuple(xs.shape)
+    (weight,) = _f32_params(what, C, xs.device, weight)
+    gy = _prep_grad(gy, gy_shape, gy.dtype, xs.device, f"{what}(gy)")
+    if gx_in is not None:
+        gx_in = _prep_grad(gx_in, tuple(xs.shape), xs.dtype, xs.device, f"{what}(gx_in)")
+    xs = xs.detach()
+    xs = xs if xs.is_contiguous() else xs.contiguous()
+    L = lib()
+    entry = require_symbol(L, "tome_layernorm_backward_amp")
+    gx = torch.empty_like(xs)
+    gx16 = torch.empty_like(xs, dtype=gy.dtype) if want_gx16 else None
+    dweight = torch.empty(C, dtype=torch.float32, device=xs.device) if want_weight else None
+    dbias = torch.empty(C, dtype=torch.float32, device=xs.device) if want_bias else None
+    with _on_device(xs.device):
+        stream = _stream(xs.device)
+        ws = _sized_workspace(L, "tome_layernorm_backward_amp_workspace_bytes", (groups * group_rows, C, DTYPES[xs.dtype]),
+                              xs.device, stream, what) if want_weight or want_bias else None
+        rc = entry(gy.data_ptr(), DTYPES[gy.dtype], xs.data_ptr(), _ptr(gx_in), DTYPES[xs.dtype], groups, group_rows,
+                   int(bool(skip_first)), C, weight.data_ptr(), float(eps), gx.data_ptr(), _ptr(gx16), _ptr(dweight),
+                   _ptr(dbias), _ptr(ws), stream)
+    _check(rc, "tome_layernorm_backward_amp")
+    return gx, gx16, dweight, dbias
 
 
 def layernorm_backward_regrouped(gy: torch.Tensor, xs: torch.Tensor, gx_in: Optional[torch.Tensor], frames: int,

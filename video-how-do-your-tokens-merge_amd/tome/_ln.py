@@ -41,6 +41,14 @@ NATIVE_LN_BACKWARD = True
 NATIVE_LN_REGROUPED_BACKWARD = True
 
 
+# False: under autocast the callers take the framework's `x + a`, its fp32 layer_norm and the consumer's cast (the
+# behaviour before tome_add_layernorm_amp existed), in both grad modes -- for A/B in tests and tools/autocast_bench.py.
+# The Function form also needs enabled() below.  What the default rests on is said in DESIGN.md section 1.
+NATIVE_LN_AUTOCAST = True
+
+AMP_DIRECT, AMP_FUNCTION = "amp_direct", "amp_function"
+
+
 def regrouped_enabled() -> bool:
     return bool(NATIVE_LN_REGROUPED_BACKWARD and enabled())
 
@@ -53,12 +61,31 @@ def enabled() -> bool:
 def route(x: torch.Tensor, norm, addend=None, regrouped: bool = False):
     """How `norm(x [+ addend])` runs: None (the framework's ops: not the kind of tensors the kernel takes), "direct" (the
     launch itself: neither x, the addend nor the norm's weight or bias wants a gradient) or, when one does, "function"
-    (the same launch with the native backward behind it) where the switches and ln_trainable allow, else None."""
-    if not (isinstance(norm, torch.nn.LayerNorm) and _abi._ln_of(x, norm) and (addend is None or addend.dtype == x.dtype)):
+    (the same launch with the native backward behind it) where the switches and ln_trainable allow, else None.  Under
+    autocast, for tensors of the kind _abi._ln_amp_of describes, "amp_direct" / "amp_function": the mixed-precision
+    launch, by the same rule."""
+    if not isinstance(norm, torch.nn.LayerNorm):
         return None
+    if not (_abi._ln_of(x, norm) and (addend is None or addend.dtype == x.dtype)):
+        return None if regrouped else _route_amp(x, norm, addend)
     if not (torch.is_grad_enabled() and _abi.needs_grad(x, addend, norm.weight, norm.bias)):
         return "direct"
     return "function" if (regrouped_enabled() if regrouped else enabled()) and _abi.ln_trainable(x, norm) else None
+
+
+def _route_amp(x, norm, addend):
+    """route's answer for tensors the 16-bit kernels do not take: the mixed-precision forms under autocast, else None."""
+    if not (NATIVE_LN_AUTOCAST and _abi._ln_amp_of(x, norm, addend)):
+        return None
+    if not (torch.is_grad_enabled() and _abi.needs_grad(x, addend, norm.weight, norm.bias)):
+        return AMP_DIRECT
+    return AMP_FUNCTION if enabled() and type(norm) is torch.nn.LayerNorm else None  # (the stock module: ln_trainable)
+
+
+def ln_backward_amp(gy, xs, gx_in, weight, eps, skip_first, want_weight, want_bias, want_gx16):
+    """The backward arithmetic of the mixed-precision Functions: (gx, gx16, dweight, dbias).  A seam, like ln_backward."""
+    return _abi.layernorm_backward_amp(gy, xs, gx_in, weight, eps, skip_first=skip_first, want_weight=want_weight,
+                                       want_bias=want_bias, want_gx16=want_gx16)
 
 
 def ln_backward(gy, xs, gx_in, weight, eps, skip_first, want_weight, want_bias):
@@ -153,6 +180,76 @@ class _AddLayerNormRegroupedFunction(torch.autograd.Function):
                 None, None)
 
 
+def _backward_amp(ctx, g_sum, g_y, want_gx16):
+    """(gx, gx16, dweight, dbias) of the mixed-precision Functions: _backward with a 16-bit gy beside a stream of its own
+    dtype, fp32 parameter gradients and the optional 16-bit copy of gx."""
+    xs, weight = ctx.saved_tensors
+    want_w, want_b = ctx.needs_input_grad[ctx.first_param], ctx.needs_input_grad[ctx.first_param + 1]
+    if g_y is None:  # nothing read the LayerNorm: the stream's gradient passes through, the parameters get zeros
+        gx = g_sum if ctx.needs_x else None
+        gx16 = gx.to(ctx.y_dtype) if (want_gx16 and gx is not None) else None
+        return gx, gx16, (torch.zeros_like(weight) if want_w else None), (torch.zeros_like(weight) if want_b else None)
+    if g_y.dtype != ctx.y_dtype:
+        g_y = g_y.to(ctx.y_dtype)
+    if g_sum is not None and g_sum.dtype != xs.dtype:
+        g_sum = g_sum.to(xs.dtype)
+    gx, gx16, dw, db = ln_backward_amp(g_y, xs, g_sum, weight, ctx.eps, ctx.skip_first, want_w, want_b, want_gx16)
+    return (gx if ctx.needs_x else None), gx16, dw, db
+
+
+class _AddLayerNormAmpFunction(torch.autograd.Function):
+    """(x + addend, LayerNorm(x + addend)) under autocast: tome_add_layernorm_amp forward, tome_layernorm_backward_amp
+    backward.  x receives gx; the addend gx when it has the stream's dtype, gx16 when it is the 16-bit addend of an fp32
+    stream."""
+
+    @staticmethod
+    def forward(ctx, x, addend, weight, bias, eps, skip_first, y_dtype):
+        x_out, y = _abi.add_layernorm_amp(x.detach(), addend.detach(), weight.detach(), bias.detach(), eps, y_dtype,
+                                          skip_first=skip_first)
+        ctx.eps, ctx.skip_first, ctx.first_param, ctx.y_dtype = float(eps), bool(skip_first), 2, y_dtype
+        ctx.needs_x = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        ctx.addend16 = addend.dtype != x.dtype
+        ctx.save_for_backward(x_out, weight)
+        ctx.set_materialize_grads(False)  # an output nobody read arrives as None, not as a tensor of zeros
+        return x_out, y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_sum, g_y):
+        need = ctx.needs_input_grad
+        gx, gx16, dw, db = _backward_amp(ctx, g_sum, g_y, want_gx16=ctx.addend16 and need[1])
+        return (gx if need[0] else None), ((gx16 if ctx.addend16 else gx) if need[1] else None), dw, db, None, None, None
+
+
+class _LayerNormAmpFunction(torch.autograd.Function):
+    """LayerNorm(x) alone under autocast: tome_add_layernorm_amp without addend, tome_layernorm_backward_amp backward."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps, skip_first, y_dtype):
+        xs, y = _abi.add_layernorm_amp(x.detach(), None, weight.detach(), bias.detach(), eps, y_dtype,
+                                       skip_first=skip_first)
+        ctx.eps, ctx.skip_first, ctx.first_param, ctx.y_dtype = float(eps), bool(skip_first), 1, y_dtype
+        ctx.needs_x = ctx.needs_input_grad[0]
+        ctx.save_for_backward(xs, weight)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_y):
+        gx, _, dw, db = _backward_amp(ctx, None, g_y, want_gx16=False)
+        return gx, dw, db, None, None, None
+
+
+def _add_layernorm_amp(x, addend, norm, skip, how):
+    """add_layernorm's two mixed-precision forms: (x + addend, norm(x + addend)) with y of the autocast dtype."""
+    y_dtype = _abi.autocast_dtype(x.device)
+    if how == AMP_DIRECT:
+        return _abi.add_layernorm_amp(x, addend, norm.weight, norm.bias, norm.eps, y_dtype, skip_first=skip)
+    if addend is None:
+        return x, _LayerNormAmpFunction.apply(x, norm.weight, norm.bias, norm.eps, skip, y_dtype)
+    return _AddLayerNormAmpFunction.apply(x, addend, norm.weight, norm.bias, norm.eps, skip, y_dtype)
+
+
 def _check(x, norm, what):
     if not _abi.ln_trainable(x, norm):
         raise _abi.TomeHipError(f"{what}: this LayerNorm of {tuple(x.shape)} {x.dtype} tokens is not one the kernels take "
@@ -189,6 +286,8 @@ def add_layernorm(x, addend, norm, skip_first: bool = False, how=False):
     skip = bool(skip_first) and x.dim() == 3 and x.shape[1] >= 2
     if how == "direct":
         return (*_abi.add_layernorm(x, addend, norm.weight, norm.bias, norm.eps, skip_first=skip), skip)
+    if how == AMP_DIRECT or how == AMP_FUNCTION:
+        return (*_add_layernorm_amp(x, addend, norm, skip, how), skip)
     if addend is None:
         return x, layernorm_native(x, norm, skip_first=skip), skip
     return (*add_layernorm_native(x, addend, norm, skip_first=skip), skip)

@@ -346,10 +346,17 @@ def finish_linear(block, x, h, linear, info):
 
 def _trailing_norm(x, norm):
     """norm(x) behind a reduction step that ran on its own (the fused merge + LayerNorm launch is inference-only): the
-    streaming LayerNorm kernel as a Function (tome/_ln.py) when a gradient is wanted, the framework's otherwise."""
-    if _FUSE_LN and torch.is_grad_enabled():  # (the no-grad layer stops here, as it always has)
+    streaming LayerNorm kernel as a Function (tome/_ln.py) when a gradient is wanted, the framework's otherwise; under
+    autocast the mixed-precision form of that kernel in both grad modes when the route offers it."""
+    if _FUSE_LN and torch.is_grad_enabled():  # (without autocast the no-grad layer stops here, as it always has)
         how = _ln.route(x, norm)
-        if how == "function":
+        if how == "function" or how == _ln.AMP_FUNCTION or how == _ln.AMP_DIRECT:
+            return _ln.add_layernorm(x, None, norm, how=how)[1]
+    elif _FUSE_LN and _abi.autocast_dtype(x.device) is not None:
+        # under autocast the mixed-precision launch in no-grad too: the framework's fp32 LayerNorm writes fp32 and the
+        # Linear behind it casts (tome/_ln.py)
+        how = _ln.route(x, norm)
+        if how == _ln.AMP_DIRECT:
             return _ln.add_layernorm(x, None, norm, how=how)[1]
     return norm(x)
 
