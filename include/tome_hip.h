@@ -513,6 +513,24 @@ int tome_short_attention_backward(const void *q, const void *k, const void *v, c
 int tome_gelu_erf(const void *x, int dtype, int64_t elements, void *y, tome_stream_t stream);
 
 /*
+ * tome_token_mean  <-  the mean pooling in front of the head of a ViT without class token and the MLP in front of it
+ *     (slowfast/models/videomae_video_model_builder.py, forward_features: `x = self.norm(x)` with norm = nn.Identity(),
+ *     `return self.fc_norm(x.mean(1))`; the last block's `Mlp.forward`: `x = self.fc2(self.act(self.fc1(x)))`).  The
+ *     last block's output is read only through that unweighted mean, and everything behind the activation is linear:
+ *         mean_t(x'_t + b2 + W2 a_t) = mean_t(x'_t) + b2 + W2 mean_t(a_t)            a = gelu(fc1(norm2(x')))
+ *     so the block needs two column means instead of fc2 over every token (addition to ABI v11, no entry changed):
+ *         out[g, c] = (1 / tokens) * sum_t v[g, t, c]
+ *     x: contiguous [groups, tokens, width] of `dtype` (TOME_BF16 / TOME_F16, width % 8 == 0), 16-byte aligned; out: fp32
+ *     [groups, width].  act = 0: v = x.  act = 1: v = the 16-bit value tome_gelu_erf would have stored for x (rounded to
+ *     `dtype`, then widened), so the mean is taken of exactly the bits fc2 used to read; nothing is written but out.
+ *     fp32 sums in one fixed order (rows ascending per wave, the waves' sums added in wave order), one division by
+ *     `tokens`: no atomics, the same bits on every run; no workspace, no allocation, no synchronisation.
+ *     groups < 1, tokens < 1, width % 8 != 0, any other dtype or act, null or misaligned pointers: TOME_EINVAL.
+ */
+int tome_token_mean(const void *x, int dtype, int64_t groups, int64_t tokens, int64_t width, int act, float *out,
+                    tome_stream_t stream);
+
+/*
  * tome_gelu_erf_backward  <-  what autograd derives from the MLP of the patched block between its two Linear layers
  *     when its input or its parameters require grad (additions to ABI v11, no entry changed; models are patched for
  *     training, tools/train_net.py:727-741):

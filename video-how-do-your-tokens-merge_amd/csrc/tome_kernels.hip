@@ -3,7 +3,8 @@
 // -ffp-contract=off -shared -fPIC (csrc/build.py).  No torch, no CUDA, no portability layer.
 //
 // One translation unit: tome_common.h (types), tome_match.h, tome_merge.h, tome_merge_bwd.h, tome_ln_bwd.h,
-// tome_gelu_bwd.h, tome_short_attn_bwd.h, tome_traj_bwd.h and tome_partition.h (kernels), this file (host).
+// tome_gelu_bwd.h, tome_token_mean.h, tome_short_attn_bwd.h, tome_traj_bwd.h and tome_partition.h (kernels), this file
+// (host).
 //
 // Launch sequence of one matching (tome_match / tome_match_keys), kernels in tome_match.h:
 //   k_unit_rows[_heads]  keys -> fp32 unit vectors, even/odd split, MFMA-fragment order (HBM bound)
@@ -36,6 +37,8 @@
 // tome_gelu_bwd.h:
 //   k_gelu_bwd           gh = ga gelu'(h) (erf or tanh form), the activation again with the forward's bits, per-workgroup
 //                        partial rows of fc1's bias gradient (summed by k_ln_param_grad)        (HBM bound)
+// and of the last block of a mean-pooling ViT (tome_token_mean), tome_token_mean.h:
+//   k_token_mean         fp32 column mean over a clip's tokens, optionally of the exact-erf GELU's stored bits (HBM bound)
 // and of the proportional attention's backward (tome_prop_attention_backward), tome_attn_bwd.h:
 //   k_attn_bwd_dq        row statistics recomputed (two sweeps over the keys), dq, L and delta to the workspace
 //   k_attn_bwd_dkv       dk and dv per block of keys over all queries                          (MFMA bound)
@@ -65,6 +68,7 @@
 #include "tome_merge_bwd.h"
 #include "tome_ln_bwd.h"
 #include "tome_gelu_bwd.h"
+#include "tome_token_mean.h"
 #include "tome_partition.h"
 #include "tome_attn.h"
 #include "tome_attn_stream.h"
@@ -1537,6 +1541,33 @@ extern "C" int tome_gelu_erf(const void *x, int dtype, int64_t elements, void *y
 
 extern "C" int tome_gelu_tanh(const void *x, int dtype, int64_t elements, void *y, tome_stream_t stream) {
     return gelu_impl<GELU_TANH>("tome_gelu_tanh", x, dtype, elements, y, stream);
+}
+
+// tome_token_mean: one launch of k_token_mean, a workgroup per (group, 512-channel slab).
+extern "C" int tome_token_mean(const void *x, int dtype, int64_t groups, int64_t tokens, int64_t width, int act,
+                               float *out, tome_stream_t stream) {
+    if (!x || !out) return fail(TOME_EINVAL, "tome_token_mean: null pointer");
+    if (int rc = not_16bit("tome_token_mean", dtype, "tensors")) return rc;
+    if (act != TOKEN_MEAN_NONE && act != TOKEN_MEAN_GELU_ERF)
+        return fail(TOME_EINVAL, "tome_token_mean: act must be 0 (none) or 1 (exact-erf GELU), got %d", act);
+    if (groups < 1 || tokens < 1 || width < 8 || width % 8)
+        return fail(TOME_EINVAL, "tome_token_mean: groups >= 1, tokens >= 1 and width %% 8 == 0 required");
+    if (!aligned16(x) || ((uintptr_t)out & 3))
+        return fail(TOME_EINVAL, "tome_token_mean: x must be 16-byte aligned, out 4-byte aligned");
+    const int64_t slabs = (width + TOKEN_MEAN_SLAB - 1) / TOKEN_MEAN_SLAB;
+    if (width > 0x7fffffffLL - TOKEN_MEAN_SLAB || tokens > 0x7fffffffLL || groups > 0x7fffffffLL / slabs
+        || groups > INT64_MAX / tokens / width)
+        return fail(TOME_EINVAL, "tome_token_mean: too large");
+    hipStream_t st = (hipStream_t)stream;
+    return dispatch_x<false>(dtype, [&](auto tx) {
+        using TX = typename decltype(tx)::type;
+        auto launch = [&](auto a) {
+            hipLaunchKernelGGL((k_token_mean<TX, decltype(a)::value>), dim3((unsigned)(groups * slabs)), dim3(256), 0, st,
+                               (const TX *)x, tokens, (int)width, (int)slabs, out);
+            return check_launch("k_token_mean");
+        };
+        return act == TOKEN_MEAN_GELU_ERF ? launch(Op<TOKEN_MEAN_GELU_ERF>{}) : launch(Op<TOKEN_MEAN_NONE>{});
+    }, [&] { return not_16bit("tome_token_mean", dtype, "tensors"); });
 }
 
 // The launch form of k_gelu_bwd with the bias gradient for `rows` rows of `width`: S column slots per thread, U passes

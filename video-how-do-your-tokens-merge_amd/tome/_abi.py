@@ -85,6 +85,7 @@ SIGNATURES = {
     "tome_layernorm_backward_amp_workspace_bytes": (sz, [i64, i64, i32], True),
     "tome_layernorm_backward_amp": (i32, [vp, i32, vp, vp, i32, i64, i64, i32, i64, vp, f32, vp, vp, vp, vp, vp, vp],
                                          True),
+    "tome_token_mean": (i32, [vp, i32, i64, i64, i64, i32, vp, vp], True),
 }
 SYMBOLS = tuple(SIGNATURES)
 
@@ -1162,6 +1163,28 @@ def gelu_tanh(x: torch.Tensor, inplace: bool = False) -> torch.Tensor:
     """The tanh GELU (HF's gelu_fast, F.gelu(approximate="tanh")) of a contiguous 16-bit tensor in the sigmoid form of
     include/tome_hip.h: x * sigma(2 beta (x + kappa x^3)), no cancellation on the negative side; one streaming pass."""
     return _gelu("gelu_tanh", x, inplace)
+
+
+def token_mean_ok(x: torch.Tensor) -> bool:
+    """Can tome_token_mean read these tokens?  A contiguous 16-bit [groups, tokens, width] device tensor with
+    width % 8 == 0, 16-byte aligned, no gradient wanted."""
+    return (x.is_cuda and x.dim() == 3 and x.dtype in _HALF and x.is_contiguous() and x.numel() > 0
+            and x.shape[-1] % 8 == 0 and x.data_ptr() % 16 == 0 and not (torch.is_grad_enabled() and needs_grad(x)))
+
+
+def token_mean(x: torch.Tensor, gelu: bool = False) -> torch.Tensor:
+    """tome_token_mean: the fp32 mean over the tokens of x [groups, tokens, width] -> [groups, width]; gelu: of the
+    16-bit values gelu_erf(x) would hold (the activation is not written).  Fixed summation order, no atomics."""
+    if not token_mean_ok(x):
+        raise TomeHipError("token_mean: contiguous 16-bit [groups, tokens, width] device tensor with width % 8 == 0 "
+                           f"required, got {tuple(x.shape)} {x.dtype} on {x.device}")
+    groups, tokens, width = x.shape
+    entry = require_symbol(lib(), "tome_token_mean")
+    out = torch.empty((groups, width), dtype=torch.float32, device=x.device)
+    with _on_device(x.device):
+        rc = entry(x.data_ptr(), DTYPES[x.dtype], groups, tokens, width, int(bool(gelu)), out.data_ptr(), _stream(x.device))
+    _check(rc, "tome_token_mean")
+    return out
 
 
 GELU_BWD_MAX_WIDTH = 8192  # csrc/tome_kernels.hip: GELU_BWD_MAX_WIDTH

@@ -25,6 +25,8 @@ _FUSE_NEXT = os.environ.get("TOME_FUSE_NEXT", "1") != "0"  # 0 = second residual
 _ATTN_KERNEL = os.environ.get("TOME_ATTN_KERNEL", "1") != "0"  # 0 = the framework's fused attention (+ bias tensor)
 _GELU_KERNEL = os.environ.get("TOME_GELU_KERNEL", "1") != "0"  # 0 = the framework's GELU pass inside the MLP
 _FUSE_FC2 = os.environ.get("TOME_FUSE_FC2", "1") != "0"  # 0 = the MLP's second GEMM writes its own tensor, then an add
+# 0 = the last block of a mean-pooling ViT runs fc2 over every token and hands [B, T', C] to the host's `x.mean(1)`
+_POOL_TAIL = os.environ.get("TOME_POOL_TAIL", "1") != "0"
 _SKIP_FIRST = os.environ.get("TOME_SKIP_FIRST", "1") != "0"  # the temporal hand-over without the class row
 
 
@@ -163,9 +165,11 @@ class one_forward_at_a_time:
         return False
 
 
-def wrap_model_forward(model_wrapper: torch.nn.Module, blocks_of: Callable) -> None:
+def wrap_model_forward(model_wrapper: torch.nn.Module, blocks_of: Callable, pool_tail: Callable = None) -> None:
     """make_tome_class (videomae.py:160-169): every forward re-reads ``self.r`` into a per-layer list and
-    clears size/source."""
+    clears size/source.  pool_tail(wrapper) -> the last block when this forward's head reads that block's output through
+    an unweighted token mean alone (tome/patch/videomae.py::pooled_tail_block), else None: the block is named in
+    `_tome_info["_pool_tail"]` for this forward only, and may then return the pooled row (pooled_tail)."""
     base = model_wrapper.__class__
     if getattr(base, "_tome_tag", None) == "ToMeVisionTransformer":
         return
@@ -179,9 +183,13 @@ def wrap_model_forward(model_wrapper: torch.nn.Module, blocks_of: Callable) -> N
             self._tome_info["source"] = None
             self._tome_info.pop("_prenorm", None)
             self._tome_info.pop("_folded", None)
+            armed = pool_tail(self) if (pool_tail is not None and _POOL_TAIL) else None
+            if armed is not None:
+                self._tome_info["_pool_tail"] = armed
             try:
                 return super(sub, self).forward(*args, **kwdargs)
             finally:
+                self._tome_info.pop("_pool_tail", None)  # (a block called on its own never finds it)
                 if param is not None:
                     _overlap.join(param.device)  # (a matching on the side stream no block waited for: a raise mid-block)
 
@@ -255,6 +263,56 @@ def mlp_residual(block, mlp, x, y, info, scale=None, drop_path=None):
     if scale is not None:
         out = scale * out
     return finish_block(block, x, out if drop_path is None else drop_path(out), info)
+
+
+def _unhooked(*modules) -> bool:
+    return not any(m._forward_hooks or m._forward_pre_hooks for m in modules)
+
+
+def pool_tail_modules_ok(vit, block) -> bool:
+    """The module side of the pooled tail's predicate, no tensor and no device involved: `vit` pools its last block's
+    output by an unweighted token mean (`norm` the identity, `fc_norm` a LayerNorm), in `.eval()` mode, and `block`, its
+    last, is a plain ToMeBlock -- no layer scale, identity drop_path, a plain MLP with a biased fc2, one 16-bit dtype for
+    norm2 / fc1 / fc2 -- and nobody observes the block's output: no forward hook or pre-hook on the ViT, its norm, the
+    block (the MLP's modules: _plain_mlp), and none registered for all modules."""
+    from torch.nn.modules import module as _m
+    if _m._global_forward_hooks or _m._global_forward_pre_hooks:
+        return False
+    norm, fc_norm = getattr(vit, "norm", None), getattr(vit, "fc_norm", None)
+    if not (type(norm) is torch.nn.Identity and isinstance(fc_norm, torch.nn.LayerNorm) and not vit.training
+            and not block.training and has_tag(block, "ToMeBlock") and getattr(block, "gamma_2", 0) is None
+            and type(getattr(block, "drop_path", None)) is torch.nn.Identity
+            and _unhooked(vit, norm, block, block.drop_path) and _plain_mlp(block.mlp)):
+        return False
+    fc1, fc2, norm2 = block.mlp.fc1, block.mlp.fc2, getattr(block, "norm2", None)
+    dtype = fc2.weight.dtype
+    return (fc2.bias is not None and dtype in _abi._HALF and fc1.weight.dtype == dtype
+            and isinstance(norm2, torch.nn.LayerNorm) and norm2.elementwise_affine and norm2.weight.dtype == dtype
+            and fc1.in_features % 8 == 0 and fc1.out_features % 8 == 0 and fc2.out_features == fc1.in_features)
+
+
+def pool_tail_armed(block, x, info) -> bool:
+    """At the top of `block`: is it the one this forward named for the pooled tail (popped here), and are these the
+    tokens the tail takes -- 16-bit device tokens of the MLP's dtype, no grad mode, no autocast?"""
+    if info.get("_pool_tail") is not block:
+        return False
+    info.pop("_pool_tail")
+    return (x.is_cuda and x.dim() == 3 and x.dtype == block.mlp.fc2.weight.dtype and not torch.is_grad_enabled()
+            and not torch.is_autocast_enabled("cuda"))
+
+
+def pooled_tail(mlp, x, y):
+    """The end of the last block of a mean-pooling ViT, `mean_t(x + fc2(gelu(fc1(y))))` as [B, 1, C]: the mean commutes
+    with everything behind the activation, so fc2 multiplies one row per clip,
+        mean_t(x_t) + b2 + W2 mean_t(a_t),      a = gelu(fc1(y)),
+    with both means on tome_token_mean (the second of the bits tome_gelu_erf would have stored; the activation is never
+    written) and fp32 from the means to the one rounding at the end.  x: the merged stream WITHOUT fc2's bias folded in."""
+    h = mlp.fc1(y)
+    abar = _abi.token_mean(h if h.is_contiguous() else h.contiguous(), gelu=True)
+    xbar = _abi.token_mean(x if x.is_contiguous() else x.contiguous())
+    fc2 = mlp.fc2
+    pooled = torch.addmm(xbar + fc2.bias.float(), abar, fc2.weight.float().t())
+    return pooled.to(x.dtype)[:, None, :]
 
 
 def pick_reduction(mode: str, merge_fn, drop_fn, hybrid_fn):

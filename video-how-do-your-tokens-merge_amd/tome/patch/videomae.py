@@ -7,6 +7,7 @@ it in place and returns None, exactly like the reference; afterwards set ``model
 from __future__ import annotations
 
 import copy
+import sys
 
 import torch
 import torch.nn.functional as F
@@ -25,9 +26,13 @@ def _block_forward(self, x):
     # x = x + attn; x = merge(x); y = norm2(x) -- one kernel when the layer merges 16-bit tokens
     # (tome_merge_wavg_ln with the residual as addend), the three steps of the reference otherwise
     # (fold: x comes back with fc2's bias in it when `x + mlp(...)` below can be fc2's GEMM accumulating onto x)
-    fold = C.foldable(self.mlp.fc2, not self.training) if (self.gamma_2 is None and C._plain_mlp(self.mlp)) else None
+    pooled = C.pool_tail_armed(self, x, info)  # the last block of a model forward whose head only reads the token mean
+    fold = (C.foldable(self.mlp.fc2, not self.training)
+            if (not pooled and self.gamma_2 is None and C._plain_mlp(self.mlp)) else None)
     x, y = C.merge_then_norm(metric, x, info, self.norm2, self.reduction_function, videomae_merge,
                              residual=self.drop_path(attn), fold=fold)
+    if pooled:  # [B, 1, C]: the host's `x.mean(1)` over the one row gives it back bit for bit
+        return C.pooled_tail(self.mlp, x, y)
     # x + mlp(...), and the next block's norm1 of it handed over when that is possible
     return C.mlp_residual(self, self.mlp, x, y, info, scale=self.gamma_2, drop_path=self.drop_path)
 
@@ -79,6 +84,27 @@ def videomae_hybrid(metric, x, _tome_info):
     return C.reduce_hybrid(metric, x, _tome_info, r) if r > 0 else x
 
 
+def pooled_tail_block(wrapper):
+    """The last block, when this forward of `wrapper` may end in the pooled tail (tome/patch/_common.py::pooled_tail), else
+    None.  The head must be known to read the last block's output through `x.mean(1)` alone: the wrapper and the ViT are
+    exactly this repository's host classes (hosts.videomae.VideoMAE / VisionTransformer, found through sys.modules: a model
+    of that class has imported it; the reference's class of the same layout is not guessed at) with no forward put on the
+    instances, and the modules pass C.pool_tail_modules_ok.  Inference only: grad mode off."""
+    if torch.is_grad_enabled():
+        return None
+    host = sys.modules.get("hosts.videomae")
+    vit = getattr(wrapper, "model", None)
+    if (host is None or type(vit) is not host.VisionTransformer or type(wrapper).__bases__ != (host.VideoMAE,)
+            or "forward" in vit.__dict__ or "forward_features" in vit.__dict__ or "forward" in wrapper.__dict__
+            or len(vit.blocks) == 0):
+        return None
+    block = vit.blocks[-1]
+    if (getattr(block, "_tome_info", None) is not wrapper._tome_info or "forward" in block.__dict__
+            or any(b is block for b in vit.blocks[:-1])):  # (the same object earlier in the list would pool there)
+        return None
+    return block if C.pool_tail_modules_ok(vit, block) else None
+
+
 def _is_block(m) -> bool:
     return all(hasattr(m, a) for a in ("attn", "mlp", "norm1", "norm2", "gamma_1"))
 
@@ -97,7 +123,7 @@ def apply_duplicate_patch(model, layer_to_duplicate, quantity):
 def apply_patch(model_wrapper, trace_source: bool = False, prop_attn: bool = False, mode: str = "merge",
                 head_aggregation: str = "mean", threshold: float = 0.0, verbose: bool = False):
     model = model_wrapper.model
-    C.wrap_model_forward(model_wrapper, lambda w: w.model.blocks)
+    C.wrap_model_forward(model_wrapper, lambda w: w.model.blocks, pool_tail=pooled_tail_block)
     model_wrapper.r = 0
     model_wrapper._tome_info = C.new_tome_info(trace_source, prop_attn, mode, head_aggregation, threshold, verbose,
                                                class_token=False)
