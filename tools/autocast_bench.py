@@ -12,57 +12,25 @@ Stack level: one forward + backward of a two-block patched stack of every family
 
 One JSON line per case; `native_slower_beyond_spread` says whether the native median is above the switch-off median by
 more than the larger of the two min-max spreads (the project's rule for excluding a shape from a default-on switch).
+The exit status is always 0: this tool reports, it does not judge.
 `--out` (default profiles/r07_autocast_bench.jsonl) also receives the lines.  `--quick`: op level only."""
-import argparse
-import json
 import os
-import statistics
 import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "video-how-do-your-tokens-merge_amd"))
+import ab
+from tome import _ln
 
-from tome import _ln  # noqa: E402
-
-DEV = "cuda:0"
+DEV = ab.DEV
 HALF = torch.bfloat16
+SWITCH = (_ln, "NATIVE_LN_AUTOCAST")
 
 
-def _time(fn, iters):
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    stop.record()
-    stop.synchronize()
-    return start.elapsed_time(stop) * 1e3 / iters  # us
-
-
-def _stats(xs):
-    return {"median_us": round(statistics.median(xs), 1), "min_us": round(min(xs), 1), "max_us": round(max(xs), 1)}
-
-
-def _compare(native, off):
-    a, b = _stats(native), _stats(off)
-    spread = max(a["max_us"] - a["min_us"], b["max_us"] - b["min_us"])
+def report(times):
+    a, b = ab.summary(times[True]), ab.summary(times[False])
     return {"native": a, "switch_off": b, "speedup_median": round(b["median_us"] / a["median_us"], 3),
-            "native_slower_beyond_spread": a["median_us"] - b["median_us"] > spread}
-
-
-def _alternate(fn, rounds, iters):
-    """fn() timed with the switch on and off in alternated rounds; ({True: [...], False: [...]})."""
-    times = {True: [], False: []}
-    for flag in (True, False):
-        _ln.NATIVE_LN_AUTOCAST = flag
-        _time(fn, 2)
-    for _ in range(rounds):
-        for flag in (True, False):
-            _ln.NATIVE_LN_AUTOCAST = flag
-            times[flag].append(_time(fn, iters))
-    _ln.NATIVE_LN_AUTOCAST = True
-    return times
+            "native_slower_beyond_spread": ab.tie_within_spread(a, b) != "tie"}
 
 
 def op_case(n, N, stream, rounds, iters, C=768):
@@ -97,8 +65,7 @@ def op_case(n, N, stream, rounds, iters, C=768):
     out = {"level": "op", "rows": n * N, "n": n, "rows_per_clip": N, "C": C, "stream": str(stream).replace("torch.", ""),
            "autocast": "bfloat16"}
     for label, fn in (("forward", forward), ("forward_backward", step)):
-        t = _alternate(fn, rounds, iters)
-        out[label] = _compare(t[True], t[False])
+        out[label] = report(ab.alternate(ab.switch_arms(*SWITCH), rounds, iters, fn=fn, warm=2))
     return out
 
 
@@ -113,47 +80,24 @@ def _stacks():
 
 
 def stack_case(name, make, clip_shape, patch, rounds, iters, batch):
-    torch.manual_seed(0)
-    model = make().to(DEV).train()
-    patch(model, prop_attn=True)
-    clip = torch.rand(batch, *clip_shape, device=DEV)
-
-    def step():
-        model.zero_grad(set_to_none=True)
-        model.r = 16
-        with torch.autocast("cuda", dtype=HALF):
-            out = model([clip])
-        out.float().square().sum().backward()
-
-    t = _alternate(step, rounds, iters)
+    times = ab.model_train_step(make, patch, clip_shape, batch, 16, SWITCH, rounds, iters, warm=2, autocast=HALF,
+                                prop_attn=True)
     return dict({"level": "stack", "family": name, "blocks": 2, "batch": batch, "mode": "train", "r": 16,
-                 "autocast": "bfloat16"}, forward_backward=_compare(t[True], t[False]))
+                 "autocast": "bfloat16"}, forward_backward=report(times))
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--iters", type=int, default=10)
+    ap = ab.parser(out=os.path.join(ab.ROOT, "profiles", "r07_autocast_bench.jsonl"))
     ap.add_argument("--batch", type=int, default=8)
-    ap.add_argument("--quick", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r07_autocast_bench.jsonl"))
     a = ap.parse_args()
-    lines = []
-
-    def emit(res):
-        lines.append(json.dumps(res))
-        print(lines[-1], flush=True)
-
-    emit(op_case(8, 1568, HALF, a.rounds, a.iters))
-    emit(op_case(8, 1 + 196 * 8, torch.float32, a.rounds, a.iters))
+    lines = ab.Lines(a.out)
+    lines.emit(op_case(8, 1568, HALF, a.rounds, a.iters))
+    lines.emit(op_case(8, 1 + 196 * 8, torch.float32, a.rounds, a.iters))
     if not a.quick:
         for name, make, clip_shape, patch in _stacks():
             torch.cuda.empty_cache()
-            emit(stack_case(name, make, clip_shape, patch, a.rounds, max(1, a.iters // 3), a.batch))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+            lines.emit(stack_case(name, make, clip_shape, patch, a.rounds, max(1, a.iters // 3), a.batch))
+    lines.write()
     return 0
 
 

@@ -15,47 +15,19 @@ entries existed).  One process, alternated rounds, device events, medians with m
      `linear`, whose backward sums three [B, S, F, C] gradients of y -- forward + backward time of that piece alone, for a
      later change to weigh.
 `verdict` (the rule of tools/mlp_backward_bench.py): "tie" when the native median is not above the switch-off median by
-more than the larger of the two paths' own min-max spreads, "native slower" otherwise.  `--quick` runs the reduced stack
-only."""
-import argparse
-import json
-import os
+more than the larger of the two paths' own min-max spreads, "native slower" otherwise; exit status 1 when a stack case
+is not a tie.  `--quick` runs the reduced stack only."""
 import statistics
 import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "video-how-do-your-tokens-merge_amd"))
+import ab
+from tome import _abi, _attn
 
-from tome import _abi, _attn  # noqa: E402
-
-DEV = "cuda:0"
-PEAK_TBS = 8.0
+DEV = ab.DEV
 BF = torch.bfloat16
 SWITCH = (_attn, "NATIVE_TRAJECTORY_BACKWARD")
-
-
-def _time(fn, iters):
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    stop.record()
-    stop.synchronize()
-    return start.elapsed_time(stop) * 1e3 / iters  # us
-
-
-def _stats(xs):
-    return {"median_us": round(statistics.median(xs), 1), "min_us": round(min(xs), 1), "max_us": round(max(xs), 1)}
-
-
-def _compare(times, what):
-    nat, fw = _stats(times[True]), _stats(times[False])
-    spread = max(nat["max_us"] - nat["min_us"], fw["max_us"] - fw["min_us"])
-    return {"native_" + what: nat, "switch_off_" + what: fw, "larger_spread_us": round(spread, 1),
-            "native_over_switch_off_median": round(nat["median_us"] / fw["median_us"], 3),
-            "verdict": "tie" if nat["median_us"] <= fw["median_us"] + spread else "native slower"}
 
 
 def stack_case(label, embed, heads, F, P, depth, B, r, rounds, iters):
@@ -83,25 +55,21 @@ def stack_case(label, embed, heads, F, P, depth, B, r, rounds, iters):
             x = blk(x, seq_len=P, num_frames=F)
         x.float().square().sum().backward()
 
-    out = {"stage": "block stack fwd + bwd", "shape": label, "embed": embed, "heads": heads, "F": F, "P": P,
-           "depth": depth, "B": B, "r": r, "dtype": "bfloat16"}
-    times = {True: [], False: []}
     peak = {}
-    for flag in (True, False):  # warm-up of every path, then its peak memory
-        setattr(*SWITCH, flag)
-        step()
+
+    def warm(flag, run):  # warm-up of every path, then its peak memory
+        run()
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
         base = torch.cuda.memory_allocated()
-        step()
+        run()
         torch.cuda.synchronize()
         peak[flag] = torch.cuda.max_memory_allocated() - base
-    for _ in range(rounds):
-        for flag in (True, False):
-            setattr(*SWITCH, flag)
-            times[flag].append(_time(step, iters))
-    setattr(*SWITCH, True)
-    out.update(_compare(times, "step"))
+
+    out = {"stage": "block stack fwd + bwd", "shape": label, "embed": embed, "heads": heads, "F": F, "P": P,
+           "depth": depth, "B": B, "r": r, "dtype": "bfloat16"}
+    times = ab.alternate(ab.switch_arms(*SWITCH), rounds, iters, fn=step, warm=warm)
+    out.update(ab.tie_report(times, "step", other="switch_off"))
     out["native_peak_bytes"], out["switch_off_peak_bytes"] = peak[True], peak[False]
     return out
 
@@ -114,12 +82,7 @@ def entries_case(B, H, F, P, rounds, iters):
     with torch.no_grad():
         q2, k2, val, g = rnd(B, S, C), rnd(B, S, F, C), rnd(B, S, F, C), rnd(B, S, C)
         mix = lambda: _abi.trajectory_mix_backward(q2, k2, val, g, H, 0.125)  # noqa: E731
-        mix()
-        t = [_time(mix, iters) for _ in range(rounds)]
-        nbytes = (4 * F + 3) * B * S * C * 2
-        med = statistics.median(t)
-        out["trajectory_mix_backward"] = dict(_stats(t), bytes=nbytes, TBps=round(nbytes / med / 1e6, 2),
-                                              share_of_8TBps=round(nbytes / med / 1e6 / PEAK_TBS, 3))
+        out["trajectory_mix_backward"] = ab.bandwidth(ab.launch_alone(mix, rounds, iters), (4 * F + 3) * B * S * C * 2)
         del k2, val
         qkv = rnd(B, 1 + S, 3, H, 64).permute(2, 0, 3, 1, 4)
         q, k, v = qkv[0][:, :, 1:], qkv[1][:, :, 1:], qkv[2][:, :, 1:]
@@ -127,11 +90,9 @@ def entries_case(B, H, F, P, rounds, iters):
         y = _abi.prop_attention_segments(q, k, v, F, 0.125, log_bias=bias)
         gy = rnd(*y.shape)
         seg = lambda: _abi.prop_attention_segments_backward(q, k, v, y, gy, F, 0.125, log_bias=bias)  # noqa: E731
-        seg()
-        t = [_time(seg, iters) for _ in range(rounds)]
+        t = ab.launch_alone(seg, rounds, iters)
         flop = 10 * B * H * S * S * 64
-        med = statistics.median(t)
-        out["segments_backward"] = dict(_stats(t), flop=flop, TFLOPs=round(flop / med / 1e6, 1))
+        out["segments_backward"] = dict(ab.summary(t), flop=flop, TFLOPs=round(flop / statistics.median(t) / 1e6, 1))
     return out
 
 
@@ -152,30 +113,23 @@ def glue_case(B, H, F, P, rounds, iters):
         k2 = proj_k(y)
         torch.autograd.backward((q2, k2, y), (gq, gk, gv))  # y itself is the mix's `val`: three gradients of y are summed
 
-    step()
-    t = [_time(step, iters) for _ in range(rounds)]
     return {"stage": "framework glue fwd + bwd (diagonal, proj_q, keys-only linear)", "B": B, "H": H, "F": F, "P": P,
-            "dtype": "bfloat16", **_stats(t)}
+            "dtype": "bfloat16", **ab.summary(ab.launch_alone(step, rounds, iters))}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--quick", action="store_true")
+    ap = ab.parser(iters=5)
     ap.add_argument("--glue", action="store_true")
-    ap.add_argument("--out", default=None, help="also write the JSON lines to this file")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("motionformer_backward_bench: needs the GPU (no CPU path, no fallback)")
-    lines, ok = [], True
+    lines, ok = ab.Lines(a.out), True
 
     def emit(res):
         nonlocal ok
         ok = ok and res.get("verdict", "tie") == "tie"
         torch.cuda.empty_cache()
-        lines.append(json.dumps(res))
-        print(lines[-1], flush=True)
+        lines.emit(res)
 
     emit(stack_case("reduced", 128, 2, 8, 49, 2, 8, 3, a.rounds, a.iters))
     if not a.quick:
@@ -184,10 +138,7 @@ def main():
         emit(entries_case(8, 12, 8, 196, a.rounds, a.iters))
         if a.glue:
             emit(glue_case(8, 12, 8, 196, a.rounds, a.iters))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    lines.write()
     return 0 if ok else 1
 
 
