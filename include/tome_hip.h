@@ -187,6 +187,32 @@ int tome_drop_regrouped(const void *x, int dtype, int64_t B, int64_t F, int64_t 
                         int has_cls, const int64_t *und_idx, void *x_out, tome_stream_t stream);
 
 /*
+ * tome_drop_ln  <-  the drop step of a patched block between its first residual and its second LayerNorm:
+ *     x = x + attn; x = drop(x); ... self.norm2(x)      (videomae_drop, tome/patch/videomae.py:103-127, with the
+ *     block around it, videomae.py:20-27; vivit_drop likewise)
+ * one launch instead of an add pass, tome_drop and a LayerNorm pass.  Added to ABI v11 after its first release.
+ * x [n,T,C], 16-bit, C % 8 == 0, C <= 1024; und_idx, distill_token and r as tome_drop.
+ * addend: NULL, or [n,T,C] like x: the rows that are kept are round_to_dtype(x + addend).
+ * x_out [n,T-r,C]: the rows tome_drop keeps of that sum, bit for bit.  y_out [n,T-r,C] = LayerNorm(x_out) (weight,
+ * bias [C] of the token dtype, eps) in fp32 from the stored row, rounded once: the arithmetic of tome_add_layernorm.
+ * x_out_bias: NULL, or [C]: as in tome_merge_wavg_ln -- stored into x_out, y_out is the norm of the row without it.
+ * Every buffer 16-byte aligned.  Each refusal is made on the host, before any launch, with its own tome_last_error.
+ */
+int tome_drop_ln(const void *x, int dtype, int64_t n, int64_t T, int64_t C, int64_t r, const int64_t *und_idx,
+                 int distill_token, const void *ln_weight, const void *ln_bias, float eps, const void *addend,
+                 void *x_out, void *y_out, const void *x_out_bias, tome_stream_t stream);
+
+/* tome_drop_ln on the interleaved layout of tome_drop_regrouped: timesformer_drop / motionformer_drop
+ * (tome/patch/timesformer.py:111-131, motionformer.py:172-193) with the residual in front and norm2 behind them
+ * (timesformer.py:52-56, motionformer.py:24-29) in one launch.  The class-token rows get the same add + LayerNorm.
+ * addend / addend_grouped / cls_addend and x_out_bias: as in tome_merge_wavg_regrouped_ln.  Added to ABI v11 after its
+ * first release. */
+int tome_drop_regrouped_ln(const void *x, int dtype, int64_t B, int64_t F, int64_t P, int64_t C, int64_t r,
+                           int has_cls, const int64_t *und_idx, const void *ln_weight, const void *ln_bias, float eps,
+                           const void *addend, int addend_grouped, const void *cls_addend, void *x_out, void *y_out,
+                           const void *x_out_bias, tome_stream_t stream);
+
+/*
  * tome_prop_attention  <-  the proportional attention of the patched attention modules:
  *     attn = softmax(q k^T * scale + size.log()[:, None, None, :, 0]) ; x = attn @ v
  *     (ToMeAttention.forward, tome/patch/videomae.py:55-66; vivit.py:95-113; timesformer.py:66-78 with the bias

@@ -631,9 +631,12 @@ static int launch_merge_rows(const void *x, const void *size, int64_t n, int64_t
             return check_launch("k_merge_rows_fast");
         };
         if (ln_p) {
-            if (OP != OP_WAVG || sizeof(TX) != 2 || cpr > 2 * WAVE || !aligned16(ln_p->y) || !aligned16(ln_p->weight) ||
-                !aligned16(ln_p->bias))
+            if ((OP != OP_WAVG && OP != OP_DROP) || sizeof(TX) != 2 || cpr > 2 * WAVE || !aligned16(ln_p->y) ||
+                !aligned16(ln_p->weight) || !aligned16(ln_p->bias))
                 return fail(TOME_EINVAL, "fused LayerNorm needs 16-bit tokens with C <= 1024 and 16-byte aligned buffers");
+            // drop: every kept row is a streamed row -- no edge waves, no EAGER form, merge_sched stays off
+            if constexpr (OP == OP_DROP && sizeof(TX) == 2)
+                return nit == 3 ? launch(FastForm<3, true, false>{}) : launch(FastForm<6, true, false>{});
             if constexpr (OP == OP_WAVG && sizeof(TX) == 2) {
                 // many destinations receive sources: the streaming waves skip those rows (EAGER, csrc/tome_merge.h)
                 if (r <= 64 && 8 * r >= T)
@@ -1097,6 +1100,73 @@ extern "C" int tome_drop_regrouped(const void *x, int dtype, int64_t B, int64_t 
             x, nullptr, n, P, C, r, nullptr, nullptr, und_idx, 0, nullptr, x_out, nullptr, (hipStream_t)stream, &lin,
             &lout, cls ? (int)B : 0);
     }, [&] { return fail(TOME_EINVAL, "tome_drop_regrouped: dtype %d", dtype); });
+}
+
+// What tome_drop_ln and tome_drop_regrouped_ln ask beyond check_merge_args, one text per fault, before any launch:
+// 16-bit tokens of C % 8 == 0, C <= 1024 channels, every buffer the kernel moves in 16-byte chunks aligned.
+static int check_drop_ln_args(const char *who, const void *x, int dtype, int64_t C, const void *ln_weight,
+                              const void *ln_bias, const void *addend, const void *cls_addend, const void *x_out,
+                              const void *y_out, const void *x_out_bias) {
+    if (!y_out || !ln_weight || !ln_bias) return fail(TOME_EINVAL, "%s: null buffer", who);
+    if (dtype != TOME_BF16 && dtype != TOME_F16) return fail(TOME_EINVAL, "%s: 16-bit tokens only (dtype=%d)", who, dtype);
+    if (C % 8 != 0 || C > 1024)
+        return fail(TOME_EINVAL, "%s: C=%lld must be a multiple of 8, at most 1024", who, (long long)C);
+    if (!aligned16(x) || !aligned16(x_out)) return fail(TOME_EINVAL, "%s: x / x_out not 16-byte aligned", who);
+    if (!aligned16(y_out)) return fail(TOME_EINVAL, "%s: y_out not 16-byte aligned", who);
+    if (!aligned16(ln_weight) || !aligned16(ln_bias))
+        return fail(TOME_EINVAL, "%s: ln_weight / ln_bias not 16-byte aligned", who);
+    if ((addend && !aligned16(addend)) || (cls_addend && !aligned16(cls_addend)))
+        return fail(TOME_EINVAL, "%s: addend not 16-byte aligned", who);
+    if (x_out_bias && !aligned16(x_out_bias)) return fail(TOME_EINVAL, "%s: x_out_bias not 16-byte aligned", who);
+    return TOME_OK;
+}
+
+// tome_drop with the residual add in front and the block's second LayerNorm behind it: the streaming waves of
+// k_merge_rows_fast<.., OP_DROP, .., LN> (every kept row is one; there are no edge waves)
+extern "C" int tome_drop_ln(const void *x, int dtype, int64_t n, int64_t T, int64_t C, int64_t r, const int64_t *und_idx,
+                            int distill_token, const void *ln_weight, const void *ln_bias, float eps,
+                            const void *addend, void *x_out, void *y_out, const void *x_out_bias,
+                            tome_stream_t stream) {
+    if (int rc = check_merge_args("tome_drop_ln", x, n, T, C, r, x_out)) return rc;
+    if (!und_idx && (T + 1) / 2 > r) return fail(TOME_EINVAL, "tome_drop_ln: null index buffer");
+    if (int rc = check_drop_ln_args("tome_drop_ln", x, dtype, C, ln_weight, ln_bias, addend, nullptr, x_out, y_out,
+                                    x_out_bias))
+        return rc;
+    const LnArgs ln{ln_weight, ln_bias, y_out, eps, addend, 0, TokLayout{0, 0, 0, 0, 1}, nullptr, 0, x_out_bias};
+    return dispatch_x<false>(dtype, [&](auto tx) {
+        return launch_merge_rows<typename decltype(tx)::type, float, OP_DROP>(
+            x, nullptr, n, T, C, r, nullptr, nullptr, und_idx, distill_token, nullptr, x_out, nullptr,
+            (hipStream_t)stream, nullptr, nullptr, 0, &ln);
+    }, [&] { return fail(TOME_EINVAL, "tome_drop_ln: 16-bit tokens only (dtype=%d)", dtype); });
+}
+
+// tome_drop_ln on the interleaved layout: the class rows take the same add + LayerNorm (the gy >= n block)
+extern "C" int tome_drop_regrouped_ln(const void *x, int dtype, int64_t B, int64_t F, int64_t P, int64_t C, int64_t r,
+                                      int has_cls, const int64_t *und_idx, const void *ln_weight, const void *ln_bias,
+                                      float eps, const void *addend, int addend_grouped, const void *cls_addend,
+                                      void *x_out, void *y_out, const void *x_out_bias, tome_stream_t stream) {
+    if (B <= 0 || F <= 0) return fail(TOME_EINVAL, "tome_drop_regrouped_ln: bad shape");
+    const int64_t n = B * F;
+    if (int rc = check_merge_args("tome_drop_regrouped_ln", x, n, P, C, r, x_out)) return rc;
+    if (!und_idx && (P + 1) / 2 > r) return fail(TOME_EINVAL, "tome_drop_regrouped_ln: null index buffer");
+    if (int rc = check_drop_ln_args("tome_drop_regrouped_ln", x, dtype, C, ln_weight, ln_bias, addend, cls_addend, x_out,
+                                    y_out, x_out_bias))
+        return rc;
+    if (addend_grouped && !addend) return fail(TOME_EINVAL, "tome_drop_regrouped_ln: addend_grouped without addend");
+    const int64_t cls = has_cls ? 1 : 0;
+    LnArgs ln{ln_weight, ln_bias, y_out, eps, addend, 0, TokLayout{0, 0, 0, 0, 1}, nullptr, 0, x_out_bias};
+    if (addend_grouped) {  // addend [B*F, has_cls + P, C], as in tome_merge_wavg_regrouped_ln
+        ln.a_own = 1;
+        ln.la = TokLayout{cls * C, (cls + P) * C, 0, C, 1};
+        ln.cls_addend = cls_addend;
+    }
+    const TokLayout lin{cls * C, (cls + P * F) * C, C, F * C, (int)F};
+    const TokLayout lout{cls * C, (cls + (P - r) * F) * C, C, F * C, (int)F};
+    return dispatch_x<false>(dtype, [&](auto tx) {
+        return launch_merge_rows<typename decltype(tx)::type, float, OP_DROP>(
+            x, nullptr, n, P, C, r, nullptr, nullptr, und_idx, 0, nullptr, x_out, nullptr, (hipStream_t)stream, &lin,
+            &lout, cls ? (int)B : 0, &ln);
+    }, [&] { return fail(TOME_EINVAL, "tome_drop_regrouped_ln: 16-bit tokens only (dtype=%d)", dtype); });
 }
 
 // The dtype x bias dispatch of the attention kernels, forward and backward: f(Dt<TX>{}, Op<BIAS>{}) for a 16-bit

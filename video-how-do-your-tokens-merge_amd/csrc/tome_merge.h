@@ -795,6 +795,8 @@ struct MergeSched {
 // read (own row + sources) by the edge waves anyway; without it they were read twice (measured, tools/regroup_layers.py:
 // 5.4 TB/s at 196 -> 164 tokens per group falling to 3.2 at 68 -> 36).  Costs the streaming waves of such launches one
 // dependent round trip (index -> rows), which the default path avoids for the r << T2 case of the benchmark.
+// OP_DROP with LN (tome_drop_ln, tome_drop_regrouped_ln): every kept row is a streamed row -- the launch has no edge
+// waves and never the EAGER form; the addend, the folded bias and ln_rows below are reached as they are for the merge.
 template <typename TX, typename TS, int OP, int NIT, bool LN = false, bool EAGER = false>
 __global__ __launch_bounds__(256) void k_merge_rows_fast(const TX *__restrict__ x, const TS *__restrict__ size,
                                                          int n, int T_, int C, int r, int R, int cpr,

@@ -86,6 +86,9 @@ SIGNATURES = {
     "tome_layernorm_backward_amp": (i32, [vp, i32, vp, vp, i32, i64, i64, i32, i64, vp, f32, vp, vp, vp, vp, vp, vp],
                                          True),
     "tome_token_mean": (i32, [vp, i32, i64, i64, i64, i32, vp, vp], True),
+    "tome_drop_ln": (i32, [vp, i32, i64, i64, i64, i64, vp, i32, vp, vp, f32, vp, vp, vp, vp, vp], True),
+    "tome_drop_regrouped_ln": (i32, [vp, i32, i64, i64, i64, i64, i64, i32, vp, vp, vp, f32, vp, i32, vp, vp, vp, vp, vp],
+                               True),
 }
 SYMBOLS = tuple(SIGNATURES)
 
@@ -628,6 +631,30 @@ def _prep_regrouped(who: str, plan: MatchPlan, x_full: torch.Tensor, frames: int
     return (x_full if x_full.is_contiguous() else x_full.contiguous()), B, C, cls, F, P
 
 
+def _regrouped_addend(who: str, plan: MatchPlan, x_full: torch.Tensor, cls: int, addend, addend_grouped, cls_addend):
+    """The residual a LayerNorm-fused regrouped reduction reads beside x_full: `addend` in x's layout, or `addend_grouped`
+    [B*F, has_cls + P, C] where the spatial attention left it (+ the class tokens' own `cls_addend` [B, 1, C]).
+    Returns (addend made contiguous or None, the entry's addend_grouped flag, cls_addend for the entry)."""
+    B, _, C = x_full.shape
+    P = plan.T
+    if addend_grouped is not None:
+        if addend is not None:
+            raise TomeHipError(f"{who}: pass addend or addend_grouped, not both")
+        if tuple(addend_grouped.shape) != (plan.n, cls + P, C) or addend_grouped.dtype != x_full.dtype \
+                or addend_grouped.device != x_full.device:
+            raise TomeHipError(f"{who}: addend_grouped must be {(plan.n, cls + P, C)} of x's dtype")
+        if cls_addend is not None:
+            if cls_addend.numel() != B * C or cls_addend.dtype != x_full.dtype or cls_addend.device != x_full.device:
+                raise TomeHipError(f"{who}: cls_addend must hold {(B, C)} values of x's dtype")
+            cls_addend = cls_addend.contiguous()
+        return (addend_grouped if addend_grouped.is_contiguous() else addend_grouped.contiguous()), 1, cls_addend
+    if addend is not None:
+        if addend.shape != x_full.shape or addend.dtype != x_full.dtype or addend.device != x_full.device:
+            raise TomeHipError(f"{who}: addend must match x in shape, dtype and device")
+        addend = addend if addend.is_contiguous() else addend.contiguous()
+    return addend, 0, None
+
+
 def merge_wavg_regrouped(plan: MatchPlan, x_full: torch.Tensor, size: Optional[torch.Tensor], frames: int,
                          has_cls: bool = True, ln=None, addend: Optional[torch.Tensor] = None,
                          log_size: bool = False, addend_grouped: Optional[torch.Tensor] = None,
@@ -655,24 +682,8 @@ def merge_wavg_regrouped(plan: MatchPlan, x_full: torch.Tensor, size: Optional[t
         _check(rc, "tome_merge_wavg_regrouped")
         return x_out, s_out
     weight, bias, eps = ln
-    grouped = 0
-    if addend_grouped is not None:
-        # the residual where the spatial attention left it: [B*F, has_cls + P, C] (+ the class tokens' own [B, 1, C])
-        if addend is not None:
-            raise TomeHipError("merge_wavg_regrouped: pass addend or addend_grouped, not both")
-        if tuple(addend_grouped.shape) != (plan.n, cls + P, C) or addend_grouped.dtype != x_full.dtype \
-                or addend_grouped.device != x_full.device:
-            raise TomeHipError(f"merge_wavg_regrouped: addend_grouped must be {(plan.n, cls + P, C)} of x's dtype")
-        addend = addend_grouped if addend_grouped.is_contiguous() else addend_grouped.contiguous()
-        grouped = 1
-        if cls_addend is not None:
-            if cls_addend.numel() != B * C or cls_addend.dtype != x_full.dtype or cls_addend.device != x_full.device:
-                raise TomeHipError(f"merge_wavg_regrouped: cls_addend must hold {(B, C)} values of x's dtype")
-            cls_addend = cls_addend.contiguous()
-    elif addend is not None:
-        if addend.shape != x_full.shape or addend.dtype != x_full.dtype or addend.device != x_full.device:
-            raise TomeHipError("merge_wavg_regrouped: addend must match x in shape, dtype and device")
-        addend = addend if addend.is_contiguous() else addend.contiguous()
+    addend, grouped, cls_addend = _regrouped_addend("merge_wavg_regrouped", plan, x_full, cls, addend, addend_grouped,
+                                                    cls_addend)
     y_out = torch.empty_like(x_out)
     with _on_device(x_full.device):
         rc = lib().tome_merge_wavg_regrouped_ln(x_full.data_ptr(), xcode, _ptr(size), DTYPES[sdtype], B, F, P, C,
@@ -709,6 +720,29 @@ def drop(plan: MatchPlan, x: torch.Tensor) -> torch.Tensor:
                              int(plan.distill_token), out.data_ptr(), _stream(x.device))
     _check(rc, "tome_drop")
     return out
+
+
+def drop_ln(plan: MatchPlan, x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float,
+            addend: Optional[torch.Tensor] = None, out_bias: Optional[torch.Tensor] = None):
+    """drop + LayerNorm of the kept tokens in one launch: returns (x_out, y_out).  `addend` and `out_bias` as in
+    merge_wavg_ln: the kept rows are those of `x + addend`, x_out is stored as x' + out_bias, y_out = LayerNorm(x')."""
+    x = _prep_x(plan, x, "drop_ln(x)", plan.T)
+    n, T, C = x.shape
+    out_bias = _out_bias(out_bias, x, C)
+    if addend is not None:
+        if addend.shape != x.shape or addend.dtype != x.dtype or addend.device != x.device:
+            raise TomeHipError("drop_ln: addend must match x in shape, dtype and device")
+        addend = addend if addend.is_contiguous() else addend.contiguous()
+    x_out = torch.empty((n, T - plan.r, C), dtype=x.dtype, device=x.device)
+    y_out = torch.empty_like(x_out)
+    L = lib()
+    entry = require_symbol(L, "tome_drop_ln")
+    with _on_device(x.device):
+        rc = entry(x.data_ptr(), dtype_code(x, "x"), n, T, C, plan.r, plan.unm_idx.data_ptr(), int(plan.distill_token),
+                   weight.data_ptr(), bias.data_ptr(), float(eps), _ptr(addend), x_out.data_ptr(), y_out.data_ptr(),
+                   _ptr(out_bias), _stream(x.device))
+    _check(rc, "tome_drop_ln")
+    return x_out, y_out
 
 
 def _head_view(t: torch.Tensor) -> bool:
@@ -1114,11 +1148,31 @@ def trajectory_mix_backward(q2: torch.Tensor, k2: torch.Tensor, val: torch.Tenso
     return dq2, dk2, dval
 
 
-def drop_regrouped(plan: MatchPlan, x_full: torch.Tensor, frames: int, has_cls: bool = True) -> torch.Tensor:
+def drop_regrouped(plan: MatchPlan, x_full: torch.Tensor, frames: int, has_cls: bool = True, ln=None,
+                   addend: Optional[torch.Tensor] = None, addend_grouped: Optional[torch.Tensor] = None,
+                   cls_addend: Optional[torch.Tensor] = None, out_bias: Optional[torch.Tensor] = None):
     """drop on the interleaved layout (see merge_wavg_regrouped): x_full [B, has_cls + P*F, C] ->
-    [B, has_cls + (P-r)*F, C], replacing rearrange -> drop -> rearrange -> cat (timesformer.py:111-131)."""
+    [B, has_cls + (P-r)*F, C], replacing rearrange -> drop -> rearrange -> cat (timesformer.py:111-131).
+    With ln=(weight, bias, eps) it returns (x_out, y_out), y_out = LayerNorm(x_out) (class-token rows included);
+    addend / addend_grouped + cls_addend / out_bias as in merge_wavg_regrouped."""
     x_full, B, C, cls, F, P = _prep_regrouped("drop_regrouped", plan, x_full, frames, has_cls)
     out = torch.empty((B, cls + (P - plan.r) * F, C), dtype=x_full.dtype, device=x_full.device)
+    out_bias = _out_bias(out_bias, x_full, C)
+    if ln is not None:
+        weight, bias, eps = ln
+        addend, grouped, cls_addend = _regrouped_addend("drop_regrouped", plan, x_full, cls, addend, addend_grouped,
+                                                        cls_addend)
+        y_out = torch.empty_like(out)
+        L = lib()
+        entry = require_symbol(L, "tome_drop_regrouped_ln")
+        with _on_device(x_full.device):
+            rc = entry(x_full.data_ptr(), dtype_code(x_full, "x"), B, F, P, C, plan.r, cls, plan.unm_idx.data_ptr(),
+                       weight.data_ptr(), bias.data_ptr(), float(eps), _ptr(addend), grouped, _ptr(cls_addend),
+                       out.data_ptr(), y_out.data_ptr(), _ptr(out_bias), _stream(x_full.device))
+        _check(rc, "tome_drop_regrouped_ln")
+        return out, y_out
+    if addend is not None or addend_grouped is not None or out_bias is not None:
+        raise TomeHipError("drop_regrouped: addend / out_bias are only fused together with ln")
     with _on_device(x_full.device):
         rc = lib().tome_drop_regrouped(x_full.data_ptr(), dtype_code(x_full, "x"), B, F, P, C, plan.r, cls,
                                        plan.unm_idx.data_ptr(), out.data_ptr(), _stream(x_full.device))

@@ -21,6 +21,9 @@ from ..utils import parse_r
 _SUBCLASSES: Dict[Tuple[type, str], type] = {}
 _FUSE_LN = os.environ.get("TOME_FUSE_LN", "1") != "0"  # measurement switch: 0 = merge and LayerNorm as two steps
 _FUSE_ADD = os.environ.get("TOME_FUSE_ADD", "1") != "0"  # measurement switch: 0 = residual add as its own pass
+# 0 = only plain 'merge' takes the fused reduction + LayerNorm launch; drop, hybrid and the random modes run add, reduction
+# and LayerNorm as three steps
+_FUSE_MODES = os.environ.get("TOME_FUSE_MODES", "1") != "0"
 _FUSE_NEXT = os.environ.get("TOME_FUSE_NEXT", "1") != "0"  # 0 = second residual and the next block's norm1 separate
 _ATTN_KERNEL = os.environ.get("TOME_ATTN_KERNEL", "1") != "0"  # 0 = the framework's fused attention (+ bias tensor)
 _GELU_KERNEL = os.environ.get("TOME_GELU_KERNEL", "1") != "0"  # 0 = the framework's GELU pass inside the MLP
@@ -328,6 +331,11 @@ def pick_reduction(mode: str, merge_fn, drop_fn, hybrid_fn):
 # ---- the reduction step on an already grouped [n, T, C] token tensor ---------------------------------
 def reduce_merge(metric, x, info, r):
     merge, _ = bipartite_soft_matching(metric, r, info["class_token"], info["distill_token"], info["mode"])
+    return _apply_merge(merge, x, info)
+
+
+def _apply_merge(merge, x, info):
+    """The steps behind the matching of reduce_merge / reduce_hybrid: source tracking, merge_wavg, the sizes."""
     if info["trace_source"]:
         info["source"] = merge_source(merge, x, info["source"])
     before = x.size(1)
@@ -419,15 +427,45 @@ def _trailing_norm(x, norm):
     return norm(x)
 
 
-def merge_then_norm(metric, x, info, norm, reduction_function, plain_merge_fn, residual=None, fold=None):
+def fused_kind(mode: str, is_merge: bool, is_drop: bool = False, is_hybrid: bool = False):
+    """Which reduction + LayerNorm launch a block in `mode` may take, given which of the model's reduction functions it
+    carries: "merge" (tome_merge_wavg_ln), "hybrid" (the same entry with the plan's threshold flags), "drop"
+    (tome_drop_ln), or None: the reduction runs on its own.  With _FUSE_MODES off only plain 'merge' has one."""
+    if is_merge and (mode == "merge" or (_FUSE_MODES and mode == "random_merge")):
+        return "merge"
+    if _FUSE_MODES and is_drop and mode in ("drop", "random_drop"):
+        return "drop"
+    if _FUSE_MODES and is_hybrid and mode == "hybrid":
+        return "hybrid"
+    return None
+
+
+def _fold_for(fold, x, mode: str):
+    """`fold` when the fused launch may put that Linear's bias into the stream x: a bias of x's dtype and width, in plain
+    'merge' mode only.  The fold moves a rounding -- round(round(x' + b) + h W) for round(x' + round(h W + b)) -- and one
+    bf16 bit in the stream is enough to reorder near-tied scores in the next layer's matching.  Plain merge has always
+    accepted that; drop, hybrid and the random modes keep the stream of the three steps, so that TOME_FUSE_MODES changes no
+    matching (tests/test_modes_models_gpu.py)."""
+    if fold is None or mode != "merge" or fold.bias.dtype != x.dtype or fold.bias.numel() != x.shape[-1]:
+        return None
+    return fold
+
+
+def merge_then_norm(metric, x, info, norm, reduction_function, plain_merge_fn, residual=None, fold=None, drop_fn=None,
+                    hybrid_fn=None):
     """The block steps `[x = x + residual;] x = reduction_function(metric, x, info); y = norm(x)` with the
-    residual add and the LayerNorm fused into the merge kernel (tome_merge_wavg_ln) when this layer merges in
-    plain 'merge' mode on 16-bit tokens; returns (x, y).  Anything else runs the steps as the reference does.
-    fold: the Linear that finishes the block (`foldable`); when the fused kernel runs, x comes back with that bias
-    added (y is the norm of x without it) and info["_folded"] says so for finish_linear."""
+    residual add and the LayerNorm fused into the reduction kernel when this layer reduces 16-bit tokens without grad:
+    tome_merge_wavg_ln for the model's plain merge function (`plain_merge_fn`; modes 'merge' and 'random_merge') and its
+    hybrid one (`hybrid_fn`), tome_drop_ln for its drop function (`drop_fn`; 'drop', 'random_drop'); returns (x, y).
+    Anything else runs the steps as the reference does.
+    fold: the Linear that finishes the block (`foldable`); when the fused kernel runs in plain 'merge' mode (_fold_for), x
+    comes back with that bias added (y is the norm of x without it) and info["_folded"] says so for finish_linear."""
     from ..merge import do_nothing
     r_list = info["r"]
-    plain = _FUSE_LN and reduction_function is plain_merge_fn and r_list and r_list[0] > 0 and info["mode"] == "merge"
+    kind = fused_kind(info["mode"], reduction_function is plain_merge_fn,
+                      drop_fn is not None and reduction_function is drop_fn,
+                      hybrid_fn is not None and reduction_function is hybrid_fn)
+    plain = _FUSE_LN and kind is not None and r_list and r_list[0] > 0
     fused = plain and _abi.ln_fusable(x, norm, residual)
     if residual is not None and not (fused and _FUSE_ADD and not info["trace_source"] and residual.dtype == x.dtype
                                      and _abi.effective_r(x.shape[1], r_list[0], info["class_token"],
@@ -437,15 +475,39 @@ def merge_then_norm(metric, x, info, norm, reduction_function, plain_merge_fn, r
         fused = fused and _abi.ln_fusable(x, norm)  # (the sum is another tensor: of another dtype, perhaps)
     if fused:
         r = r_list.pop(0)
-        merge, _ = bipartite_soft_matching(metric, r, info["class_token"], info["distill_token"], info["mode"])
+        fold = _fold_for(fold, x, info["mode"])
+        if kind == "drop":
+            drop = bipartite_soft_matching_drop(metric, r, info["class_token"], info["distill_token"], info["mode"])
+            if isinstance(drop, tuple):  # clamped r == 0: reduce_drop's steps around a drop that does nothing
+                if residual is not None:
+                    x = x + residual
+                x = _apply_drop(drop[0], x, info)
+                return x, norm(x)
+            if info["trace_source"]:
+                info["source"] = _drop_source(drop, info["source"], x.shape[0], x.shape[1], x.device)
+            before = x.size(1)
+            x, y = _abi.drop_ln(drop.plan, x, norm.weight, norm.bias, norm.eps, addend=residual,
+                                out_bias=None if fold is None else fold.bias)
+            info["size"] = torch.ones((x.size(0), x.size(1), 1), device=x.device)
+            if fold is not None:
+                info["_folded"] = (x, fold)
+            if info["verbose"]:
+                print(f"Dropped {before} to {x.size(1)} tokens")
+            return x, y
+        if kind == "hybrid":
+            merge, _ = bipartite_soft_matching_hybrid(metric, r, info["class_token"], info["distill_token"], info["mode"],
+                                                      info["threshold"])
+        else:
+            merge, _ = bipartite_soft_matching(metric, r, info["class_token"], info["distill_token"], info["mode"])
         if merge is do_nothing:
             if residual is not None:
                 x = x + residual
+            if info["mode"] != "merge":  # (plain 'merge' leaves size and source alone here, as it always has)
+                x = _apply_merge(merge, x, info)
             return x, norm(x)
         if info["trace_source"]:
             info["source"] = merge_source(merge, x, info["source"])
         before = x.size(1)
-        fold = fold if (fold is not None and fold.bias.dtype == x.dtype and fold.bias.numel() == x.shape[-1]) else None
         x, y, info["size"] = _abi.merge_wavg_ln(merge.plan, x, info["size"], norm.weight, norm.bias, norm.eps,
                                                 addend=residual, log_size=info["prop_attn"],
                                                 out_bias=None if fold is None else fold.bias)
@@ -529,14 +591,16 @@ class GroupedResidual:
 
 
 def merge_then_norm_regrouped(metric, x_full, info, norm, unfused_reduce, is_plain_merge: bool, frames: int,
-                              residual=None, fold=None):
+                              residual=None, fold=None, is_drop: bool = False, is_hybrid: bool = False):
     """merge_then_norm for the interleaved layouts (TimeSformer '(p t)', Motionformer '(s f)'): x_full is
     [B, 1 + P*F, C]; `unfused_reduce(x)` is the model's own reduction step (it pops r itself).  `residual`: a tensor
-    in x's layout, or a GroupedResidual."""
+    in x's layout, or a GroupedResidual.  is_plain_merge / is_drop / is_hybrid: which of the model's reduction functions
+    the block carries (fused_kind)."""
     from ..merge import do_nothing
     r_list = info["r"]
     grouped = residual if isinstance(residual, GroupedResidual) else None
-    fusable = (_FUSE_LN and is_plain_merge and r_list and r_list[0] > 0 and info["mode"] == "merge"
+    kind = fused_kind(info["mode"], is_plain_merge, is_drop, is_hybrid)
+    fusable = (_FUSE_LN and kind is not None and r_list and r_list[0] > 0
                and not info["trace_source"]
                and _abi.ln_fusable(x_full, norm, *((residual,) if grouped is None else (grouped.rs, grouped.cls_new)))
                and _abi.effective_r((x_full.shape[1] - 1) // frames, r_list[0], False, False) > 0)
@@ -551,12 +615,29 @@ def merge_then_norm_regrouped(metric, x_full, info, norm, unfused_reduce, is_pla
         x_full = x_full + residual
         residual = None
     r = r_list.pop(0)
-    merge, _ = bipartite_soft_matching(metric, r, info["class_token"], info["distill_token"], info["mode"])
+    fold = _fold_for(fold, x_full, info["mode"])
+    out_bias = None if fold is None else fold.bias
+    if kind == "drop":
+        drop = bipartite_soft_matching_drop(metric, r, info["class_token"], info["distill_token"], info["mode"])
+        assert not isinstance(drop, tuple)
+        plan = drop.plan
+        where = (dict(addend=residual) if grouped is None
+                 else dict(addend_grouped=grouped.rs, cls_addend=grouped.cls_new))
+        x_out, y_out = _abi.drop_regrouped(plan, x_full, frames, has_cls=True, ln=(norm.weight, norm.bias, norm.eps),
+                                           out_bias=out_bias, **where)
+        info["size"] = torch.ones((plan.n, plan.T - plan.r, 1), device=x_full.device)
+        if fold is not None:
+            info["_folded"] = (x_out, fold)
+        if info["verbose"]:
+            print(f"Dropped {plan.T} to {plan.T - plan.r} tokens")
+        return x_out, y_out
+    if kind == "hybrid":
+        merge, _ = bipartite_soft_matching_hybrid(metric, r, info["class_token"], info["distill_token"], info["mode"],
+                                                  info["threshold"])
+    else:
+        merge, _ = bipartite_soft_matching(metric, r, info["class_token"], info["distill_token"], info["mode"])
     assert merge is not do_nothing
     plan = merge.plan
-    fold = fold if (fold is not None and fold.bias.dtype == x_full.dtype
-                    and fold.bias.numel() == x_full.shape[-1]) else None
-    out_bias = None if fold is None else fold.bias
     if grouped is not None:
         x_out, y_out, info["size"] = _abi.merge_wavg_regrouped(
             plan, x_full, info["size"], frames, has_cls=True, ln=(norm.weight, norm.bias, norm.eps),
@@ -587,6 +668,11 @@ def reduce_drop(metric, x, info, r):
     drop = bipartite_soft_matching_drop(metric, r, info["class_token"], info["distill_token"], info["mode"])
     if isinstance(drop, tuple):  # clamped r == 0: the reference returns the do_nothing pair here
         drop = drop[0]
+    return _apply_drop(drop, x, info)
+
+
+def _apply_drop(drop, x, info):
+    """The steps behind the matching of reduce_drop: source tracking, the drop, sizes of one."""
     if info["trace_source"]:
         info["source"] = _drop_source(drop, info["source"], x.shape[0], x.shape[1], x.device)
     before = x.size(1)
@@ -620,10 +706,4 @@ def reduce_drop_regrouped(metric, x_full, info, r, frames: int):
 def reduce_hybrid(metric, x, info, r):
     merge, _ = bipartite_soft_matching_hybrid(metric, r, info["class_token"], info["distill_token"], info["mode"],
                                               info["threshold"])
-    if info["trace_source"]:
-        info["source"] = merge_source(merge, x, info["source"])
-    before = x.size(1)
-    x, info["size"] = merge_wavg(merge, x, info["size"], log_size=info["prop_attn"])
-    if info["verbose"]:
-        print(f"Merged {before} to {x.size(1)} tokens")
-    return x
+    return _apply_merge(merge, x, info)

@@ -27,7 +27,8 @@ def _block_forward(self, x, seq_len=196, num_frames=8, approx="none", num_landma
     x, y = C.merge_then_norm_regrouped(
         metric, x, info, self.norm2, lambda z: self.reduction_function(metric, z, info, num_frames),
         self.reduction_function is motionformer_merge, num_frames, residual=self.drop_path(attn_out),
-        fold=C.foldable(self.mlp.fc2, not self.training) if C._plain_mlp(self.mlp) else None)
+        fold=C.foldable(self.mlp.fc2, not self.training) if C._plain_mlp(self.mlp) else None,
+        is_drop=self.reduction_function is motionformer_drop, is_hybrid=self.reduction_function is motionformer_hybrid)
     return C.mlp_residual(self, self.mlp, x, y, info, drop_path=self.drop_path)
 
 

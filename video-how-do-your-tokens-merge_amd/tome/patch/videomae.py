@@ -30,7 +30,7 @@ def _block_forward(self, x):
     fold = (C.foldable(self.mlp.fc2, not self.training)
             if (not pooled and self.gamma_2 is None and C._plain_mlp(self.mlp)) else None)
     x, y = C.merge_then_norm(metric, x, info, self.norm2, self.reduction_function, videomae_merge,
-                             residual=self.drop_path(attn), fold=fold)
+                             residual=self.drop_path(attn), fold=fold, drop_fn=videomae_drop, hybrid_fn=videomae_hybrid)
     if pooled:  # [B, 1, C]: the host's `x.mean(1)` over the one row gives it back bit for bit
         return C.pooled_tail(self.mlp, x, y)
     # x + mlp(...), and the next block's norm1 of it handed over when that is possible

@@ -31,7 +31,8 @@ def _layer_forward(self, hidden_states, head_mask=None, output_attentions=False)
     eval_mode = not self.training
     hidden_states, normed = C.merge_then_norm(metric, hidden_states, info, self.layernorm_after,
                                               self.reduction_function, vivit_merge, residual=attention_output,
-                                              fold=C.foldable(self.output.dense, eval_mode))
+                                              fold=C.foldable(self.output.dense, eval_mode), drop_fn=vivit_drop,
+                                              hybrid_fn=vivit_hybrid)
     # under grad the MLP pair runs as one Function around the two GEMMs (tome/_mlp.py: tome_gelu_tanh forward,
     # tome_gelu_tanh_backward backward; one hidden tensor saved instead of two); grad mode is tested first, so that
     # nothing is looked up on the no-grad forward
