@@ -388,6 +388,36 @@ int tome_layernorm_backward_regrouped(const void *gy, const void *xs, const void
                                       void *dbias, void *workspace, tome_stream_t stream);
 
 /*
+ * tome_merge_ln_backward  <-  what autograd derives from the middle of the patched flat block when the tokens or the
+ *     norm require grad (additions to ABI v11, no entry changed; models are patched for training,
+ *     tools/train_net.py:727-741):
+ *         x = x + attn; x, size = merge_wavg(merge, x, size); self.norm2(x)    tome/patch/videomae.py:20-29
+ *         the same in the ViViT layer                                          tome/patch/vivit.py:35-41
+ *     i.e. the backward of tome_merge_wavg_ln and tome_drop_ln (flat layout, no x_out_bias) as ONE launch.  xs is the
+ *     forward's stored x_out [n,T-r,C], the rows it normalised; gy the gradient of y_out; gx_out (or NULL) the gradient
+ *     that reaches x_out through the residual stream.  With o(t) the merged row of token t (row_map / distill_token as
+ *     in tome_merge_backward), gw = gy * weight, xhat = (xs - mean) * rstd:
+ *         gm[o] = gx_out[o] + rstd * (gw - mean(gw) - xhat * mean(gw * xhat))       fp32, not rounded
+ *         gx[t] = (gm[o(t)] / out_div[o(t)]) * in_mul[t]                            one rounding to x_dtype
+ *     -- one rounding fewer than tome_layernorm_backward followed by tome_merge_backward.  gx [n,T,C] is the gradient
+ *     of x and of the addend alike.  out_div = size_out [n,T-r], in_mul = size [n,T] or NULL, of size_dtype (= x_dtype
+ *     or TOME_F32; ignored when both are NULL).  drop != 0 (tome_drop_ln): no scales, a merged-away token gets 0.
+ *     mean and rstd are recomputed from xs with the arithmetic of tome_layernorm_backward.
+ *         dweight[c] = sum over the merged rows of gy * xhat,   dbias[c] = sum over the merged rows of gy
+ *     every merged row once (a destination's term is computed once per token that landed in it, counted once), fp32
+ *     partial rows in `workspace` summed in a fixed order, no atomics, same bits on every run, one rounding to x_dtype.
+ *     dweight / dbias may be NULL one by one; both NULL (frozen LayerNorm): no parameter work and no workspace.
+ *     Otherwise workspace holds tome_merge_ln_backward_workspace_bytes(n, T, C) bytes (0 for an illegal shape).
+ *     16-bit tokens, C <= 1024, C % 8 == 0, 0 < r <= T/2, 16-byte aligned buffers; anything else is refused with a
+ *     status and a tome_last_error text before any launch.
+ */
+size_t tome_merge_ln_backward_workspace_bytes(int64_t n, int64_t T, int64_t C);
+int tome_merge_ln_backward(const void *gy, const void *gx_out, const void *xs, int x_dtype, const void *out_div,
+                           const void *in_mul, int size_dtype, int64_t n, int64_t T, int64_t C, int64_t r,
+                           const int32_t *row_map, int distill_token, int drop, const void *weight, float eps, void *gx,
+                           void *dweight, void *dbias, void *workspace, tome_stream_t stream);
+
+/*
  * tome_add_layernorm_amp  <-  tome_add_layernorm / tome_add_layernorm_skip_first for a model that runs under autocast
  *     with fp32 master weights (additions to ABI v11, no entry changed):
  *         with torch.cuda.amp.autocast(enabled=cfg.TRAIN.MIXED_PRECISION):   tools/train_net.py:123

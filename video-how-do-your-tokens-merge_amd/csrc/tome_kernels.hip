@@ -3,7 +3,7 @@
 // -ffp-contract=off -shared -fPIC (csrc/build.py).  No torch, no CUDA, no portability layer.
 //
 // One translation unit: tome_common.h (types), tome_match.h, tome_merge.h, tome_merge_bwd.h, tome_ln_bwd.h,
-// tome_gelu_bwd.h, tome_token_mean.h, tome_short_attn_bwd.h, tome_traj_bwd.h and tome_partition.h (kernels), this file
+// tome_merge_ln_bwd.h, tome_gelu_bwd.h, tome_token_mean.h, tome_short_attn_bwd.h, tome_traj_bwd.h and tome_partition.h (kernels), this file
 // (host).
 //
 // Launch sequence of one matching (tome_match / tome_match_keys), kernels in tome_match.h:
@@ -25,6 +25,9 @@
 //   k_ln_param_grad      the partial rows summed in a fixed order
 //   k_ln_rows_bwd<REGROUP>  the same behind TimeSformer's mid-block regrouping (tome_layernorm_backward_regrouped): the
 //                        row map in front of gy, a class row's F gradients summed in fp32              (HBM bound)
+// and of the fused residual add + merge + LayerNorm (tome_merge_ln_backward), tome_merge_ln_bwd.h:
+//   k_merge_ln_rows_bwd  the two above as one pass: the LayerNorm term of row o(t) in fp32, scaled and rounded once
+//                        per input token; parameter gradients over the merged rows, each counted once    (HBM bound)
 // and their mixed-precision forms for a model under autocast with fp32 master weights (tome_add_layernorm_amp,
 // tome_layernorm_backward_amp), tome_merge.h / tome_ln_bwd.h:
 //   k_add_ln_rows_amp    k_add_ln_rows with fp32 weight / bias, a 16-bit y and a 16-bit or fp32 residual stream
@@ -67,6 +70,7 @@
 #include "tome_merge.h"
 #include "tome_merge_bwd.h"
 #include "tome_ln_bwd.h"
+#include "tome_merge_ln_bwd.h"
 #include "tome_gelu_bwd.h"
 #include "tome_token_mean.h"
 #include "tome_partition.h"
@@ -1881,6 +1885,75 @@ extern "C" int tome_merge_backward_regrouped(const void *grad_out, int x_dtype, 
     }, [&] {
         return fail(TOME_EINVAL, "tome_merge_backward_regrouped: unsupported dtypes x=%d size=%d", x_dtype, size_dtype);
     });
+}
+
+// ------------------------------------------------------------------------------------------------
+// backward of tome_merge_wavg_ln / tome_drop_ln in the flat layout (kernel in tome_merge_ln_bwd.h)
+// ------------------------------------------------------------------------------------------------
+// The launch form of k_merge_ln_rows_bwd: R input-token rows per wave (three chunks per lane, as ln_bwd_form), wpg
+// waves per group; with parameter gradients the n * wpg slabs are walked by at most LN_BWD_MAX_PARTS workgroups.
+struct MergeLnBwdForm { int R; int64_t wpg; int64_t spw; int64_t parts; };
+static MergeLnBwdForm merge_ln_bwd_form(int64_t n, int64_t T, int64_t C) {
+    const int R = ln_rows_per_wave(C / 8, 3);
+    const int64_t wpg = (T + R - 1) / R;
+    const int64_t wgs = (n * wpg + 3) / 4;
+    const int64_t spw = (wgs + LN_BWD_MAX_PARTS - 1) / LN_BWD_MAX_PARTS;
+    return MergeLnBwdForm{R, wpg, spw, (wgs + spw - 1) / spw};
+}
+
+static bool merge_ln_bwd_shape_ok(int64_t n, int64_t T, int64_t C) {
+    return n > 0 && T > 0 && n * T <= 0x7fffffffLL && C > 0 && C % 8 == 0 && C / 8 <= 2 * WAVE;
+}
+
+extern "C" size_t tome_merge_ln_backward_workspace_bytes(int64_t n, int64_t T, int64_t C) {
+    if (!merge_ln_bwd_shape_ok(n, T, C)) return 0;
+    return align_up((size_t)merge_ln_bwd_form(n, T, C).parts * 2 * (size_t)C * sizeof(float), 256);
+}
+
+extern "C" int tome_merge_ln_backward(const void *gy, const void *gx_out, const void *xs, int x_dtype,
+                                      const void *out_div, const void *in_mul, int size_dtype, int64_t n, int64_t T,
+                                      int64_t C, int64_t r, const int32_t *row_map, int distill_token, int drop,
+                                      const void *weight, float eps, void *gx, void *dweight, void *dbias,
+                                      void *workspace, tome_stream_t stream) {
+    const char *who = "tome_merge_ln_backward";
+    if (!xs || !weight) return fail(TOME_EINVAL, "%s: null buffer", who);
+    if (int rc = check_merge_args(who, gy, n, T, C, r, gx)) return rc;
+    if (int rc = not_16bit(who, x_dtype)) return rc;
+    if (!row_map) return fail(TOME_EINVAL, "%s: null row_map", who);
+    if (drop && (out_div || in_mul)) return fail(TOME_EINVAL, "%s: drop takes no scales", who);
+    if (!merge_ln_bwd_shape_ok(n, T, C))
+        return fail(TOME_EINVAL, "%s: C %% 8 == 0 and C <= 1024 required (C=%lld)", who, (long long)C);
+    if (!aligned16(gy) || !aligned16(gx_out) || !aligned16(xs) || !aligned16(weight) || !aligned16(gx) ||
+        !aligned16(workspace))
+        return fail(TOME_EINVAL, "%s: 16-byte aligned buffers required", who);
+    const bool params = dweight || dbias;
+    if (params && !workspace)
+        return fail(TOME_EWORKSPACE, "%s: parameter gradients need a workspace of %s_workspace_bytes()", who, who);
+    const int64_t cpr = C / 8;
+    const MergeLnBwdForm f = merge_ln_bwd_form(n, T, C);
+    const int64_t bpg = (f.wpg + 3) / 4;
+    const int64_t gy_ = n < 65535 ? n : 65535, gz = (n + gy_ - 1) / gy_;
+    if (gz > 65535) return fail(TOME_EINVAL, "%s: too many groups (%lld)", who, (long long)n);
+    hipStream_t st = (hipStream_t)stream;
+    return dispatch_xs<false>(x_dtype, (out_div || in_mul) ? size_dtype : x_dtype, [&](auto tx, auto ts) {
+        using TX = typename decltype(tx)::type;
+        using TS = typename decltype(ts)::type;
+        if (params) {
+            hipLaunchKernelGGL((k_merge_ln_rows_bwd<TX, TS, 3, true>), dim3((unsigned)f.parts), dim3(256), 0, st,
+                               (const TX *)gy, (const TX *)gx_out, (const TX *)xs, (const TS *)out_div,
+                               (const TS *)in_mul, (const TX *)weight, (int)n, (int)T, (int)C, (int)r, f.R, (int)cpr,
+                               (int)f.wpg, (int)f.spw, eps, row_map, distill_token ? 1 : 0, drop ? 1 : 0, (TX *)gx,
+                               (float *)workspace);
+            if (int rc = check_launch("k_merge_ln_rows_bwd")) return rc;
+            return launch_param_grad<TX>(workspace, f.parts, 2 * C, C, dweight, dbias, st);
+        }
+        // frozen LayerNorm: one slab per wave, no column sums, no workspace
+        hipLaunchKernelGGL((k_merge_ln_rows_bwd<TX, TS, 3, false>), dim3((unsigned)bpg, (unsigned)gy_, (unsigned)gz),
+                           dim3(256), 0, st, (const TX *)gy, (const TX *)gx_out, (const TX *)xs, (const TS *)out_div,
+                           (const TS *)in_mul, (const TX *)weight, (int)n, (int)T, (int)C, (int)r, f.R, (int)cpr,
+                           (int)f.wpg, 1, eps, row_map, distill_token ? 1 : 0, drop ? 1 : 0, (TX *)gx, (float *)nullptr);
+        return check_launch("k_merge_ln_rows_bwd");
+    }, [&] { return fail(TOME_EINVAL, "%s: unsupported dtypes x=%d size=%d", who, x_dtype, size_dtype); });
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -89,6 +89,9 @@ SIGNATURES = {
     "tome_drop_ln": (i32, [vp, i32, i64, i64, i64, i64, vp, i32, vp, vp, f32, vp, vp, vp, vp, vp], True),
     "tome_drop_regrouped_ln": (i32, [vp, i32, i64, i64, i64, i64, i64, i32, vp, vp, vp, f32, vp, i32, vp, vp, vp, vp, vp],
                                True),
+    "tome_merge_ln_backward_workspace_bytes": (sz, [i64, i64, i64], True),
+    "tome_merge_ln_backward": (i32, [vp, vp, vp, i32, vp, vp, i32, i64, i64, i64, i64, vp, i32, i32, vp, f32, vp, vp, vp,
+                                    vp, vp], True),
 }
 SYMBOLS = tuple(SIGNATURES)
 
@@ -438,6 +441,21 @@ def ln_trainable(x: torch.Tensor, norm) -> bool:
     tome_layernorm_backward[_regrouped] behind them (tome/_ln.py) when x or its parameters require grad?  The stock
     module only: a subclass may carry a forward of its own, which a training run must keep; and a bias of x's dtype."""
     return type(norm) is torch.nn.LayerNorm and _ln_of(x, norm) and norm.bias.dtype == x.dtype
+
+
+def merge_ln_trainable(x: torch.Tensor, norm, addend: Optional[torch.Tensor], merge=None) -> bool:
+    """Can `norm(merge_wavg(merge, x + addend))` (or the drop form) run as tome_merge_wavg_ln / tome_drop_ln with
+    tome_merge_ln_backward behind it (tome/_ln.py::_MergeLnFunction) when a participant requires grad?  Device tokens,
+    ln_trainable, an addend that is absent or of x's shape, dtype and device, and the even/odd matching of a MatchPlan
+    without threshold flags (hybrid) -- a partition plan (kth_ / random_) has no row map of this kind.  merge: the
+    callable that carries the plan; None asks about the tensors alone (before the matching exists)."""
+    if not (x.is_cuda and x.dim() == 3 and ln_trainable(x, norm)
+            and (addend is None or (addend.shape == x.shape and addend.dtype == x.dtype and addend.device == x.device))):
+        return False
+    if merge is None:
+        return True
+    plan = getattr(merge, "plan", None)
+    return type(plan) is MatchPlan and plan.edge_keep is None and plan.r > 0 and plan.device == x.device
 
 
 def autocast_dtype(device) -> Optional[torch.dtype]:
@@ -1483,6 +1501,49 @@ def layernorm_backward(gy: torch.Tensor, xs: torch.Tensor, gx_in: Optional[torch
         gy_shape = tuple(xs.shape)
     return _layernorm_backward_call("layernorm_backward", gy, gy_shape, xs, gx_in, weight, eps, want_weight, want_bias,
                                     (groups, group_rows, int(bool(skip_first))), (groups * group_rows, C))
+
+
+def merge_ln_backward(plan: MatchPlan, gy: torch.Tensor, gx_out: Optional[torch.Tensor], xs: torch.Tensor,
+                      out_div: Optional[torch.Tensor], in_mul: Optional[torch.Tensor], weight: torch.Tensor, eps: float,
+                      drop: bool = False, want_weight: bool = True, want_bias: bool = True):
+    """tome_merge_ln_backward: the backward of merge_wavg_ln / drop_ln as one launch.  xs [n, T-r, C]: the forward's
+    stored x_out; gy its y_out's gradient; gx_out (or None) the gradient that reaches x_out through the residual stream;
+    out_div = size_out, in_mul = size or None (both None with drop).  Returns (gx [n, T, C], dweight, dbias); a
+    gradient that is not wanted is None.  No CPU path."""
+    what = "merge_ln_backward"
+    require_device(xs, f"{what}(xs)")
+    if xs.dtype not in _HALF:
+        raise TomeHipError(f"{what}: 16-bit tokens only, got {xs.dtype}")
+    n, T, To = plan.n, plan.T, plan.T - plan.r
+    if xs.dim() != 3 or tuple(xs.shape[:2]) != (n, To):
+        raise TomeHipError(f"{what}: xs must be [{n}, {To}, C], got {tuple(xs.shape)}")
+    C = xs.shape[-1]
+    if weight.numel() != C or weight.dtype != xs.dtype or weight.device != xs.device:
+        raise TomeHipError(f"{what}: weight must hold {C} values of {xs.dtype} on {xs.device}")
+    if drop and (out_div is not None or in_mul is not None):
+        raise TomeHipError(f"{what}: drop takes no scales")
+    gy = _prep_grad(gy, (n, To, C), xs.dtype, xs.device, f"{what}(gy)")
+    if gx_out is not None:
+        gx_out = _prep_grad(gx_out, (n, To, C), xs.dtype, xs.device, f"{what}(gx_out)")
+    out_div, in_mul, sdtype = _prep_scales(out_div, in_mul, n, T, To, xs.dtype, xs.device, what)
+    xs = xs.detach()
+    xs = xs if xs.is_contiguous() else xs.contiguous()
+    weight = weight.detach().contiguous()
+    row_map = plan_row_map(plan)
+    L = lib()
+    entry = require_symbol(L, "tome_merge_ln_backward")
+    gx = torch.empty((n, T, C), dtype=xs.dtype, device=xs.device)
+    dweight = torch.empty(C, dtype=xs.dtype, device=xs.device) if want_weight else None
+    dbias = torch.empty(C, dtype=xs.dtype, device=xs.device) if want_bias else None
+    with _on_device(xs.device):
+        stream = _stream(xs.device)
+        ws = _sized_workspace(L, "tome_merge_ln_backward_workspace_bytes", (n, T, C), xs.device, stream,
+                              what) if want_weight or want_bias else None
+        rc = entry(gy.data_ptr(), _ptr(gx_out), xs.data_ptr(), dtype_code(xs, "xs"), _ptr(out_div), _ptr(in_mul),
+                   DTYPES[sdtype], n, T, C, plan.r, row_map.data_ptr(), int(plan.distill_token), int(bool(drop)),
+                   weight.data_ptr(), float(eps), gx.data_ptr(), _ptr(dweight), _ptr(dbias), _ptr(ws), stream)
+    _check(rc, "tome_merge_ln_backward")
+    return gx, dweight, dbias
 
 
 def layernorm_backward_amp(gy: torch.Tensor, xs: torch.Tensor, gx_in: Optional[torch.Tensor], weight: torch.Tensor,

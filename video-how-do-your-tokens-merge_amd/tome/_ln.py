@@ -19,6 +19,10 @@ The backward recomputes mean and rstd from the stored sum (the row the forward n
 nothing but the tensors it returns anyway.  The gradient of the sum that arrives through the residual stream and the
 gradient through the LayerNorm are added inside the one launch and rounded once; x and addend receive the same
 tensor.  Double backward raises.
+merge_ln_native(plan, x, addend, size, norm, drop, log_size) -> (x', norm(x'), size'): the fused residual add + merge (or
+drop) + LayerNorm launch (tome_merge_wavg_ln / tome_drop_ln) as a Function, tome_merge_ln_backward behind it -- one
+launch each way.  Reached through tome.merge.merge_wavg_ln / drop_ln, which route (the patched blocks take them only with
+tome.patch._common.TRAIN_FUSED_LN on).
 The regrouped form is the middle of TimeSformer's divided space-time block (tome_add_layernorm_regrouped forward,
 tome_layernorm_backward_regrouped backward): x [B, 1 + P*T, C] and addend [B, P*T, C] receive gx and its view gx[:, 1:].
 """
@@ -178,6 +182,64 @@ class _AddLayerNormRegroupedFunction(torch.autograd.Function):
         need = ctx.needs_input_grad
         return ((gx if need[0] and gx is not None else None), (gx[:, 1:] if need[1] and gx is not None else None), dw, db,
                 None, None)
+
+
+def merge_ln_backward(plan, gy, gx_out, xs, out_div, in_mul, weight, eps, drop, want_weight, want_bias):
+    """The backward arithmetic of _MergeLnFunction: (gx, dweight, dbias).  A seam of its own, like ln_backward."""
+    return _abi.merge_ln_backward(plan, gy, gx_out, xs, out_div, in_mul, weight, eps, drop=drop,
+                                  want_weight=want_weight, want_bias=want_bias)
+
+
+class _MergeLnFunction(torch.autograd.Function):
+    """(x', LayerNorm(x'), size', log size') with x' = merge_wavg(x + addend) or drop(x + addend): tome_merge_wavg_ln /
+    tome_drop_ln forward (no x_out_bias), tome_merge_ln_backward backward -- one launch, the gradient of the merged rows
+    never rounded on its way to the tokens.  x and the addend receive the same tensor; the sizes carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, addend, size, weight, bias, eps, plan, drop, log_size):
+        det = lambda t: None if t is None else t.detach()  # noqa: E731
+        _abi.plan_row_map(plan)
+        if drop:
+            x_out, y = _abi.drop_ln(plan, x.detach(), weight.detach(), bias.detach(), eps, addend=det(addend))
+            s_out = log = None
+        else:
+            x_out, y, s_out = _abi.merge_wavg_ln(plan, x.detach(), det(size), weight.detach(), bias.detach(), eps,
+                                                 addend=det(addend), log_size=log_size)
+            log = getattr(s_out, "_tome_log", None)
+            ctx.mark_non_differentiable(*(t for t in (s_out, log) if t is not None))
+        ctx.plan, ctx.eps, ctx.drop = plan, float(eps), bool(drop)
+        ctx.needs_x = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        ctx.save_for_backward(x_out, weight, size, s_out)
+        ctx.set_materialize_grads(False)  # an output nobody read arrives as None, not as a tensor of zeros
+        return x_out, y, s_out, log
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_x, g_y, _gs, _gl):
+        xs, weight, size, s_out = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        want_w, want_b = need[3], need[4]
+        cast = lambda g: g if g is None or g.dtype == xs.dtype else g.to(xs.dtype)  # noqa: E731
+        if g_y is None:  # nothing read the LayerNorm: the merge alone, the parameters get zeros
+            gx = None
+            if ctx.needs_x and g_x is not None:
+                gx = _abi.merge_backward(ctx.plan, cast(g_x), out_div=s_out, in_mul=size, drop=ctx.drop)
+            dw = torch.zeros_like(weight) if want_w else None
+            db = torch.zeros_like(weight) if want_b else None
+        else:
+            gx, dw, db = merge_ln_backward(ctx.plan, cast(g_y), cast(g_x), xs, s_out, size, weight, ctx.eps, ctx.drop,
+                                           want_w, want_b)
+        return ((gx if need[0] else None), (gx if need[1] else None), None, dw, db, None, None, None, None)
+
+
+def merge_ln_native(plan, x, addend, size, norm, drop: bool = False, log_size: bool = False):
+    """`x = x + addend; x, size = merge_wavg(merge, x, size); y = norm(x)` (drop: `x = drop(x)`, no sizes) for
+    participants that require grad: (x, y, size or None)."""
+    x_out, y, s_out, log = _MergeLnFunction.apply(x, addend, size, norm.weight, norm.bias, norm.eps, plan, bool(drop),
+                                                  bool(log_size))
+    if log is not None:
+        s_out._tome_log = log  # (the size a Function returns is a new tensor object: _abi.log_of_size finds it again)
+    return x_out, y, s_out
 
 
 def _backward_amp(ctx, g_sum, g_y, want_gx16):

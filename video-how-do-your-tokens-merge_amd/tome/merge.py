@@ -573,6 +573,62 @@ def merge_wavg(merge: Callable, x: torch.Tensor, size: Optional[torch.Tensor] = 
     return x, size
 
 
+def _ln_route(merge: Callable, x: torch.Tensor, norm, residual, size=None) -> Optional[str]:
+    """How merge_wavg_ln / drop_ln below run: "direct" (the fused launch: no gradient wanted), "function" (the same
+    launch as tome/_ln.py::_MergeLnFunction, tome_merge_ln_backward behind it) or None: the three unfused steps."""
+    from . import _ln
+    plan = getattr(merge, "plan", None)
+    if not (isinstance(plan, _abi.MatchPlan) and x.is_cuda and x.dim() == 3 and x.device == plan.device
+            and isinstance(norm, torch.nn.LayerNorm)
+            and (residual is None or (residual.shape == x.shape and residual.dtype == x.dtype
+                                      and residual.device == x.device))):
+        return None
+    wanted = _abi.needs_grad(x, residual, size, norm.weight, norm.bias)
+    if not wanted:
+        return "direct" if _abi.ln_fusable(x, norm, residual) else None
+    if size is not None and _wants_autograd(size):
+        return None
+    return "function" if _ln.enabled() and _abi.merge_ln_trainable(x, norm, residual, merge) else None
+
+
+def merge_wavg_ln(merge: Callable, x: torch.Tensor, size: Optional[torch.Tensor], norm,
+                  residual: Optional[torch.Tensor] = None, log_size: bool = False
+                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``x = x + residual; x, size = merge_wavg(merge, x, size); y = norm(x)``: returns (x, y, size).  One launch
+    (tome_merge_wavg_ln) for 16-bit device tokens, a matching of this package and an nn.LayerNorm over C <= 1024
+    channels; when x, the residual or the norm requires grad, the same launch as an autograd Function whose backward
+    is one launch too (tome_merge_ln_backward) where `_abi.merge_ln_trainable` holds.  Anything else -- a size that
+    requires grad, a hybrid or partition matching, fp32 tokens, a LayerNorm subclass under grad, CPU tensors -- runs the
+    three steps, so there always is an answer."""
+    from . import _ln
+    how = _ln_route(merge, x, norm, residual, size)
+    if how == "direct":
+        return _abi.merge_wavg_ln(merge.plan, x, size, norm.weight, norm.bias, norm.eps, addend=residual,
+                                  log_size=log_size)
+    if how == "function":
+        return _ln.merge_ln_native(merge.plan, x, residual, size, norm, log_size=log_size)
+    if residual is not None:
+        x = x + residual
+    x, size = merge_wavg(merge, x, size, log_size=log_size)
+    return x, norm(x), size
+
+
+def drop_ln(drop: Callable, x: torch.Tensor, norm, residual: Optional[torch.Tensor] = None
+            ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``x = x + residual; x = drop(x); y = norm(x)`` for the callable of bipartite_soft_matching_drop: returns (x, y).
+    Routed as merge_wavg_ln: tome_drop_ln, with tome_merge_ln_backward behind it under grad, else the three steps."""
+    from . import _ln
+    how = _ln_route(drop, x, norm, residual)
+    if how == "direct":
+        return _abi.drop_ln(drop.plan, x, norm.weight, norm.bias, norm.eps, addend=residual)
+    if how == "function":
+        return _ln.merge_ln_native(drop.plan, x, residual, None, norm, drop=True)[:2]
+    if residual is not None:
+        x = x + residual
+    x = drop(x)
+    return x, norm(x)
+
+
 def merge_source(merge: Callable, x: torch.Tensor, source: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Source tracking: adjacency between the initial tokens and the merged groups."""
     plan = getattr(merge, "plan", None)

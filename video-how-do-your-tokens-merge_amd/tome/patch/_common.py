@@ -451,6 +451,45 @@ def _fold_for(fold, x, mode: str):
     return fold
 
 
+# True: a flat-layout block (VideoMAE, ViViT) in mode 'merge' / 'random_merge' / 'drop' / 'random_drop' whose tokens,
+# residual or norm require grad takes the fused add + reduction + LayerNorm launch as an autograd Function
+# (tome/_ln.py::_MergeLnFunction, tome_merge_ln_backward behind it) where _abi.merge_ln_trainable holds, instead of the
+# three steps `x + residual`, the merge Function and the LayerNorm Function.  Off by default: what that rests on is
+# said in DESIGN.md section 1 (measure with tools/merge_ln_backward_bench.py).
+TRAIN_FUSED_LN = False
+
+
+def _train_fused(kind: str, x, norm, residual, info) -> bool:
+    """May this layer's reduction run as _MergeLnFunction?  Asked before the matching: the facts about the tensors."""
+    if kind not in ("merge", "drop") or info["trace_source"] or not _ln.enabled():
+        return False
+    size = info["size"]
+    if not _abi.needs_grad(x, residual, norm.weight, norm.bias) or _abi.needs_grad(size):
+        return False
+    if size is not None and (size.device != x.device or size.shape != (x.shape[0], x.shape[1], 1)):
+        return False
+    return (_abi.merge_ln_trainable(x, norm, residual)
+            and _abi.effective_r(x.shape[1], info["r"][0], info["class_token"], info["distill_token"]) > 0)
+
+
+def _merge_then_norm_trained(metric, x, info, norm, residual, kind: str):
+    """merge_then_norm's steps through tome.merge.merge_wavg_ln / drop_ln for participants that require grad.  `fold` has
+    no place here: the stream is the one the three steps store."""
+    from ..merge import drop_ln, merge_wavg_ln
+    r = info["r"].pop(0)
+    before = x.size(1)
+    if kind == "drop":
+        drop = bipartite_soft_matching_drop(metric, r, info["class_token"], info["distill_token"], info["mode"])
+        x, y = drop_ln(drop, x, norm, residual)
+        info["size"] = torch.ones((x.size(0), x.size(1), 1), device=x.device)
+    else:
+        merge, _ = bipartite_soft_matching(metric, r, info["class_token"], info["distill_token"], info["mode"])
+        x, y, info["size"] = merge_wavg_ln(merge, x, info["size"], norm, residual, log_size=info["prop_attn"])
+    if info["verbose"]:
+        print(f"{'Dropped' if kind == 'drop' else 'Merged'} {before} to {x.size(1)} tokens")
+    return x, y
+
+
 def merge_then_norm(metric, x, info, norm, reduction_function, plain_merge_fn, residual=None, fold=None, drop_fn=None,
                     hybrid_fn=None):
     """The block steps `[x = x + residual;] x = reduction_function(metric, x, info); y = norm(x)` with the
@@ -459,13 +498,17 @@ def merge_then_norm(metric, x, info, norm, reduction_function, plain_merge_fn, r
     hybrid one (`hybrid_fn`), tome_drop_ln for its drop function (`drop_fn`; 'drop', 'random_drop'); returns (x, y).
     Anything else runs the steps as the reference does.
     fold: the Linear that finishes the block (`foldable`); when the fused kernel runs in plain 'merge' mode (_fold_for), x
-    comes back with that bias added (y is the norm of x without it) and info["_folded"] says so for finish_linear."""
+    comes back with that bias added (y is the norm of x without it) and info["_folded"] says so for finish_linear.
+    With TRAIN_FUSED_LN on, a layer of kind "merge" or "drop" whose participants require grad takes the same launch as an
+    autograd Function (_merge_then_norm_trained); `fold` is ignored there."""
     from ..merge import do_nothing
     r_list = info["r"]
     kind = fused_kind(info["mode"], reduction_function is plain_merge_fn,
                       drop_fn is not None and reduction_function is drop_fn,
                       hybrid_fn is not None and reduction_function is hybrid_fn)
     plain = _FUSE_LN and kind is not None and r_list and r_list[0] > 0
+    if TRAIN_FUSED_LN and plain and _train_fused(kind, x, norm, residual, info):
+        return _merge_then_norm_trained(metric, x, info, norm, residual, kind)
     fused = plain and _abi.ln_fusable(x, norm, residual)
     if residual is not None and not (fused and _FUSE_ADD and not info["trace_source"] and residual.dtype == x.dtype
                                      and _abi.effective_r(x.shape[1], r_list[0], info["class_token"],
