@@ -439,6 +439,44 @@ int tome_add_layernorm_amp(const void *x, int x_dtype, const void *addend, int a
                            float eps, void *x_out, void *y_out, int y_dtype, tome_stream_t stream);
 
 /*
+ * tome_merge_wavg_ln_amp  <-  tome_merge_wavg_ln for a model that runs under autocast with fp32 master weights
+ *     (additions to ABI v11, no entry changed; tools/train_net.py:123, tome/utils.py:54 as for tome_add_layernorm_amp):
+ *         x = x + attn; x, size = merge_wavg(merge, x, size); self.norm2(x)    tome/patch/videomae.py:20-27
+ *         the same in the ViViT layer                                          tome/patch/vivit.py:35-41
+ *     one launch: x' = x + addend (addend NULL: x' = x), x_out / size_out / log_size_out = tome_merge_wavg(x', size),
+ *     y_out = LayerNorm(x_out).  Dtypes as in tome_add_layernorm_amp:
+ *         x [n,T,C], x_out [n,T-r,C] of x_dtype; y_out [n,T-r,C] of y_dtype (16-bit); weight_f32, bias_f32 [C] fp32.
+ *         x_dtype == y_dtype:  addend of the same dtype; x' = round16(x + addend), the bits tome_merge_wavg_ln merges.
+ *         x_dtype == TOME_F32: addend of y_dtype or fp32; x' = the fp32 sum, one rounding (`x + addend.float()`).
+ *         size, size_out, log_size_out of size_dtype (x_dtype or TOME_F32) as in tome_merge_wavg; size may be NULL (ones),
+ *         log_size_out may be NULL.  Any other dtype combination: TOME_EINVAL.
+ *     The merge is tome_merge_wavg's contract, bit for bit: fp32 products, the destination's own term first, then its
+ *     sources in src_idx order, one division, one rounding to x_dtype (none for fp32); rows nothing merges into, of
+ *     size 1, move as raw bits.  edge_keep and distill_token as in tome_merge_wavg_ln.  The LayerNorm's statistics are
+ *     taken in fp32 from the STORED x_out (two passes, centred variance), y_out is rounded once.
+ *     Flat layout only, no x_out_bias, no backward.  C % 8 == 0, C <= 1024, 0 < r <= T/2, 16-byte aligned buffers; each
+ *     refusal is made on the host before any launch, with its own tome_last_error.
+ */
+int tome_merge_wavg_ln_amp(const void *x, int x_dtype, const void *addend, int addend_dtype, const void *size,
+                           int size_dtype, int64_t n, int64_t T, int64_t C, int64_t r, const int64_t *src_idx,
+                           const int64_t *dst_idx, const int64_t *unm_idx, int distill_token, const uint8_t *edge_keep,
+                           const void *weight_f32, const void *bias_f32, float eps, void *x_out, void *y_out, int y_dtype,
+                           void *size_out, void *log_size_out, tome_stream_t stream);
+
+/*
+ * tome_drop_ln_amp  <-  tome_drop_ln under autocast with fp32 master weights (additions to ABI v11, no entry changed;
+ *     tools/train_net.py:123, tome/utils.py:54): the drop step between the first residual and the second LayerNorm of
+ *     the block (tome/patch/videomae.py:20-27, vivit.py:35-41 with videomae_drop / vivit_drop as the reduction).
+ *     x' = x + addend as in tome_merge_wavg_ln_amp; x_out [n,T-r,C] of x_dtype: the rows tome_drop keeps of x', bit for
+ *     bit; y_out [n,T-r,C] of y_dtype = LayerNorm(x_out) with the fp32 weight_f32 / bias_f32, statistics from the stored
+ *     row, rounded once.  und_idx, distill_token and r as tome_drop.  Dtypes, limits and refusals as in
+ *     tome_merge_wavg_ln_amp.
+ */
+int tome_drop_ln_amp(const void *x, int x_dtype, const void *addend, int addend_dtype, int64_t n, int64_t T, int64_t C,
+                     int64_t r, const int64_t *und_idx, int distill_token, const void *weight_f32, const void *bias_f32,
+                     float eps, void *x_out, void *y_out, int y_dtype, tome_stream_t stream);
+
+/*
  * tome_layernorm_backward_amp  <-  the backward of tome_add_layernorm_amp: tome_layernorm_backward's formula for a model
  *     that trains under autocast with a GradScaler and fp32 master weights (additions to ABI v11, no entry changed;
  *     tools/train_net.py:123 and :680, tome/utils.py:54).

@@ -68,6 +68,7 @@
 #include "tome_match.h"
 #include "tome_match_filter.h"
 #include "tome_merge.h"
+#include "tome_merge_ln_amp.h"
 #include "tome_merge_bwd.h"
 #include "tome_ln_bwd.h"
 #include "tome_merge_ln_bwd.h"
@@ -1171,6 +1172,90 @@ extern "C" int tome_drop_regrouped_ln(const void *x, int dtype, int64_t B, int64
             x, nullptr, n, P, C, r, nullptr, nullptr, und_idx, 0, nullptr, x_out, nullptr, (hipStream_t)stream, &lin,
             &lout, cls ? (int)B : 0, &ln);
     }, [&] { return fail(TOME_EINVAL, "tome_drop_regrouped_ln: 16-bit tokens only (dtype=%d)", dtype); });
+}
+
+// ------------------------------------------------------------------------------------------------
+// tome_merge_wavg_ln_amp / tome_drop_ln_amp: the add + reduction + LayerNorm launch under autocast (k_merge_rows_ln_amp,
+// csrc/tome_merge_ln_amp.h) in the dtypes of tome_add_layernorm_amp (dispatch_amp) and its launch form (three slots per
+// lane, ln_rows_per_wave); the grid is launch_merge_rows' (blocks of one group, group in y and z).  Every refusal is
+// made here, before the launch, each with a text of its own.
+// ------------------------------------------------------------------------------------------------
+template <int OP>
+static int merge_ln_amp_impl(const char *who, const void *x, int x_dtype, const void *addend, int addend_dtype,
+                             const void *size, int size_dtype, int64_t n, int64_t T, int64_t C, int64_t r,
+                             const int64_t *src_idx, const int64_t *dst_idx, const int64_t *unm_idx, int distill_token,
+                             const uint8_t *edge_keep, const void *weight_f32, const void *bias_f32, float eps,
+                             void *x_out, void *y_out, int y_dtype, void *size_out, void *log_size_out,
+                             tome_stream_t stream) {
+    if (int rc = check_merge_args(who, x, n, T, C, r, x_out)) return rc;
+    if (!y_out || !weight_f32 || !bias_f32 || (!unm_idx && (T + 1) / 2 > r) ||
+        (OP == OP_WAVG && (!src_idx || !dst_idx || !size_out)))
+        return fail(TOME_EINVAL, "%s: null buffer", who);
+    auto bad_dtypes = [&] {
+        return fail(TOME_EINVAL, "%s: unsupported dtypes x=%d addend=%d y=%d (a 16-bit y; x of y's dtype with an addend of "
+                                 "the same, or fp32 x with an addend of y's dtype or fp32)", who, x_dtype, addend_dtype,
+                    y_dtype);
+    };
+    if (int rc = dispatch_amp(x_dtype, addend_dtype, addend != nullptr, y_dtype,
+                              [](auto, auto, auto) -> int { return TOME_OK; }, bad_dtypes))
+        return rc;
+    if (OP == OP_WAVG && size_dtype != TOME_F32 && size_dtype != x_dtype)
+        return fail(TOME_EINVAL, "%s: sizes must be of x's dtype or fp32 (x=%d size=%d)", who, x_dtype, size_dtype);
+    if (C % 8 != 0 || C > 1024)
+        return fail(TOME_EINVAL, "%s: C=%lld must be a multiple of 8, at most 1024", who, (long long)C);
+    if (!aligned16(x) || !aligned16(x_out)) return fail(TOME_EINVAL, "%s: x / x_out not 16-byte aligned", who);
+    if (!aligned16(addend)) return fail(TOME_EINVAL, "%s: addend not 16-byte aligned", who);
+    if (!aligned16(y_out)) return fail(TOME_EINVAL, "%s: y_out not 16-byte aligned", who);
+    if (!aligned16(weight_f32) || !aligned16(bias_f32))
+        return fail(TOME_EINVAL, "%s: weight_f32 / bias_f32 not 16-byte aligned", who);
+    const int64_t To = T - r, cpr = C / 8;
+    const int R = ln_rows_per_wave(cpr, 3);
+    const int64_t rg = (To + R - 1) / R;
+    const int64_t bpg = (rg + (OP == OP_DROP ? 0 : r) + 3) / 4;
+    const int64_t gy = n < 65535 ? n : 65535, gz = (n + gy - 1) / gy;
+    if (gz > 65535) return fail(TOME_EINVAL, "%s: too many groups (%lld)", who, (long long)n);
+    const dim3 grid((unsigned)bpg, (unsigned)gy, (unsigned)gz);
+    hipStream_t st = (hipStream_t)stream;
+    return dispatch_amp(x_dtype, addend_dtype, addend != nullptr, y_dtype, [&](auto tx, auto ta, auto ty) {
+        using TX = typename decltype(tx)::type;
+        using TA = typename decltype(ta)::type;
+        using TY = typename decltype(ty)::type;
+        auto launch = [&](auto ts) {
+            using TS = typename decltype(ts)::type;
+            hipLaunchKernelGGL((k_merge_rows_ln_amp<TX, TA, TY, TS, OP, 3>), grid, dim3(256), 0, st, (const TX *)x,
+                               (const TA *)addend, (const TS *)size, (int)n, (int)T, (int)C, (int)r, R, (int)cpr, (int)rg,
+                               src_idx, dst_idx, unm_idx, distill_token, edge_keep, (const float *)weight_f32,
+                               (const float *)bias_f32, eps, (TX *)x_out, (TY *)y_out, (TS *)size_out,
+                               (TS *)log_size_out);
+            return check_launch("k_merge_rows_ln_amp");
+        };
+        if constexpr (OP == OP_DROP) {
+            return launch(Dt<float>{});  // (no sizes: one instantiation per dtype triple)
+        } else {
+            if (size_dtype == TOME_F32) return launch(Dt<float>{});
+            return launch(tx);
+        }
+    }, bad_dtypes);
+}
+
+extern "C" int tome_merge_wavg_ln_amp(const void *x, int x_dtype, const void *addend, int addend_dtype, const void *size,
+                                      int size_dtype, int64_t n, int64_t T, int64_t C, int64_t r, const int64_t *src_idx,
+                                      const int64_t *dst_idx, const int64_t *unm_idx, int distill_token,
+                                      const uint8_t *edge_keep, const void *weight_f32, const void *bias_f32, float eps,
+                                      void *x_out, void *y_out, int y_dtype, void *size_out, void *log_size_out,
+                                      tome_stream_t stream) {
+    return merge_ln_amp_impl<OP_WAVG>("tome_merge_wavg_ln_amp", x, x_dtype, addend, addend_dtype, size, size_dtype, n, T, C,
+                                      r, src_idx, dst_idx, unm_idx, distill_token, edge_keep, weight_f32, bias_f32, eps,
+                                      x_out, y_out, y_dtype, size_out, log_size_out, stream);
+}
+
+extern "C" int tome_drop_ln_amp(const void *x, int x_dtype, const void *addend, int addend_dtype, int64_t n, int64_t T,
+                                int64_t C, int64_t r, const int64_t *und_idx, int distill_token, const void *weight_f32,
+                                const void *bias_f32, float eps, void *x_out, void *y_out, int y_dtype,
+                                tome_stream_t stream) {
+    return merge_ln_amp_impl<OP_DROP>("tome_drop_ln_amp", x, x_dtype, addend, addend_dtype, nullptr, TOME_F32, n, T, C, r,
+                                      nullptr, nullptr, und_idx, distill_token, nullptr, weight_f32, bias_f32, eps, x_out,
+                                      y_out, y_dtype, nullptr, nullptr, stream);
 }
 
 // The dtype x bias dispatch of the attention kernels, forward and backward: f(Dt<TX>{}, Op<BIAS>{}) for a 16-bit

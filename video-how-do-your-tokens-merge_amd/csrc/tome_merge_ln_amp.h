@@ -1,0 +1,356 @@
+// tome_merge_ln_amp.h -- part of the single translation unit csrc/tome_kernels.hip (the residual add + merge + LayerNorm
+// launch for a model under autocast: tome_merge_wavg_ln_amp, tome_drop_ln_amp).
+#pragma once
+// ------------------------------------------------------------------------------------------------
+// k_merge_rows_ln_amp: k_merge_rows_fast<.., LN = true> (csrc/tome_merge.h) for the tensors a block has under
+// torch.autocast with fp32 master weights (tools/train_net.py:123, tome/utils.py:54):
+//     x = x + attn; x, size = merge_wavg(merge, x, size); self.norm2(x)       tome/patch/videomae.py:20-27
+//     the same in the ViViT layer                                              tome/patch/vivit.py:35-41
+// TX: the residual stream (x, x_out), 16-bit or fp32; TA: the addend; TY: y, the 16-bit autocast dtype; TS: the sizes;
+// LayerNorm weight and bias fp32.
+//   16-bit stream: x' = round16(x + a), the bits k_merge_rows_fast merges
+//   fp32 stream:   x' = x + (float)a, the fp32 sum, one rounding -- `x + a.float()` bit for bit
+// The merge is tome_merge_wavg's contract (fp32 products, the destination's own term first, then its sources in src_idx
+// order, one division, one rounding to TX -- none for fp32); the LayerNorm is k_add_ln_rows_amp's (statistics from the
+// STORED row, two passes, centred variance, fp32 parameters, y rounded once to TY).
+// Work layout: the lane SLOTS of k_add_ln_rows_amp (8 channels: one 16-byte move of a 16-bit row, two of an fp32 one), so
+// rows per wave and slots per lane are those of the 16-bit launch.  What keeps k_merge_rows_fast at the memory rate is kept:
+// every row load of a wave is issued before any use and is unconditional (a lane without a slot re-reads the start of the
+// wave's first row); rows that receive sources are left to edge waves (one per rank, the first edge into a destination
+// builds it); grid.x = the blocks of one group, grid.(y, z) = the group, so no wave starts with an integer division;
+// OP_DROP has no edge waves.  Flat layout only, no folded bias.
+// ------------------------------------------------------------------------------------------------
+template <typename TX, typename TA> __device__ __forceinline__ Slot<TX> slot_add(const Slot<TX> &x, const Slot<TA> &a) {
+    float xv[8], av[8];
+    slot_f32<TX>(x, xv);
+    slot_f32<TA>(a, av);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) xv[e] = __fadd_rn(xv[e], av[e]);
+    return f32_slot<TX>(xv);
+}
+
+// One destination row (odd token 2j+1 plus every source merged into it) by a whole wave, two slots per lane (C <= 1024):
+// merge_dst_row's arithmetic and order, then the LayerNorm of the row as stored.  k: the rank whose edge wave this is;
+// returns without a store when an earlier rank merges into the same destination.
+template <typename TX, typename TA, typename TY, typename TS, int OP>
+__device__ __forceinline__ void merge_dst_row_amp(const TX *__restrict__ xg, const TA *__restrict__ ag,
+                                                  const TS *__restrict__ sg, int C, int cpr, int r, int g, int k,
+                                                  const int64_t *__restrict__ srcg, const int64_t *__restrict__ dstg,
+                                                  const uint8_t *__restrict__ keep, TX *__restrict__ og,
+                                                  TY *__restrict__ yg, TS *__restrict__ sog, TS *__restrict__ log,
+                                                  int U, int distill, int lane, const float *__restrict__ lw,
+                                                  const float *__restrict__ lb, float eps) {
+    constexpr int VEC = 8;
+    const int j = (int)dstg[k];
+    // which rank is the first edge into j, and (hybrid, merge.py:326) does any edge into j fall below the threshold
+    int first = -1;
+    bool kill = false;
+    for (int base = 0; base < r; base += WAVE) {
+        const int kk = base + lane;
+        const bool m = (kk < r) && ((int)dstg[kk] == j);
+        const unsigned long long mk = __ballot(m);
+        if (first < 0 && mk != 0ull) first = base + (int)__ffsll((long long)mk) - 1;
+        if (keep) kill = kill || (__ballot(m && keep[(int64_t)g * r + kk] == 0) != 0ull);
+    }
+    if (first != k) return;  // (wave-uniform)
+    const int t = 2 * j + 1;
+    const int c0 = lane, c1 = WAVE + lane;
+    const bool a0 = c0 < cpr, a1 = c1 < cpr;
+    const int c0s = a0 ? c0 : 0, c1s = a1 ? c1 : 0;  // (unconditional loads: a lane without a slot re-reads slot 0)
+    const bool add = ag != nullptr, has_s = sg != nullptr;
+    const TX *xr = xg + (int64_t)t * C;
+    Slot<TX> x0 = ld_slot<TX>(xr, c0s), x1 = ld_slot<TX>(xr, c1s);
+    if (add) {
+        const TA *ar = ag + (int64_t)t * C;
+        const Slot<TA> y0 = ld_slot<TA>(ar, c0s), y1 = ld_slot<TA>(ar, c1s);
+        x0 = slot_add<TX, TA>(x0, y0);
+        x1 = slot_add<TX, TA>(x1, y1);
+    }
+    const float s_own = has_s ? to_f32(sg[t]) : 1.0f;
+    float acc0[VEC], acc1[VEC];
+    slot_f32<TX>(x0, acc0);
+    slot_f32<TX>(x1, acc1);
+    float ssum = s_own;
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+        acc0[e] = __fmul_rn(acc0[e], s_own);
+        acc1[e] = __fmul_rn(acc1[e], s_own);
+    }
+    if (kill) {
+        ssum = __fmul_rn(ssum, 0.0f);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            acc0[e] = __fmul_rn(acc0[e], 0.0f);
+            acc1[e] = __fmul_rn(acc1[e], 0.0f);
+        }
+    }
+    for (int base = 0; base < r; base += WAVE) {
+        const int kk = base + lane;
+        const int ks = kk < r ? kk : 0;
+        const int d_l = kk < r ? (int)dstg[ks] : -1;
+        unsigned long long mk = __ballot(d_l == j);
+        if (mk == 0ull) continue;
+        // the block's source tokens and sizes, one rank per lane: one vector load each
+        const int ts_l = 2 * (int)srcg[ks];
+        const float sz_l = has_s ? to_f32(sg[ts_l]) : 1.0f;
+        while (mk) {
+            const int b = (int)__ffsll((long long)mk) - 1;
+            mk &= mk - 1ull;
+            const int ts = __builtin_amdgcn_readlane(ts_l, b);
+            const float sq = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(sz_l), b));
+            const TX *sr = xg + (int64_t)ts * C;
+            Slot<TX> p0 = ld_slot<TX>(sr, c0s), p1 = ld_slot<TX>(sr, c1s);
+            if (add) {
+                const TA *sa = ag + (int64_t)ts * C;
+                const Slot<TA> q0 = ld_slot<TA>(sa, c0s), q1 = ld_slot<TA>(sa, c1s);
+                p0 = slot_add<TX, TA>(p0, q0);
+                p1 = slot_add<TX, TA>(p1, q1);
+            }
+            float v0[VEC], v1[VEC];
+            slot_f32<TX>(p0, v0);
+            slot_f32<TX>(p1, v1);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                acc0[e] = __fadd_rn(acc0[e], __fmul_rn(v0[e], sq));
+                acc1[e] = __fadd_rn(acc1[e], __fmul_rn(v1[e], sq));
+            }
+            ssum = __fadd_rn(ssum, sq);
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+        acc0[e] = __fdiv_rn(acc0[e], ssum);
+        acc1[e] = __fdiv_rn(acc1[e], ssum);
+    }
+    const int o = out_row_dst(j, U, distill);
+    const Slot<TX> o0 = f32_slot<TX>(acc0), o1 = f32_slot<TX>(acc1);
+    TX *orow = og + (int64_t)o * C;
+    if (a0) st_slot<TX>(orow, c0, o0);
+    if (a1) st_slot<TX>(orow, c1, o1);
+    if (lane == 0) store_size<TS>(sog + o, log ? log + o : nullptr, ssum);
+    // LayerNorm of the row as stored
+    float w0[VEC], w1[VEC], b0[VEC], b1[VEC];
+    ld_param8(lw, c0s, w0);
+    ld_param8(lw, c1s, w1);
+    ld_param8(lb, c0s, b0);
+    ld_param8(lb, c1s, b1);
+    const float inv_c = __builtin_amdgcn_rcpf((float)C);
+    slot_f32<TX>(o0, acc0);
+    slot_f32<TX>(o1, acc1);
+    const float m = wave_total((a0 ? slot_sum<TX>(o0) : 0.0f) + (a1 ? slot_sum<TX>(o1) : 0.0f)) * inv_c;
+    float u0 = 0.0f, u1 = 0.0f;
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+        acc0[e] = acc0[e] - m;
+        acc1[e] = acc1[e] - m;
+        u0 = __fmaf_rn(acc0[e], acc0[e], u0);
+        u1 = __fmaf_rn(acc1[e], acc1[e], u1);
+    }
+    const float rs = __builtin_amdgcn_rsqf(wave_total((a0 ? u0 : 0.0f) + (a1 ? u1 : 0.0f)) * inv_c + eps);
+    TY *yrow = yg + (int64_t)o * C;
+    float yv[VEC];
+    if (a0) {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) yv[e] = __fmaf_rn(acc0[e], w0[e] * rs, b0[e]);
+        st_slot<TY>(yrow, c0, f32_slot<TY>(yv));
+    }
+    if (a1) {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) yv[e] = __fmaf_rn(acc1[e], w1[e] * rs, b1[e]);
+        st_slot<TY>(yrow, c1, f32_slot<TY>(yv));
+    }
+}
+
+template <typename TX, typename TA, typename TY, typename TS, int OP, int NIT>
+__global__ __launch_bounds__(256) void k_merge_rows_ln_amp(const TX *__restrict__ x, const TA *__restrict__ a,
+                                                           const TS *__restrict__ size, int n, int T_, int C, int r,
+                                                           int R, int cpr, int rg_per_group,
+                                                           const int64_t *__restrict__ src_idx,
+                                                           const int64_t *__restrict__ dst_idx,
+                                                           const int64_t *__restrict__ unm_idx, int distill,
+                                                           const uint8_t *__restrict__ keep,
+                                                           const float *__restrict__ lw, const float *__restrict__ lb,
+                                                           float eps, TX *__restrict__ xout, TY *__restrict__ y,
+                                                           TS *__restrict__ sout, TS *__restrict__ lsout) {
+    constexpr int VEC = 8;
+    const int lane = threadIdx.x & 63;
+    const int To = T_ - r;
+    // grid: x = the blocks of ONE group (streaming waves, then the r edge waves), (y, z) = the group
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int g = (int)(blockIdx.z * gridDim.y + blockIdx.y);
+    if (g >= n) return;
+    const int wg = (int)blockIdx.x * (int)(blockDim.x >> 6) + wv;
+    const bool add = a != nullptr;
+    const TX *xg = x + (int64_t)g * T_ * C;
+    const TA *ag = add ? a + (int64_t)g * T_ * C : nullptr;
+    TX *og = xout + (int64_t)g * To * C;
+    TY *yg = y + (int64_t)g * To * C;
+    const TS *sg = (OP == OP_WAVG && size) ? size + (int64_t)g * T_ : nullptr;
+    const int T1 = (T_ + 1) >> 1, U = T1 - r;
+    if (wg >= rg_per_group) {
+        const int k = wg - rg_per_group;
+        if (OP == OP_DROP || k >= r) return;
+        merge_dst_row_amp<TX, TA, TY, TS, OP>(xg, ag, sg, C, cpr, r, g, k, src_idx + (int64_t)g * r,
+                                              dst_idx + (int64_t)g * r, keep, og, yg, sout + (int64_t)g * To,
+                                              lsout ? lsout + (int64_t)g * To : nullptr, U, distill, lane, lw, lb, eps);
+        return;
+    }
+    const int o0 = wg * R;
+    const int64_t *dstg = OP != OP_DROP ? dst_idx + (int64_t)g * r : nullptr;
+    // per-row facts by lanes 0..R-1, broadcast as wave-uniform scalars (k_merge_rows_fast): source token, B-row number,
+    // size.  The first block of dst_idx and the unm_idx entries go out together; which rows receive sources is decided
+    // after the row loads have been issued.
+    const int d_first = (OP != OP_DROP && lane < r) ? (int)dstg[lane] : -2;
+    const bool my_valid = lane < R && (o0 + lane) < To;
+    bool is_dst;
+    int idx;
+    decode_out_row(my_valid ? o0 + lane : 0, U, distill, is_dst, idx);
+    int my_tok = 2 * idx + 1, my_j = idx;
+    const bool all_dst = (!distill && o0 >= U) || o0 > U;
+    if (U > 0 && !all_dst) {  // (wave-uniform; unm_idx may be absent when every even token is merged away)
+        const int ut = 2 * (int)unm_idx[(int64_t)g * U + ((my_valid && !is_dst) ? idx : 0)];
+        my_tok = is_dst ? my_tok : ut;
+        my_j = is_dst ? my_j : -1;
+    }
+    my_tok = my_valid ? my_tok : 0;
+    my_j = my_valid ? my_j : -1;
+    // (read unconditionally -- from the tokens themselves when there are no sizes: no branch in front of the row loads)
+    const bool load_size = sg != nullptr;  // wave-uniform
+    const TS my_s_raw = (load_size ? sg : reinterpret_cast<const TS *>(xg))[my_tok];
+    const unsigned long long vmask = __ballot(my_valid);
+    const int tok0 = __builtin_amdgcn_readlane(my_tok, 0), tok1 = __builtin_amdgcn_readlane(my_tok, 1),
+              tok2 = __builtin_amdgcn_readlane(my_tok, 2), tok3 = __builtin_amdgcn_readlane(my_tok, 3);
+    const int j0 = __builtin_amdgcn_readlane(my_j, 0), j1 = __builtin_amdgcn_readlane(my_j, 1),
+              j2 = __builtin_amdgcn_readlane(my_j, 2), j3 = __builtin_amdgcn_readlane(my_j, 3);
+    const bool va0 = vmask & 1ull, va1 = vmask & 2ull, va2 = vmask & 4ull, va3 = vmask & 8ull;
+
+    // flattened slot loop: slot q of the R-row slab -> (row q / cpr, slot column q % cpr)
+    const int total = R * cpr;
+    Slot<TX> raw[NIT];
+    Slot<TA> rawa[NIT] = {};
+    int rowof[NIT];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const int q = it * WAVE + lane;
+        const int rr = (q >= cpr) + (q >= 2 * cpr) + (q >= 3 * cpr);
+        const int t = rr == 0 ? tok0 : (rr == 1 ? tok1 : (rr == 2 ? tok2 : tok3));
+        const bool ok = (rr == 0 ? va0 : (rr == 1 ? va1 : (rr == 2 ? va2 : va3))) && (q < total);
+        rowof[it] = ok ? rr : -1;
+        const int64_t toff = (int64_t)(ok ? t : tok0) * C;
+        const int cc = ok ? q - rr * cpr : 0;
+        raw[it] = ld_slot<TX>(xg + toff, cc);
+        if (add) rawa[it] = ld_slot<TA>(ag + toff, cc);  // (wave-uniform)
+    }
+    bool e0 = false, e1 = false, e2 = false, e3 = false;  // rows that receive sources: the edge waves build them
+    if (OP != OP_DROP) {
+        e0 = __ballot(d_first == j0) != 0ull;
+        e1 = __ballot(d_first == j1) != 0ull;
+        e2 = __ballot(d_first == j2) != 0ull;
+        e3 = __ballot(d_first == j3) != 0ull;
+        for (int base = WAVE; base < r; base += WAVE) {
+            const int k = base + lane;
+            const int d = (k < r) ? (int)dstg[k] : -2;
+            e0 = e0 || (__ballot(d == j0) != 0ull);
+            e1 = e1 || (__ballot(d == j1) != 0ull);
+            e2 = e2 || (__ballot(d == j2) != 0ull);
+            e3 = e3 || (__ballot(d == j3) != 0ull);
+        }
+    }
+    const bool ok0 = va0 && !e0, ok1 = va1 && !e1, ok2 = va2 && !e2, ok3 = va3 && !e3;
+    // the parameter slots of every slot column this lane holds: requested now, used after the two reductions
+    float wvv[NIT][VEC], bvv[NIT][VEC];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const int rr = rowof[it];
+        const bool ok = rr >= 0 && (rr == 0 ? ok0 : (rr == 1 ? ok1 : (rr == 2 ? ok2 : ok3)));
+        rowof[it] = ok ? rr : -1;
+        const int cc = ok ? it * WAVE + lane - rr * cpr : 0;
+        ld_param8(lw, cc, wvv[it]);
+        ld_param8(lb, cc, bvv[it]);
+    }
+    const float my_s = (load_size && my_valid) ? to_f32(my_s_raw) : 1.0f;
+    const float sz0 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_s), 0)),
+                sz1 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_s), 1)),
+                sz2 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_s), 2)),
+                sz3 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_s), 3));
+    // x' = x + a, the merge of a row without sources ((x' s) / s: raw bits when that is x' itself), the store, and the
+    // first pass of the LayerNorm over the stored values
+    constexpr bool narrow = sizeof(TX) == 2;
+    const float inv_c = __builtin_amdgcn_rcpf((float)C);
+    float d[NIT][VEC];
+    float p0 = 0.0f, p1 = 0.0f, p2 = 0.0f, p3 = 0.0f;
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const int rr = rowof[it];
+        if (rr >= 0) {
+            if (add) raw[it] = slot_add<TX, TA>(raw[it], rawa[it]);
+            if (OP == OP_WAVG) {
+                const float s = rr == 0 ? sz0 : (rr == 1 ? sz1 : (rr == 2 ? sz2 : sz3));
+                const uint32_t sb = __float_as_uint(s);
+                const bool exact = (s == 1.0f) || (narrow && (sb & 0x007FFFFFu) == 0u && s >= 1.0f && s <= 65536.0f);
+                if (!exact) {
+                    float v[VEC];
+                    slot_f32<TX>(raw[it], v);
+#pragma unroll
+                    for (int e = 0; e < VEC; ++e) v[e] = __fdiv_rn(__fmul_rn(v[e], s), s);
+                    raw[it] = f32_slot<TX>(v);
+                }
+            }
+            st_slot<TX>(og + (int64_t)(o0 + rr) * C, it * WAVE + lane - rr * cpr, raw[it]);
+        }
+        slot_f32<TX>(raw[it], d[it]);  // the stored values; centred below
+        const float t = rr >= 0 ? slot_sum<TX>(raw[it]) : 0.0f;
+        p0 += rr == 0 ? t : 0.0f;
+        if (R > 1) p1 += rr == 1 ? t : 0.0f;
+        if (R > 2) {
+            p2 += rr == 2 ? t : 0.0f;
+            p3 += rr == 3 ? t : 0.0f;
+        }
+    }
+    if (OP == OP_WAVG && my_valid) {
+        const bool mine_has_edges = lane == 0 ? e0 : (lane == 1 ? e1 : (lane == 2 ? e2 : e3));
+        if (!mine_has_edges)
+            store_size<TS>(sout + (int64_t)g * To + o0 + lane, lsout ? lsout + (int64_t)g * To + o0 + lane : nullptr, my_s);
+    }
+    float m0 = wave_total(p0) * inv_c, m1 = 0.0f, m2 = 0.0f, m3 = 0.0f;
+    if (R > 1) m1 = wave_total(p1) * inv_c;
+    if (R > 2) {
+        m2 = wave_total(p2) * inv_c;
+        m3 = wave_total(p3) * inv_c;
+    }
+    p0 = p1 = p2 = p3 = 0.0f;
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const int rr = rowof[it];
+        const float m = pick4(rr, m0, m1, m2, m3, R);
+        float u = 0.0f;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            d[it][e] = d[it][e] - m;
+            u = __fmaf_rn(d[it][e], d[it][e], u);
+        }
+        u = rr >= 0 ? u : 0.0f;
+        p0 += rr == 0 ? u : 0.0f;
+        if (R > 1) p1 += rr == 1 ? u : 0.0f;
+        if (R > 2) {
+            p2 += rr == 2 ? u : 0.0f;
+            p3 += rr == 3 ? u : 0.0f;
+        }
+    }
+    float r0 = __builtin_amdgcn_rsqf(wave_total(p0) * inv_c + eps), r1 = 0.0f, r2 = 0.0f, r3 = 0.0f;
+    if (R > 1) r1 = __builtin_amdgcn_rsqf(wave_total(p1) * inv_c + eps);
+    if (R > 2) {
+        r2 = __builtin_amdgcn_rsqf(wave_total(p2) * inv_c + eps);
+        r3 = __builtin_amdgcn_rsqf(wave_total(p3) * inv_c + eps);
+    }
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const int rr = rowof[it];
+        if (rr < 0) continue;
+        const float rs = pick4(rr, r0, r1, r2, r3, R);
+        float yv[VEC];
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) yv[e] = __fmaf_rn(d[it][e], wvv[it][e] * rs, bvv[it][e]);
+        st_slot<TY>(yg + (int64_t)(o0 + rr) * C, it * WAVE + lane - rr * cpr, f32_slot<TY>(yv));
+    }
+}

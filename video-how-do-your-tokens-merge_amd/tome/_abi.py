@@ -92,6 +92,9 @@ SIGNATURES = {
     "tome_merge_ln_backward_workspace_bytes": (sz, [i64, i64, i64], True),
     "tome_merge_ln_backward": (i32, [vp, vp, vp, i32, vp, vp, i32, i64, i64, i64, i64, vp, i32, i32, vp, f32, vp, vp, vp,
                                     vp, vp], True),
+    "tome_merge_wavg_ln_amp": (i32, [vp, i32, vp, i32, vp, i32, i64, i64, i64, i64, vp, vp, vp, i32, vp, vp, vp, f32, vp,
+                                    vp, i32, vp, vp, vp], True),
+    "tome_drop_ln_amp": (i32, [vp, i32, vp, i32, i64, i64, i64, i64, vp, i32, vp, vp, f32, vp, vp, i32, vp], True),
 }
 SYMBOLS = tuple(SIGNATURES)
 
@@ -602,6 +605,72 @@ def add_layernorm_amp(x: torch.Tensor, addend: Optional[torch.Tensor], weight: t
                    _ptr(x_out), y_out.data_ptr(), DTYPES[y_dtype], _stream(x.device))
     _check(rc, "tome_add_layernorm_amp")
     return (x if addend is None else x_out), y_out
+
+
+def ln_amp_fusable(x: torch.Tensor, norm, *others) -> bool:
+    """Can tome_merge_wavg_ln_amp / tome_drop_ln_amp produce norm(x') for this LayerNorm module under autocast (the
+    tensors of _ln_amp_of; others[0], when given, is the addend the launch reads beside x), no gradient wanted of any
+    participant?  False whenever autocast is off."""
+    addend = others[0] if others else None
+    return (isinstance(norm, torch.nn.LayerNorm) and x.is_cuda and _ln_amp_of(x, norm, addend)
+            and not (torch.is_grad_enabled() and needs_grad(x, norm.weight, norm.bias, *others)))
+
+
+def _amp_merge_args(what: str, plan: MatchPlan, x: torch.Tensor, weight, bias, y_dtype, addend):
+    """The checks merge_wavg_ln_amp and drop_ln_amp share: (x, weight, bias, addend) as the entries take them."""
+    x = _prep_x(plan, x, f"{what}(x)", plan.T)
+    if y_dtype not in _HALF:
+        raise TomeHipError(f"{what}: y_dtype must be a 16-bit dtype, got {y_dtype}")
+    weight, bias = _f32_params(what, x.shape[-1], x.device, weight, bias)
+    if addend is not None:
+        if addend.shape != x.shape or addend.device != x.device:
+            raise TomeHipError(f"{what}: addend must match x in shape and device")
+        addend = addend if addend.is_contiguous() else addend.contiguous()
+    return x, weight, bias, addend
+
+
+def merge_wavg_ln_amp(plan: MatchPlan, x: torch.Tensor, size: Optional[torch.Tensor], weight: torch.Tensor,
+                      bias: torch.Tensor, eps: float, y_dtype: torch.dtype, addend: Optional[torch.Tensor] = None,
+                      log_size: bool = False):
+    """tome_merge_wavg_ln_amp: merge_wavg_ln for a model under autocast -- fp32 weight and bias, y_out of the 16-bit
+    `y_dtype`, x of y_dtype (addend of the same) or fp32 (addend of y_dtype or fp32; the tokens that are merged are
+    `x + addend.float()`).  Returns (x_out, y_out, size_out): x_out and size_out are merge_wavg's of the sum, bit for bit,
+    y_out = LayerNorm(x_out)."""
+    x, weight, bias, addend = _amp_merge_args("merge_wavg_ln_amp", plan, x, weight, bias, y_dtype, addend)
+    n, T, C = x.shape
+    size, sdtype = _prep_size(size, n, T, x)
+    L = lib()
+    entry = require_symbol(L, "tome_merge_wavg_ln_amp")
+    x_out = torch.empty((n, T - plan.r, C), dtype=x.dtype, device=x.device)
+    y_out = torch.empty((n, T - plan.r, C), dtype=y_dtype, device=x.device)
+    s_out = torch.empty((n, T - plan.r, 1), dtype=sdtype, device=x.device)
+    log = _log_size_like(s_out, log_size)
+    with _on_device(x.device):
+        rc = entry(x.data_ptr(), dtype_code(x, "x"), _ptr(addend), 0 if addend is None else dtype_code(addend, "addend"),
+                   _ptr(size), DTYPES[sdtype], n, T, C, plan.r, plan.src_idx.data_ptr(), plan.dst_idx.data_ptr(),
+                   plan.unm_idx.data_ptr(), int(plan.distill_token), _ptr(plan.edge_keep), weight.data_ptr(),
+                   bias.data_ptr(), float(eps), x_out.data_ptr(), y_out.data_ptr(), DTYPES[y_dtype], s_out.data_ptr(),
+                   _ptr(log), _stream(x.device))
+    _check(rc, "tome_merge_wavg_ln_amp")
+    return x_out, y_out, s_out
+
+
+def drop_ln_amp(plan: MatchPlan, x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float,
+                y_dtype: torch.dtype, addend: Optional[torch.Tensor] = None):
+    """tome_drop_ln_amp: drop_ln for a model under autocast (dtypes as in merge_wavg_ln_amp).  Returns (x_out, y_out): the
+    rows drop keeps of `x + addend`, bit for bit, and their LayerNorm in y_dtype."""
+    x, weight, bias, addend = _amp_merge_args("drop_ln_amp", plan, x, weight, bias, y_dtype, addend)
+    n, T, C = x.shape
+    L = lib()
+    entry = require_symbol(L, "tome_drop_ln_amp")
+    x_out = torch.empty((n, T - plan.r, C), dtype=x.dtype, device=x.device)
+    y_out = torch.empty((n, T - plan.r, C), dtype=y_dtype, device=x.device)
+    with _on_device(x.device):
+        rc = entry(x.data_ptr(), dtype_code(x, "x"), _ptr(addend), 0 if addend is None else dtype_code(addend, "addend"),
+                   n, T, C, plan.r, plan.unm_idx.data_ptr(), int(plan.distill_token), weight.data_ptr(), bias.data_ptr(),
+                   float(eps), x_out.data_ptr(), y_out.data_ptr(), DTYPES[y_dtype], _stream(x.device))
+    _check(rc, "tome_drop_ln_amp")
+    return x_out, y_out
 
 
 def add_layernorm_regrouped(x: torch.Tensor, addend: torch.Tensor, frames: int, weight: torch.Tensor,

@@ -575,17 +575,27 @@ def merge_wavg(merge: Callable, x: torch.Tensor, size: Optional[torch.Tensor] = 
 
 def _ln_route(merge: Callable, x: torch.Tensor, norm, residual, size=None) -> Optional[str]:
     """How merge_wavg_ln / drop_ln below run: "direct" (the fused launch: no gradient wanted), "function" (the same
-    launch as tome/_ln.py::_MergeLnFunction, tome_merge_ln_backward behind it) or None: the three unfused steps."""
+    launch as tome/_ln.py::_MergeLnFunction, tome_merge_ln_backward behind it), "amp_direct" (under autocast, tensors of
+    the kind _abi._ln_amp_of describes and no gradient wanted: tome_merge_wavg_ln_amp / tome_drop_ln_amp, while
+    tome._ln.NATIVE_LN_AUTOCAST is on) or None: the three unfused steps.  Without autocast the answers are those of the
+    first three alone."""
     from . import _ln
     plan = getattr(merge, "plan", None)
     if not (isinstance(plan, _abi.MatchPlan) and x.is_cuda and x.dim() == 3 and x.device == plan.device
             and isinstance(norm, torch.nn.LayerNorm)
-            and (residual is None or (residual.shape == x.shape and residual.dtype == x.dtype
-                                      and residual.device == x.device))):
+            and (residual is None or (residual.shape == x.shape and residual.device == x.device))):
         return None
+    same_dtype = residual is None or residual.dtype == x.dtype
     wanted = _abi.needs_grad(x, residual, size, norm.weight, norm.bias)
     if not wanted:
-        return "direct" if _abi.ln_fusable(x, norm, residual) else None
+        if same_dtype and _abi.ln_fusable(x, norm, residual):
+            return "direct"
+        if (_ln.NATIVE_LN_AUTOCAST and _abi.autocast_dtype(x.device) is not None
+                and _abi.ln_amp_fusable(x, norm, residual)):
+            return _ln.AMP_DIRECT
+        return None
+    if not same_dtype:
+        return None
     if size is not None and _wants_autograd(size):
         return None
     return "function" if _ln.enabled() and _abi.merge_ln_trainable(x, norm, residual, merge) else None
@@ -599,12 +609,17 @@ def merge_wavg_ln(merge: Callable, x: torch.Tensor, size: Optional[torch.Tensor]
     channels; when x, the residual or the norm requires grad, the same launch as an autograd Function whose backward
     is one launch too (tome_merge_ln_backward) where `_abi.merge_ln_trainable` holds.  Anything else -- a size that
     requires grad, a hybrid or partition matching, fp32 tokens, a LayerNorm subclass under grad, CPU tensors -- runs the
-    three steps, so there always is an answer."""
+    three steps, so there always is an answer.  Under torch.autocast, with an fp32 LayerNorm, a 16-bit or fp32 x and no
+    gradient wanted, the launch is tome_merge_wavg_ln_amp (`_ln_route`: "amp_direct"): y comes back in the autocast dtype,
+    x and size are those of the three steps bit for bit."""
     from . import _ln
     how = _ln_route(merge, x, norm, residual, size)
     if how == "direct":
         return _abi.merge_wavg_ln(merge.plan, x, size, norm.weight, norm.bias, norm.eps, addend=residual,
                                   log_size=log_size)
+    if how == _ln.AMP_DIRECT:
+        return _abi.merge_wavg_ln_amp(merge.plan, x, size, norm.weight, norm.bias, norm.eps,
+                                      _abi.autocast_dtype(x.device), addend=residual, log_size=log_size)
     if how == "function":
         return _ln.merge_ln_native(merge.plan, x, residual, size, norm, log_size=log_size)
     if residual is not None:
@@ -616,11 +631,15 @@ def merge_wavg_ln(merge: Callable, x: torch.Tensor, size: Optional[torch.Tensor]
 def drop_ln(drop: Callable, x: torch.Tensor, norm, residual: Optional[torch.Tensor] = None
             ) -> Tuple[torch.Tensor, torch.Tensor]:
     """``x = x + residual; x = drop(x); y = norm(x)`` for the callable of bipartite_soft_matching_drop: returns (x, y).
-    Routed as merge_wavg_ln: tome_drop_ln, with tome_merge_ln_backward behind it under grad, else the three steps."""
+    Routed as merge_wavg_ln: tome_drop_ln, with tome_merge_ln_backward behind it under grad, tome_drop_ln_amp under
+    autocast without grad ("amp_direct"), else the three steps."""
     from . import _ln
     how = _ln_route(drop, x, norm, residual)
     if how == "direct":
         return _abi.drop_ln(drop.plan, x, norm.weight, norm.bias, norm.eps, addend=residual)
+    if how == _ln.AMP_DIRECT:
+        return _abi.drop_ln_amp(drop.plan, x, norm.weight, norm.bias, norm.eps, _abi.autocast_dtype(x.device),
+                                addend=residual)
     if how == "function":
         return _ln.merge_ln_native(drop.plan, x, residual, None, norm, drop=True)[:2]
     if residual is not None:

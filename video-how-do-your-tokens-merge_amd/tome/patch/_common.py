@@ -490,6 +490,50 @@ def _merge_then_norm_trained(metric, x, info, norm, residual, kind: str):
     return x, y
 
 
+# True: under torch.autocast (fp32 LayerNorm parameters, a 16-bit or fp32 residual stream) a flat-layout block (VideoMAE,
+# ViViT) of kind "merge", "hybrid" or "drop" (fused_kind) with nothing wanting a gradient and no trace_source takes the
+# residual add, the reduction and the LayerNorm as ONE launch (tome_merge_wavg_ln_amp / tome_drop_ln_amp) instead of the
+# framework's add, the reduction kernel and tome_add_layernorm_amp.  The stream and the sizes keep their bits; y is the
+# same LayerNorm of the same stored rows by another fp32 summation order.  Yields to tome._ln.NATIVE_LN_AUTOCAST = False,
+# TOME_FUSE_LN=0, TOME_FUSE_MODES=0 (all kinds but plain merge) and TOME_FUSE_ADD=0 (the add stays the framework's).  Off
+# by default: what that rests on is said in DESIGN.md section 1 (measure with tools/autocast_merge_ln_bench.py).
+AUTOCAST_FUSED_LN = False
+
+
+def _autocast_fused(x, norm, residual, info) -> bool:
+    """May this layer's reduction run as the mixed-precision launch?  Asked before the matching, of the tensors alone:
+    autocast on, the 16-bit launch not applicable (it keeps its place), the kinds of _abi.ln_amp_fusable."""
+    if info["trace_source"] or not _ln.NATIVE_LN_AUTOCAST or _abi.autocast_dtype(x.device) is None:
+        return False
+    if x.dim() != 3 or _abi.ln_fusable(x, norm, residual):
+        return False
+    return (_abi.ln_amp_fusable(x, norm, residual)
+            and _abi.effective_r(x.shape[1], info["r"][0], info["class_token"], info["distill_token"]) > 0)
+
+
+def _merge_then_norm_autocast(metric, x, info, norm, residual, kind: str):
+    """merge_then_norm's steps as one mixed-precision launch (AUTOCAST_FUSED_LN); `fold` has no place here: under
+    autocast the Linear that finishes the block writes a 16-bit tensor of its own."""
+    half = _abi.autocast_dtype(x.device)
+    r = info["r"].pop(0)
+    before = x.size(1)
+    if kind == "drop":
+        drop = bipartite_soft_matching_drop(metric, r, info["class_token"], info["distill_token"], info["mode"])
+        x, y = _abi.drop_ln_amp(drop.plan, x, norm.weight, norm.bias, norm.eps, half, addend=residual)
+        info["size"] = torch.ones((x.size(0), x.size(1), 1), device=x.device)
+    else:
+        if kind == "hybrid":
+            merge, _ = bipartite_soft_matching_hybrid(metric, r, info["class_token"], info["distill_token"], info["mode"],
+                                                      info["threshold"])
+        else:
+            merge, _ = bipartite_soft_matching(metric, r, info["class_token"], info["distill_token"], info["mode"])
+        x, y, info["size"] = _abi.merge_wavg_ln_amp(merge.plan, x, info["size"], norm.weight, norm.bias, norm.eps, half,
+                                                    addend=residual, log_size=info["prop_attn"])
+    if info["verbose"]:
+        print(f"{'Dropped' if kind == 'drop' else 'Merged'} {before} to {x.size(1)} tokens")
+    return x, y
+
+
 def merge_then_norm(metric, x, info, norm, reduction_function, plain_merge_fn, residual=None, fold=None, drop_fn=None,
                     hybrid_fn=None):
     """The block steps `[x = x + residual;] x = reduction_function(metric, x, info); y = norm(x)` with the
@@ -509,6 +553,10 @@ def merge_then_norm(metric, x, info, norm, reduction_function, plain_merge_fn, r
     plain = _FUSE_LN and kind is not None and r_list and r_list[0] > 0
     if TRAIN_FUSED_LN and plain and _train_fused(kind, x, norm, residual, info):
         return _merge_then_norm_trained(metric, x, info, norm, residual, kind)
+    if AUTOCAST_FUSED_LN and plain and _autocast_fused(x, norm, residual if _FUSE_ADD else None, info):
+        if residual is not None and not _FUSE_ADD:
+            x, residual = x + residual, None
+        return _merge_then_norm_autocast(metric, x, info, norm, residual, kind)
     fused = plain and _abi.ln_fusable(x, norm, residual)
     if residual is not None and not (fused and _FUSE_ADD and not info["trace_source"] and residual.dtype == x.dtype
                                      and _abi.effective_r(x.shape[1], r_list[0], info["class_token"],
