@@ -18,6 +18,7 @@ import test_modes_route_cpu as base
 BF, HF, F32 = base.BF, base.HF, base.F32
 MERGE_LN, DROP_LN, UNFUSED = base.MERGE_LN, base.DROP_LN, base.UNFUSED
 MERGE_AMP, DROP_AMP = "merge_wavg_ln_amp", "drop_ln_amp"
+FUNCTION = "function"  # the public call, which takes _MergeLnFunction on a device
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CUDA = torch.device("cuda", 0)
 
@@ -130,6 +131,41 @@ def test_ln_route_other_refusals(monkeypatch):
     assert M._ln_route(merge, T(F32, shape=(2, 8, 1032)), torch.nn.LayerNorm(1032), None) is None  # C > 1024
 
 
+WITH_PLAN = [r for r in ROUTE if r[5] in ("even_odd", "hybrid")]
+
+
+@pytest.mark.parametrize("row", WITH_PLAN, ids=[i for i, r in zip(_route_ids(), ROUTE) if r in WITH_PLAN])
+def test_one_rule_before_and_behind_the_matching(row, monkeypatch):
+    """`_ln_route` asked without a matching (merge=None) answers as with one on the same tensors -- but for what only
+    the plan can say: its threshold flags refuse the Function.  And the patched blocks' route (both switches on) gives the
+    same "function" / "amp_direct" answers, with its kind standing in for the flags."""
+    autocast, xd, rd, pd, who, plan_kind, native, want = row
+    from tome import _abi, _ln
+    from tome import merge as M
+    from tome.patch import _common as C
+    monkeypatch.setattr(_abi, "autocast_dtype", lambda device: autocast)
+    monkeypatch.setattr(_ln, "NATIVE_LN_AUTOCAST", native)
+    monkeypatch.setattr(C, "TRAIN_FUSED_LN", True)
+    monkeypatch.setattr(C, "AUTOCAST_FUSED_LN", True)
+    x = T(xd, who == "x")
+    res = None if rd is None else T(rd, who == "residual")
+    size = T(F32, who == "size", shape=(2, 8, 1))
+    norm = _norm(pd, who == "norm")
+    behind = M._ln_route(types.SimpleNamespace(plan=_plan(plan_kind)), x, norm, res, size)
+    before = M._ln_route(None, x, norm, res, size)
+    assert behind == want
+    if plan_kind == "hybrid" and before == "function":
+        assert behind is None
+    else:
+        assert before == behind
+    mode = "hybrid" if plan_kind == "hybrid" else "merge"
+    info = base._info(mode, False, 2)
+    info["size"] = size
+    got = C.fused_route(mode, x, norm, res, info)
+    switched = ("function", "amp_direct")
+    assert (got if got in switched else None) == (behind if behind in switched else None)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # merge_then_norm
 # ---------------------------------------------------------------------------------------------------------------------
@@ -188,12 +224,38 @@ def _block_ids():
     return ["-".join(str(v).replace("torch.", "") for v in row[:12]) for row in BLOCK]
 
 
-def _run_block(monkeypatch, row):
+def _train_seams(monkeypatch, seams, C):
+    """TRAIN_FUSED_LN on, with the Function route's seams of tests/test_merge_ln_route_cpu.py: the device-free copy of
+    `_abi.merge_ln_trainable` and recorders in place of the two public calls."""
+    from tome import _abi
+    from tome import merge as M
+    monkeypatch.setattr(C, "TRAIN_FUSED_LN", True)
+
+    def trainable(x, norm, addend, merge=None):
+        return (x.dim() == 3 and _abi.ln_trainable(x, norm)
+                and (addend is None or (addend.shape == x.shape and addend.dtype == x.dtype)))
+
+    def public_merge(merge, x, size, norm, residual=None, log_size=False):
+        seams.calls.append((FUNCTION, "merge", residual is not None))
+        return x[:, 2:] * 1, x[:, 2:] * 1, torch.ones(x.shape[0], x.shape[1] - 2, 1)
+
+    def public_drop(drop, x, norm, residual=None):
+        seams.calls.append((FUNCTION, "drop", residual is not None))
+        return x[:, 2:] * 1, x[:, 2:] * 1
+
+    monkeypatch.setattr(_abi, "merge_ln_trainable", trainable)
+    monkeypatch.setattr(M, "merge_wavg_ln", public_merge)
+    monkeypatch.setattr(M, "drop_ln", public_drop)
+
+
+def _run_block(monkeypatch, row, train=False):
     mode, autocast, xd, rd, pd, who, trace, attr, native, fuse_modes, fuse_ln, fuse_add = row[:12]
     from tome import _abi, _ln
     seams, C, _ = base._setup(monkeypatch, (mode, False, xd, autocast, trace, fuse_ln, fuse_add, fuse_modes, False))
     monkeypatch.setattr(C, "AUTOCAST_FUSED_LN", attr)
     monkeypatch.setattr(_ln, "NATIVE_LN_AUTOCAST", native)
+    if train:
+        _train_seams(monkeypatch, seams, C)
 
     def ln_amp_fusable(x, norm, *others):  # _abi.ln_amp_fusable without `x.is_cuda`
         return (isinstance(norm, torch.nn.LayerNorm) and _abi._ln_amp_of(x, norm, others[0] if others else None)
@@ -223,7 +285,7 @@ def _run_block(monkeypatch, row):
         xo, y = C.merge_then_norm(None, x, info, norm, fn, merge_fn, residual=res, fold=base._fc2(xd), drop_fn=drop_fn,
                                   hybrid_fn=hybrid_fn)
     assert info["r"] == [2], "exactly one r is consumed"
-    return seams, info, xo, y, [c for c in seams.calls if c[0] in (MERGE_LN, DROP_LN, UNFUSED, MERGE_AMP, DROP_AMP)]
+    return seams, info, xo, y, [c for c in seams.calls if c[0] in (MERGE_LN, DROP_LN, UNFUSED, MERGE_AMP, DROP_AMP, FUNCTION)]
 
 
 @pytest.mark.parametrize("row", BLOCK, ids=_block_ids())
@@ -255,6 +317,65 @@ def test_attribute_off_is_the_present_path(row, monkeypatch):
     assert not [c for c in got if c[0] in (MERGE_AMP, DROP_AMP)]
     if row[1]:
         assert [c for c in seams.calls if c[0] == "trailing_ln_kernel"] == [("trailing_ln_kernel", "amp_direct")]
+
+
+# TRAIN_FUSED_LN and AUTOCAST_FUSED_LN on together: the Function first, then the mixed-precision launch, then the 16-bit one
+# mode, autocast, stream, residual, parameters, who wants grad, trace, FUSE_ADD -> launch, residual fused as addend
+PRECEDENCE = [
+    # no-grad without autocast: the 16-bit launch
+    ("merge", False, BF, BF, BF, None, False, True, MERGE_LN, True),
+    ("hybrid", False, BF, BF, BF, None, False, True, MERGE_LN, True),
+    ("drop", False, HF, HF, HF, None, False, True, DROP_LN, True),
+    # no-grad under autocast with an fp32 norm: the mixed-precision launch
+    ("merge", True, F32, BF, F32, None, False, True, MERGE_AMP, True),
+    ("hybrid", True, BF, BF, F32, None, False, True, MERGE_AMP, True),
+    ("drop", True, BF, BF, F32, None, False, True, DROP_AMP, True),
+    # grad without autocast, kinds merge and drop: the Function; hybrid: three steps
+    ("merge", False, BF, BF, BF, "x", False, True, FUNCTION, True),
+    ("random_merge", False, BF, BF, BF, "residual", False, True, FUNCTION, True),
+    ("drop", False, BF, BF, BF, "norm", False, True, FUNCTION, True),
+    ("hybrid", False, BF, BF, BF, "x", False, True, UNFUSED, False),
+    # grad under autocast with an fp32 norm: three steps, then the trailing mixed-precision LayerNorm
+    ("merge", True, F32, BF, F32, "x", False, True, UNFUSED, False),
+    ("drop", True, BF, BF, F32, "x", False, True, UNFUSED, False),
+    # trace_source: the 16-bit launch in no-grad (the add stays the framework's), three steps under grad
+    ("merge", False, BF, BF, BF, None, True, True, MERGE_LN, False),
+    ("drop", False, BF, BF, BF, None, True, True, DROP_LN, False),
+    ("merge", False, BF, BF, BF, "x", True, True, UNFUSED, False),
+    ("merge", True, F32, BF, F32, None, True, True, UNFUSED, False),
+    # TOME_FUSE_ADD off under autocast: the framework's add, then the mixed-precision launch without addend
+    ("merge", True, F32, BF, F32, None, False, False, MERGE_AMP, False),
+    ("drop", True, BF, BF, F32, None, False, False, DROP_AMP, False),
+]
+
+
+@pytest.mark.parametrize("row", PRECEDENCE, ids=["-".join(str(v).replace("torch.", "") for v in r[:8]) for r in PRECEDENCE])
+def test_both_switches_on_precedence(row, monkeypatch):
+    mode, autocast, xd, rd, pd, who, trace, fuse_add, want, want_add = row
+    seams, info, xo, y, got = _run_block(
+        monkeypatch, (mode, autocast, xd, rd, pd, who, trace, True, True, True, True, fuse_add), train=True)
+    assert len(got) == 1 and got[0][0] == want, got
+    trailing = [c for c in seams.calls if c[0] == "trailing_ln_kernel"]
+    if want == UNFUSED:
+        if autocast:
+            assert trailing == [("trailing_ln_kernel", "amp_function" if who else "amp_direct")]
+    else:
+        assert not trailing, "the launch holds the LayerNorm"
+        which = "drop" if mode in ("drop", "random_drop") else "hybrid" if mode == "hybrid" else "merge"
+        assert [c[:2] for c in seams.calls if c[0] == "match"] == [("match", which)]
+        tracked = [c[0] for c in seams.calls if c[0].endswith("_source")]
+        assert tracked == ([] if not trace else ["drop_source" if which == "drop" else "merge_source"])
+    if want == FUNCTION:
+        assert got[0][1:] == ("drop" if mode in ("drop", "random_drop") else "merge", True), got
+        assert "_folded" not in info
+    elif want in (MERGE_AMP, DROP_AMP):
+        _, added, y_dtype, x_dtype, a_dtype = got[0]
+        assert added is want_add and y_dtype == BF
+        assert x_dtype == (xd if want_add else torch.promote_types(xd, rd)) and a_dtype == (rd if want_add else None)
+        assert "_folded" not in info
+    elif want in (MERGE_LN, DROP_LN):
+        assert got[0][1] is want_add
+        assert got[0][2] is (mode == "merge") and ("_folded" in info) is (mode == "merge"), got
 
 
 def test_the_attribute_is_off_by_default_and_the_entries_exist():

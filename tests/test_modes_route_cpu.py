@@ -282,6 +282,40 @@ def test_positional_call_forms_behave_as_before(monkeypatch):
     assert [c[0] for c in seams.launches()] == [UNFUSED]
 
 
+@pytest.mark.parametrize("kind, mode", [("merge", "merge"), ("merge", "random_merge"), ("hybrid", "hybrid"),
+                                        ("drop", "drop"), ("drop", "random_drop")])
+def test_matching_helper(kind, mode, monkeypatch):
+    """`matching(kind, metric, r, info)`: the kind's own matching, looked up on the module, with info's tokens, mode and
+    threshold; the callable that carries the plan, or None exactly when the matching reports a clamped r of 0 -- the
+    (do_nothing, do_nothing) pair, which is also the tuple the drop matching then answers with."""
+    from tome.merge import do_nothing
+    for r0 in (False, True):
+        seams = Seams(monkeypatch, r0)
+        C = seams.C
+        info = _info(mode, False, 2)
+        info["class_token"], info["distill_token"] = True, False
+        got = C.matching(kind, "metric", 3, info)
+        assert seams.calls == [("match", kind, 3, mode, 0.25 if kind == "hybrid" else None)]
+        if r0:
+            assert got is None
+        else:
+            assert got is not None and got is not do_nothing and got.plan.r == 2
+    # the answers' forms one by one, and the arguments as the matchings receive them
+    seen = []
+    carrier = types.SimpleNamespace(plan="plan")
+    for name, answer in (("bipartite_soft_matching", (carrier, "unmerge")),
+                         ("bipartite_soft_matching_hybrid", (carrier, "unmerge")),
+                         ("bipartite_soft_matching_drop", carrier)):
+        monkeypatch.setattr(C, name, lambda *a, _name=name, _answer=answer: seen.append((_name,) + a) or _answer)
+    assert C.matching(kind, "metric", 3, info) is carrier
+    which = {"merge": "bipartite_soft_matching", "hybrid": "bipartite_soft_matching_hybrid",
+             "drop": "bipartite_soft_matching_drop"}[kind]
+    assert seen == [(which, "metric", 3, True, False, mode) + ((0.25,) if kind == "hybrid" else ())]
+    for name in ("bipartite_soft_matching", "bipartite_soft_matching_hybrid", "bipartite_soft_matching_drop"):
+        monkeypatch.setattr(C, name, lambda *a: (do_nothing, do_nothing))
+    assert C.matching(kind, "metric", 3, info) is None
+
+
 def test_fused_kind_table():
     from tome.patch import _common as C
     assert C._FUSE_MODES is True  # the default

@@ -498,6 +498,16 @@ def _out_bias(out_bias, x, C):
     return out_bias.contiguous()
 
 
+def _addend(who: str, addend: Optional[torch.Tensor], x: torch.Tensor, same_dtype: bool = True):
+    """The addend a launch reads beside x, made contiguous (None: none): of x's shape and device -- and dtype, unless the
+    entry converts (same_dtype=False: the mixed-precision ones)."""
+    if addend is None:
+        return None
+    if addend.shape != x.shape or addend.device != x.device or (same_dtype and addend.dtype != x.dtype):
+        raise TomeHipError(f"{who}: addend must match x in shape{', dtype' if same_dtype else ''} and device")
+    return addend if addend.is_contiguous() else addend.contiguous()
+
+
 def merge_wavg_ln(plan: MatchPlan, x: torch.Tensor, size: Optional[torch.Tensor], weight: torch.Tensor,
                   bias: torch.Tensor, eps: float, addend: Optional[torch.Tensor] = None, log_size: bool = False,
                   out_bias: Optional[torch.Tensor] = None):
@@ -508,10 +518,7 @@ def merge_wavg_ln(plan: MatchPlan, x: torch.Tensor, size: Optional[torch.Tensor]
     x = _prep_x(plan, x, "merge_wavg_ln(x)", plan.T)
     n, T, C = x.shape
     out_bias = _out_bias(out_bias, x, C)
-    if addend is not None:
-        if addend.shape != x.shape or addend.dtype != x.dtype or addend.device != x.device:
-            raise TomeHipError("merge_wavg_ln: addend must match x in shape, dtype and device")
-        addend = addend if addend.is_contiguous() else addend.contiguous()
+    addend = _addend("merge_wavg_ln", addend, x)
     xcode = dtype_code(x, "x")
     size, sdtype = _prep_size(size, n, T, x)
     x_out = torch.empty((n, T - plan.r, C), dtype=x.dtype, device=x.device)
@@ -536,10 +543,7 @@ def add_layernorm(x: torch.Tensor, addend: Optional[torch.Tensor], weight: torch
     require_device(x, "add_layernorm(x)")
     x = x if x.is_contiguous() else x.contiguous()
     C = x.shape[-1]
-    if addend is not None:
-        if addend.shape != x.shape or addend.dtype != x.dtype or addend.device != x.device:
-            raise TomeHipError("add_layernorm: addend must match x in shape, dtype and device")
-        addend = addend if addend.is_contiguous() else addend.contiguous()
+    addend = _addend("add_layernorm", addend, x)
     if skip_first and (x.dim() != 3 or x.shape[1] < 2):
         raise TomeHipError("add_layernorm(skip_first): x must be [B, N >= 2, C]")
     # without addend: LayerNorm only, x holds the finished sum already (returned as it is)
@@ -591,10 +595,7 @@ def add_layernorm_amp(x: torch.Tensor, addend: Optional[torch.Tensor], weight: t
     C = x.shape[-1]
     groups, group_rows = _amp_rows("add_layernorm_amp", x, skip_first)
     weight, bias = _f32_params("add_layernorm_amp", C, x.device, weight, bias)
-    if addend is not None:
-        if addend.shape != x.shape or addend.device != x.device:
-            raise TomeHipError("add_layernorm_amp: addend must match x in shape and device")
-        addend = addend if addend.is_contiguous() else addend.contiguous()
+    addend = _addend("add_layernorm_amp", addend, x, same_dtype=False)
     L = lib()
     entry = require_symbol(L, "tome_add_layernorm_amp")
     x_out = None if addend is None else torch.empty_like(x)
@@ -622,11 +623,7 @@ def _amp_merge_args(what: str, plan: MatchPlan, x: torch.Tensor, weight, bias, y
     if y_dtype not in _HALF:
         raise TomeHipError(f"{what}: y_dtype must be a 16-bit dtype, got {y_dtype}")
     weight, bias = _f32_params(what, x.shape[-1], x.device, weight, bias)
-    if addend is not None:
-        if addend.shape != x.shape or addend.device != x.device:
-            raise TomeHipError(f"{what}: addend must match x in shape and device")
-        addend = addend if addend.is_contiguous() else addend.contiguous()
-    return x, weight, bias, addend
+    return x, weight, bias, _addend(what, addend, x, same_dtype=False)
 
 
 def merge_wavg_ln_amp(plan: MatchPlan, x: torch.Tensor, size: Optional[torch.Tensor], weight: torch.Tensor,
@@ -735,11 +732,7 @@ def _regrouped_addend(who: str, plan: MatchPlan, x_full: torch.Tensor, cls: int,
                 raise TomeHipError(f"{who}: cls_addend must hold {(B, C)} values of x's dtype")
             cls_addend = cls_addend.contiguous()
         return (addend_grouped if addend_grouped.is_contiguous() else addend_grouped.contiguous()), 1, cls_addend
-    if addend is not None:
-        if addend.shape != x_full.shape or addend.dtype != x_full.dtype or addend.device != x_full.device:
-            raise TomeHipError(f"{who}: addend must match x in shape, dtype and device")
-        addend = addend if addend.is_contiguous() else addend.contiguous()
-    return addend, 0, None
+    return _addend(who, addend, x_full), 0, None
 
 
 def merge_wavg_regrouped(plan: MatchPlan, x_full: torch.Tensor, size: Optional[torch.Tensor], frames: int,
@@ -816,10 +809,7 @@ def drop_ln(plan: MatchPlan, x: torch.Tensor, weight: torch.Tensor, bias: torch.
     x = _prep_x(plan, x, "drop_ln(x)", plan.T)
     n, T, C = x.shape
     out_bias = _out_bias(out_bias, x, C)
-    if addend is not None:
-        if addend.shape != x.shape or addend.dtype != x.dtype or addend.device != x.device:
-            raise TomeHipError("drop_ln: addend must match x in shape, dtype and device")
-        addend = addend if addend.is_contiguous() else addend.contiguous()
+    addend = _addend("drop_ln", addend, x)
     x_out = torch.empty((n, T - plan.r, C), dtype=x.dtype, device=x.device)
     y_out = torch.empty_like(x_out)
     L = lib()

@@ -573,16 +573,20 @@ def merge_wavg(merge: Callable, x: torch.Tensor, size: Optional[torch.Tensor] = 
     return x, size
 
 
-def _ln_route(merge: Callable, x: torch.Tensor, norm, residual, size=None) -> Optional[str]:
+def _ln_route(merge: Optional[Callable], x: torch.Tensor, norm, residual, size=None) -> Optional[str]:
     """How merge_wavg_ln / drop_ln below run: "direct" (the fused launch: no gradient wanted), "function" (the same
     launch as tome/_ln.py::_MergeLnFunction, tome_merge_ln_backward behind it), "amp_direct" (under autocast, tensors of
     the kind _abi._ln_amp_of describes and no gradient wanted: tome_merge_wavg_ln_amp / tome_drop_ln_amp, while
     tome._ln.NATIVE_LN_AUTOCAST is on) or None: the three unfused steps.  Without autocast the answers are those of the
-    first three alone."""
+    first three alone.
+    merge: the callable that carries the plan; None asks about the tensors alone, before the matching exists (the patched
+    blocks: tome/patch/_common.py::fused_route).  The device is asked by each answer's own predicate in _abi."""
     from . import _ln
-    plan = getattr(merge, "plan", None)
-    if not (isinstance(plan, _abi.MatchPlan) and x.is_cuda and x.dim() == 3 and x.device == plan.device
-            and isinstance(norm, torch.nn.LayerNorm)
+    if merge is not None:
+        plan = getattr(merge, "plan", None)
+        if not (isinstance(plan, _abi.MatchPlan) and x.device == plan.device):
+            return None
+    if not (x.dim() == 3 and isinstance(norm, torch.nn.LayerNorm)
             and (residual is None or (residual.shape == x.shape and residual.device == x.device))):
         return None
     same_dtype = residual is None or residual.dtype == x.dtype

@@ -13,8 +13,9 @@ from typing import Callable, Dict, Tuple
 import torch
 
 from .. import _abi, _attn, _ln, _mlp, _overlap
+from .. import merge as tm
 from .._mlp import _plain_mlp, _stock_module  # (the module-kind predicates live beside the MLP's route)
-from ..merge import (bipartite_soft_matching, bipartite_soft_matching_drop, bipartite_soft_matching_hybrid,
+from ..merge import (bipartite_soft_matching, bipartite_soft_matching_drop, bipartite_soft_matching_hybrid, do_nothing,
                      drop_regrouped, merge_source, merge_wavg, merge_wavg_regrouped)
 from ..utils import parse_r
 
@@ -328,10 +329,25 @@ def pick_reduction(mode: str, merge_fn, drop_fn, hybrid_fn):
     raise ValueError(f"unknown ToMe mode {mode!r}")
 
 
+def matching(kind: str, metric, r: int, info):
+    """This layer's matching for a reduction of `kind` ("merge", "hybrid" or "drop": fused_kind): the callable that carries
+    `.plan` -- merge(x, mode) or drop(x) -- or None when the clamped r is 0, which the matchings report as the
+    (do_nothing, do_nothing) pair."""
+    if kind == "drop":
+        found = bipartite_soft_matching_drop(metric, r, info["class_token"], info["distill_token"], info["mode"])
+    elif kind == "hybrid":
+        found = bipartite_soft_matching_hybrid(metric, r, info["class_token"], info["distill_token"], info["mode"],
+                                               info["threshold"])
+    else:
+        found = bipartite_soft_matching(metric, r, info["class_token"], info["distill_token"], info["mode"])
+    if isinstance(found, tuple):  # (merge, unmerge); the drop matching answers with a pair for a clamped r of 0 alone
+        found = found[0]
+    return None if found is do_nothing else found
+
+
 # ---- the reduction step on an already grouped [n, T, C] token tensor ---------------------------------
 def reduce_merge(metric, x, info, r):
-    merge, _ = bipartite_soft_matching(metric, r, info["class_token"], info["distill_token"], info["mode"])
-    return _apply_merge(merge, x, info)
+    return _apply_merge(matching("merge", metric, r, info) or do_nothing, x, info)
 
 
 def _apply_merge(merge, x, info):
@@ -458,38 +474,6 @@ def _fold_for(fold, x, mode: str):
 # said in DESIGN.md section 1 (measure with tools/merge_ln_backward_bench.py).
 TRAIN_FUSED_LN = False
 
-
-def _train_fused(kind: str, x, norm, residual, info) -> bool:
-    """May this layer's reduction run as _MergeLnFunction?  Asked before the matching: the facts about the tensors."""
-    if kind not in ("merge", "drop") or info["trace_source"] or not _ln.enabled():
-        return False
-    size = info["size"]
-    if not _abi.needs_grad(x, residual, norm.weight, norm.bias) or _abi.needs_grad(size):
-        return False
-    if size is not None and (size.device != x.device or size.shape != (x.shape[0], x.shape[1], 1)):
-        return False
-    return (_abi.merge_ln_trainable(x, norm, residual)
-            and _abi.effective_r(x.shape[1], info["r"][0], info["class_token"], info["distill_token"]) > 0)
-
-
-def _merge_then_norm_trained(metric, x, info, norm, residual, kind: str):
-    """merge_then_norm's steps through tome.merge.merge_wavg_ln / drop_ln for participants that require grad.  `fold` has
-    no place here: the stream is the one the three steps store."""
-    from ..merge import drop_ln, merge_wavg_ln
-    r = info["r"].pop(0)
-    before = x.size(1)
-    if kind == "drop":
-        drop = bipartite_soft_matching_drop(metric, r, info["class_token"], info["distill_token"], info["mode"])
-        x, y = drop_ln(drop, x, norm, residual)
-        info["size"] = torch.ones((x.size(0), x.size(1), 1), device=x.device)
-    else:
-        merge, _ = bipartite_soft_matching(metric, r, info["class_token"], info["distill_token"], info["mode"])
-        x, y, info["size"] = merge_wavg_ln(merge, x, info["size"], norm, residual, log_size=info["prop_attn"])
-    if info["verbose"]:
-        print(f"{'Dropped' if kind == 'drop' else 'Merged'} {before} to {x.size(1)} tokens")
-    return x, y
-
-
 # True: under torch.autocast (fp32 LayerNorm parameters, a 16-bit or fp32 residual stream) a flat-layout block (VideoMAE,
 # ViViT) of kind "merge", "hybrid" or "drop" (fused_kind) with nothing wanting a gradient and no trace_source takes the
 # residual add, the reduction and the LayerNorm as ONE launch (tome_merge_wavg_ln_amp / tome_drop_ln_amp) instead of the
@@ -500,115 +484,106 @@ def _merge_then_norm_trained(metric, x, info, norm, residual, kind: str):
 AUTOCAST_FUSED_LN = False
 
 
-def _autocast_fused(x, norm, residual, info) -> bool:
-    """May this layer's reduction run as the mixed-precision launch?  Asked before the matching, of the tensors alone:
-    autocast on, the 16-bit launch not applicable (it keeps its place), the kinds of _abi.ln_amp_fusable."""
-    if info["trace_source"] or not _ln.NATIVE_LN_AUTOCAST or _abi.autocast_dtype(x.device) is None:
-        return False
-    if x.dim() != 3 or _abi.ln_fusable(x, norm, residual):
-        return False
-    return (_abi.ln_amp_fusable(x, norm, residual)
-            and _abi.effective_r(x.shape[1], info["r"][0], info["class_token"], info["distill_token"]) > 0)
-
-
-def _merge_then_norm_autocast(metric, x, info, norm, residual, kind: str):
-    """merge_then_norm's steps as one mixed-precision launch (AUTOCAST_FUSED_LN); `fold` has no place here: under
-    autocast the Linear that finishes the block writes a 16-bit tensor of its own."""
-    half = _abi.autocast_dtype(x.device)
-    r = info["r"].pop(0)
-    before = x.size(1)
-    if kind == "drop":
-        drop = bipartite_soft_matching_drop(metric, r, info["class_token"], info["distill_token"], info["mode"])
-        x, y = _abi.drop_ln_amp(drop.plan, x, norm.weight, norm.bias, norm.eps, half, addend=residual)
-        info["size"] = torch.ones((x.size(0), x.size(1), 1), device=x.device)
-    else:
-        if kind == "hybrid":
-            merge, _ = bipartite_soft_matching_hybrid(metric, r, info["class_token"], info["distill_token"], info["mode"],
-                                                      info["threshold"])
+def fused_route(kind, x, norm, residual, info):
+    """How a flat-layout layer runs `x + residual`, its reduction of `kind` (fused_kind) and `norm` as ONE launch, asked
+    before the matching exists: "direct" (tome_merge_wavg_ln / tome_drop_ln: 16-bit tokens, nothing wants a gradient),
+    "function" (the same launch as tome/_ln.py::_MergeLnFunction: TRAIN_FUSED_LN, a participant wants one),
+    _ln.AMP_DIRECT (tome_merge_wavg_ln_amp / tome_drop_ln_amp: AUTOCAST_FUSED_LN under autocast, nothing wants one), or
+    None: the three steps.  residual: what the launch would read beside x (None: x is the finished sum).
+    The two switched answers are tome.merge._ln_route's rule about the tensors, asked without a matching; the patch
+    layer's own gates go on top: the Function covers the kinds "merge" and "drop" and sizes as the previous launch left
+    them, neither answer tracks sources, and both want a clamped r > 0 up front (their launches have no r == 0 form)."""
+    r_list = info["r"]
+    if not (_FUSE_LN and kind is not None and r_list and r_list[0] > 0):
+        return None
+    if (TRAIN_FUSED_LN or AUTOCAST_FUSED_LN) and not info["trace_source"]:
+        size = info["size"]
+        if torch.is_grad_enabled() and _abi.needs_grad(x, residual, norm.weight, norm.bias):
+            want = TRAIN_FUSED_LN and kind != "hybrid" and "function"
+            if size is not None and (size.device != x.device or size.shape != (x.shape[0], x.shape[1], 1)):
+                want = False
+            addend = residual  # (the Function reads the residual itself, whatever _FUSE_ADD says)
         else:
-            merge, _ = bipartite_soft_matching(metric, r, info["class_token"], info["distill_token"], info["mode"])
-        x, y, info["size"] = _abi.merge_wavg_ln_amp(merge.plan, x, info["size"], norm.weight, norm.bias, norm.eps, half,
-                                                    addend=residual, log_size=info["prop_attn"])
+            want = AUTOCAST_FUSED_LN and _abi.autocast_dtype(x.device) is not None and _ln.AMP_DIRECT
+            addend = residual if _FUSE_ADD else None  # (else the framework adds first, and the sum is asked again)
+        if (want and tm._ln_route(None, x, norm, addend, size) == want
+                and _abi.effective_r(x.shape[1], r_list[0], info["class_token"], info["distill_token"]) > 0):
+            return want
+    return "direct" if _abi.ln_fusable(x, norm, residual) else None
+
+
+# (route, is it a drop) -> the launch behind the matching `m`: (x, y, size) of a merge, (x, y) of a drop.  Every entry is
+# looked up on its module at the call: the stage timers and the route tables replace them there.
+_LAUNCH = {
+    ("direct", False): lambda m, x, info, norm, addend, fold: _abi.merge_wavg_ln(
+        m.plan, x, info["size"], norm.weight, norm.bias, norm.eps, addend=addend, log_size=info["prop_attn"],
+        out_bias=None if fold is None else fold.bias),
+    ("direct", True): lambda m, x, info, norm, addend, fold: _abi.drop_ln(
+        m.plan, x, norm.weight, norm.bias, norm.eps, addend=addend, out_bias=None if fold is None else fold.bias),
+    ("function", False): lambda m, x, info, norm, addend, fold: tm.merge_wavg_ln(
+        m, x, info["size"], norm, addend, log_size=info["prop_attn"]),
+    ("function", True): lambda m, x, info, norm, addend, fold: tm.drop_ln(m, x, norm, addend),
+    (_ln.AMP_DIRECT, False): lambda m, x, info, norm, addend, fold: _abi.merge_wavg_ln_amp(
+        m.plan, x, info["size"], norm.weight, norm.bias, norm.eps, _abi.autocast_dtype(x.device), addend=addend,
+        log_size=info["prop_attn"]),
+    (_ln.AMP_DIRECT, True): lambda m, x, info, norm, addend, fold: _abi.drop_ln_amp(
+        m.plan, x, norm.weight, norm.bias, norm.eps, _abi.autocast_dtype(x.device), addend=addend),
+}
+
+
+def _launched(kind, plan, out, info, fold):
+    """What follows a fused launch in either layout: the sizes (ones behind a drop), the folded bias, the message."""
+    x, y = out[0], out[1]
+    info["size"] = torch.ones((plan.n, plan.T - plan.r, 1), device=x.device) if kind == "drop" else out[2]
+    if fold is not None:
+        info["_folded"] = (x, fold)
     if info["verbose"]:
-        print(f"{'Dropped' if kind == 'drop' else 'Merged'} {before} to {x.size(1)} tokens")
+        print(f"{'Dropped' if kind == 'drop' else 'Merged'} {plan.T} to {plan.T - plan.r} tokens")
     return x, y
 
 
 def merge_then_norm(metric, x, info, norm, reduction_function, plain_merge_fn, residual=None, fold=None, drop_fn=None,
                     hybrid_fn=None):
     """The block steps `[x = x + residual;] x = reduction_function(metric, x, info); y = norm(x)` with the
-    residual add and the LayerNorm fused into the reduction kernel when this layer reduces 16-bit tokens without grad:
-    tome_merge_wavg_ln for the model's plain merge function (`plain_merge_fn`; modes 'merge' and 'random_merge') and its
-    hybrid one (`hybrid_fn`), tome_drop_ln for its drop function (`drop_fn`; 'drop', 'random_drop'); returns (x, y).
+    residual add and the LayerNorm fused into the reduction kernel where fused_route names a launch: tome_merge_wavg_ln
+    for the model's plain merge function (`plain_merge_fn`; modes 'merge' and 'random_merge') and its hybrid one
+    (`hybrid_fn`), tome_drop_ln for its drop function (`drop_fn`; 'drop', 'random_drop'); returns (x, y).
     Anything else runs the steps as the reference does.
-    fold: the Linear that finishes the block (`foldable`); when the fused kernel runs in plain 'merge' mode (_fold_for), x
-    comes back with that bias added (y is the norm of x without it) and info["_folded"] says so for finish_linear.
-    With TRAIN_FUSED_LN on, a layer of kind "merge" or "drop" whose participants require grad takes the same launch as an
-    autograd Function (_merge_then_norm_trained); `fold` is ignored there."""
-    from ..merge import do_nothing
-    r_list = info["r"]
+    fold: the Linear that finishes the block (`foldable`); when the 16-bit launch runs in plain 'merge' mode (_fold_for), x
+    comes back with that bias added (y is the norm of x without it) and info["_folded"] says so for finish_linear.  The
+    Function and the mixed-precision launch ignore it: their stream is the one the three steps store."""
     kind = fused_kind(info["mode"], reduction_function is plain_merge_fn,
                       drop_fn is not None and reduction_function is drop_fn,
                       hybrid_fn is not None and reduction_function is hybrid_fn)
-    plain = _FUSE_LN and kind is not None and r_list and r_list[0] > 0
-    if TRAIN_FUSED_LN and plain and _train_fused(kind, x, norm, residual, info):
-        return _merge_then_norm_trained(metric, x, info, norm, residual, kind)
-    if AUTOCAST_FUSED_LN and plain and _autocast_fused(x, norm, residual if _FUSE_ADD else None, info):
-        if residual is not None and not _FUSE_ADD:
+    how = fused_route(kind, x, norm, residual, info)
+    if residual is not None and how != "function":
+        # the launch reads the residual as its addend; the 16-bit one only an addend of x's dtype, without source tracking
+        # and with a clamped r > 0.  Else the framework adds first, and the sum -- another tensor -- is asked again
+        as_addend = how is not None and _FUSE_ADD and (how != "direct" or (
+            not info["trace_source"] and residual.dtype == x.dtype
+            and _abi.effective_r(x.shape[1], info["r"][0], info["class_token"], info["distill_token"]) > 0))
+        if not as_addend:
             x, residual = x + residual, None
-        return _merge_then_norm_autocast(metric, x, info, norm, residual, kind)
-    fused = plain and _abi.ln_fusable(x, norm, residual)
-    if residual is not None and not (fused and _FUSE_ADD and not info["trace_source"] and residual.dtype == x.dtype
-                                     and _abi.effective_r(x.shape[1], r_list[0], info["class_token"],
-                                                          info["distill_token"]) > 0):
-        x = x + residual
-        residual = None
-        fused = fused and _abi.ln_fusable(x, norm)  # (the sum is another tensor: of another dtype, perhaps)
-    if fused:
-        r = r_list.pop(0)
-        fold = _fold_for(fold, x, info["mode"])
+            how = how and fused_route(kind, x, norm, None, info)
+    if how is None:
+        x = reduction_function(metric, x, info)
+        return x, _trailing_norm(x, norm)
+    r = info["r"].pop(0)
+    reduce = matching(kind, metric, r, info)
+    if reduce is None:  # clamped r == 0: the unfused steps around a reduction that does nothing
+        if residual is not None:
+            x = x + residual
         if kind == "drop":
-            drop = bipartite_soft_matching_drop(metric, r, info["class_token"], info["distill_token"], info["mode"])
-            if isinstance(drop, tuple):  # clamped r == 0: reduce_drop's steps around a drop that does nothing
-                if residual is not None:
-                    x = x + residual
-                x = _apply_drop(drop[0], x, info)
-                return x, norm(x)
-            if info["trace_source"]:
-                info["source"] = _drop_source(drop, info["source"], x.shape[0], x.shape[1], x.device)
-            before = x.size(1)
-            x, y = _abi.drop_ln(drop.plan, x, norm.weight, norm.bias, norm.eps, addend=residual,
-                                out_bias=None if fold is None else fold.bias)
-            info["size"] = torch.ones((x.size(0), x.size(1), 1), device=x.device)
-            if fold is not None:
-                info["_folded"] = (x, fold)
-            if info["verbose"]:
-                print(f"Dropped {before} to {x.size(1)} tokens")
-            return x, y
-        if kind == "hybrid":
-            merge, _ = bipartite_soft_matching_hybrid(metric, r, info["class_token"], info["distill_token"], info["mode"],
-                                                      info["threshold"])
-        else:
-            merge, _ = bipartite_soft_matching(metric, r, info["class_token"], info["distill_token"], info["mode"])
-        if merge is do_nothing:
-            if residual is not None:
-                x = x + residual
-            if info["mode"] != "merge":  # (plain 'merge' leaves size and source alone here, as it always has)
-                x = _apply_merge(merge, x, info)
-            return x, norm(x)
-        if info["trace_source"]:
-            info["source"] = merge_source(merge, x, info["source"])
-        before = x.size(1)
-        x, y, info["size"] = _abi.merge_wavg_ln(merge.plan, x, info["size"], norm.weight, norm.bias, norm.eps,
-                                                addend=residual, log_size=info["prop_attn"],
-                                                out_bias=None if fold is None else fold.bias)
-        if fold is not None:
-            info["_folded"] = (x, fold)
-        if info["verbose"]:
-            print(f"Merged {before} to {x.size(1)} tokens")
-        return x, y
-    x = reduction_function(metric, x, info)
-    return x, _trailing_norm(x, norm)
+            x = _apply_drop(do_nothing, x, info)
+        elif info["mode"] != "merge":  # (plain 'merge' leaves size and source alone here, as it always has)
+            x = _apply_merge(do_nothing, x, info)
+        return x, norm(x)
+    if info["trace_source"]:  # (the 16-bit launch alone gets here with it)
+        info["source"] = (_drop_source(reduce, info["source"], x.shape[0], x.shape[1], x.device) if kind == "drop"
+                          else merge_source(reduce, x, info["source"]))
+    fold = _fold_for(fold, x, info["mode"]) if how == "direct" else None
+    out = _LAUNCH[how, kind == "drop"](reduce, x, info, norm, residual, fold)
+    return _launched(kind, reduce.plan, out, info, fold)
 
 
 def _regrouped_by_views(reduce_grouped, metric, x_full, info, r, frames):
@@ -628,7 +603,6 @@ def _native_regrouped(kind: str, x_full, size=None) -> bool:
     """Tokens that require grad: does the regrouped reduction run as a native Function (tome/merge.py: the regrouped
     kernel forward, tome_merge_backward_regrouped backward) instead of `_regrouped_by_views`?  Plain merge and drop
     on 16-byte rows; the matching of these models has no distillation token and, here, no threshold."""
-    from .. import merge as tm
     return (tm.native_backward_covers(kind, even_odd=True, on_device=x_full.is_cuda and x_full.dim() == 3,
                                       dtype=x_full.dtype,
                                       size_requires_grad=size is not None and _abi.needs_grad(size))
@@ -639,16 +613,11 @@ def reduce_merge_regrouped(metric, x_full, info, r, frames, hybrid=False):
     """reduce_merge / reduce_hybrid for the models whose merge groups are interleaved in the token sequence
     (TimeSformer '(p t)', Motionformer '(s f)'): x_full is [B, 1 + P*F, C] with the class token in front; the
     kernel addresses the groups in place and returns [B, 1 + (P-r)*F, C] (no permuted copies of x)."""
-    from ..merge import do_nothing
     training = _abi.needs_grad(x_full)
     if training and (hybrid or info["trace_source"] or not _native_regrouped("merge_wavg", x_full, info["size"])):
         return _regrouped_by_views(reduce_hybrid if hybrid else reduce_merge, metric, x_full, info, r, frames)
-    if hybrid:
-        merge, _ = bipartite_soft_matching_hybrid(metric, r, info["class_token"], info["distill_token"], info["mode"],
-                                                  info["threshold"])
-    else:
-        merge, _ = bipartite_soft_matching(metric, r, info["class_token"], info["distill_token"], info["mode"])
-    if merge is do_nothing:
+    merge = matching("hybrid" if hybrid else "merge", metric, r, info)
+    if merge is None:
         return x_full
     plan = merge.plan
     if info["trace_source"]:
@@ -687,7 +656,6 @@ def merge_then_norm_regrouped(metric, x_full, info, norm, unfused_reduce, is_pla
     [B, 1 + P*F, C]; `unfused_reduce(x)` is the model's own reduction step (it pops r itself).  `residual`: a tensor
     in x's layout, or a GroupedResidual.  is_plain_merge / is_drop / is_hybrid: which of the model's reduction functions
     the block carries (fused_kind)."""
-    from ..merge import do_nothing
     r_list = info["r"]
     grouped = residual if isinstance(residual, GroupedResidual) else None
     kind = fused_kind(info["mode"], is_plain_merge, is_drop, is_hybrid)
@@ -705,43 +673,18 @@ def merge_then_norm_regrouped(metric, x_full, info, norm, unfused_reduce, is_pla
     if grouped is None and residual is not None and (not _FUSE_ADD or residual.dtype != x_full.dtype):
         x_full = x_full + residual
         residual = None
-    r = r_list.pop(0)
+    reduce = matching(kind, metric, r_list.pop(0), info)
+    assert reduce is not None  # (the clamped r was asked up front)
+    plan = reduce.plan
     fold = _fold_for(fold, x_full, info["mode"])
-    out_bias = None if fold is None else fold.bias
+    where = dict(addend=residual) if grouped is None else dict(addend_grouped=grouped.rs, cls_addend=grouped.cls_new)
+    ln, out_bias = (norm.weight, norm.bias, norm.eps), None if fold is None else fold.bias
     if kind == "drop":
-        drop = bipartite_soft_matching_drop(metric, r, info["class_token"], info["distill_token"], info["mode"])
-        assert not isinstance(drop, tuple)
-        plan = drop.plan
-        where = (dict(addend=residual) if grouped is None
-                 else dict(addend_grouped=grouped.rs, cls_addend=grouped.cls_new))
-        x_out, y_out = _abi.drop_regrouped(plan, x_full, frames, has_cls=True, ln=(norm.weight, norm.bias, norm.eps),
-                                           out_bias=out_bias, **where)
-        info["size"] = torch.ones((plan.n, plan.T - plan.r, 1), device=x_full.device)
-        if fold is not None:
-            info["_folded"] = (x_out, fold)
-        if info["verbose"]:
-            print(f"Dropped {plan.T} to {plan.T - plan.r} tokens")
-        return x_out, y_out
-    if kind == "hybrid":
-        merge, _ = bipartite_soft_matching_hybrid(metric, r, info["class_token"], info["distill_token"], info["mode"],
-                                                  info["threshold"])
+        out = _abi.drop_regrouped(plan, x_full, frames, has_cls=True, ln=ln, out_bias=out_bias, **where)
     else:
-        merge, _ = bipartite_soft_matching(metric, r, info["class_token"], info["distill_token"], info["mode"])
-    assert merge is not do_nothing
-    plan = merge.plan
-    if grouped is not None:
-        x_out, y_out, info["size"] = _abi.merge_wavg_regrouped(
-            plan, x_full, info["size"], frames, has_cls=True, ln=(norm.weight, norm.bias, norm.eps),
-            addend_grouped=grouped.rs, cls_addend=grouped.cls_new, log_size=info["prop_attn"], out_bias=out_bias)
-    else:
-        x_out, y_out, info["size"] = _abi.merge_wavg_regrouped(plan, x_full, info["size"], frames, has_cls=True,
-                                                              ln=(norm.weight, norm.bias, norm.eps), addend=residual,
-                                                              log_size=info["prop_attn"], out_bias=out_bias)
-    if fold is not None:
-        info["_folded"] = (x_out, fold)
-    if info["verbose"]:
-        print(f"Merged {plan.T} to {plan.T - plan.r} tokens")
-    return x_out, y_out
+        out = _abi.merge_wavg_regrouped(plan, x_full, info["size"], frames, has_cls=True, ln=ln,
+                                        log_size=info["prop_attn"], out_bias=out_bias, **where)
+    return _launched(kind, plan, out, info, fold)
 
 
 def _drop_source(drop, source, n, t, device):
@@ -756,10 +699,7 @@ def _drop_source(drop, source, n, t, device):
 
 
 def reduce_drop(metric, x, info, r):
-    drop = bipartite_soft_matching_drop(metric, r, info["class_token"], info["distill_token"], info["mode"])
-    if isinstance(drop, tuple):  # clamped r == 0: the reference returns the do_nothing pair here
-        drop = drop[0]
-    return _apply_drop(drop, x, info)
+    return _apply_drop(matching("drop", metric, r, info) or do_nothing, x, info)
 
 
 def _apply_drop(drop, x, info):
@@ -781,8 +721,8 @@ def reduce_drop_regrouped(metric, x_full, info, r, frames: int):
     training = _abi.needs_grad(x_full)
     if training and (info["trace_source"] or not _native_regrouped("drop", x_full)):
         return _regrouped_by_views(reduce_drop, metric, x_full, info, r, frames)
-    drop = bipartite_soft_matching_drop(metric, r, info["class_token"], info["distill_token"], info["mode"])
-    if isinstance(drop, tuple):
+    drop = matching("drop", metric, r, info)
+    if drop is None:
         return x_full
     plan = drop.plan
     if info["trace_source"]:
@@ -795,6 +735,4 @@ def reduce_drop_regrouped(metric, x_full, info, r, frames: int):
 
 
 def reduce_hybrid(metric, x, info, r):
-    merge, _ = bipartite_soft_matching_hybrid(metric, r, info["class_token"], info["distill_token"], info["mode"],
-                                              info["threshold"])
-    return _apply_merge(merge, x, info)
+    return _apply_merge(matching("hybrid", metric, r, info) or do_nothing, x, info)
