@@ -1,4 +1,4 @@
-"""The mixed-precision add + LayerNorm kernels on the GPU (tome_add_layernorm_amp / k_add_ln_rows_amp,
+"""The mixed-precision add + LayerNorm kernels on the GPU (tome_add_layernorm_amp / k_add_ln_rows,
 tome_layernorm_backward_amp / k_ln_rows_bwd_amp): every width and every legal type combination against the bounds of
 tests/ln_amp_oracle.py, the stored sum bit for bit, launches whose workgroups walk several slabs, bit-level properties
 and every refusal."""

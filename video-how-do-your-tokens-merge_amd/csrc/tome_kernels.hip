@@ -2,8 +2,9 @@
 // C ABI declared in include/tome_hip.h.  Built with: hipcc --offload-arch=gfx950 -O3
 // -ffp-contract=off -shared -fPIC (csrc/build.py).  No torch, no CUDA, no portability layer.
 //
-// One translation unit: tome_common.h (types), tome_match.h, tome_merge.h, tome_merge_bwd.h, tome_ln_bwd.h,
-// tome_merge_ln_bwd.h, tome_gelu_bwd.h, tome_token_mean.h, tome_short_attn_bwd.h, tome_traj_bwd.h and tome_partition.h (kernels), this file
+// One translation unit: tome_common.h (types), tome_match.h, tome_ln_rows.h (the row statistics the forward LayerNorm
+// kernels and k_ln_rows_bwd_amp share), tome_merge.h, tome_merge_ln_amp.h, tome_merge_bwd.h, tome_ln_bwd.h, tome_merge_ln_bwd.h,
+// tome_gelu_bwd.h, tome_token_mean.h, tome_short_attn_bwd.h, tome_traj_bwd.h and tome_partition.h (kernels), this file
 // (host).
 //
 // Launch sequence of one matching (tome_match / tome_match_keys), kernels in tome_match.h:
@@ -15,24 +16,28 @@
 // and of one merge (tome_merge_wavg[_regrouped] / tome_merge / tome_drop / tome_unmerge), tome_merge.h:
 //   k_merge_rows_fast    streaming waves (2-4 output rows each) + edge waves (rows that receive sources);
 //                        <LN>: residual add in front and LayerNorm behind fused in (tome_merge_wavg_ln)
-//   k_add_ln_rows        second residual + the next block's first LayerNorm (tome_add_layernorm)
+//   k_add_ln_rows        second residual + the next block's first LayerNorm (tome_add_layernorm; with fp32 weight /
+//                        bias, a 16-bit y and a 16-bit or fp32 residual stream: tome_add_layernorm_amp)
+//   k_add_ln_regroup     the same in the middle of TimeSformer's block, y written regrouped (tome_add_layernorm_regrouped)
 //   k_merge_rows / k_unmerge_rows   generic one-wave-per-row forms                        (HBM bound)
 // and of its backward (tome_merge_backward[_regrouped]), tome_merge_bwd.h:
 //   k_merge_rows_bwd     gx[t] = gy[row of t] / out_div * in_mul, streaming gather             (HBM bound)
 // and of the add + LayerNorm backward (tome_layernorm_backward), tome_ln_bwd.h:
 //   k_ln_rows_bwd        gx = gx_in + rstd (gw - mean gw - xhat mean(gw xhat)), statistics recomputed from the stored
-//                        rows; per-workgroup partial rows of dweight / dbias                    (HBM bound)
+//                        rows with ln_rows' arithmetic (its own copy of the rounds); per-workgroup partial rows of
+//                        dweight / dbias                                                        (HBM bound)
 //   k_ln_param_grad      the partial rows summed in a fixed order
 //   k_ln_rows_bwd<REGROUP>  the same behind TimeSformer's mid-block regrouping (tome_layernorm_backward_regrouped): the
 //                        row map in front of gy, a class row's F gradients summed in fp32              (HBM bound)
 // and of the fused residual add + merge + LayerNorm (tome_merge_ln_backward), tome_merge_ln_bwd.h:
 //   k_merge_ln_rows_bwd  the two above as one pass: the LayerNorm term of row o(t) in fp32, scaled and rounded once
 //                        per input token; parameter gradients over the merged rows, each counted once    (HBM bound)
-// and their mixed-precision forms for a model under autocast with fp32 master weights (tome_add_layernorm_amp,
-// tome_layernorm_backward_amp), tome_merge.h / tome_ln_bwd.h:
-//   k_add_ln_rows_amp    k_add_ln_rows with fp32 weight / bias, a 16-bit y and a 16-bit or fp32 residual stream
-//   k_ln_rows_bwd_amp    k_ln_rows_bwd with a 16-bit gy, the stream's dtype for xs / gx_in / gx, fp32 partial rows summed
-//                        into fp32 parameters, optionally gx rounded to 16 bits as a second output       (HBM bound)
+// and their mixed-precision forms for a model under autocast with fp32 master weights (tome_merge_wavg_ln_amp /
+// tome_drop_ln_amp, tome_layernorm_backward_amp), tome_merge_ln_amp.h / tome_ln_bwd.h:
+//   k_merge_rows_ln_amp  k_merge_rows_fast<LN> with fp32 weight / bias, a 16-bit y and a 16-bit or fp32 residual stream
+//   k_ln_rows_bwd_amp    k_ln_rows_bwd on the forward's own rounds (tome_ln_rows.h) with a 16-bit gy, the stream's dtype
+//                        for xs / gx_in / gx, fp32 partial rows summed into fp32 parameters, optionally gx rounded
+//                        to 16 bits as a second output                                                   (HBM bound)
 // and of TimeSformer's temporal attention (tome_short_attention_backward), tome_short_attn_bwd.h:
 //   k_short_attention_bwd  P recomputed, dq / dk / dv of sequences of <= 8 tokens in one pass, eight lanes per
 //                        (sequence, head), dk / dv accumulated in registers                           (HBM bound)
@@ -67,6 +72,7 @@
 #include "tome_common.h"
 #include "tome_match.h"
 #include "tome_match_filter.h"
+#include "tome_ln_rows.h"
 #include "tome_merge.h"
 #include "tome_merge_ln_amp.h"
 #include "tome_merge_bwd.h"
@@ -610,7 +616,7 @@ static int launch_merge_rows(const void *x, const void *size, int64_t n, int64_t
     const TokLayout lout = lout_p ? *lout_p : contiguous_layout(To, C);
     const bool vec_ok = (C % VEC == 0) && aligned16(x) && aligned16(xout);
     const int64_t cpr = C / VEC;  // 16-byte chunks per row
-    const LnArgs no_ln{nullptr, nullptr, nullptr, 0.0f, nullptr, 0, TokLayout{0, 0, 0, 0, 1}, nullptr, 0, nullptr};
+    const LnArgs no_ln{nullptr, nullptr, nullptr, 0.0f, nullptr, 0, TokLayout{0, 0, 0, 0, 1}, nullptr, nullptr};
     if (vec_ok && cpr <= FAST_NIT * WAVE) {
         // rows per wave: measured on MI355X, NIT=6 (four 1536-byte rows per wave for 768-channel bf16 tokens)
         // beats NIT=3 by ~4 %; with the LayerNorm fused and the residual stream next to x 3 chunks per lane
@@ -699,7 +705,7 @@ extern "C" int tome_merge_wavg_ln(const void *x, int x_dtype, const void *size, 
     if (x_out_bias && !aligned16(x_out_bias)) return fail(TOME_EINVAL, "tome_merge_wavg_ln: x_out_bias not 16-byte aligned");
     if (!src_idx || !dst_idx || (!unm_idx && (T + 1) / 2 > r) || !size_out || !y_out || !ln_weight || !ln_bias)
         return fail(TOME_EINVAL, "tome_merge_wavg_ln: null buffer");
-    const LnArgs ln{ln_weight, ln_bias, y_out, eps, addend, 0, TokLayout{0, 0, 0, 0, 1}, nullptr, 0, x_out_bias};
+    const LnArgs ln{ln_weight, ln_bias, y_out, eps, addend, 0, TokLayout{0, 0, 0, 0, 1}, nullptr, x_out_bias};
     return dispatch_xs<false>(x_dtype, size_dtype, [&](auto tx, auto ts) {
         return launch_merge_rows<typename decltype(tx)::type, typename decltype(ts)::type, OP_WAVG>(
             x, size, n, T, C, r, src_idx, dst_idx, unm_idx, distill_token, edge_keep, x_out, size_out,
@@ -750,7 +756,7 @@ extern "C" int tome_merge_wavg_regrouped_ln(const void *x, int x_dtype, const vo
     if ((addend && !aligned16(addend)) || (cls_addend && !aligned16(cls_addend)))
         return fail(TOME_EINVAL, "tome_merge_wavg_regrouped_ln: addend alignment");
     if (addend_grouped && !addend) return fail(TOME_EINVAL, "tome_merge_wavg_regrouped_ln: addend_grouped without addend");
-    LnArgs ln{ln_weight, ln_bias, y_out, eps, addend, 0, TokLayout{0, 0, 0, 0, 1}, nullptr, 0, x_out_bias};
+    LnArgs ln{ln_weight, ln_bias, y_out, eps, addend, 0, TokLayout{0, 0, 0, 0, 1}, nullptr, x_out_bias};
     if (addend_grouped) {  // addend [B*F, has_cls + P, C]: group g's token p at (g*(cls+P) + cls + p)*C
         const int64_t cls = has_cls ? 1 : 0;
         ln.a_own = 1;
@@ -769,6 +775,21 @@ static inline int ln_rows_per_wave(int64_t cpr, int nit) {
     return R > FAST_MAXR ? FAST_MAXR : (int)R;
 }
 
+// One launch of k_add_ln_rows (three slots per lane) for the 16-bit entries and the autocast entry alike.
+template <typename TS, typename TA, typename TY, typename TP>
+static int launch_add_ln_rows(const char *who, const void *x, const void *addend, int64_t rows, int64_t C,
+                              const void *ln_weight, const void *ln_bias, float eps, int64_t y_group, void *x_out,
+                              void *y_out, tome_stream_t stream) {
+    const int64_t cpr = C / 8;
+    const int R = ln_rows_per_wave(cpr, 3);  // 3 slots per lane: 100.6 us vs 105 us with 6 (batch 64)
+    const int64_t waves = (rows + R - 1) / R;
+    if ((waves + 3) / 4 > 0x7fffffffLL) return fail(TOME_EINVAL, "%s: too many rows", who);
+    hipLaunchKernelGGL((k_add_ln_rows<TS, TA, TY, TP, 3>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0,
+                       (hipStream_t)stream, (const TS *)x, (const TA *)addend, rows, (int)C, R, (int)cpr,
+                       (const TP *)ln_weight, (const TP *)ln_bias, eps, (int)y_group, (TS *)x_out, (TY *)y_out);
+    return check_launch("k_add_ln_rows");
+}
+
 static int add_layernorm_impl(const void *x, const void *addend, int dtype, int64_t rows, int64_t C,
                               const void *ln_weight, const void *ln_bias, float eps, void *x_out, void *y_out,
                               int64_t y_group, tome_stream_t stream) {
@@ -776,25 +797,13 @@ static int add_layernorm_impl(const void *x, const void *addend, int dtype, int6
     if (!x || !ln_weight || !ln_bias || (addend && !x_out) || !y_out || rows <= 0 || C <= 0)
         return fail(TOME_EINVAL, "tome_add_layernorm: bad shape/pointer");
     if (int rc = not_16bit("tome_add_layernorm", dtype)) return rc;
-    const int64_t cpr = C / 8;
-    if (C % 8 || cpr > 2 * WAVE || !aligned16(x) || !aligned16(addend) || (addend && !aligned16(x_out)) ||
+    if (C % 8 || C / 8 > 2 * WAVE || !aligned16(x) || !aligned16(addend) || (addend && !aligned16(x_out)) ||
         !aligned16(y_out) || !aligned16(ln_weight) || !aligned16(ln_bias))
         return fail(TOME_EINVAL, "tome_add_layernorm: C %% 8 == 0, C <= 1024 and 16-byte aligned buffers required");
-    const int nit = (cpr <= 3 * WAVE) ? 3 : FAST_NIT;  // 3 chunks per lane: 100.6 us vs 105 us with 6 (batch 64)
-    const int R = ln_rows_per_wave(cpr, nit);
-    const int64_t waves = (rows + R - 1) / R;
-    const LnArgs ln{ln_weight, ln_bias, y_out, eps, nullptr, 0, TokLayout{0, 0, 0, 0, 1}, nullptr, (int)y_group, nullptr};
-    const dim3 grid((unsigned)((waves + 3) / 4));
-    hipStream_t st = (hipStream_t)stream;
     return dispatch_x<false>(dtype, [&](auto tx) {
         using TX = typename decltype(tx)::type;
-        if (nit == 3)
-            hipLaunchKernelGGL((k_add_ln_rows<TX, 3>), grid, dim3(256), 0, st, (const TX *)x, (const TX *)addend, rows,
-                               (int)C, R, (int)cpr, ln, (TX *)x_out);
-        else
-            hipLaunchKernelGGL((k_add_ln_rows<TX, FAST_NIT>), grid, dim3(256), 0, st, (const TX *)x, (const TX *)addend,
-                               rows, (int)C, R, (int)cpr, ln, (TX *)x_out);
-        return check_launch("k_add_ln_rows");
+        return launch_add_ln_rows<TX, TX, TX, TX>("tome_add_layernorm", x, addend, rows, C, ln_weight, ln_bias, eps,
+                                                  y_group, x_out, y_out, stream);
     }, [&] { return not_16bit("tome_add_layernorm", dtype); });
 }
 
@@ -829,7 +838,7 @@ extern "C" int tome_add_layernorm_regrouped(const void *x, const void *addend, i
     const int R = ln_rows_per_wave(cpr, 3);
     if (R < 1) return fail(TOME_EINVAL, "tome_add_layernorm_regrouped: row too wide");
     const int64_t waves = (rows + R - 1) / R;
-    const LnArgs ln{ln_weight, ln_bias, y_out, eps, nullptr, 0, TokLayout{0, 0, 0, 0, 1}, nullptr, 0, nullptr};
+    const LnArgs ln{ln_weight, ln_bias, y_out, eps, nullptr, 0, TokLayout{0, 0, 0, 0, 1}, nullptr, nullptr};
     const dim3 grid((unsigned)((waves + 3) / 4));
     hipStream_t st = (hipStream_t)stream;
     return dispatch_x<false>(dtype, [&](auto tx) {
@@ -951,7 +960,7 @@ extern "C" int tome_layernorm_backward_regrouped(const void *gy, const void *xs,
 }
 
 // ------------------------------------------------------------------------------------------------
-// The mixed-precision forms (a model under autocast with fp32 master weights): k_add_ln_rows_amp and
+// The mixed-precision forms (a model under autocast with fp32 master weights): k_add_ln_rows with fp32 parameters and
 // k_ln_rows_bwd_amp in the launch forms of the entries above (three slots per lane, ln_rows_per_wave, ln_bwd_form).
 // ------------------------------------------------------------------------------------------------
 // f(Dt<TS>{}, Dt<TA>{}, Dt<TY>{}) for the legal (stream, addend, y) dtypes: a 16-bit stream with everything of its
@@ -980,20 +989,10 @@ extern "C" int tome_add_layernorm_amp(const void *x, int x_dtype, const void *ad
     if (C % 8 || cpr > 2 * WAVE || !aligned16(x) || !aligned16(addend) || (addend && !aligned16(x_out)) ||
         !aligned16(y_out) || !aligned16(weight_f32) || !aligned16(bias_f32))
         return fail(TOME_EINVAL, "%s: C %% 8 == 0, C <= 1024 and 16-byte aligned buffers required", who);
-    const int R = ln_rows_per_wave(cpr, 3);
-    const int64_t waves = (rows + R - 1) / R;
-    if ((waves + 3) / 4 > 0x7fffffffLL) return fail(TOME_EINVAL, "%s: too many rows", who);
-    const dim3 grid((unsigned)((waves + 3) / 4));
-    const int y_group = skip_first ? (int)group_rows : 0;
-    hipStream_t st = (hipStream_t)stream;
     return dispatch_amp(x_dtype, addend_dtype, addend != nullptr, y_dtype, [&](auto ts, auto ta, auto ty) {
-        using TS = typename decltype(ts)::type;
-        using TA = typename decltype(ta)::type;
-        using TY = typename decltype(ty)::type;
-        hipLaunchKernelGGL((k_add_ln_rows_amp<TS, TA, TY, 3>), grid, dim3(256), 0, st, (const TS *)x, (const TA *)addend,
-                           rows, (int)C, R, (int)cpr, (const float *)weight_f32, (const float *)bias_f32, eps, y_group,
-                           (TS *)x_out, (TY *)y_out);
-        return check_launch("k_add_ln_rows_amp");
+        return launch_add_ln_rows<typename decltype(ts)::type, typename decltype(ta)::type, typename decltype(ty)::type,
+                                  float>(who, x, addend, rows, C, weight_f32, bias_f32, eps,
+                                         skip_first ? group_rows : 0, x_out, y_out, stream);
     }, [&] {
         return fail(TOME_EINVAL, "%s: unsupported dtypes x=%d addend=%d y=%d (a 16-bit y; x of y's dtype with an addend "
                                  "of the same, or fp32 x with an addend of y's dtype or fp32)", who, x_dtype,
@@ -1137,7 +1136,7 @@ extern "C" int tome_drop_ln(const void *x, int dtype, int64_t n, int64_t T, int6
     if (int rc = check_drop_ln_args("tome_drop_ln", x, dtype, C, ln_weight, ln_bias, addend, nullptr, x_out, y_out,
                                     x_out_bias))
         return rc;
-    const LnArgs ln{ln_weight, ln_bias, y_out, eps, addend, 0, TokLayout{0, 0, 0, 0, 1}, nullptr, 0, x_out_bias};
+    const LnArgs ln{ln_weight, ln_bias, y_out, eps, addend, 0, TokLayout{0, 0, 0, 0, 1}, nullptr, x_out_bias};
     return dispatch_x<false>(dtype, [&](auto tx) {
         return launch_merge_rows<typename decltype(tx)::type, float, OP_DROP>(
             x, nullptr, n, T, C, r, nullptr, nullptr, und_idx, distill_token, nullptr, x_out, nullptr,
@@ -1159,7 +1158,7 @@ extern "C" int tome_drop_regrouped_ln(const void *x, int dtype, int64_t B, int64
         return rc;
     if (addend_grouped && !addend) return fail(TOME_EINVAL, "tome_drop_regrouped_ln: addend_grouped without addend");
     const int64_t cls = has_cls ? 1 : 0;
-    LnArgs ln{ln_weight, ln_bias, y_out, eps, addend, 0, TokLayout{0, 0, 0, 0, 1}, nullptr, 0, x_out_bias};
+    LnArgs ln{ln_weight, ln_bias, y_out, eps, addend, 0, TokLayout{0, 0, 0, 0, 1}, nullptr, x_out_bias};
     if (addend_grouped) {  // addend [B*F, has_cls + P, C], as in tome_merge_wavg_regrouped_ln
         ln.a_own = 1;
         ln.la = TokLayout{cls * C, (cls + P) * C, 0, C, 1};

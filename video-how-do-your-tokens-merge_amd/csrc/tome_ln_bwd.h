@@ -7,9 +7,14 @@
 // xhat = d * rstd:
 //     gx = gx_in + rstd * (gw - mean(gw) - xhat * mean(gw * xhat))
 // gx_in (optional) is the gradient that reaches x' directly through the residual stream; the sum is rounded once.
-// mean and rstd are RECOMPUTED from x' with the arithmetic of ln_rows (two passes, centred variance, wave_total,
-// v_rsq_f32, 1/C as a multiplication): the forward normalised the row as stored, so nothing is saved by the forward.
-// Two reduction rounds per row: sum x, then sum d^2, sum gw and sum gw*d together.
+// mean and rstd are RECOMPUTED from x' with the arithmetic of ln_rows (tome_ln_rows.h: two passes, centred variance,
+// wave_total, v_rsq_f32, 1/C as a multiplication): the forward normalised the row as stored, so nothing is saved by
+// the forward.  Two reduction rounds per row: sum x, then sum d^2, sum gw and sum gw*d together.
+// The two rounds are this kernel's OWN COPY, not ln_row_means / ln_rows_bwd_stats of tome_ln_rows.h, which
+// k_ln_rows_bwd_amp calls: through the shared rounds the frozen bf16 form needs 141 registers instead of 127 (3 waves
+// per SIMD instead of 4) and every form measured 0.3-2.1 % slower (one row array with a class-row bit and one set of
+// row comparisons here, against two row arrays and two sets there).  What keeps the copy honest is a test of bits:
+// tests/test_layernorm_forms_agree_gpu.py holds gx of this kernel to gx of k_ln_rows_bwd_amp on a 16-bit stream.
 // Packing of k_add_ln_rows: a wave owns R consecutive rows, NIT 16-byte chunks per lane flattened over the rows, all
 // loads of a slab issued before any use, non-temporal both ways, fp32 arithmetic.
 // group_rows > 0 (backward of tome_add_layernorm_skip_first): rows come in groups of group_rows whose first row (a
@@ -310,11 +315,11 @@ __global__ __launch_bounds__(LN_PG_RUNS * WAVE) void k_ln_param_grad(const float
 
 // ------------------------------------------------------------------------------------------------
 // k_ln_rows_bwd_amp: k_ln_rows_bwd for a model that runs under autocast with fp32 master weights
-// (tome_layernorm_backward_amp; tools/train_net.py:123, tome/utils.py:54): the backward of k_add_ln_rows_amp.
+// (tome_layernorm_backward_amp; tools/train_net.py:123, tome/utils.py:54): the backward of k_add_ln_rows with fp32 parameters.
 // TG: gy, the 16-bit autocast dtype; TS: the residual stream (xs, gx_in, gx), 16-bit or fp32; weight fp32; the partial
 // rows of dweight / dbias fp32 as before, summed by k_ln_param_grad<float> into fp32 parameters.  Formula, reduction
 // rounds, packing (slots of 8 channels, tome_merge.h), slab walk and the order of every sum are those of k_ln_rows_bwd;
-// mean and rstd are recomputed from the stored row with k_add_ln_rows_amp's arithmetic.  gx is rounded once to TS (not
+// mean and rstd are recomputed from the stored row as in k_ln_rows_bwd.  gx is rounded once to TS (not
 // at all for an fp32 stream).  gx16 (fp32 stream, optional): round16(gx) from the same registers, the gradient of a
 // 16-bit addend without a cast pass; a class row's is round16(gx_in).
 // ------------------------------------------------------------------------------------------------
@@ -340,7 +345,7 @@ __global__ __launch_bounds__(256, 2) void k_ln_rows_bwd_amp(const TG *__restrict
         const bool slot = q < R * cpr;
         rr_of[it] = slot ? rr : -1;
         cc_of[it] = slot ? q - rr * cpr : 0;
-        ld_param8(weight, cc_of[it], wgt[it]);
+        slot_f32<float>(ld_param_slot<float>(weight, cc_of[it]), wgt[it]);
     }
     float aw[NIT][VEC], ab[NIT][VEC];
     if (PARAMS) {
@@ -370,8 +375,8 @@ __global__ __launch_bounds__(256, 2) void k_ln_rows_bwd_amp(const TG *__restrict
         const TS *xsl = xs + (int64_t)row0 * C;
         const TS *gil = (has_in ? gx_in : xs) + (int64_t)row0 * C;
         Slot<TS> xraw[NIT], iraw[NIT];
-        uint4 graw[NIT];
-        int rowof[NIT];  // row-in-wave of a live slot, -1: no slot; bit 2 set: slot of a class row
+        Slot<TG> graw[NIT];
+        int srow[NIT], grow[NIT];  // as in k_ln_rows_bwd
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             const int q = it * WAVE + lane;
@@ -383,101 +388,27 @@ __global__ __launch_bounds__(256, 2) void k_ln_rows_bwd_amp(const TG *__restrict
             int gr = (live && g >= 0) ? g : 0;
             gr = gr < gy_rows ? gr : gy_rows - 1;
             xraw[it] = ld_slot<TS>(xsl, live ? q : 0);
-            graw[it] = ld16(reinterpret_cast<const uint4 *>(gy) + (int64_t)gr * cpr + cc_of[it]);
+            graw[it] = ld_slot<TG>(gy + (int64_t)gr * C, cc_of[it]);
             if (has_in) iraw[it] = ld_slot<TS>(gil, live ? q : 0);
-            rowof[it] = live ? (g < 0 ? (rr | 4) : rr) : -1;
+            srow[it] = live ? rr : -1;
+            grow[it] = (live && g >= 0) ? rr : -1;
         }
 
-        // round 1: mean of every row (as k_add_ln_rows_amp)
-        float p0 = 0.0f, p1 = 0.0f, p2 = 0.0f, p3 = 0.0f;
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int rr = rowof[it] < 0 ? -1 : (rowof[it] & 3);
-            const float t = rr >= 0 ? slot_sum<TS>(xraw[it]) : 0.0f;
-            p0 += rr == 0 ? t : 0.0f;
-            if (R > 1) p1 += rr == 1 ? t : 0.0f;
-            if (R > 2) {
-                p2 += rr == 2 ? t : 0.0f;
-                p3 += rr == 3 ? t : 0.0f;
-            }
-        }
-        float m0 = wave_total(p0) * inv_c, m1 = 0.0f, m2 = 0.0f, m3 = 0.0f;
-        if (R > 1) m1 = wave_total(p1) * inv_c;
-        if (R > 2) {
-            m2 = wave_total(p2) * inv_c;
-            m3 = wave_total(p3) * inv_c;
-        }
-
-        // round 2: sum d^2, sum gw, sum gw * d
+        // mean and rstd of every row with the forward's own functions, then mean(gw) and k (tome_ln_rows.h)
         float d[NIT][VEC];
-        float v0 = 0.0f, v1 = 0.0f, v2 = 0.0f, v3 = 0.0f;  // sum d^2
-        float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;  // sum gw
-        float b0 = 0.0f, b1 = 0.0f, b2 = 0.0f, b3 = 0.0f;  // sum gw * d
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int ro = rowof[it];
-            const int rr = ro < 0 ? -1 : (ro & 3);
-            const bool grad = ro >= 0 && ro < 4;  // a live slot of a row that has a gradient
-            const float m = pick4(rr, m0, m1, m2, m3, R);
-            Pack<TG, VEC> pg;
-            __builtin_memcpy(&pg, &graw[it], 16);
-            slot_f32<TS>(xraw[it], d[it]);
-            float u = 0.0f, sa = 0.0f, sb = 0.0f;
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) {
-                d[it][e] = d[it][e] - m;
-                const float gwe = to_f32(pg.e[e]) * wgt[it][e];
-                u = __fmaf_rn(d[it][e], d[it][e], u);
-                sa += gwe;
-                sb = __fmaf_rn(gwe, d[it][e], sb);
-            }
-            u = rr >= 0 ? u : 0.0f;
-            sa = grad ? sa : 0.0f;
-            sb = grad ? sb : 0.0f;
-            v0 += rr == 0 ? u : 0.0f;
-            a0 += rr == 0 ? sa : 0.0f;
-            b0 += rr == 0 ? sb : 0.0f;
-            if (R > 1) {
-                v1 += rr == 1 ? u : 0.0f;
-                a1 += rr == 1 ? sa : 0.0f;
-                b1 += rr == 1 ? sb : 0.0f;
-            }
-            if (R > 2) {
-                v2 += rr == 2 ? u : 0.0f;
-                a2 += rr == 2 ? sa : 0.0f;
-                b2 += rr == 2 ? sb : 0.0f;
-                v3 += rr == 3 ? u : 0.0f;
-                a3 += rr == 3 ? sa : 0.0f;
-                b3 += rr == 3 ? sb : 0.0f;
-            }
-        }
-        // per row: rstd, mean(gw), k = rstd * mean(gw * xhat) = rstd^2 * sum(gw * d) / C   (xhat * mean(.) = d * k)
-        float r0 = __builtin_amdgcn_rsqf(wave_total(v0) * inv_c + eps), r1 = 0.0f, r2 = 0.0f, r3 = 0.0f;
-        float g_0 = wave_total(a0) * inv_c, g_1 = 0.0f, g_2 = 0.0f, g_3 = 0.0f;
-        float k0 = r0 * (r0 * (wave_total(b0) * inv_c)), k1 = 0.0f, k2 = 0.0f, k3 = 0.0f;
-        if (R > 1) {
-            r1 = __builtin_amdgcn_rsqf(wave_total(v1) * inv_c + eps);
-            g_1 = wave_total(a1) * inv_c;
-            k1 = r1 * (r1 * (wave_total(b1) * inv_c));
-        }
-        if (R > 2) {
-            r2 = __builtin_amdgcn_rsqf(wave_total(v2) * inv_c + eps);
-            g_2 = wave_total(a2) * inv_c;
-            k2 = r2 * (r2 * (wave_total(b2) * inv_c));
-            r3 = __builtin_amdgcn_rsqf(wave_total(v3) * inv_c + eps);
-            g_3 = wave_total(a3) * inv_c;
-            k3 = r3 * (r3 * (wave_total(b3) * inv_c));
-        }
+        const LnBwdRows st = ln_rows_bwd_stats<TS, NIT>(
+            xraw, srow, grow, ln_row_means<TS, NIT>(xraw, srow, R, inv_c), R, inv_c, eps,
+            [&](int it, int e) __attribute__((always_inline)) { return slot_at<TG>(graw[it], e) * wgt[it][e]; }, d);
 
         TS *gxl = gx + (int64_t)row0 * C;
         TG *g16l = gx16 ? gx16 + (int64_t)row0 * C : nullptr;
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
-            const int ro = rowof[it];
-            if (ro < 0) continue;
+            if (srow[it] < 0) continue;
             const int q = it * WAVE + lane;
+            const int ro = grow[it];
             float o[VEC];
-            if (ro >= 4) {  // class row: its gradient is what the residual stream brings, moved as raw bits
+            if (ro < 0) {  // class row: its gradient is what the residual stream brings, moved as raw bits
                 Slot<TS> z = {};
                 if (has_in) z = iraw[it];
                 st_slot<TS>(gxl, q, z);
@@ -487,15 +418,12 @@ __global__ __launch_bounds__(256, 2) void k_ln_rows_bwd_amp(const TG *__restrict
                 }
                 continue;
             }
-            const float rs = pick4(ro, r0, r1, r2, r3, R), mg = pick4(ro, g_0, g_1, g_2, g_3, R),
-                        kk = pick4(ro, k0, k1, k2, k3, R);
+            const float rs = st.rstd.at(ro, R), mg = st.mgw.at(ro, R), kk = st.k.at(ro, R);
             float gi[VEC];
             if (has_in) slot_f32<TS>(iraw[it], gi);
-            Pack<TG, VEC> pg;
-            __builtin_memcpy(&pg, &graw[it], 16);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) {
-                const float gyv = to_f32(pg.e[e]);
+                const float gyv = slot_at<TG>(graw[it], e);
                 const float t = __fmaf_rn(-d[it][e], kk, gyv * wgt[it][e] - mg);
                 // one rounding to the stream's dtype (none for fp32); gx16 rounds the stored fp32 value
                 o[e] = to_f32(from_f32<TS>(has_in ? __fmaf_rn(rs, t, gi[e]) : rs * t));

@@ -44,7 +44,6 @@ struct LnArgs {
     int a_own;
     TokLayout la;
     const void *cls_addend;
-    int y_group;  // k_add_ln_rows only: see there
     // optional [C]: the rows of x_out are stored as round(x' + xbias) while y stays LayerNorm(x').  The caller's next
     // GEMM accumulates onto x_out in place (`x = x + fc2(...)`, tome/patch/videomae.py:29, as beta = 1 on the residual
     // buffer), so its bias has to be in the buffer beforehand and the separate residual add disappears.
@@ -63,22 +62,6 @@ __device__ __forceinline__ uint4 add_xbias(const uint4 &v, const TX *__restrict_
     uint4 o;
     __builtin_memcpy(&o, &pk, 16);
     return o;
-}
-
-// 16-byte moves of the streaming kernels (k_merge_rows_fast, k_add_ln_rows, k_add_ln_regroup): tokens are read once
-// and written once, 0.3-1.2 GB per launch against 256 MB of Infinity Cache, so both directions are issued
-// non-temporal.  Measured at batch 128, same box, alternating builds: merge+LN 226 -> 214 us (5.12 -> 5.40 TB/s),
-// add+LN 215 -> 189 us (5.37 -> 6.12 TB/s); inside the model (rocprofv3) 228 -> 221 and 204 -> 188 us with the GEMMs
-// that read the results unchanged (581 vs 578 us).
-typedef unsigned int nt_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint4 ld16(const void *p) {
-    const nt_u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_u32x4 *>(p));
-    return uint4{v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ void st16(void *p, const uint4 &v) {
-    nt_u32x4 w;
-    w.x = v.x; w.y = v.y; w.z = v.z; w.w = v.w;
-    __builtin_nontemporal_store(w, reinterpret_cast<nt_u32x4 *>(p));
 }
 
 // round(x + a) in the token dtype, element-wise on two 16-byte packs (what torch's `x + a` stores)
@@ -104,152 +87,6 @@ __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
     return v;
-}
-
-// ------------------------------------------------------------------------------------------------
-// LayerNorm tail of the streaming kernels (k_merge_rows_fast, k_add_ln_rows, k_add_ln_regroup).  These kernels sit at
-// the vector-issue limit of the SIMDs, not only at the HBM limit (measured in round 2: adding ~75 vector instructions
-// per lane cost the merge kernel 6 %; occupancy and index prefetch changed nothing), so the tail is written for few
-// instructions:
-//   * the sum of a 16-byte chunk by dot products with a vector of ones (v_dot2c_f32_bf16 / _f16: two elements per
-//     instruction, no unpacking);
-//   * wave totals by a DPP scan (row_shr 1/2/4/8, row_bcast 15/31) read back from lane 63 as a wave-uniform scalar,
-//     instead of six ds_bpermute round trips per total -- and only for the rows the wave really holds (R of 4);
-//   * the centred values d = x - mean kept in registers between the variance pass and the output pass;
-//   * y = d * (rstd * w) + b as one multiply and one fma per element; 1/C as a multiplication, rstd by v_rsq_f32.
-// Two passes as before (mean, then centred variance): a row far from zero keeps its variance.
-// ------------------------------------------------------------------------------------------------
-template <int CTRL, int ROW_MASK> __device__ __forceinline__ float dpp_add(float v) {
-    const int t = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, false);
-    return v + __int_as_float(t);
-}
-__device__ __forceinline__ float wave_total(float v) {  // sum over the 64 lanes, wave-uniform
-    v = dpp_add<0x111, 0xf>(v);  // row_shr:1
-    v = dpp_add<0x112, 0xf>(v);  // row_shr:2
-    v = dpp_add<0x114, 0xf>(v);  // row_shr:4
-    v = dpp_add<0x118, 0xf>(v);  // row_shr:8  -> lane 15 of every row of 16 holds the row's total
-    v = dpp_add<0x142, 0xa>(v);  // row_bcast:15 into rows 1 and 3
-    v = dpp_add<0x143, 0xc>(v);  // row_bcast:31 into rows 2 and 3 -> lane 63 holds the total
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-
-typedef __bf16 dot_bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 dot_f16x2 __attribute__((ext_vector_type(2)));
-template <typename TX> __device__ __forceinline__ float chunk_sum(const uint4 &v);
-template <> __device__ __forceinline__ float chunk_sum<bf16_t>(const uint4 &v) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w}, ones = 0x3f803f80u;
-    dot_bf16x2 o, p;
-    __builtin_memcpy(&o, &ones, 4);
-    float t = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        __builtin_memcpy(&p, &w[i], 4);
-        t = __builtin_amdgcn_fdot2_f32_bf16(p, o, t, false);
-    }
-    return t;
-}
-template <> __device__ __forceinline__ float chunk_sum<f16_t>(const uint4 &v) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w}, ones = 0x3c003c00u;
-    dot_f16x2 o, p;
-    __builtin_memcpy(&o, &ones, 4);
-    float t = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        __builtin_memcpy(&p, &w[i], 4);
-        t = __builtin_amdgcn_fdot2(p, o, t, false);
-    }
-    return t;
-}
-
-__device__ __forceinline__ float pick4(int rr, float a0, float a1, float a2, float a3, int R) {
-    float v = a0;
-    if (R > 1) v = rr == 1 ? a1 : v;
-    if (R > 2) {
-        v = rr == 2 ? a2 : v;
-        v = rr == 3 ? a3 : v;
-    }
-    return v;
-}
-
-// raw[it]: the stored bits of chunk `it` of this lane (16-bit tokens, 8 per chunk), rowof[it] its row 0..R-1 or -1;
-// store_y(it, rr, cc, bits) writes one normalised chunk (cc = 16-byte column of the chunk in its row).
-template <typename TX, int NIT, typename StoreY>
-__device__ __forceinline__ void ln_rows(const uint4 (&raw)[NIT], const int (&rowof)[NIT], int R, int cpr, int C,
-                                        float eps, const TX *__restrict__ lw, const TX *__restrict__ lb, int lane,
-                                        StoreY store_y) {
-    constexpr int VEC = 8;
-    const float inv_c = __builtin_amdgcn_rcpf((float)C);
-    // weight and bias chunks of every chunk column this lane holds: requested now, used after the two reductions
-    uint4 wraw[NIT], braw[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int rr = rowof[it];
-        const int cc = rr < 0 ? 0 : it * WAVE + lane - rr * cpr;
-        wraw[it] = *(reinterpret_cast<const uint4 *>(lw) + cc);
-        braw[it] = *(reinterpret_cast<const uint4 *>(lb) + cc);
-    }
-    float p0 = 0.0f, p1 = 0.0f, p2 = 0.0f, p3 = 0.0f;
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int rr = rowof[it];
-        const float t = rr >= 0 ? chunk_sum<TX>(raw[it]) : 0.0f;
-        p0 += rr == 0 ? t : 0.0f;
-        if (R > 1) p1 += rr == 1 ? t : 0.0f;
-        if (R > 2) {
-            p2 += rr == 2 ? t : 0.0f;
-            p3 += rr == 3 ? t : 0.0f;
-        }
-    }
-    float m0 = wave_total(p0) * inv_c, m1 = 0.0f, m2 = 0.0f, m3 = 0.0f;
-    if (R > 1) m1 = wave_total(p1) * inv_c;
-    if (R > 2) {
-        m2 = wave_total(p2) * inv_c;
-        m3 = wave_total(p3) * inv_c;
-    }
-    float d[NIT][VEC];
-    p0 = p1 = p2 = p3 = 0.0f;
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int rr = rowof[it];
-        const float m = pick4(rr, m0, m1, m2, m3, R);
-        Pack<TX, VEC> pk;
-        __builtin_memcpy(&pk, &raw[it], 16);
-        float u = 0.0f;
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-            d[it][e] = to_f32(pk.e[e]) - m;
-            u = __fmaf_rn(d[it][e], d[it][e], u);
-        }
-        u = rr >= 0 ? u : 0.0f;
-        p0 += rr == 0 ? u : 0.0f;
-        if (R > 1) p1 += rr == 1 ? u : 0.0f;
-        if (R > 2) {
-            p2 += rr == 2 ? u : 0.0f;
-            p3 += rr == 3 ? u : 0.0f;
-        }
-    }
-    float r0 = __builtin_amdgcn_rsqf(wave_total(p0) * inv_c + eps), r1 = 0.0f, r2 = 0.0f, r3 = 0.0f;
-    if (R > 1) r1 = __builtin_amdgcn_rsqf(wave_total(p1) * inv_c + eps);
-    if (R > 2) {
-        r2 = __builtin_amdgcn_rsqf(wave_total(p2) * inv_c + eps);
-        r3 = __builtin_amdgcn_rsqf(wave_total(p3) * inv_c + eps);
-    }
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int rr = rowof[it];
-        if (rr < 0) continue;
-        const int cc = it * WAVE + lane - rr * cpr;
-        const float rs = pick4(rr, r0, r1, r2, r3, R);
-        Pack<TX, VEC> pw, pb, pk;
-        __builtin_memcpy(&pw, &wraw[it], 16);
-        __builtin_memcpy(&pb, &braw[it], 16);
-#pragma unroll
-        for (int e = 0; e < VEC; ++e)
-            pk.e[e] = from_f32<TX>(__fmaf_rn(d[it][e], to_f32(pw.e[e]) * rs, to_f32(pb.e[e])));
-        uint4 yv;
-        __builtin_memcpy(&yv, &pk, 16);
-        store_y(it, rr, cc, yv);
-    }
 }
 
 // The tail of one destination row held by a whole wave as two 16-byte column chunks per lane (acc0 at column c0, acc1
@@ -1106,14 +943,18 @@ __global__ __launch_bounds__(256) void k_merge_rows_fast(const TX *__restrict__ 
         if (LN) raw[it] = outv;  // keep the merged bits: LayerNorm runs on x' itself (what is written without xbias)
     }
     if constexpr (LN) {
-        // LayerNorm of the (up to) four rows of this wave as they were stored (ln_rows above)
+        // LayerNorm of the (up to) four rows of this wave as they were stored (ln_rows, tome_ln_rows.h)
         TX *yg = group_ptr(reinterpret_cast<TX *>(ln.y), lout, g);
         const int64_t ystride = lout.tok_stride;
-        ln_rows<TX, NIT>(raw, rowof, R, cpr, C, ln.eps, reinterpret_cast<const TX *>(ln.weight),
-                         reinterpret_cast<const TX *>(ln.bias), lane,
-                         [&](int, int rr, int cc, const uint4 &yv) __attribute__((always_inline)) {
-                             st16(reinterpret_cast<char *>(yg + (int64_t)(o0 + rr) * ystride) + cc * 16, yv);
-                         });
+        const LnParams<TX, NIT> prm = ln_params<TX, NIT>(reinterpret_cast<const TX *>(ln.weight),
+                                                         reinterpret_cast<const TX *>(ln.bias), rowof, cpr, lane);
+        Slot<TX> stored[NIT];
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) stored[it].q[0] = raw[it];
+        ln_rows<TX, TX, TX, NIT>(stored, rowof, R, cpr, C, ln.eps, prm, lane,
+                                 [&](int rr, int cc, const Slot<TX> &yv) __attribute__((always_inline)) {
+                                     st_slot<TX>(yg + (int64_t)(o0 + rr) * ystride, cc, yv);
+                                 });
     }
     if (OP == OP_WAVG && lane < R && my_valid) {
         const bool mine_has_edges = lane == 0 ? e0 : (lane == 1 ? e1 : (lane == 2 ? e2 : e3));
@@ -1125,235 +966,62 @@ __global__ __launch_bounds__(256) void k_merge_rows_fast(const TX *__restrict__ 
 // k_add_ln_rows: the other residual of the patched block, fused with the LayerNorm that reads its result:
 //     x = x + mlp(norm2(x))            (tome/patch/videomae.py:29, end of ToMeBlock.forward)
 //     ... next block: self.norm1(x)    (tome/patch/videomae.py:19)
-// x' = round(x + a) and y = LayerNorm(x') in one pass (same arithmetic as the LN tail of k_merge_rows_fast).
-// A wave owns R consecutive rows, NIT 16-byte chunks per lane, everything loaded before use.
-template <typename TX, int NIT>
-__global__ __launch_bounds__(256) void k_add_ln_rows(const TX *__restrict__ x, const TX *__restrict__ a,
-                                                     int64_t rows, int C, int R, int cpr, LnArgs ln,
-                                                     TX *__restrict__ xout) {
-    constexpr int VEC = 16 / sizeof(TX);
+// x' = x + a and y = LayerNorm(x') in one pass (ln_rows, tome_ln_rows.h).  A wave owns R consecutive rows, NIT slots per
+// lane, everything loaded before use.  TS: the residual stream (x, x'); TA: the addend; TY: y; TP: weight and bias.
+//   tome_add_layernorm[_skip_first]: everything of one 16-bit dtype; x' = round16(x + a)
+//   tome_add_layernorm_amp (a model under autocast, fp32 master weights): TP fp32, TY the 16-bit autocast dtype,
+//     16-bit stream: x' = round16(x + a), the same bits;  fp32 stream: x' = x + (float)a -- `x + a.float()` bit for bit
+// The statistics are taken from the STORED row; y is rounded once to TY.
+// a == nullptr: LayerNorm only (x is the finished sum -- the caller's GEMM accumulated onto it), nothing is written to
+// xout.
+// y_group > 0: rows come in groups of y_group whose FIRST row (a class token) has no place in y -- y holds the other
+// y_group - 1 rows of every group, compacted (TimeSformer's temporal_norm1 feeds only the patch tokens,
+// tome/patch/timesformer.py:24-26, so `xn[:, 1:]` regrouped '(b p) t m' is a view instead of a copy)
+template <typename TS, typename TA, typename TY, typename TP, int NIT>
+__global__ __launch_bounds__(256) void k_add_ln_rows(const TS *__restrict__ x, const TA *__restrict__ a, int64_t rows,
+                                                     int C, int R, int cpr, const TP *__restrict__ lw,
+                                                     const TP *__restrict__ lb, float eps, int y_group,
+                                                     TS *__restrict__ xout, TY *__restrict__ y) {
     const int lane = threadIdx.x & 63;
     const int64_t w = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t row0 = w * R;
     if (row0 >= rows) return;
     const int nrow = (int)((rows - row0) < R ? (rows - row0) : R);
     const int total = nrow * cpr;
-    // a == nullptr: LayerNorm only (x is the finished sum -- the caller's GEMM accumulated onto it), nothing is
-    // written to xout
     const bool add = a != nullptr;
-    const uint4 *xs = reinterpret_cast<const uint4 *>(x + row0 * C),
-                *as = reinterpret_cast<const uint4 *>((add ? a : x) + row0 * C);
-    uint4 raw[NIT], rawa[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int q = it * WAVE + lane;
-        if (q < total) {
-            raw[it] = ld16(xs + q);
-            if (add) rawa[it] = ld16(as + q);
-        }
-    }
-    uint4 *xo = reinterpret_cast<uint4 *>(xout + row0 * C);
-    int rowof[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int q = it * WAVE + lane;
-        const int rr = (q >= cpr) + (q >= 2 * cpr) + (q >= 3 * cpr);
-        rowof[it] = q < total ? rr : -1;
-        if (q >= total || !add) continue;
-        Pack<TX, VEC> ps, pa;
-        __builtin_memcpy(&ps, &raw[it], 16);
-        __builtin_memcpy(&pa, &rawa[it], 16);
-        ps = add_packs<TX, VEC>(ps, pa);
-        __builtin_memcpy(&raw[it], &ps, 16);
-        st16(xo + q, raw[it]);
-    }
-    // y_group > 0: rows come in groups of y_group whose FIRST row (a class token) has no place in y -- y holds the other
-    // y_group - 1 rows of every group, compacted (TimeSformer's temporal_norm1 feeds only the patch tokens,
-    // tome/patch/timesformer.py:24-26, so `xn[:, 1:]` regrouped '(b p) t m' is a view instead of a copy)
-    const int yg = ln.y_group;
-    TX *yb = reinterpret_cast<TX *>(ln.y);
-    ln_rows<TX, NIT>(raw, rowof, nrow, cpr, C, ln.eps, reinterpret_cast<const TX *>(ln.weight),
-                     reinterpret_cast<const TX *>(ln.bias), lane,
-                     [&](int, int rr, int cc, const uint4 &yv) __attribute__((always_inline)) {
-                         int64_t yrow = row0 + rr;
-                         if (yg > 0) {
-                             const int64_t gb = yrow / yg;
-                             if (yrow - gb * yg == 0) return;
-                             yrow -= gb + 1;
-                         }
-                         st16(reinterpret_cast<uint4 *>(yb + yrow * C) + cc, yv);
-                     });
-}
-
-// ------------------------------------------------------------------------------------------------
-// Mixed precision (training under torch.autocast with fp32 master weights: tools/train_net.py:123,
-// tome/utils.py:54).  A lane SLOT is the 8 channels a 16-byte chunk of 16-bit tokens holds, whatever the byte width of
-// the tensor it is taken from: 16 bytes of a 16-bit tensor, 32 bytes (two 16-byte moves) of an fp32 one.  Slot q of a
-// wave's rows sits in lane q % 64, iteration q / 64, as the chunks of k_add_ln_rows do, so the packing (rows per wave,
-// slots per lane) of the two kernels is the same.
-// ------------------------------------------------------------------------------------------------
-template <typename T> struct Slot { uint4 q[sizeof(T) / 2]; };
-
-template <typename T> __device__ __forceinline__ Slot<T> ld_slot(const T *base, int64_t slot) {
-    Slot<T> s;
-    const uint4 *p = reinterpret_cast<const uint4 *>(base) + slot * (int64_t)(sizeof(T) / 2);
-#pragma unroll
-    for (int k = 0; k < (int)(sizeof(T) / 2); ++k) s.q[k] = ld16(p + k);
-    return s;
-}
-template <typename T> __device__ __forceinline__ void st_slot(T *base, int64_t slot, const Slot<T> &s) {
-    uint4 *p = reinterpret_cast<uint4 *>(base) + slot * (int64_t)(sizeof(T) / 2);
-#pragma unroll
-    for (int k = 0; k < (int)(sizeof(T) / 2); ++k) st16(p + k, s.q[k]);
-}
-template <typename T> __device__ __forceinline__ void slot_f32(const Slot<T> &s, float (&v)[8]) {
-    Pack<T, 8> p;
-    __builtin_memcpy(&p, &s, sizeof(p));
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = to_f32(p.e[e]);
-}
-template <typename T> __device__ __forceinline__ Slot<T> f32_slot(const float (&v)[8]) {  // one rounding (none: fp32)
-    Pack<T, 8> p;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) p.e[e] = from_f32<T>(v[e]);
-    Slot<T> s;
-    __builtin_memcpy(&s, &p, sizeof(p));
-    return s;
-}
-// the sum of a slot's 8 stored values: chunk_sum's dot products for 16-bit rows (ln_rows' bits), a chain of seven fp32
-// additions in channel order for fp32 rows
-template <typename T> __device__ __forceinline__ float slot_sum(const Slot<T> &s) {
-    if constexpr (std::is_same<T, float>::value) {
-        float v[8];
-        slot_f32<T>(s, v);
-        float t = v[0];
-#pragma unroll
-        for (int e = 1; e < 8; ++e) t += v[e];
-        return t;
-    } else {
-        return chunk_sum<T>(s.q[0]);
-    }
-}
-// the 8 fp32 values of a parameter slot (weight, bias: always fp32 under autocast), plain cached loads
-__device__ __forceinline__ void ld_param8(const float *__restrict__ p, int cc, float (&v)[8]) {
-    const float4 lo = *reinterpret_cast<const float4 *>(p + cc * 8), hi = *reinterpret_cast<const float4 *>(p + cc * 8 + 4);
-    v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w;
-    v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
-}
-
-// k_add_ln_rows_amp: k_add_ln_rows for a model that runs under autocast (tome_add_layernorm_amp).  TS: the residual
-// stream (x, x'), 16-bit or fp32; TA: the addend; TY: y, the 16-bit autocast dtype; weight and bias fp32.
-//   fp32 stream:   x' = x + (float)a, the fp32 sum, one rounding -- `x + a.float()` bit for bit
-//   16-bit stream: x' = round16(x + a), the bits k_add_ln_rows stores
-// The statistics are taken from the STORED row with ln_rows' arithmetic (two passes, centred variance, wave_total,
-// v_rsq_f32, 1/C as a multiplication); y = d * (rstd * w) + b as one multiply and one fma, rounded once to TY.
-// y_group as in k_add_ln_rows.  All loads of the wave's slots are issued before any use.
-template <typename TS, typename TA, typename TY, int NIT>
-__global__ __launch_bounds__(256) void k_add_ln_rows_amp(const TS *__restrict__ x, const TA *__restrict__ a, int64_t rows,
-                                                         int C, int R, int cpr, const float *__restrict__ lw,
-                                                         const float *__restrict__ lb, float eps, int y_group,
-                                                         TS *__restrict__ xout, TY *__restrict__ y) {
-    constexpr int VEC = 8;
-    const int lane = threadIdx.x & 63;
-    const int64_t w = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t row0 = w * R;
-    if (row0 >= rows) return;
-    const int nrow = (int)((rows - row0) < R ? (rows - row0) : R);
-    const int total = nrow * cpr;
-    const bool add = a != nullptr;  // nullptr: LayerNorm only, nothing is written to xout
-    const float inv_c = __builtin_amdgcn_rcpf((float)C);
     const TS *xs = x + row0 * C;
     const TA *as = a + row0 * C;
     Slot<TS> raw[NIT] = {};
     Slot<TA> rawa[NIT] = {};
     int rowof[NIT];
-    float wv[NIT][VEC], bv[NIT][VEC];
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         const int q = it * WAVE + lane;
-        const int rr = (q >= cpr) + (q >= 2 * cpr) + (q >= 3 * cpr);
-        const bool live = q < total;
-        rowof[it] = live ? rr : -1;
-        if (live) {
+        rowof[it] = q < total ? (q >= cpr) + (q >= 2 * cpr) + (q >= 3 * cpr) : -1;
+        if (q < total) {
             raw[it] = ld_slot<TS>(xs, q);
             if (add) rawa[it] = ld_slot<TA>(as, q);
         }
-        const int cc = live ? q - rr * cpr : 0;
-        ld_param8(lw, cc, wv[it]);
-        ld_param8(lb, cc, bv[it]);
     }
-    // x' and the first pass: the sums of the stored rows
-    float d[NIT][VEC];
-    float p0 = 0.0f, p1 = 0.0f, p2 = 0.0f, p3 = 0.0f;
+    const LnParams<TP, NIT> prm = ln_params<TP, NIT>(lw, lb, rowof, cpr, lane);
+    if (add) {
 #pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int rr = rowof[it];
-        if (add && rr >= 0) {
-            float xa[VEC], av[VEC];
-            slot_f32<TS>(raw[it], xa);
-            slot_f32<TA>(rawa[it], av);
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) xa[e] = __fadd_rn(xa[e], av[e]);
-            raw[it] = f32_slot<TS>(xa);
+        for (int it = 0; it < NIT; ++it) {
+            if (rowof[it] < 0) continue;
+            raw[it] = slot_add<TS, TA>(raw[it], rawa[it]);
             st_slot<TS>(xout + row0 * C, it * WAVE + lane, raw[it]);
         }
-        slot_f32<TS>(raw[it], d[it]);  // the stored values; centred below
-        const float t = rr >= 0 ? slot_sum<TS>(raw[it]) : 0.0f;
-        p0 += rr == 0 ? t : 0.0f;
-        if (R > 1) p1 += rr == 1 ? t : 0.0f;
-        if (R > 2) {
-            p2 += rr == 2 ? t : 0.0f;
-            p3 += rr == 3 ? t : 0.0f;
-        }
     }
-    float m0 = wave_total(p0) * inv_c, m1 = 0.0f, m2 = 0.0f, m3 = 0.0f;
-    if (R > 1) m1 = wave_total(p1) * inv_c;
-    if (R > 2) {
-        m2 = wave_total(p2) * inv_c;
-        m3 = wave_total(p3) * inv_c;
-    }
-    p0 = p1 = p2 = p3 = 0.0f;
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int rr = rowof[it];
-        const float m = pick4(rr, m0, m1, m2, m3, R);
-        float u = 0.0f;
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-            d[it][e] = d[it][e] - m;
-            u = __fmaf_rn(d[it][e], d[it][e], u);
-        }
-        u = rr >= 0 ? u : 0.0f;
-        p0 += rr == 0 ? u : 0.0f;
-        if (R > 1) p1 += rr == 1 ? u : 0.0f;
-        if (R > 2) {
-            p2 += rr == 2 ? u : 0.0f;
-            p3 += rr == 3 ? u : 0.0f;
-        }
-    }
-    float r0 = __builtin_amdgcn_rsqf(wave_total(p0) * inv_c + eps), r1 = 0.0f, r2 = 0.0f, r3 = 0.0f;
-    if (R > 1) r1 = __builtin_amdgcn_rsqf(wave_total(p1) * inv_c + eps);
-    if (R > 2) {
-        r2 = __builtin_amdgcn_rsqf(wave_total(p2) * inv_c + eps);
-        r3 = __builtin_amdgcn_rsqf(wave_total(p3) * inv_c + eps);
-    }
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int rr = rowof[it];
-        if (rr < 0) continue;
-        const int cc = it * WAVE + lane - rr * cpr;
-        const float rs = pick4(rr, r0, r1, r2, r3, R);
-        int64_t yrow = row0 + rr;
-        if (y_group > 0) {  // (k_add_ln_rows: the first row of every group has no place in y)
-            const int64_t gb = yrow / y_group;
-            if (yrow - gb * y_group == 0) continue;
-            yrow -= gb + 1;
-        }
-        float yv[VEC];
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) yv[e] = __fmaf_rn(d[it][e], wv[it][e] * rs, bv[it][e]);
-        st_slot<TY>(y + yrow * C, cc, f32_slot<TY>(yv));
-    }
+    ln_rows<TS, TP, TY, NIT>(raw, rowof, nrow, cpr, C, eps, prm, lane,
+                             [&](int rr, int cc, const Slot<TY> &yv) __attribute__((always_inline)) {
+                                 int64_t yrow = row0 + rr;
+                                 if (y_group > 0) {
+                                     const int64_t gb = yrow / y_group;
+                                     if (yrow - gb * y_group == 0) return;
+                                     yrow -= gb + 1;
+                                 }
+                                 st_slot<TY>(y + yrow * C, cc, yv);
+                             });
 }
 
 // k_unmerge_rows: merge.py:87-100 as a scatter from the merged sequence: one wave per INPUT row; a
@@ -1461,7 +1129,6 @@ template <typename TX, int NIT>
 __global__ __launch_bounds__(256) void k_add_ln_regroup(const TX *__restrict__ x, const TX *__restrict__ a, int B, int F,
                                                         int P, int C, int R, int cpr, LnArgs ln,
                                                         TX *__restrict__ xout) {
-    constexpr int VEC = 16 / sizeof(TX);
     const int lane = threadIdx.x & 63;
     const int64_t w = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int N = 1 + P * F;
@@ -1486,8 +1153,8 @@ __global__ __launch_bounds__(256) void k_add_ln_regroup(const TX *__restrict__ x
             yrow[rr] = (b * F + t) * (int64_t)(1 + P) + 1 + p;
         }
     }
-    const uint4 *xs = reinterpret_cast<const uint4 *>(x + row0 * C);
-    uint4 raw[NIT], rawa[NIT];
+    const TX *xs = x + row0 * C;
+    Slot<TX> raw[NIT], rawa[NIT];
     int rowof[NIT];
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
@@ -1495,37 +1162,30 @@ __global__ __launch_bounds__(256) void k_add_ln_regroup(const TX *__restrict__ x
         const int rr = (q >= cpr) + (q >= 2 * cpr) + (q >= 3 * cpr);
         rowof[it] = q < total ? rr : -1;
         if (q >= total) continue;
-        raw[it] = ld16(xs + q);
+        raw[it] = ld_slot<TX>(xs, q);
         const int64_t ar = rr == 0 ? arow[0] : (rr == 1 ? arow[1] : (rr == 2 ? arow[2] : arow[3]));
-        if (ar >= 0) rawa[it] = ld16(reinterpret_cast<const uint4 *>(a + ar * C) + (q - rr * cpr));
+        if (ar >= 0) rawa[it] = ld_slot<TX>(a + ar * C, q - rr * cpr);
     }
-    uint4 *xo = reinterpret_cast<uint4 *>(xout + row0 * C);
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         const int rr = rowof[it];
         if (rr < 0) continue;
-        const int q = it * WAVE + lane;
         const int64_t ar = rr == 0 ? arow[0] : (rr == 1 ? arow[1] : (rr == 2 ? arow[2] : arow[3]));
-        if (ar >= 0) {
-            Pack<TX, VEC> ps, pa;
-            __builtin_memcpy(&ps, &raw[it], 16);
-            __builtin_memcpy(&pa, &rawa[it], 16);
-            ps = add_packs<TX, VEC>(ps, pa);
-            __builtin_memcpy(&raw[it], &ps, 16);
-        }
-        st16(xo + q, raw[it]);
+        if (ar >= 0) raw[it] = slot_add<TX, TX>(raw[it], rawa[it]);
+        st_slot<TX>(xout + row0 * C, it * WAVE + lane, raw[it]);
     }
     TX *yb = reinterpret_cast<TX *>(ln.y);
-    ln_rows<TX, NIT>(raw, rowof, nrow, cpr, C, ln.eps, reinterpret_cast<const TX *>(ln.weight),
-                     reinterpret_cast<const TX *>(ln.bias), lane,
-                     [&](int, int rr, int cc, const uint4 &yv) __attribute__((always_inline)) {
-                         const int64_t ar = rr == 0 ? arow[0] : (rr == 1 ? arow[1] : (rr == 2 ? arow[2] : arow[3]));
-                         const int64_t yr = rr == 0 ? yrow[0] : (rr == 1 ? yrow[1] : (rr == 2 ? yrow[2] : yrow[3]));
-                         uint4 *yp = reinterpret_cast<uint4 *>(yb + yr * C) + cc;
-                         st16(yp, yv);
-                         if (ar < 0)  // class token: the same normalised row in front of every frame's tokens
-                             for (int t = 1; t < F; ++t) st16(yp + (int64_t)t * (1 + P) * cpr, yv);
-                     });
+    const LnParams<TX, NIT> prm = ln_params<TX, NIT>(reinterpret_cast<const TX *>(ln.weight),
+                                                     reinterpret_cast<const TX *>(ln.bias), rowof, cpr, lane);
+    ln_rows<TX, TX, TX, NIT>(raw, rowof, nrow, cpr, C, ln.eps, prm, lane,
+                             [&](int rr, int cc, const Slot<TX> &yv) __attribute__((always_inline)) {
+                                 const int64_t ar = rr == 0 ? arow[0] : (rr == 1 ? arow[1] : (rr == 2 ? arow[2] : arow[3]));
+                                 const int64_t yr = rr == 0 ? yrow[0] : (rr == 1 ? yrow[1] : (rr == 2 ? yrow[2] : yrow[3]));
+                                 TX *yp = yb + yr * C;
+                                 st_slot<TX>(yp, cc, yv);
+                                 if (ar < 0)  // class token: the same normalised row in front of every frame's tokens
+                                     for (int t = 1; t < F; ++t) st_slot<TX>(yp + (int64_t)t * (1 + P) * C, cc, yv);
+                             });
 }
 
 // k_gelu_erf: the activation between the two GEMMs of the MLP the patched block calls (`self.mlp(self.norm2(x))`,

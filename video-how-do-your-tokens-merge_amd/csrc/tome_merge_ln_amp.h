@@ -11,24 +11,15 @@
 //   16-bit stream: x' = round16(x + a), the bits k_merge_rows_fast merges
 //   fp32 stream:   x' = x + (float)a, the fp32 sum, one rounding -- `x + a.float()` bit for bit
 // The merge is tome_merge_wavg's contract (fp32 products, the destination's own term first, then its sources in src_idx
-// order, one division, one rounding to TX -- none for fp32); the LayerNorm is k_add_ln_rows_amp's (statistics from the
+// order, one division, one rounding to TX -- none for fp32); the LayerNorm is ln_rows (tome_ln_rows.h: statistics from the
 // STORED row, two passes, centred variance, fp32 parameters, y rounded once to TY).
-// Work layout: the lane SLOTS of k_add_ln_rows_amp (8 channels: one 16-byte move of a 16-bit row, two of an fp32 one), so
+// Work layout: the lane SLOTS of k_add_ln_rows (8 channels: one 16-byte move of a 16-bit row, two of an fp32 one), so
 // rows per wave and slots per lane are those of the 16-bit launch.  What keeps k_merge_rows_fast at the memory rate is kept:
 // every row load of a wave is issued before any use and is unconditional (a lane without a slot re-reads the start of the
 // wave's first row); rows that receive sources are left to edge waves (one per rank, the first edge into a destination
 // builds it); grid.x = the blocks of one group, grid.(y, z) = the group, so no wave starts with an integer division;
 // OP_DROP has no edge waves.  Flat layout only, no folded bias.
 // ------------------------------------------------------------------------------------------------
-template <typename TX, typename TA> __device__ __forceinline__ Slot<TX> slot_add(const Slot<TX> &x, const Slot<TA> &a) {
-    float xv[8], av[8];
-    slot_f32<TX>(x, xv);
-    slot_f32<TA>(a, av);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) xv[e] = __fadd_rn(xv[e], av[e]);
-    return f32_slot<TX>(xv);
-}
-
 // One destination row (odd token 2j+1 plus every source merged into it) by a whole wave, two slots per lane (C <= 1024):
 // merge_dst_row's arithmetic and order, then the LayerNorm of the row as stored.  k: the rank whose edge wave this is;
 // returns without a store when an earlier rank merges into the same destination.
@@ -128,37 +119,18 @@ __device__ __forceinline__ void merge_dst_row_amp(const TX *__restrict__ xg, con
     if (a0) st_slot<TX>(orow, c0, o0);
     if (a1) st_slot<TX>(orow, c1, o1);
     if (lane == 0) store_size<TS>(sog + o, log ? log + o : nullptr, ssum);
-    // LayerNorm of the row as stored
-    float w0[VEC], w1[VEC], b0[VEC], b1[VEC];
-    ld_param8(lw, c0s, w0);
-    ld_param8(lw, c1s, w1);
-    ld_param8(lb, c0s, b0);
-    ld_param8(lb, c1s, b1);
+    // LayerNorm of the row as stored: ln_rows' body behind the mean (NIT = 2, R = 1).  The mean is taken here: the
+    // lane's two sums are added to each other, not onto ln_row_means' 0.0f, and 0.0f + t is not t for a negative zero.
+    const Slot<TX> stored[2] = {o0, o1};
+    const int rowof[2] = {a0 ? 0 : -1, a1 ? 0 : -1};
+    const LnParams<float, 2> prm = ln_params<float, 2>(lw, lb, rowof, cpr, lane);
     const float inv_c = __builtin_amdgcn_rcpf((float)C);
-    slot_f32<TX>(o0, acc0);
-    slot_f32<TX>(o1, acc1);
     const float m = wave_total((a0 ? slot_sum<TX>(o0) : 0.0f) + (a1 ? slot_sum<TX>(o1) : 0.0f)) * inv_c;
-    float u0 = 0.0f, u1 = 0.0f;
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-        acc0[e] = acc0[e] - m;
-        acc1[e] = acc1[e] - m;
-        u0 = __fmaf_rn(acc0[e], acc0[e], u0);
-        u1 = __fmaf_rn(acc1[e], acc1[e], u1);
-    }
-    const float rs = __builtin_amdgcn_rsqf(wave_total((a0 ? u0 : 0.0f) + (a1 ? u1 : 0.0f)) * inv_c + eps);
     TY *yrow = yg + (int64_t)o * C;
-    float yv[VEC];
-    if (a0) {
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) yv[e] = __fmaf_rn(acc0[e], w0[e] * rs, b0[e]);
-        st_slot<TY>(yrow, c0, f32_slot<TY>(yv));
-    }
-    if (a1) {
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) yv[e] = __fmaf_rn(acc1[e], w1[e] * rs, b1[e]);
-        st_slot<TY>(yrow, c1, f32_slot<TY>(yv));
-    }
+    ln_rows_finish<TX, float, TY, 2>(stored, rowof, 1, cpr, inv_c, eps, Row4{m, 0.0f, 0.0f, 0.0f}, prm, lane,
+                                     [&](int, int cc, const Slot<TY> &yv) __attribute__((always_inline)) {
+                                         st_slot<TY>(yrow, cc, yv);
+                                     });
 }
 
 template <typename TX, typename TA, typename TY, typename TS, int OP, int NIT>
@@ -257,100 +229,48 @@ __global__ __launch_bounds__(256) void k_merge_rows_ln_amp(const TX *__restrict_
         }
     }
     const bool ok0 = va0 && !e0, ok1 = va1 && !e1, ok2 = va2 && !e2, ok3 = va3 && !e3;
-    // the parameter slots of every slot column this lane holds: requested now, used after the two reductions
-    float wvv[NIT][VEC], bvv[NIT][VEC];
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         const int rr = rowof[it];
         const bool ok = rr >= 0 && (rr == 0 ? ok0 : (rr == 1 ? ok1 : (rr == 2 ? ok2 : ok3)));
         rowof[it] = ok ? rr : -1;
-        const int cc = ok ? it * WAVE + lane - rr * cpr : 0;
-        ld_param8(lw, cc, wvv[it]);
-        ld_param8(lb, cc, bvv[it]);
     }
+    // the parameter slots of every slot column this lane holds: requested now, used after the two reductions
+    const LnParams<float, NIT> prm = ln_params<float, NIT>(lw, lb, rowof, cpr, lane);
     const float my_s = (load_size && my_valid) ? to_f32(my_s_raw) : 1.0f;
     const float sz0 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_s), 0)),
                 sz1 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_s), 1)),
                 sz2 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_s), 2)),
                 sz3 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_s), 3));
-    // x' = x + a, the merge of a row without sources ((x' s) / s: raw bits when that is x' itself), the store, and the
-    // first pass of the LayerNorm over the stored values
+    // x' = x + a, the merge of a row without sources ((x' s) / s: raw bits when that is x' itself) and the store
     constexpr bool narrow = sizeof(TX) == 2;
-    const float inv_c = __builtin_amdgcn_rcpf((float)C);
-    float d[NIT][VEC];
-    float p0 = 0.0f, p1 = 0.0f, p2 = 0.0f, p3 = 0.0f;
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         const int rr = rowof[it];
-        if (rr >= 0) {
-            if (add) raw[it] = slot_add<TX, TA>(raw[it], rawa[it]);
-            if (OP == OP_WAVG) {
-                const float s = rr == 0 ? sz0 : (rr == 1 ? sz1 : (rr == 2 ? sz2 : sz3));
-                const uint32_t sb = __float_as_uint(s);
-                const bool exact = (s == 1.0f) || (narrow && (sb & 0x007FFFFFu) == 0u && s >= 1.0f && s <= 65536.0f);
-                if (!exact) {
-                    float v[VEC];
-                    slot_f32<TX>(raw[it], v);
+        if (rr < 0) continue;
+        if (add) raw[it] = slot_add<TX, TA>(raw[it], rawa[it]);
+        if (OP == OP_WAVG) {
+            const float s = rr == 0 ? sz0 : (rr == 1 ? sz1 : (rr == 2 ? sz2 : sz3));
+            const uint32_t sb = __float_as_uint(s);
+            const bool exact = (s == 1.0f) || (narrow && (sb & 0x007FFFFFu) == 0u && s >= 1.0f && s <= 65536.0f);
+            if (!exact) {
+                float v[VEC];
+                slot_f32<TX>(raw[it], v);
 #pragma unroll
-                    for (int e = 0; e < VEC; ++e) v[e] = __fdiv_rn(__fmul_rn(v[e], s), s);
-                    raw[it] = f32_slot<TX>(v);
-                }
+                for (int e = 0; e < VEC; ++e) v[e] = __fdiv_rn(__fmul_rn(v[e], s), s);
+                raw[it] = f32_slot<TX>(v);
             }
-            st_slot<TX>(og + (int64_t)(o0 + rr) * C, it * WAVE + lane - rr * cpr, raw[it]);
         }
-        slot_f32<TX>(raw[it], d[it]);  // the stored values; centred below
-        const float t = rr >= 0 ? slot_sum<TX>(raw[it]) : 0.0f;
-        p0 += rr == 0 ? t : 0.0f;
-        if (R > 1) p1 += rr == 1 ? t : 0.0f;
-        if (R > 2) {
-            p2 += rr == 2 ? t : 0.0f;
-            p3 += rr == 3 ? t : 0.0f;
-        }
+        st_slot<TX>(og + (int64_t)(o0 + rr) * C, it * WAVE + lane - rr * cpr, raw[it]);
     }
     if (OP == OP_WAVG && my_valid) {
         const bool mine_has_edges = lane == 0 ? e0 : (lane == 1 ? e1 : (lane == 2 ? e2 : e3));
         if (!mine_has_edges)
             store_size<TS>(sout + (int64_t)g * To + o0 + lane, lsout ? lsout + (int64_t)g * To + o0 + lane : nullptr, my_s);
     }
-    float m0 = wave_total(p0) * inv_c, m1 = 0.0f, m2 = 0.0f, m3 = 0.0f;
-    if (R > 1) m1 = wave_total(p1) * inv_c;
-    if (R > 2) {
-        m2 = wave_total(p2) * inv_c;
-        m3 = wave_total(p3) * inv_c;
-    }
-    p0 = p1 = p2 = p3 = 0.0f;
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int rr = rowof[it];
-        const float m = pick4(rr, m0, m1, m2, m3, R);
-        float u = 0.0f;
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-            d[it][e] = d[it][e] - m;
-            u = __fmaf_rn(d[it][e], d[it][e], u);
-        }
-        u = rr >= 0 ? u : 0.0f;
-        p0 += rr == 0 ? u : 0.0f;
-        if (R > 1) p1 += rr == 1 ? u : 0.0f;
-        if (R > 2) {
-            p2 += rr == 2 ? u : 0.0f;
-            p3 += rr == 3 ? u : 0.0f;
-        }
-    }
-    float r0 = __builtin_amdgcn_rsqf(wave_total(p0) * inv_c + eps), r1 = 0.0f, r2 = 0.0f, r3 = 0.0f;
-    if (R > 1) r1 = __builtin_amdgcn_rsqf(wave_total(p1) * inv_c + eps);
-    if (R > 2) {
-        r2 = __builtin_amdgcn_rsqf(wave_total(p2) * inv_c + eps);
-        r3 = __builtin_amdgcn_rsqf(wave_total(p3) * inv_c + eps);
-    }
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int rr = rowof[it];
-        if (rr < 0) continue;
-        const float rs = pick4(rr, r0, r1, r2, r3, R);
-        float yv[VEC];
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) yv[e] = __fmaf_rn(d[it][e], wvv[it][e] * rs, bvv[it][e]);
-        st_slot<TY>(yg + (int64_t)(o0 + rr) * C, it * WAVE + lane - rr * cpr, f32_slot<TY>(yv));
-    }
+    // LayerNorm of the rows as stored
+    ln_rows<TX, float, TY, NIT>(raw, rowof, R, cpr, C, eps, prm, lane,
+                                [&](int rr, int cc, const Slot<TY> &yv) __attribute__((always_inline)) {
+                                    st_slot<TY>(yg + (int64_t)(o0 + rr) * C, cc, yv);
+                                });
 }
