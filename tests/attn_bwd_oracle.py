@@ -34,7 +34,9 @@ channel's rounding of q~ with the same sign, ~0.04 on unit-variance heads where 
 walk over 64 channels -- so a correct kernel sits at ~0.01 of the dq / dk bounds and ~0.05-0.1 of dv's (fp16: the same
 ratios, u being 8 x smaller on both sides).  What it catches is therefore a structural error (a term, a key tile, a
 bias, a factor, a head: test_attn_bwd_oracle_cpu.py; a dropped 64-key tile of a 197-key row is caught in bf16 through dv
-at 2.3 x, not through dq / dk at 0.8 / 0.5 x), not a slip of a per cent in dq or dk alone.  `check` prints the RMS of
+at 2.3 x, not through dq / dk at 0.8 / 0.5 x -- attn_bwd_accounting.py closes that gap: on inputs whose softmax is known
+(q = 0 or k = 0) E vanishes, rho collapses to eta, and this same bound rejects a single key missing from dq or a single
+query missing from dk), not a slip of a per cent in dq or dk alone.  `check` prints the RMS of
 error / bound beside the worst element as a figure for that regime; no bound on it is derived here, so none is asserted.
 
 None of the constants is fitted to GPU output.  CPU-importable (torch only).
