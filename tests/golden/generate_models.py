@@ -18,6 +18,11 @@ Three groups of fixtures (see `specs` in main): embed 32 / head dim 16 (generic 
 (the production path: tome_match_keys on the qkv buffer's keys in-model) with proportional attention on and off,
 and `apply_duplicate_patch` (videomae.py:154-157, timesformer.py:170-172, motionformer.py:230-232) per family.
     python tests/golden/generate_models.py [fixture names ...]     # no names: all of them
+A run with names carries every other manifest entry over and refuses to start if it would leave a models_<name>.npz
+without one (check_partial_run).
+    python tests/golden/generate_models.py --spread [entry names ...]
+records in every head-dim-64, mode, full-size and config0 entry how far the reference's OWN forward moves in fp64 and in
+bf16 (record_spread: `ref_spread`, the yardstick of the model tests); no seed search, no .npz rewritten.
 """
 from __future__ import annotations
 
@@ -537,10 +542,131 @@ def _wrap(inner, tag):
     return wrap
 
 
-def main():
-    install_stubs()
-    torch.manual_seed(0)
-    metas = []
+def check_partial_run(only, manifest, sections, out_dir):
+    """A run that regenerates only the named fixtures carries every other entry over from the old manifest.  It must
+    never LOSE one: a fixture that is neither regenerated nor in the old manifest while its .npz is in the tree would
+    leave a committed file that no test reads (this happened to two drop fixtures).  Checked before anything is
+    generated or written; an unknown name is refused too (it would regenerate nothing and say nothing)."""
+    known = {n for names in sections.values() for n in names}
+    unknown = sorted(only - known)
+    if unknown:
+        raise SystemExit(f"unknown fixture name(s) {unknown}; known: {sorted(known)}")
+    if not only:
+        return
+    lost = []
+    for section, names in sections.items():
+        entry = manifest.get(section, [])
+        have = {entry["name"]} if isinstance(entry, dict) else {m["name"] for m in entry}
+        lost += [f"{section}/{n}" for n in names
+                 if n not in only and n not in have and os.path.exists(os.path.join(out_dir, f"models_{n}.npz"))]
+    if lost:
+        raise SystemExit(f"partial run refused: {lost} have a models_<name>.npz in {out_dir} but no entry in manifest.json "
+                         "and are not regenerated by this run -- they would stay unregistered.  Name them too (or delete "
+                         "the files if the fixtures are retired).")
+
+
+def retired(only, old, names):
+    """Old entries of a section whose names this generator no longer produces: a partial run keeps them (it cannot
+    know that they are retired), a full run drops them."""
+    return [m for n, m in old.items() if only and n not in names]
+
+
+def spread_model(section, meta, families, prop_attn=None):
+    """The reference's patched model of one manifest entry, rebuilt from the entry alone, in fp32: (model, patch module).
+    prop_attn: overrides the entry's (record_spread's detour for drop mode in bf16)."""
+    prop_attn = meta["prop_attn"] if prop_attn is None else prop_attn
+    if section in ("full", "config0"):
+        model, patch, _, _, wseed, _ = _full_size_model(meta["host"])
+        patch.apply_patch(model, prop_attn=prop_attn, trace_source=True)
+    else:
+        build, patch, _ = families[meta["host"]]
+        model, cfg, _, wseed = build(meta["cfg"]["embed_dim"])
+        assert cfg == meta["cfg"], (cfg, meta["cfg"])
+        synth.fill_parameters(model, wseed)
+        if meta.get("duplicate"):
+            patch.apply_duplicate_patch(model, layer_to_duplicate=meta["duplicate"][0], quantity=meta["duplicate"][1])
+        kw = dict(prop_attn=prop_attn, trace_source=bool(meta.get("trace_source", False)))
+        if meta.get("head_aggregation"):
+            kw["head_aggregation"] = meta["head_aggregation"]
+        if section == "modes":
+            kw.update(mode=meta["mode"], threshold=-1.0)
+        patch.apply_patch(model, **kw)
+        if section == "modes":
+            model._tome_info["threshold"] = meta["threshold"] if meta["mode"] == "hybrid" else 0.0
+    assert wseed == meta["weight_seed"], (wseed, meta["weight_seed"])
+    return model, patch
+
+
+def record_spread(names, specs):
+    """`--spread [names ...]`: how far the REFERENCE's own forward moves when only its number format changes.  Per entry
+    (default: every head-dim-64, mode, full-size and config0 entry) the reference's patched model is rebuilt from the
+    manifest entry, its fp32 forward must reproduce the stored logits bit for bit (else the fixture is stale: stop), and
+    its fp64 and bf16 forwards (weights and clip cast, each from a freshly filled fp32 model) are compared with the stored
+    fp32 results: `ref_spread = {"fp64": {"logit_err", "agree"}, "bf16": {...}}` in the entry -- max |logit diff|, and
+    where the fixture stores partitions the per-layer share of original tokens in the stored merged group, as
+    tests/test_models_gpu.py computes it; for the mode fixtures also the dtype of the final sizes in that format.
+    Searches no seeds and rewrites no .npz."""
+    man_path = os.path.join(HERE, "manifest.json")
+    manifest = json.load(open(man_path))
+    entries = [("models", m) for m in manifest["models"] if m["cfg"]["embed_dim"] // m["cfg"]["num_heads"] == 64]
+    entries += [("modes", m) for m in manifest["modes"]] + [("full", m) for m in manifest["full"]]
+    entries.append(("config0", manifest["config0"]))
+    unknown = sorted(set(names) - {m["name"] for _, m in entries})
+    if unknown:
+        raise SystemExit(f"--spread: no such entry {unknown}")
+    families = reduced_families()
+    for section, meta in entries:
+        if names and meta["name"] not in names:
+            continue
+        z = np.load(os.path.join(HERE, f"models_{meta['name']}.npz"))
+        if section == "config0":
+            stored = list(z["partitions"])
+        else:
+            stored = [z[f"P{i}"] for i in range(len(meta["tokens"]))] if "P0" in z.files else None
+        clip = clip_of(meta["clip_shape"], meta["seeds"])
+        spread = {}
+        runs = [("fp32", torch.float32, None), ("fp64", torch.float64, None), ("bf16", torch.bfloat16, None)]
+        while runs:
+            key, dtype, prop = runs.pop(0)
+            model, patch = spread_model(section, meta, families, prop_attn=prop)
+            parts = [] if stored is not None else None
+            try:
+                out, layers = run_traced(patch, model.to(dtype), clip.to(dtype), meta["r"], partitions=parts)
+            except RuntimeError as e:
+                # The reference cannot run drop mode with prop_attn in 16 bits: drop resets the sizes to fp32 ones
+                # (videomae.py:123), and Motionformer's `q_dot_k + size.log()` (motionformer.py:110) is then an fp32
+                # tensor that its einsum refuses beside bf16 values.  The bias is log(1) = 0 there, so prop_attn=False
+                # is the same arithmetic -- shown on the spot: its fp32 forward must reproduce the stored logits bit
+                # for bit -- and its bf16 forward is the yardstick.
+                if not (key == "bf16" and prop is None and meta.get("mode") == "drop" and meta["prop_attn"]):
+                    raise
+                print(f"{meta['name']}: reference bf16 forward refused ({e}); prop_attn=False in its place", flush=True)
+                spread["bf16_prop_attn"] = False
+                runs = [("fp32", torch.float32, False), ("bf16", torch.bfloat16, False)]
+                continue
+            assert [l["T"] for l in layers] == meta["tokens"] and [l["r"] for l in layers] == meta["r_eff"], key
+            if key == "fp32":
+                if not np.array_equal(out.numpy(), z["logits"]):
+                    raise SystemExit(f"{meta['name']}: the reference's fp32 forward no longer reproduces the stored logits "
+                                     f"(max |diff| {np.abs(out.numpy() - z['logits']).max():.3e}): the fixture is stale")
+                continue
+            spread[key] = {"logit_err": float(np.abs(out.double().numpy() - z["logits"].astype(np.float64)).max())}
+            if stored is not None:
+                assert len(parts) == len(stored)
+                spread[key]["agree"] = [float((got == want).mean()) for got, want in zip(parts, stored)]
+            if section == "modes":  # (drop: fp32 ones whatever the tokens are; hybrid: ones_like(tokens), merge.py:362)
+                spread[key]["size_dtype"] = str(model._tome_info["size"].dtype)
+        meta["ref_spread"] = spread
+        print(meta["name"], "scale %.4g" % float(np.abs(z["logits"]).max()),
+              {k: (v["logit_err"], min(v["agree"]) if "agree" in v else None) for k, v in spread.items()
+               if isinstance(v, dict)}, flush=True)
+    with open(man_path, "w") as f:
+        json.dump(manifest, f, indent=1)
+
+
+def reduced_families():
+    """name -> (builder(embed) -> (model, cfg, clip shape, weight seed), the reference's patch module, r) of the three
+    reduced-width families.  (After install_stubs.)"""
     vm = importlib.import_module("slowfast.models.videomae_video_model_builder")
     pv = importlib.import_module("tome.patch.videomae")
     tsm = importlib.import_module("slowfast.models.timesformer")
@@ -578,7 +704,14 @@ def main():
         torch.manual_seed(13)
         return mb.Motionformer(mcfg).eval(), cfg, (2, 3, 8, 224, 224), 303
 
-    families = {"videomae": (videomae, pv, 5), "timesformer": (timesformer, pt, 6), "motionformer": (motionformer, pm, 5)}
+    return {"videomae": (videomae, pv, 5), "timesformer": (timesformer, pt, 6), "motionformer": (motionformer, pm, 5)}
+
+
+def main():
+    install_stubs()
+    torch.manual_seed(0)
+    metas = []
+    families = reduced_families()
     # layer-0 r-boundary gap demanded of the three VideoMAE head-dim-64 fixtures (16-bit cosine noise is ~3e-3: the
     # bf16 run of these fixtures then has every group's source SET to answer for, not only destinations)
     L0_GAP = {"videomae_hd64_prop0": 1e-2, "videomae_hd64_prop1": 1e-2, "videomae_hd64_dup": 1e-2,
@@ -601,9 +734,16 @@ def main():
              # head_aggregation="concat" (videomae.py:74-75; experiments.sh:164-169): the metric is the keys of all
              # heads side by side (D = 128 here, 768 at full size)
              ("videomae_hd64_concat", "videomae", 128, False, None)]
-    only = set(sys.argv[1:])
+    argv = sys.argv[1:]
+    if "--spread" in argv:
+        return record_spread([a for a in argv if a != "--spread"], {s[0]: s for s in specs})
+    only = set(argv)
     man_path = os.path.join(HERE, "manifest.json")
     manifest = json.load(open(man_path))
+    mode_names = [f"{fam}_hd64_{mode}" for fam in ("videomae", "timesformer", "motionformer") for mode in ("drop", "hybrid")]
+    sections = {"models": [s[0] for s in specs], "config0": ["config0_videomae_b"], "modes": mode_names,
+                "full": list(FULL_SPECS)}
+    check_partial_run(only, manifest, sections, HERE)
     old = {m["name"]: m for m in manifest.get("models", [])}
     for name, fam, embed, prop, dup in specs:
         if only and name not in only:
@@ -627,7 +767,7 @@ def main():
             patch_mod.apply_patch(model, prop_attn=prop)
         metas.append(emit(name, model, lambda: model._tome_info, clip_shape, r_arg, patch_mod, False, extra, HERE, prop,
                           l0_set_gap=L0_GAP.get(name, 0.0)))
-    manifest["models"] = metas
+    manifest["models"] = metas + retired(only, old, sections["models"])
     if not only or "config0_videomae_b" in only:
         manifest["config0"] = emit_config0(HERE)
     mode_old = {m["name"]: m for m in manifest.get("modes", [])}
@@ -641,11 +781,12 @@ def main():
                 continue
             build, patch_mod, r = families[fam]
             mode_metas.append(emit_mode(name, build, patch_mod, r, mode, fam != "videomae", HERE))
-    manifest["modes"] = mode_metas
+    manifest["modes"] = mode_metas + retired(only, mode_old, mode_names)
     full_old = {m["name"]: m for m in manifest.get("full", [])}
     manifest["full"] = [emit_full(HERE, key, attempts=int(os.environ.get("TOME_FULL_ATTEMPTS", "24")))
                         if (not only or key in only) else full_old[key]
                         for key in FULL_SPECS if (not only or key in only or key in full_old)]
+    manifest["full"] += retired(only, full_old, sections["full"])
     manifest["models_tau"] = TAU
     with open(man_path, "w") as f:
         json.dump(manifest, f, indent=1)

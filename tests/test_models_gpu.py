@@ -202,7 +202,62 @@ def _logit_tol(name, key, scale, ceiling):
     m = _measured().get(name, {}).get(key)
     if m is None:
         return ceiling * scale
-    return max(_MEASURED_FACTOR * m, 2e-3 * scale)
+    return min(max(_MEASURED_FACTOR * m, 2e-3 * scale), ceiling * scale)  # (a recorded regression cannot lift the ceiling)
+
+
+# ---- What the REFERENCE's own forward allows (`ref_spread` of the manifest entry: generate_models.py --spread ran the
+# reference's patched model of the fixture in fp64 and in bf16 on CPU and recorded how far its logits and, per layer, its
+# merged groups move from its stored fp32 forward).  measured.json above says "as the last build"; these rules say
+# "acceptable", and nothing of them comes from a run of this package:
+#   R1  bf16 logits:            err16 <= 2 * ref_spread.bf16.logit_err + 2e-3 * scale
+#   R2  fp32 logits (full size): err32 <= 2 * ref_spread.fp64.logit_err + 2e-3 * scale
+#   R3  fp32 groups, per layer:  agree32[l] >= ref_spread.bf16.agree[l]
+# The factor 2 is stated, not measured: this package's run and the reference's run in the other format are two
+# independent realisations of the same rounding noise through the same network (merges that flip inside the noise
+# included); one sample of the reference is the only yardstick there is, and a second draw of equal variance is not
+# expected beyond twice the first.  2e-3 * scale is the floor of _logit_tol (last bits of the library GEMMs differ
+# between builds).  R3 needs no margin: an fp32 forward must not leave the reference's groups further than the
+# reference's own 16-bit forward does.
+def _ref_tol(meta, key, scale):
+    """R1 (key "bf16") / R2 (key "fp64") for this fixture."""
+    return 2.0 * meta["ref_spread"][key]["logit_err"] + 2e-3 * scale
+
+
+# R2 does not hold as written for the fixtures listed here, for the stated reason; their fp32 logits are held to the
+# reference's own 16-bit error WITHOUT a factor instead (an fp32 run must still beat the reference's bf16 run).  The
+# table may hold this one fixture and no other (asserted below): a second one is a finding, not an entry.
+_R2_STATED = {
+    "config4_motionformer_r16":
+        "The reference's fp32 and fp64 forwards of this fixture make identical decisions in all 12 layers, so its "
+        "fp32-to-fp64 spread (8e-8) holds no flipped merge and is no yardstick for a run on other arithmetic.  In layer "
+        "0, group 6, the row maxima of the unmerged rows 19 and 55 are 5.0e-8 apart in exact arithmetic -- below one fp32 "
+        "ulp at 0.86 (6.0e-8) -- and their order decides which tokens are sources in layer 1.  The fp32 keys of any "
+        "machine carry ~2e-6 of GEMM rounding (measured against fp64 on the GEMM's own inputs: this package 1.8e-6 "
+        "relative, the reference's CPU run 1.7e-6) and move such a cosine by ~5e-7: with this package's keys the gap "
+        "is 2.0e-8 the other way (tome_match's fp32 row maxima are within 3.3e-7 of fp64 there), and the groups part "
+        "from layer 2 on; with that one pair put in the reference's order they stay the reference's through layer 3.  The order of the unmerged rows below the "
+        "fixture's tau (2e-5) is certified nowhere (SURVEY 7.1; 1240 of 1312 positions are); every op of the fp32 "
+        "forward was measured against fp64 on its own inputs (DESIGN.md section 2) and none exceeds 4e-6 relative.",
+}
+assert set(_R2_STATED) <= {"config4_motionformer_r16"}
+
+
+def _ref_fp32_tol(meta, scale):
+    if meta["name"] in _R2_STATED:
+        return meta["ref_spread"]["bf16"]["logit_err"], "the reference's bf16 error, no factor (R2 stated: _R2_STATED)"
+    return _ref_tol(meta, "fp64", scale), "R2"
+
+
+def _check_r3(meta, agree):
+    """R3, and what a log needs to see whether the run behaves like the reference's fp64 run."""
+    spread = meta["ref_spread"]
+    lead = lambda a: next((i for i, v in enumerate(a) if v < 1.0), len(a))  # noqa: E731
+    print(f"{meta['name']} fp32 agreement per layer {[round(a, 4) for a in agree]} ({lead(agree)} leading layers at 1.0); "
+          f"reference fp64 {[round(a, 4) for a in spread['fp64']['agree']]} ({lead(spread['fp64']['agree'])} leading); "
+          f"reference bf16 (the floor, R3) {[round(a, 4) for a in spread['bf16']['agree']]}; smallest room "
+          f"{min(a - f for a, f in zip(agree, spread['bf16']['agree'])):.4f}")
+    assert len(agree) == len(spread["bf16"]["agree"])
+    assert all(a >= f for a, f in zip(agree, spread["bf16"]["agree"])), (agree, spread["bf16"]["agree"])
 
 
 @pytest.mark.parametrize("meta", _HD64, ids=lambda m: m["name"])
@@ -266,9 +321,11 @@ def _check_layer0_and_logits(meta, z, plans32, plans16, out16):
     nm, _ = s32.max(-1)
     snm = nm.sort(dim=-1, descending=True).values
     set_ok = ((snm[:, r - 1] - snm[:, r]) > 2 * noise).cpu().numpy()
-    want_src, want_dst = z["L0_src"].astype(np.int64), z["L0_dst"].astype(np.int64)
+    has_dst = "L0_dst" in z.files  # (a drop fixture has sources and no destinations)
+    want_src = z["L0_src"].astype(np.int64)
+    want_dst = z["L0_dst"].astype(np.int64) if has_dst else np.zeros_like(want_src)
     got_src = plans16[0][1].src_idx.cpu().numpy()[..., 0]
-    got_dst = plans16[0][1].dst_idx.cpu().numpy()[..., 0]
+    got_dst = plans16[0][1].dst_idx.cpu().numpy()[..., 0] if has_dst else np.zeros_like(got_src)
     checked_sets = checked_dst = 0
     top2 = s32.topk(2, dim=-1).values
     row_gap = (top2[..., 0] - top2[..., 1]).cpu().numpy()
@@ -278,12 +335,15 @@ def _check_layer0_and_logits(meta, z, plans32, plans16, out16):
             checked_sets += 1
         got_map = dict(zip(got_src[g].tolist(), got_dst[g].tolist()))
         for i, j in zip(want_src[g].tolist(), want_dst[g].tolist()):
-            if i in got_map and row_gap[g, i] > 2 * noise:
+            if has_dst and i in got_map and row_gap[g, i] > 2 * noise:
                 assert got_map[i] == j, f"group {g}: destination of source row {i}"
                 checked_dst += 1
     print(f"{meta['name']}: bf16 score noise {noise:.2e}; {checked_sets}/{want_src.shape[0]} source sets and "
-          f"{checked_dst}/{want_src.size} destinations above it, all equal to the reference")
-    assert checked_dst > 0, "no layer-0 decision lies above the bf16 noise: the fixture does not test this path"
+          f"{checked_dst}/{want_src.size if has_dst else 0} destinations above it, all equal to the reference")
+    if has_dst:
+        assert checked_dst > 0, "no layer-0 decision lies above the bf16 noise: the fixture does not test this path"
+    else:
+        assert checked_sets > 0, "no layer-0 source set lies above the bf16 noise: the fixture does not test this path"
     if meta.get("l0_set_gap"):
         # these fixtures' clips were chosen with a layer-0 r-boundary gap of >= 1e-2 in every group (the generator's
         # l0_set_gap): every group's source SET is then above the 16-bit noise and has been compared
@@ -292,9 +352,13 @@ def _check_layer0_and_logits(meta, z, plans32, plans16, out16):
     err = float(np.abs(out16.float().cpu().numpy() - ref).max())
     scale = float(np.abs(ref).max())
     tol = _logit_tol(meta["name"], "bf16_logit_err", scale, BF16_LOGIT_TOL)
-    print(f"{meta['name']}: bf16 logits max |diff| {err:.3e} (largest |logit| {scale:.3e}, tolerance {tol:.3e})")
+    r1 = _ref_tol(meta, "bf16", scale)
+    print(f"{meta['name']}: bf16 logits max |diff| {err:.3e} (largest |logit| {scale:.3e}, tolerance {tol:.3e}; "
+          f"R1 bound {r1:.3e}, err / bound {err / r1:.2f})")
     _note_measured(meta["name"], bf16_logit_err=err)
     assert err <= tol, (err, tol, scale)
+    assert err <= r1, (err, r1, meta["ref_spread"]["bf16"]["logit_err"], scale)
+    return noise, nm
 
 
 def test_videomae_schedule_and_modes():
@@ -584,11 +648,16 @@ def test_config0_videomae_b_full_size_against_the_reference(monkeypatch):
     print(f"config0 full size fp32: merged groups identical to the reference's through layer {exact - 1}; share of "
           f"original tokens with the same group per layer: {[round(a, 4) for a in agree]}")
     assert min(agree) >= 0.9, agree
+    _check_r3(meta, agree)
     sizes = model._tome_info["size"].cpu().numpy()[..., 0]
     assert sizes.shape == z["size"].shape[:2] and (sizes.sum(1) == 1568.0).all() and (z["size"].sum((1, 2)) == 1568.0).all()
     err = float(np.abs(out.cpu().numpy() - z["logits"]).max())
-    print(f"config0 full size fp32: logits max |diff| {err:.3e} (largest |logit| {np.abs(z['logits']).max():.3e})")
-    assert err <= 5e-3 * float(np.abs(z["logits"]).max()), err
+    scale = float(np.abs(z["logits"]).max())
+    r2 = _ref_tol(meta, "fp64", scale)
+    print(f"config0 full size fp32: logits max |diff| {err:.3e} (largest |logit| {scale:.3e}; R2 bound {r2:.3e}, "
+          f"err / bound {err / r2:.2f})")
+    assert err <= 5e-3 * scale, err
+    assert err <= r2, (err, r2)
     # ---- the same clips as the benchmark runs them: bf16, every fused kernel on
     monkeypatch.setattr(_common, "merge_source", real_ms)
     model16 = H["videomae"].VideoMAE(num_frames=16, num_classes=400, tubelet_size=2, **cfg)
@@ -599,9 +668,12 @@ def test_config0_videomae_b_full_size_against_the_reference(monkeypatch):
     assert [s[1] for s, _ in plans16] == meta["tokens"]
     err16 = float(np.abs(out16.float().cpu().numpy() - z["logits"]).max())
     tol16 = _logit_tol("config0_videomae_b", "bf16_logit_err", float(np.abs(z["logits"]).max()), BF16_LOGIT_TOL)
-    print(f"config0 full size bf16: logits max |diff| {err16:.3e} (tolerance {tol16:.3e})")
+    r1 = _ref_tol(meta, "bf16", scale)
+    print(f"config0 full size bf16: logits max |diff| {err16:.3e} (tolerance {tol16:.3e}; R1 bound {r1:.3e}, "
+          f"err / bound {err16 / r1:.2f})")
     _note_measured("config0_videomae_b", bf16_logit_err=err16, fp32_logit_err=err, agree=agree)
     assert err16 <= tol16, (err16, tol16)
+    assert err16 <= r1, (err16, r1)
 
 
 def _full_metas():
@@ -628,7 +700,10 @@ def test_full_size_config_against_the_reference(meta, monkeypatch):
         reference's, per layer, printed, and held to the share a run on MI355X measured minus 2 points
         (tests/golden/measured.json; >= 0.5 while none is stored); sizes sum to the tokens of a group;
       * fp32 logits within 1.5x the measured error; the same clips in bf16 through the production kernels (asserted by
-        call count): token trace exact, logits within 1.5x the measured bf16 error."""
+        call count): token trace exact, logits within 1.5x the measured bf16 error;
+      * and, from the reference alone (`ref_spread`, rules R1 - R3 above `_ref_tol`): the per-layer share not below
+        that of the reference's own bf16 forward, fp32 logits within twice the reference's fp32-to-fp64 move (one
+        fixture: within the reference's bf16 error, `_R2_STATED`), bf16 logits within twice the reference's bf16 error."""
     z = np.load(os.path.join(G.GOLDEN, f"models_{meta['name']}.npz"))
     tome, model, patch = _build(meta)
     patch(model, prop_attn=meta["prop_attn"], trace_source=True)
@@ -677,6 +752,7 @@ def test_full_size_config_against_the_reference(meta, monkeypatch):
     known = _measured().get(meta["name"], {})
     floor = [max(0.0, a - 0.02) for a in known["agree"]] if "agree" in known else [0.5] * len(agree)
     assert all(a >= f for a, f in zip(agree, floor)), (agree, floor)
+    _check_r3(meta, agree)
     sizes = model._tome_info["size"].cpu().numpy()[..., 0]
     t0 = meta["tokens"][0]
     assert sizes.shape == z["size"].shape[:2] and (sizes.sum(1) == float(t0)).all()
@@ -684,8 +760,11 @@ def test_full_size_config_against_the_reference(meta, monkeypatch):
     scale = float(np.abs(z["logits"]).max())
     err = float(np.abs(out.cpu().numpy() - z["logits"]).max())
     tol = _logit_tol(meta["name"], "fp32_logit_err", scale, 0.02)
-    print(f"{meta['name']} fp32: logits max |diff| {err:.3e} (largest |logit| {scale:.3e}, tolerance {tol:.3e})")
+    r2, r2_what = _ref_fp32_tol(meta, scale)
+    print(f"{meta['name']} fp32: logits max |diff| {err:.3e} (largest |logit| {scale:.3e}, tolerance {tol:.3e}; bound "
+          f"by {r2_what} {r2:.3e}, err / bound {err / r2:.2f}; R2 as written {_ref_tol(meta, 'fp64', scale):.3e})")
     assert err <= tol, (err, tol)
+    assert err <= r2, (err, r2, r2_what)
     # ---- the same clips as the benchmark runs them: bf16, every fused kernel on
     monkeypatch.setattr(_common, "merge_source", real_ms)
     del model
@@ -701,9 +780,12 @@ def test_full_size_config_against_the_reference(meta, monkeypatch):
         _assert_production_calls(calls, meta, len(plans16), n_match=asked)
     err16 = float(np.abs(out16.float().cpu().numpy() - z["logits"]).max())
     tol16 = _logit_tol(meta["name"], "bf16_logit_err", scale, BF16_LOGIT_TOL)
-    print(f"{meta['name']} bf16: logits max |diff| {err16:.3e} (tolerance {tol16:.3e})")
+    r1 = _ref_tol(meta, "bf16", scale)
+    print(f"{meta['name']} bf16: logits max |diff| {err16:.3e} (tolerance {tol16:.3e}; R1 bound {r1:.3e}, "
+          f"err / bound {err16 / r1:.2f})")
     _note_measured(meta["name"], fp32_logit_err=err, bf16_logit_err=err16, agree=agree)
     assert err16 <= tol16, (err16, tol16)
+    assert err16 <= r1, (err16, r1)
 
 
 @pytest.mark.parametrize("meta", G.manifest().get("modes", []), ids=lambda m: m["name"])
@@ -743,6 +825,69 @@ def test_patch_level_drop_and_hybrid_against_the_reference(meta):
     np.testing.assert_array_equal(size.cpu().numpy(), z["size"])
     np.testing.assert_array_equal(info["source"].cpu().numpy().astype(np.uint8), z["source"])
     np.testing.assert_allclose(out.cpu().numpy(), z["logits"], atol=2e-4, rtol=1e-4)
+
+
+@pytest.mark.parametrize("meta", G.manifest().get("modes", []), ids=lambda m: m["name"])
+def test_mode_fixtures_production_path_bf16_against_the_reference(meta, monkeypatch):
+    """The drop / hybrid fixtures of the reference run the way the benchmark runs: bf16 weights and clips, every switch
+    at its default (no source tracing), so every merging block takes the ONE add + reduction + LayerNorm launch
+    (tome_drop_ln / tome_drop_regrouped / tome_merge_wavg_ln / tome_merge_wavg_regrouped with a LayerNorm) -- which
+    tests/test_modes_models_gpu.py compares only with this package's own unfused arm.  Against the reference:
+      * token counts and r_eff of every layer exactly;
+      * one fused launch per merging layer, no reduction on its own, no framework LayerNorm on norm2's input (counted
+        as test_modes_models_gpu.Counters counts them);
+      * the dtype of the final sizes: what the reference's own bf16 forward leaves (ref_spread.bf16.size_dtype) -- drop
+        resets them to ones of fp32 whatever the tokens are (the entry's size_dtype), hybrid sums ones_like(tokens);
+      * layer 0, certificate-aware as test_production_path_bf16_against_reference_fixture: source sets where the
+        r-boundary gap exceeds twice the measured bf16 cosine noise (at least one; a drop fixture has no destinations),
+        hybrid: destinations above the noise, and the keep flag of every edge of a source both runs selected whose
+        |score - threshold| exceeds twice that noise (at least one);
+      * logits by R1."""
+    from test_modes_models_gpu import Counters
+    from tome.patch import _common
+    z = np.load(os.path.join(G.GOLDEN, f"models_{meta['name']}.npz"))
+    kw = dict(prop_attn=meta["prop_attn"], mode=meta["mode"])
+    if meta["mode"] == "hybrid":
+        kw["threshold"] = meta["threshold"]
+    clip32 = _clip(meta)
+    tome, model32, patch = _build(meta)
+    patch(model32, **kw)
+    _, plans32 = _trace(tome, model32, clip32, meta["r"], keep_metric=True)
+    tome, model16, patch = _build(meta)
+    model16 = model16.to(torch.bfloat16)
+    patch(model16, **kw)
+    blocks = model16.blocks if meta["host"] == "motionformer" else model16.model.blocks
+    counted = Counters(monkeypatch, [b.norm2 for b in blocks])
+    out16, plans16 = _trace(tome, model16, clip32.bfloat16(), meta["r"], keep_metric=True)
+    assert [s[1] for s, *_ in plans16] == meta["tokens"] and [p.r for _, p, _ in plans16] == meta["r_eff"]
+    assert [s[0] for s, *_ in plans16] == meta["groups"]
+    n_layers = len(plans16)
+    assert n_layers == len(blocks)  # every block of these fixtures reduces
+    if all((_common._FUSE_LN, _common._FUSE_ADD, _common._FUSE_NEXT, _common._FUSE_MODES, _common._ATTN_KERNEL)):
+        assert counted.n == dict(fused=n_layers, fused_with_addend=n_layers, alone=0, drop=0, norm2_layer_norm=0), counted.n
+    info = model16._tome_info
+    assert info["mode"] == meta["mode"] and info["size"].shape[1] == z["size"].shape[1]
+    assert str(info["size"].dtype) == meta["ref_spread"]["bf16"]["size_dtype"]
+    if meta["mode"] == "drop":
+        assert str(info["size"].dtype) == meta["size_dtype"] == "torch.float32" and bool((info["size"] == 1).all())
+    noise, nm = _check_layer0_and_logits(meta, z, plans32, plans16, out16)
+    if meta["mode"] == "hybrid":
+        thr = meta["threshold"]
+        want_src, want_keep = z["L0_src"].astype(np.int64), z["L0_keep"]
+        p16 = plans16[0][1]
+        got_src = p16.src_idx.cpu().numpy()[..., 0]
+        got_keep = p16.edge_keep.cpu().numpy().astype(bool).reshape(got_src.shape)
+        score = nm.cpu().numpy()  # fp64 row maxima of the fp32 run's layer-0 metric
+        checked = 0
+        for g in range(want_src.shape[0]):
+            mine = dict(zip(got_src[g].tolist(), got_keep[g].tolist()))
+            for i, keep in zip(want_src[g].tolist(), want_keep[g].tolist()):
+                if i in mine and abs(score[g, i] - thr) > 2 * noise:
+                    assert mine[i] == bool(keep), f"group {g}: keep flag of the edge of source row {i}"
+                    checked += 1
+        print(f"{meta['name']}: {checked}/{want_keep.size} layer-0 keep flags further than 2 x {noise:.2e} from the "
+              f"threshold {thr:.4f}, all equal to the reference")
+        assert checked > 0, "no layer-0 edge lies clear of the threshold: the fixture does not test the flags in 16 bits"
 
 
 def test_config0_videomae_b_fp32_vs_cpu_port():
