@@ -148,7 +148,7 @@ class Reference(NamedTuple):
 
 def kernel_q(q: torch.Tensor, scale: float) -> torch.Tensor:
     """What the kernels multiply the keys with: q * (scale * log2 e), both factors in fp32, rounded once to q's
-    16-bit format (tome_attn.h:205-216, tome_attn_resident.h:127-139, tome_attn_stream.h:196-209).  This rounding is
+    16-bit format (att_scaled in tome_attn_tile.h, called by every attention kernel).  This rounding is
     part of the kernels' definition of the logits -- the prescaled q of any fused attention -- not an error to bound:
     its effect on a logit, ~u * |q.k| * scale, would exceed 2u of a weight on rows with large logits."""
     sl = torch.tensor(scale, dtype=torch.float32) * torch.tensor(LOG2E, dtype=torch.float32)
@@ -219,7 +219,7 @@ def weighted_reference(q: torch.Tensor, k: torch.Tensor, log_bias: Optional[torc
 def weighted_bound(ref_c: torch.Tensor, dtype, nk: int, eta=2.0 ** -16) -> torch.Tensor:
     """Largest |out_c - ref_c| the kernels' arithmetic allows for a channel of mass ref_c (one-hot v):
         2u * ref_c + eta * ref_c + floor.
-    Derivation (tome_attn.h:409-436, 497-521; tome_attn_resident.h:236-288; tome_attn_stream.h:452-460): the row sum
+    Derivation (att_fast_weights, att_sum_*, att_store_row in tome_attn_tile.h and their callers): the row sum
     l adds the fp32 weights P (unrounded); the PV product multiplies the same weights rounded to the 16-bit format,
     P16 = P (1 + d), |d| <= u, by v in {0, 1}, so O_c = (1 + d') * mass_c with |d'| <= u; out = round16(O_c * (1/l))
     adds one more relative u.  Round-to-nearest keeps each of the two below u / (1 + u), so together they stay

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+import attn_oracle
 import golden_io as G
 import oracle
 import synth
@@ -1374,18 +1375,28 @@ def test_prop_attention_tile_edges_each_workgroup_shape(N, waves, monkeypatch):
         assert float((y.float() - want.reshape(B, N * F, F, H * 64)).abs().max()) <= 1e-2
 
 
-@pytest.mark.parametrize("waves", ["4", "8"])
+RERUN_SWITCHES = ("TOME_ATTN_RESIDENT", "TOME_ATTN_WAVES", "TOME_ATTN_STREAM")
+# (N, form) for every launch form the dispatcher reaches at B * H = 6 with that form's switches set
+RERUN_GRID = [pytest.param(N, form, id=f"N{N}-{form}") for N in (200, 224, 700) for form, env in attn_oracle.FORMS.items()
+              if attn_oracle.expected_form(N, N, 2 * 3, env) == form]
+assert {p.values[1] for p in RERUN_GRID} == set(attn_oracle.FORMS), "the rerun shapes no longer reach every launch form"
+
+
 @pytest.mark.parametrize("dtype,tol,jump", [(torch.bfloat16, 2e-2, 70.0), (torch.float16, 4e-3, 18.0),
                                             (torch.float16, 4e-3, 70.0)])
-@pytest.mark.parametrize("N", [200, 224, 700])
-def test_prop_attention_rerun_path(N, dtype, tol, jump, waves, monkeypatch):
+@pytest.mark.parametrize("N,form", RERUN_GRID)
+def test_prop_attention_rerun_path(N, form, dtype, tol, jump, monkeypatch):
     """The first pass keeps the reference point of tile 0 and is void when a row sum leaves the 16-bit format's
-    range; the workgroup then repeats the block on the general path.  Forced here: the logits of every query sit
-    near 0 in the first tile and `jump` (log2 units: > 60 for bf16, > 15 for fp16) higher from some later tile on --
-    the un-rescaled weights overflow, only the rerun gives finite, correct rows.  Plain, size-biased, TimeSformer's
-    bias_skip form and key segments; last tiles with <= 32 and > 32 keys; both workgroup shapes."""
+    range; the block is then repeated on the general path -- by the wave (resident, stream) or by the whole workgroup
+    (k_prop_attention with 4 and 8 waves).  Forced here: the logits of every query sit near 0 in the first tile and
+    `jump` (log2 units: > 60 for bf16, > 15 for fp16) higher from some later tile on -- the un-rescaled weights
+    overflow, only the rerun gives finite, correct rows.  Plain, size-biased, TimeSformer's bias_skip form and key
+    segments; last tiles with <= 32 and > 32 keys; every launch form, forced through the dispatcher's switches."""
     from tome import _abi
-    monkeypatch.setenv("TOME_ATTN_WAVES", waves)
+    for name in RERUN_SWITCHES:
+        monkeypatch.delenv(name, raising=False)
+    for name, value in attn_oracle.FORMS[form].items():
+        monkeypatch.setenv(name, value)
     g = torch.Generator(device=DEV).manual_seed(N + int(jump))
     B, H = 2, 3
     direction = torch.randn(B, H, 1, 64, device=DEV, generator=g)

@@ -50,18 +50,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tome_attn_tile.h"  // tile constants, fragment types and the arithmetic shared by all attention kernels
 #include "tome_common.h"
-
-#define ATT_D 64        // head dim
-#define ATT_BN 64       // keys per tile
-#define ATT_KS 72       // K tile row stride in elements (144 B: conflict-free ds_read_b128 over 16 rows)
-#define ATT_VS 96       // V tile row stride in elements (192 B: conflict-free ds_read_b64_tr_b16 over 4 rows)
-
-typedef float att_f32x16 __attribute__((ext_vector_type(16)));
-typedef short att_s16x4 __attribute__((ext_vector_type(4)));
-typedef short att_s16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 att_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 att_f16x8 __attribute__((ext_vector_type(8)));
 
 struct AttnArgs {
     const void *q, *k, *v;
@@ -80,47 +70,6 @@ struct AttnArgs {
     int nseg;
     int64_t k_seg, v_seg, o_seg, ls_seg;
 };
-
-template <typename TX> struct AttMfma;
-template <> struct AttMfma<bf16_t> {
-    static __device__ __forceinline__ att_f32x16 run(att_s16x8 a, att_s16x8 b, att_f32x16 c) {
-        att_bf16x8 x, y;
-        __builtin_memcpy(&x, &a, 16);
-        __builtin_memcpy(&y, &b, 16);
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, c, 0, 0, 0);
-    }
-};
-template <> struct AttMfma<f16_t> {
-    static __device__ __forceinline__ att_f32x16 run(att_s16x8 a, att_s16x8 b, att_f32x16 c) {
-        att_f16x8 x, y;
-        __builtin_memcpy(&x, &a, 16);
-        __builtin_memcpy(&y, &b, 16);
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(x, y, c, 0, 0, 0);
-    }
-};
-
-// Largest lane sum of un-normalised weights the plain path accepts before it moves the reference point: the weights
-// go to the second product in the 16-bit format (fp16 tops out at 65504; bf16 has fp32's range) and O / l
-// accumulate N of them in fp32.
-template <typename TX> struct AttLimit;
-template <> struct AttLimit<bf16_t> { static constexpr float value = 1.152921504606847e18f; };  // 2^60
-template <> struct AttLimit<f16_t> { static constexpr float value = 32768.0f; };                // 2^15
-
-__device__ __forceinline__ float att_add(float x, float y) {
-    // one v_add_f32 that the vectoriser cannot pair into v_pk_add_f32: the sum passes through an empty asm statement
-    // (the add itself stays a compiler instruction, so its hazards -- a transcendental result read by the next
-    // VALU instruction -- are padded by hipcc, which it would not do inside an asm string)
-    float r = x + y;
-    asm("" : "+v"(r));
-    return r;
-}
-
-template <typename TX> __device__ __forceinline__ short att_bits(float f) {
-    const TX t = from_f32<TX>(f);
-    short s;
-    __builtin_memcpy(&s, &t, 2);
-    return s;
-}
 
 // ------------------------------------------------------------------------------------------------
 // k_prop_attention<TX, WAVES, BIAS>: the kernel described at the top of this file.  BIAS = false: no per-key term
@@ -180,13 +129,10 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_prop_attention(AttnArgs a) { 
         g_att_stamps[((size_t)blockIdx.x * 8 + wave) * ATT_DIAG_N + 7] = __builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11));
 #endif
     const int qblocks = (a.N + ATT_BM - 1) / ATT_BM;
-    // XCD-aware mapping: the query blocks of one (batch, head, segment) stream the same K/V -> same XCD (ids congruent
-    // mod 8).  (Measured: persistent workgroups walking a run of items each are 3 % slower than this.)
-    const int L = blockIdx.x;
-    const int xcd = L & 7, sq = L >> 3;
-    const int bhs = (sq / qblocks) * 8 + xcd;
-    if (bhs >= a.B * a.H * a.nseg) return;
-    const int qb = sq % qblocks;
+    // XCD-aware mapping (att_item): the query blocks of one (batch, head, segment) stream the same K/V -> same XCD.
+    // (Measured: persistent workgroups walking a run of items each are 3 % slower than this.)
+    int bhs, qb;
+    if (!att_item(blockIdx.x, qblocks, a.B * a.H * a.nseg, bhs, qb)) return;
     const int bh = bhs / a.nseg, seg = bhs - bh * a.nseg;
     const int b = bh / a.H, h = bh % a.H;
     const short *qp = reinterpret_cast<const short *>(a.q) + b * a.q_sb + h * a.q_sh;
@@ -204,16 +150,8 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_prop_attention(AttnArgs a) { 
     const float sl = a.scale * LOG2E;
     att_s16x8 qf[4];  // q * scale * log2(e), rounded once to the 16-bit format (see the top of this file)
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-        const att_s16x8 raw = *reinterpret_cast<const att_s16x8 *>(qp + (int64_t)qload * a.q_sn + 16 * ks + 8 * hf);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            TX tq;
-            const short r = raw[e];
-            __builtin_memcpy(&tq, &r, 2);
-            qf[ks][e] = att_bits<TX>(to_f32(tq) * sl);
-        }
-    }
+    for (int ks = 0; ks < 4; ++ks)
+        qf[ks] = att_scaled<TX>(*reinterpret_cast<const att_s16x8 *>(qp + (int64_t)qload * a.q_sn + 16 * ks + 8 * hf), sl);
 
     ATT_STAMP(1);  // Q fragment requested / in registers
     att_f32x16 o0, o1, negm;
@@ -257,23 +195,9 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_prop_attention(AttnArgs a) { 
         }
         if (BIAS && tid < ATT_BN) lds_bias[0][S * ATT_BN + tid] = breg;
     };
-    // V^T fragments of a whole tile (layout: see O += V P below); lane-constant base
-    typedef __attribute__((address_space(3))) att_s16x4 *lds_s16x4_p;
-    const short *const vbase = &lds_v[0][0] + (4 * hf + ((lane & 15) >> 2)) * ATT_VS + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+    // V^T fragments of a whole tile, read one step before they are multiplied (att_tr_read_tile); lane-constant base
+    const short *const vbase = att_tr_base(&lds_v[0][0], lane, 0);
     att_s16x4 vfr[2][2][4];
-    auto v_fragments = [&](int S) __attribute__((always_inline)) {
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                const short *va = vbase + S * ATT_BN * ATT_VS + (32 * kb + 16 * p) * ATT_VS;
-                vfr[kb][p][0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(va));
-                vfr[kb][p][1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(va + 8 * ATT_VS));
-                vfr[kb][p][2] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(va + 32));
-                vfr[kb][p][3] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(va + 8 * ATT_VS + 32));
-            }
-    };
-    const short *const kbase = &lds_k[0][0] + col * ATT_KS + 8 * hf;
     att_f32x16 s0, s1;
     // per-key bias of this lane's registers (register v <-> key (v&3) + 8*(v>>2) + 4*hf, +32 for the second block)
     // added to a start block: the score accumulators then deliver s + log2e*log(size) - m_run
@@ -296,86 +220,24 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_prop_attention(AttnArgs a) { 
         s0 = cinit;
         s1 = cinit;
         if (BIAS) add_bias(S, s0, s1);
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks)
-            s0 = AttMfma<TX>::run(*reinterpret_cast<const att_s16x8 *>(kbase + S * ATT_BN * ATT_KS + 16 * ks), qf[ks], s0);
-        if (!first_half_only) {
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks)
-                s1 = AttMfma<TX>::run(*reinterpret_cast<const att_s16x8 *>(kbase + S * ATT_BN * ATT_KS + 32 * ATT_KS + 16 * ks),
-                                      qf[ks], s1);
-        }
+        const short *kt = &lds_k[0][0] + S * ATT_BN * ATT_KS;
+        att_rows_block<TX>(kt, col, hf, 0, qf, s0);
+        if (!first_half_only) att_rows_block<TX>(kt, col, hf, 1, qf, s1);
     };
-    // P (fp32 weights in s0, s1) -> the four 16-bit B fragments of O^T += V^T P^T
-    att_s16x8 pf[2][2];
-    auto pack_p = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int p = 0; p < 2; ++p)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                pf[0][p][e] = att_bits<TX>(s0[8 * p + e]);
-                pf[1][p][e] = att_bits<TX>(s1[8 * p + e]);
-            }
-    };
+    att_s16x8 pf[2][2];  // P (fp32 weights in s0, s1) as the four 16-bit B fragments of O^T += V^T P^T
     // general softmax of tile t from scores that start at zero: range mask, maximum, rescale of O and l
     auto general_softmax = [&](int t, int S) __attribute__((always_inline)) {
         att_f32x16 zero;
 #pragma unroll
         for (int v = 0; v < 16; ++v) zero[v] = 0.0f;
         scores(S, zero);
-        const int key0 = t * ATT_BN + 4 * hf;
-        float mt = -INFINITY;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int key = key0 + (v & 3) + 8 * (v >> 2);
-            s0[v] = key < a.Nk ? s0[v] : -INFINITY;
-            s1[v] = key + 32 < a.Nk ? s1[v] : -INFINITY;
-            mt = fmaxf(mt, fmaxf(s0[v], s1[v]));
-        }
-        {
-            const unsigned mb = __float_as_uint(mt);
-            const auto sw = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);
-            mt = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-        }
-        const float m_new = fmaxf(m_run, mt);  // finite: every tile holds at least one key in range
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-        float lsum = 0.0f;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            s0[v] = __builtin_amdgcn_exp2f(s0[v] - m_new);
-            s1[v] = __builtin_amdgcn_exp2f(s1[v] - m_new);
-            lsum += s0[v] + s1[v];
-        }
-        l_run = l_run * alpha + lsum;
-        m_run = m_new;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            o0[v] *= alpha;
-            o1[v] *= alpha;
-            negm[v] = -m_new;
-        }
-        pack_p();
+        att_general_softmax<TX>(s0, s1, t * ATT_BN + 4 * hf, a.Nk, m_run, l_run, o0, o1, negm, pf);
     };
     // O^T += V(t)^T P(t)^T from the fragments in registers (first_half_only: the weights of keys 32..63 are zero)
     auto pv = [&](bool first_half_only = false) __attribute__((always_inline)) {
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            if (kb == 1 && first_half_only) break;
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                att_s16x8 vf0, vf1;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    vf0[e] = vfr[kb][p][0][e];
-                    vf0[4 + e] = vfr[kb][p][1][e];
-                    vf1[e] = vfr[kb][p][2][e];
-                    vf1[4 + e] = vfr[kb][p][3][e];
-                }
-                o0 = AttMfma<TX>::run(vf0, pf[kb][p], o0);
-                o1 = AttMfma<TX>::run(vf1, pf[kb][p], o1);
-            }
-        }
+        att_tr_mfma_tile<TX>(vfr, pf, first_half_only, o0, o1);
     };
+    auto v_fragments = [&](int S) __attribute__((always_inline)) { att_tr_read_tile(vbase + S * ATT_BN * ATT_VS, vfr); };
     // One iteration = tile t (weights and V fragments in registers) is accumulated while tile t+1 (slot S after the
     // barrier) gets its scores and weights.
     //   fast_step: tile t+1 holds 64 keys.  Straight-line code -- 16 MFMAs and ~80 vector instructions free to
@@ -405,33 +267,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_prop_attention(AttnArgs a) { 
         pv();
         v_fragments(S);
         if (!(BIAS && WAVES == 4)) __builtin_amdgcn_s_setprio(1);  // (that instance would spill: the builtin fences the scheduler)
-#pragma unroll
-        for (int v = 0; v < 16; ++v) s0[v] = __builtin_amdgcn_exp2f(s0[v]);
-#pragma unroll
-        for (int v = 0; v < 16; ++v) s1[v] = __builtin_amdgcn_exp2f(s1[v]);
-        if (masked) {  // the partly filled last tile: keys past the end weigh nothing
-            const int key0 = (t + 1) * ATT_BN + 4 * hf;
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int key = key0 + (v & 3) + 8 * (v >> 2);
-                s0[v] = key < a.Nk ? s0[v] : 0.0f;
-                s1[v] = key + 32 < a.Nk ? s1[v] : 0.0f;
-            }
-        }
-        float c0s = att_add(s0[0], s0[4]), c1s = att_add(s0[1], s0[5]), c2s = att_add(s0[2], s0[6]),
-              c3s = att_add(s0[3], s0[7]);
-#pragma unroll
-        for (int v = 8; v < 16; v += 4) {
-            c0s = att_add(c0s, s0[v]);     c1s = att_add(c1s, s0[v + 1]);
-            c2s = att_add(c2s, s0[v + 2]); c3s = att_add(c3s, s0[v + 3]);
-        }
-#pragma unroll
-        for (int v = 0; v < 16; v += 4) {
-            c0s = att_add(c0s, s1[v]);     c1s = att_add(c1s, s1[v + 1]);
-            c2s = att_add(c2s, s1[v + 2]); c3s = att_add(c3s, s1[v + 3]);
-        }
-        const float lsum = att_add(att_add(c0s, c1s), att_add(c2s, c3s));
-        pack_p();
+        const float lsum = att_fast_weights<TX>(s0, s1, masked, (t + 1) * ATT_BN + 4 * hf, a.Nk, pf);
         if (!(BIAS && WAVES == 4)) __builtin_amdgcn_s_setprio(0);
         l_run += lsum;
         bad = bad || !(lsum <= AttLimit<TX>::value);  // inf / NaN / too large: this pass is void (rerun below)
@@ -494,32 +330,12 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_prop_attention(AttnArgs a) { 
         }
     }
 
-    // ---- out[b, q, h*64 + d] = O^T[d][q] / l ; register v <-> channel (v&3) + 8*(v>>2) + 4*hf (+32)
+    // ---- out[b, q, h*64 + d] = O^T[d][q] / l (att_store_row: 16-byte stores after a permlane32 swap)
     const float l_tot = l_run + __shfl_xor(l_run, 32);
     const float inv = 1.0f / l_tot;
-    // A lane holds channels 8g + 4*hf .. +3 (w0) and 32 + 8g + 4*hf .. +3 (w1) of its query; its partner lane l^32 holds
-    // the other halves.  One v_permlane32_swap per dword hands the lower lane the partner's w0 and the upper lane the
-    // partner's w1, so every lane stores 16 contiguous bytes (channels 8g .. 8g+7, +32 for the upper lanes): four
-    // 16-byte stores per lane instead of eight 8-byte ones.  (All 64 lanes take part in the swaps; only the stores are
-    // predicated.)
-    short *op = reinterpret_cast<short *>(a.out) + b * a.o_sb + (int64_t)(qrow < a.N ? qrow : 0) * a.o_sn + h * a.o_sh +
-                seg * a.o_seg + 32 * hf;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        att_s16x4 w0, w1;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            w0[e] = att_bits<TX>(o0[4 * g + e] * inv);
-            w1[e] = att_bits<TX>(o1[4 * g + e] * inv);
-        }
-        unsigned a2[2], b2[2];
-        __builtin_memcpy(a2, &w0, 8);
-        __builtin_memcpy(b2, &w1, 8);
-        const auto s0w = __builtin_amdgcn_permlane32_swap(a2[0], b2[0], false, false);
-        const auto s1w = __builtin_amdgcn_permlane32_swap(a2[1], b2[1], false, false);
-        const uint4 row16 = uint4{s0w[0], s1w[0], s0w[1], s1w[1]};
-        if (qrow < a.N) *reinterpret_cast<uint4 *>(op + 8 * g) = row16;
-    }
+    short *op = reinterpret_cast<short *>(a.out) + b * a.o_sb + (int64_t)(qrow < a.N ? qrow : 0) * a.o_sn + h * a.o_sh + seg * a.o_seg +
+                32 * hf;
+    att_store_row<TX>(op, qrow < a.N, o0, o1, inv);
     ATT_STAMP(5);  // stores issued
 #ifdef ATT_DIAG
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -29,7 +29,8 @@
 // multiplied), two barriers per tile; a tile that one product reads by rows and another by columns is kept as two
 // images (row stride 144 B for the ds_read_b128 rows, 192 B for the transposed reads: the forward's conflict-free
 // strides).  32 matrix instructions (32x32x16) per wave and tile in each kernel: eight tile products where the forward
-// does two.
+// does two.  The products, q~, the masked maximum, the output rows and the item numbering are the forward's functions
+// (tome_attn_tile.h).
 //
 // The segmented form (SEG = true: the backward of tome_prop_attention_segments, Motionformer's per-frame stage,
 // tome/patch/motionformer.py:98-121) shares every line of the two kernels.  Segment s has keys, values, bias, O, dO, dK
@@ -66,105 +67,6 @@ struct AttnBwdArgs {
     int64_t k_seg, v_seg, o_seg, do_seg, dk_seg, dv_seg, ls_seg;
 };
 
-// A 16-byte chunk of 16-bit values times a fp32 factor, rounded once to the format (q -> q~)
-template <typename TX> __device__ __forceinline__ att_s16x8 attb_scaled(const att_s16x8 raw, float f) {
-    att_s16x8 r;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        TX t;
-        const short s = raw[e];
-        __builtin_memcpy(&t, &s, 2);
-        r[e] = att_bits<TX>(to_f32(t) * f);
-    }
-    return r;
-}
-
-// c += X_blk Y^T for rows 32 blk .. 32 blk + 31 of a 64-row tile X (LDS row image, stride ATT_KS) and this wave's Y fragment
-template <typename TX>
-__device__ __forceinline__ void attb_rows_block(const short *img, int col, int hf, int blk, const att_s16x8 (&yf)[4],
-                                                att_f32x16 &c) {
-    const short *base = img + (32 * blk + col) * ATT_KS + 8 * hf;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) c = AttMfma<TX>::run(*reinterpret_cast<const att_s16x8 *>(base + 16 * ks), yf[ks], c);
-}
-template <typename TX>
-__device__ __forceinline__ void attb_rows_product(const short *img, int col, int hf, const att_s16x8 (&yf)[4],
-                                                  att_f32x16 &c0, att_f32x16 &c1) {
-    attb_rows_block<TX>(img, col, hf, 0, yf, c0);
-    attb_rows_block<TX>(img, col, hf, 1, yf, c1);
-}
-
-// (acc0, acc1) += X_blk^T W for rows 32 blk .. 32 blk + 31 of a 64-row tile X (LDS image for transposed reads, stride
-// ATT_VS; channels 0..31 -> acc0, 32..63 -> acc1) and W = an accumulator block rounded to the 16-bit format: the k order
-// of an accumulator block used as B operand is the forward's (tome_attn.h, O += V P).
-template <typename TX>
-__device__ __forceinline__ void attb_tr_block(const short *img, int lane, int blk, const att_f32x16 &w, att_f32x16 &acc0,
-                                              att_f32x16 &acc1) {
-    typedef __attribute__((address_space(3))) att_s16x4 *lds_s16x4_p;
-    const int hf = lane >> 5;
-    const short *base = img + (32 * blk + 4 * hf + ((lane & 15) >> 2)) * ATT_VS + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        att_s16x8 wf;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) wf[e] = att_bits<TX>(w[8 * p + e]);
-        const short *va = base + 16 * p * ATT_VS;
-        const att_s16x4 f0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(va));
-        const att_s16x4 f1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(va + 8 * ATT_VS));
-        const att_s16x4 f2 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(va + 32));
-        const att_s16x4 f3 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(va + 8 * ATT_VS + 32));
-        att_s16x8 x0, x1;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            x0[e] = f0[e];
-            x0[4 + e] = f1[e];
-            x1[e] = f2[e];
-            x1[4 + e] = f3[e];
-        }
-        acc0 = AttMfma<TX>::run(x0, wf, acc0);
-        acc1 = AttMfma<TX>::run(x1, wf, acc1);
-    }
-}
-template <typename TX>
-__device__ __forceinline__ void attb_tr_product(const short *img, int lane, const att_f32x16 &w0, const att_f32x16 &w1,
-                                                att_f32x16 &acc0, att_f32x16 &acc1) {
-    attb_tr_block<TX>(img, lane, 0, w0, acc0, acc1);
-    attb_tr_block<TX>(img, lane, 1, w1, acc0, acc1);
-}
-
-// row[0..63] = f * (acc0, acc1)^T of this lane's column, one rounding: register v <-> channel (v&3) + 8*(v>>2) + 4*hf
-// (+32), the forward's epilogue (16-byte stores after a permlane32 swap).  All lanes take part; `on` predicates the stores.
-template <typename TX>
-__device__ __forceinline__ void attb_store_row(short *row, int hf, bool on, const att_f32x16 &acc0,
-                                               const att_f32x16 &acc1, float f) {
-    short *op = row + 32 * hf;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        att_s16x4 w0, w1;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            w0[e] = att_bits<TX>(acc0[4 * g + e] * f);
-            w1[e] = att_bits<TX>(acc1[4 * g + e] * f);
-        }
-        unsigned a2[2], b2[2];
-        __builtin_memcpy(a2, &w0, 8);
-        __builtin_memcpy(b2, &w1, 8);
-        const auto s0w = __builtin_amdgcn_permlane32_swap(a2[0], b2[0], false, false);
-        const auto s1w = __builtin_amdgcn_permlane32_swap(a2[1], b2[1], false, false);
-        const uint4 row16 = uint4{s0w[0], s1w[0], s0w[1], s1w[1]};
-        if (on) *reinterpret_cast<uint4 *>(op + 8 * g) = row16;
-    }
-}
-
-// workgroup -> (batch*head, block): the blocks of one (batch, head) share an XCD (ids congruent mod 8), as the forward
-__device__ __forceinline__ bool attb_item(int blocks, int BH, int &bh, int &blk) {
-    const int L = blockIdx.x;
-    const int xcd = L & 7, sq = L >> 3;
-    bh = (sq / blocks) * 8 + xcd;
-    blk = sq % blocks;
-    return bh < BH;
-}
-
 template <typename TX, bool BIAS, bool SEG = false>
 __global__ __launch_bounds__(64 * ATTB_WAVES, 2) void k_attn_bwd_dq(AttnBwdArgs a) {
     __shared__ __attribute__((aligned(16))) short lds_kr[ATT_BN * ATT_KS];  // K, rows      (S^T)
@@ -175,7 +77,7 @@ __global__ __launch_bounds__(64 * ATTB_WAVES, 2) void k_attn_bwd_dq(AttnBwdArgs 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int col = lane & 31, hf = lane >> 5;
     int bh, qb;
-    if (!attb_item((a.N + ATTB_BM - 1) / ATTB_BM, a.B * a.H, bh, qb)) return;
+    if (!att_item(blockIdx.x, (a.N + ATTB_BM - 1) / ATTB_BM, a.B * a.H, bh, qb)) return;
     const int b = bh / a.H, h = bh % a.H;
     const short *qp = reinterpret_cast<const short *>(a.q) + b * a.q_sb + h * a.q_sh;
     // (SEG: the five below move on by a segment offset at the end of every pass of the segment loop)
@@ -197,7 +99,7 @@ __global__ __launch_bounds__(64 * ATTB_WAVES, 2) void k_attn_bwd_dq(AttnBwdArgs 
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
         const att_s16x8 raw = *reinterpret_cast<const att_s16x8 *>(qp + (int64_t)qload * a.q_sn + 16 * ks + 8 * hf);
-        qf[ks] = attb_scaled<TX>(raw, sl);
+        qf[ks] = att_scaled<TX>(raw, sl);
         gf[ks] = *reinterpret_cast<const att_s16x8 *>(gp + (int64_t)qload * a.do_sn + 16 * ks + 8 * hf);
         const att_s16x8 of = *reinterpret_cast<const att_s16x8 *>(op + (int64_t)qload * a.o_sn + 16 * ks + 8 * hf);
 #pragma unroll
@@ -296,21 +198,8 @@ __global__ __launch_bounds__(64 * ATTB_WAVES, 2) void k_attn_bwd_dq(AttnBwdArgs 
             __syncthreads();
             att_f32x16 s0, s1;
             start(0.0f, s0, s1);
-            attb_rows_product<TX>(lds_kr, col, hf, qf, s0, s1);
-            const int key0 = t * ATT_BN + 4 * hf;
-            float mt = -INFINITY;
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int key = key0 + (v & 3) + 8 * (v >> 2);
-                s0[v] = key < a.Nk ? s0[v] : -INFINITY;
-                s1[v] = key + 32 < a.Nk ? s1[v] : -INFINITY;
-                mt = fmaxf(mt, fmaxf(s0[v], s1[v]));
-            }
-            {
-                const unsigned mb = __float_as_uint(mt);
-                const auto sw = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);
-                mt = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-            }
+            att_rows_product<TX>(lds_kr, col, hf, qf, s0, s1);
+            const float mt = att_masked_max(s0, s1, t * ATT_BN + 4 * hf, a.Nk);
             const float m_new = fmaxf(m_run, mt);  // finite: every tile holds at least one key in range
             float lsum = 0.0f;
 #pragma unroll
@@ -340,10 +229,10 @@ __global__ __launch_bounds__(64 * ATTB_WAVES, 2) void k_attn_bwd_dq(AttnBwdArgs 
             __syncthreads();
             att_f32x16 s0, s1, p0, p1;
             start(-lse, s0, s1);
-            attb_rows_product<TX>(lds_kr, col, hf, qf, s0, s1);
+            att_rows_product<TX>(lds_kr, col, hf, qf, s0, s1);
 #pragma unroll
             for (int v = 0; v < 16; ++v) p0[v] = p1[v] = -delta;
-            attb_rows_product<TX>(lds_vr, col, hf, gf, p0, p1);
+            att_rows_product<TX>(lds_vr, col, hf, gf, p0, p1);
             const int key0 = t * ATT_BN + 4 * hf;
 #pragma unroll
             for (int v = 0; v < 16; ++v) {
@@ -353,7 +242,7 @@ __global__ __launch_bounds__(64 * ATTB_WAVES, 2) void k_attn_bwd_dq(AttnBwdArgs 
                 s0[v] = w0 * p0[v];
                 s1[v] = w1 * p1[v];
             }
-            attb_tr_product<TX>(lds_kt, lane, s0, s1, dq0, dq1);
+            att_tr_product<TX>(lds_kt, lane, s0, s1, dq0, dq1);
         }
         if (SEG) {  // the next segment's keys, values, bias, O and dO
             kp += a.k_seg; vp += a.v_seg; op += a.o_seg; gp += a.do_seg;
@@ -361,7 +250,7 @@ __global__ __launch_bounds__(64 * ATTB_WAVES, 2) void k_attn_bwd_dq(AttnBwdArgs 
         }
     }  // segments
     short *dqp = reinterpret_cast<short *>(a.dq) + b * a.dq_sb + h * a.dq_sh + (int64_t)(qon ? qrow : 0) * a.dq_sn;
-    attb_store_row<TX>(dqp, hf, qon, dq0, dq1, a.scale);
+    att_store_row<TX>(dqp + 32 * hf, qon, dq0, dq1, a.scale);
 }
 
 template <typename TX, bool BIAS, bool SEG = false>
@@ -376,7 +265,7 @@ __global__ __launch_bounds__(64 * ATTB_WAVES, 2) void k_attn_bwd_dkv(AttnBwdArgs
     const int col = lane & 31, hf = lane >> 5;
     int bh, kb;
     const int BH = a.B * a.H;
-    if (!attb_item((a.Nk + ATTB_BM - 1) / ATTB_BM, SEG ? BH * a.nseg : BH, bh, kb)) return;
+    if (!att_item(blockIdx.x, (a.Nk + ATTB_BM - 1) / ATTB_BM, SEG ? BH * a.nseg : BH, bh, kb)) return;
     const int seg = SEG ? bh / BH : 0;  // (SEG: the items are (segment, batch*head) pairs)
     if (SEG) bh -= seg * BH;
     const int b = bh / a.H, h = bh % a.H;
@@ -430,7 +319,7 @@ __global__ __launch_bounds__(64 * ATTB_WAVES, 2) void k_attn_bwd_dkv(AttnBwdArgs
         for (int i = 0; i < 2; ++i) {
             att_s16x8 raw;
             __builtin_memcpy(&raw, &qreg[i], 16);
-            *reinterpret_cast<att_s16x8 *>(lds_qr + (r0 + 32 * i) * ATT_KS + 8 * c0) = attb_scaled<TX>(raw, sl);
+            *reinterpret_cast<att_s16x8 *>(lds_qr + (r0 + 32 * i) * ATT_KS + 8 * c0) = att_scaled<TX>(raw, sl);
             *reinterpret_cast<uint4 *>(lds_qt + (r0 + 32 * i) * ATT_VS + 8 * c0) = qreg[i];
             *reinterpret_cast<uint4 *>(lds_gr + (r0 + 32 * i) * ATT_KS + 8 * c0) = greg[i];
             *reinterpret_cast<uint4 *>(lds_gt + (r0 + 32 * i) * ATT_VS + 8 * c0) = greg[i];
@@ -463,22 +352,22 @@ __global__ __launch_bounds__(64 * ATTB_WAVES, 2) void k_attn_bwd_dkv(AttnBwdArgs
             start(lds_row + 32 * qb, beta, s);
             // the skip form's class query (query 0: register 0 of the lower lanes, block 0 of tile 0) carries no bias
             if (BIAS && qb == 0 && a.bias_skip && t == 0 && hf == 0) s[0] = lds_row[0];
-            attb_rows_block<TX>(lds_qr, col, hf, qb, kf, s);
+            att_rows_block<TX>(lds_qr, col, hf, qb, kf, s);
             start(lds_row + ATT_BN + 32 * qb, 0.0f, p);
-            attb_rows_block<TX>(lds_gr, col, hf, qb, vf, p);
+            att_rows_block<TX>(lds_gr, col, hf, qb, vf, p);
             const int q0 = t * ATT_BN + 32 * qb + 4 * hf;
 #pragma unroll
             for (int v = 0; v < 16; ++v)  // out-of-range queries contribute nothing
                 s[v] = q0 + (v & 3) + 8 * (v >> 2) < a.N ? __builtin_amdgcn_exp2f(s[v]) : 0.0f;
-            attb_tr_block<TX>(lds_gt, lane, qb, s, dv0, dv1);
+            att_tr_block<TX>(lds_gt, lane, qb, s, dv0, dv1);
 #pragma unroll
             for (int v = 0; v < 16; ++v) s[v] *= p[v];
-            attb_tr_block<TX>(lds_qt, lane, qb, s, dk0, dk1);
+            att_tr_block<TX>(lds_qt, lane, qb, s, dk0, dk1);
         }
     }
     const int64_t kst = kon ? krow : 0;
     short *dkp = reinterpret_cast<short *>(a.dk) + b * a.dk_sb + h * a.dk_sh + kst * a.dk_sn + (SEG ? seg * a.dk_seg : 0);
     short *dvp = reinterpret_cast<short *>(a.dv) + b * a.dv_sb + h * a.dv_sh + kst * a.dv_sn + (SEG ? seg * a.dv_seg : 0);
-    attb_store_row<TX>(dkp, hf, kon, dk0, dk1, a.scale);
-    attb_store_row<TX>(dvp, hf, kon, dv0, dv1, 1.0f);
+    att_store_row<TX>(dkp + 32 * hf, kon, dk0, dk1, a.scale);
+    att_store_row<TX>(dvp + 32 * hf, kon, dv0, dv1, 1.0f);
 }

@@ -12,8 +12,9 @@
 // share a CU and one's staging runs under the other's arithmetic) are written to LDS once, ONE barrier, and then the
 // eight waves walk the query tiles of 32 rows with no further synchronisation -- TimeSformer: one tile per wave;
 // Motionformer: all 1 + S*F queries of the clip against the resident frame, 50 tiles per workgroup.
-// The arithmetic is k_prop_attention's: S^T = K Q~^T and O^T += V^T P^T on v_mfma_f32_32x32x16 (Q~ = q * scale * log2 e
-// rounded once to the 16-bit format), first tile with the general softmax, later tiles with score accumulators that
+// The arithmetic is k_prop_attention's, one 32-key block at a time, from the same functions (tome_attn_tile.h; two
+// address expressions are written out here, see below): S^T = K Q~^T and O^T += V^T P^T on v_mfma_f32_32x32x16 (Q~ = q *
+// scale * log2 e rounded once to the 16-bit format), first tile with the general softmax, later tiles with score accumulators that
 // START at -m_run (+ the key's log(size)), a row sum that doubles as overflow guard; a wave whose guard trips repeats
 // ITS query tile on the general path (reference point following the maximum tile by tile) -- the keys are resident, so
 // nobody else is involved.  Roofline of the TimeSformer shape: 100 KB of q/k/v/out per 9.9 MFLOP item = HBM bound at
@@ -40,12 +41,10 @@ __global__ __launch_bounds__(512, 4) void k_resident_attention(AttnArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int col = lane & 31, hf = lane >> 5;
     ATT_STAMP(0);  // entry (diagnostic build only: tools/attn_diag.py)
-    // XCD-aware item numbering: the nseg segments of one (batch, head) read the same Q rows -> same XCD (workgroup L
-    // runs on XCD L % 8), one after the other
-    const int L = blockIdx.x;
-    const int xcd = L & 7, sq = L >> 3;
-    const int bh = (sq / a.nseg) * 8 + xcd, seg = sq % a.nseg;
-    if (bh >= a.B * a.H) return;
+    // XCD-aware item numbering (att_item with the segments as blocks): the nseg segments of one (batch, head) read the
+    // same Q rows -> same XCD (workgroup L runs on XCD L % 8), one after the other
+    int bh, seg;
+    if (!att_item(blockIdx.x, a.nseg, a.B * a.H, bh, seg)) return;
     const int b = bh / a.H, h = bh % a.H;
     const short *qp = reinterpret_cast<const short *>(a.q) + b * a.q_sb + h * a.q_sh;
     const short *kp = reinterpret_cast<const short *>(a.k) + b * a.k_sb + h * a.k_sh + seg * a.k_seg;
@@ -103,8 +102,9 @@ __global__ __launch_bounds__(512, 4) void k_resident_attention(AttnArgs a) {
     __syncthreads();  // the only barrier: from here on the waves are on their own
     ATT_STAMP(2);  // K / V resident
 
-    typedef __attribute__((address_space(3))) att_s16x4 *lds_s16x4_p;
     const short *const kbase = lds_k + col * ATT_KS + 8 * hf;
+    // (att_tr_base(lds_v, lane, 0) written out: through the function the plain instantiations take 44 bytes of scratch
+    // for 32 -- the same arithmetic, another allocation)
     const short *const vbase = lds_v + (4 * hf + ((lane & 15) >> 2)) * ATT_VS + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
     const float sl = a.scale * LOG2E;
 
@@ -129,13 +129,7 @@ __global__ __launch_bounds__(512, 4) void k_resident_attention(AttnArgs a) {
         for (int ks = 0; ks < 4; ++ks) {
             att_s16x8 raw;
             __builtin_memcpy(&raw, &qraw[ks], 16);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                TX tq;
-                const short r = raw[e];
-                __builtin_memcpy(&tq, &r, 2);
-                qf[ks][e] = att_bits<TX>(to_f32(tq) * sl);
-            }
+            qf[ks] = att_scaled<TX>(raw, sl);
         }
 
         // The keys are walked in BLOCKS of 32 (one accumulator of scores at a time: with 64-key steps the live registers
@@ -148,6 +142,8 @@ __global__ __launch_bounds__(512, 4) void k_resident_attention(AttnArgs a) {
         auto scores = [&](int blk) __attribute__((always_inline)) {
 #pragma unroll
             for (int v = 0; v < 16; ++v) sc[v] = 0.0f;
+            // (att_rows_block with the lane's row address kept in kbase: through the function the plain instantiations run
+            // 1-2 % slower than the parent's slowest round at 512 x 12 x 165 and 64 x 12 x (196 x 8))
             const short *kt = kbase + blk * 32 * ATT_KS;
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) sc = AttMfma<TX>::run(*reinterpret_cast<const att_s16x8 *>(kt + 16 * ks), qf[ks], sc);
@@ -155,48 +151,23 @@ __global__ __launch_bounds__(512, 4) void k_resident_attention(AttnArgs a) {
         };
         auto pack_p = [&]() __attribute__((always_inline)) {
 #pragma unroll
-            for (int p = 0; p < 2; ++p)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) pf[p][e] = att_bits<TX>(sc[8 * p + e]);
+            for (int p = 0; p < 2; ++p) pf[p] = att_pack<TX>(sc, p);
         };
         // O^T += V(blk)^T P(blk)^T; the V^T fragments are read where they are used (ds_read_b64_tr_b16: 4 consecutive keys
         // of one channel per lane)
         auto pv = [&](int blk) __attribute__((always_inline)) {
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
-                const short *va = vbase + (blk * 32 + 16 * p) * ATT_VS;
-                const att_s16x4 f0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(va));
-                const att_s16x4 f1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(va + 8 * ATT_VS));
-                const att_s16x4 f2 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(va + 32));
-                const att_s16x4 f3 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(va + 8 * ATT_VS + 32));
-                att_s16x8 vf0, vf1;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    vf0[e] = f0[e];
-                    vf0[4 + e] = f1[e];
-                    vf1[e] = f2[e];
-                    vf1[4 + e] = f3[e];
-                }
-                o0 = AttMfma<TX>::run(vf0, pf[p], o0);
-                o1 = AttMfma<TX>::run(vf1, pf[p], o1);
+                att_s16x4 f0, f1, f2, f3;
+                att_tr_read(vbase + (blk * 32 + 16 * p) * ATT_VS, f0, f1, f2, f3);
+                att_tr_mfma<TX>(f0, f1, f2, f3, pf[p], o0, o1);
             }
         };
         // general softmax of a block (scores from zero): range mask, maximum, rescale of O and l
         auto general_softmax = [&](int blk) __attribute__((always_inline)) {
             qx[2] = qx[3] = 0;
             scores(blk);
-            const int key0 = blk * 32 + 4 * hf;
-            float mt = -INFINITY;
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                sc[v] = key0 + (v & 3) + 8 * (v >> 2) < nk ? sc[v] : -INFINITY;
-                mt = fmaxf(mt, sc[v]);
-            }
-            {
-                const unsigned mb = __float_as_uint(mt);
-                const auto sw = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);
-                mt = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-            }
+            const float mt = att_masked_max(sc, blk * 32 + 4 * hf, nk);
             const float m_new = fmaxf(m_run, mt);  // finite: every block holds at least one key in range
             const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
             float lsum = 0.0f;
@@ -234,19 +205,11 @@ __global__ __launch_bounds__(512, 4) void k_resident_attention(AttnArgs a) {
             scores(blk);
 #pragma unroll
             for (int v = 0; v < 16; ++v) sc[v] = __builtin_amdgcn_exp2f(sc[v]);
-            if ((blk + 1) * 32 > nk) {  // the partly filled last block: keys past the end weigh nothing
-                const int key0 = blk * 32 + 4 * hf;
-#pragma unroll
-                for (int v = 0; v < 16; ++v) sc[v] = key0 + (v & 3) + 8 * (v >> 2) < nk ? sc[v] : 0.0f;
-            }
-            float c0s = att_add(sc[0], sc[4]), c1s = att_add(sc[1], sc[5]), c2s = att_add(sc[2], sc[6]),
-                  c3s = att_add(sc[3], sc[7]);
-#pragma unroll
-            for (int v = 8; v < 16; v += 4) {
-                c0s = att_add(c0s, sc[v]);     c1s = att_add(c1s, sc[v + 1]);
-                c2s = att_add(c2s, sc[v + 2]); c3s = att_add(c3s, sc[v + 3]);
-            }
-            const float lsum = att_add(att_add(c0s, c1s), att_add(c2s, c3s));
+            // the partly filled last block: keys past the end weigh nothing
+            if ((blk + 1) * 32 > nk) att_fill_tail(sc, blk * 32 + 4 * hf, nk, 0.0f);
+            float c[4];
+            att_sum_block(sc, c);
+            const float lsum = att_sum_end(c);
             pack_p();
             l_run += lsum;
             bad = bad || !(lsum <= AttLimit<TX>::value);  // inf / NaN / too large: this pass is void
@@ -265,28 +228,12 @@ __global__ __launch_bounds__(512, 4) void k_resident_attention(AttnArgs a) {
             pv(last_blk);
         }
 
-        // ---- out[b, q, h*64 + d] = O^T[d][q] / l ; register v <-> channel (v&3) + 8*(v>>2) + 4*hf (+32)
+        // ---- out[b, q, h*64 + d] = O^T[d][q] / l (att_store_row)
         const float l_tot = l_run + __shfl_xor(l_run, 32);
         const float inv = 1.0f / l_tot;
         // (token offsets inside one (batch, head) slice fit 32 bits -- the host checks it: scalar base + 32-bit lane offset)
         short *const obase = reinterpret_cast<short *>(a.out) + b * a.o_sb + h * a.o_sh + seg * a.o_seg;
-        short *op = obase + ((unsigned)(qrow < a.N ? qrow : 0) * (unsigned)a.o_sn + 32u * hf);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            att_s16x4 w0, w1;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                w0[e] = att_bits<TX>(o0[4 * g + e] * inv);
-                w1[e] = att_bits<TX>(o1[4 * g + e] * inv);
-            }
-            unsigned a2[2], b2[2];
-            __builtin_memcpy(a2, &w0, 8);
-            __builtin_memcpy(b2, &w1, 8);
-            const auto s0w = __builtin_amdgcn_permlane32_swap(a2[0], b2[0], false, false);
-            const auto s1w = __builtin_amdgcn_permlane32_swap(a2[1], b2[1], false, false);
-            const uint4 row16 = uint4{s0w[0], s1w[0], s0w[1], s1w[1]};
-            if (qrow < a.N) *reinterpret_cast<uint4 *>(op + 8 * g) = row16;
-        }
+        att_store_row<TX>(obase + ((unsigned)(qrow < a.N ? qrow : 0) * (unsigned)a.o_sn + 32u * hf), qrow < a.N, o0, o1, inv);
         ATT_STAMP(5);  // this tile's stores issued
         if (qt + 8 < ntq) {  // the next tile's rows (wave-uniform); the other waves of the SIMD cover their latency
             const int qload = min((qt + 8) * 32 + col, a.N - 1);

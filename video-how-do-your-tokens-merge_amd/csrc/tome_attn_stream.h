@@ -18,8 +18,9 @@
 //     workgroup-wide repeat of the block, hence no second code path through the whole item.
 // The ring slot of a tile is (tiles streamed so far) & 1 -- a run-time value here (tiles per item may be odd).
 // Everything else -- fragment layouts, the first-pass softmax against the first tile's reference point with the
-// accumulators started at -m, the overflow guard with the general-path repeat, masked last tile, bias forms, segments
-// -- is k_prop_attention's and shares its device functions' contracts (see tome_attn.h).
+// accumulators started at -m, the overflow guard with the general-path repeat, masked last tile, segments -- is
+// k_prop_attention's, and both kernels call the same device functions for it (tome_attn_tile.h): item numbering, q~,
+// the score and PV products, the fast step's weights, the general softmax, the output exchange.
 //
 // Needs at least two key tiles (Nk > 64) and eight waves; the host takes k_prop_attention otherwise.
 #pragma once
@@ -75,15 +76,13 @@ __global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, in
     // ---- item numbering (k_prop_attention's): the query blocks of one (batch, head, segment) -> ids congruent mod 8
     struct Item { int b, h, seg, qb; };
     auto item_ok = [&](int L) -> bool {
-        if (L >= nitems) return false;
-        const int sq = L >> 3;
-        return (sq / qblocks) * 8 + (L & 7) < nbhs;
+        int bhs, qb;
+        return L < nitems && att_item(L, qblocks, nbhs, bhs, qb);
     };
     auto decode = [&](int L) -> Item {
-        const int sq = L >> 3;
-        const int bhs = (sq / qblocks) * 8 + (L & 7);
+        int bhs;
         Item it;
-        it.qb = sq % qblocks;
+        att_item(L, qblocks, nbhs, bhs, it.qb);
         const int bh = bhs / nseg;
         it.seg = bhs - bh * nseg;
         it.b = bh / nheads;
@@ -198,13 +197,7 @@ __global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, in
         for (int ks = 0; ks < 4; ++ks) {
             att_s16x8 raw;
             __builtin_memcpy(&raw, &qraw[ks], 16);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                TX tq;
-                const short r = raw[e];
-                __builtin_memcpy(&tq, &r, 2);
-                qf[ks][e] = att_bits<TX>(to_f32(tq) * sl);
-            }
+            qf[ks] = att_scaled<TX>(raw, sl);
         }
     };
 
@@ -222,23 +215,9 @@ __global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, in
     };
 
     // ---- fragments and products (tome_attn.h's layouts; the slot is a run-time value)
-    typedef __attribute__((address_space(3))) att_s16x4 *lds_s16x4_p;
-    const short *const vbase = &lds_v[0][0] + (4 * hf + ((lane & 15) >> 2)) * ATT_VS + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-    const short *const kbase = &lds_k[0][0] + col * ATT_KS + 8 * hf;
+    const short *const vbase = att_tr_base(&lds_v[0][0], lane, 0);
     att_s16x4 vfr[2][2][4];
-    auto v_fragments = [&](int S) __attribute__((always_inline)) {
-        const short *vs = vbase + S * ATT_BN * ATT_VS;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                const short *va = vs + (32 * kb + 16 * p) * ATT_VS;
-                vfr[kb][p][0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(va));
-                vfr[kb][p][1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(va + 8 * ATT_VS));
-                vfr[kb][p][2] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(va + 32));
-                vfr[kb][p][3] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(va + 8 * ATT_VS + 32));
-            }
-    };
+    auto v_fragments = [&](int S) __attribute__((always_inline)) { att_tr_read_tile(vbase + S * ATT_BN * ATT_VS, vfr); };
     // BIAS: the per-key term rides on the matrix pipe as a fifth k-step of the score product -- K gets two more
     // "channels" (hi, lo of the bias), Q gets bfac in both -- instead of 32 fma + 8 wide LDS reads per tile on the
     // vector pipe; the lanes of the upper half (channels 8..15 of that k-step) hold zeros
@@ -255,67 +234,21 @@ __global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, in
         s1 = AttMfma<TX>::run(f1, fq, s1);
     };
     auto scores = [&](int S, const att_f32x16 &cinit, bool first_half_only) __attribute__((always_inline)) {
-        const short *ks0 = kbase + S * ATT_BN * ATT_KS;
+        const short *kt = &lds_k[0][0] + S * ATT_BN * ATT_KS;
         s0 = cinit;
         s1 = cinit;
         if (BIAS) bias_step(S);
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks)
-            s0 = AttMfma<TX>::run(*reinterpret_cast<const att_s16x8 *>(ks0 + 16 * ks), qf[ks], s0);
-        if (!first_half_only) {
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks)
-                s1 = AttMfma<TX>::run(*reinterpret_cast<const att_s16x8 *>(ks0 + 32 * ATT_KS + 16 * ks), qf[ks], s1);
-        }
+        att_rows_block<TX>(kt, col, hf, 0, qf, s0);
+        if (!first_half_only) att_rows_block<TX>(kt, col, hf, 1, qf, s1);
     };
     att_s16x8 pf[2][2];
-    auto pack_p = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int p = 0; p < 2; ++p)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                pf[0][p][e] = att_bits<TX>(s0[8 * p + e]);
-                pf[1][p][e] = att_bits<TX>(s1[8 * p + e]);
-            }
-    };
     // general softmax of tile t from scores that start at zero: range mask, maximum, rescale of O and l
     auto general_softmax = [&](int t, int S) __attribute__((always_inline)) {
         att_f32x16 zero;
 #pragma unroll
         for (int v = 0; v < 16; ++v) zero[v] = 0.0f;
         scores(S, zero, false);
-        const int key0 = t * ATT_BN + 4 * hf;
-        float mt = -INFINITY;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int key = key0 + (v & 3) + 8 * (v >> 2);
-            s0[v] = key < nk ? s0[v] : -INFINITY;
-            s1[v] = key + 32 < nk ? s1[v] : -INFINITY;
-            mt = fmaxf(mt, fmaxf(s0[v], s1[v]));
-        }
-        {
-            const unsigned mb = __float_as_uint(mt);
-            const auto sw = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);
-            mt = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-        }
-        const float m_new = fmaxf(m_run, mt);  // finite: every tile holds at least one key in range
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-        float lsum = 0.0f;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            s0[v] = __builtin_amdgcn_exp2f(s0[v] - m_new);
-            s1[v] = __builtin_amdgcn_exp2f(s1[v] - m_new);
-            lsum += s0[v] + s1[v];
-        }
-        l_run = l_run * alpha + lsum;
-        m_run = m_new;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            o0[v] *= alpha;
-            o1[v] *= alpha;
-            negm[v] = -m_new;
-        }
-        pack_p();
+        att_general_softmax<TX>(s0, s1, t * ATT_BN + 4 * hf, nk, m_run, l_run, o0, o1, negm, pf);
     };
     // the first tile of an item (full: an item has at least two tiles): nothing to rescale, nothing to mask --
     // m = the tile's row maximum, P = exp2(s - m), l = the row sum
@@ -327,11 +260,7 @@ __global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, in
         float mt = fmaxf(s0[0], s1[0]);
 #pragma unroll
         for (int v = 1; v < 16; ++v) mt = fmaxf(mt, fmaxf(s0[v], s1[v]));
-        {
-            const unsigned mb = __float_as_uint(mt);
-            const auto sw = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);
-            mt = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-        }
+        mt = att_half_max(mt);
         float lsum = 0.0f;
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
@@ -343,26 +272,10 @@ __global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, in
         m_run = mt;
 #pragma unroll
         for (int v = 0; v < 16; ++v) negm[v] = -mt;
-        pack_p();
+        att_pack_tile<TX>(s0, s1, pf);
     };
     auto pv = [&](bool first_half_only) __attribute__((always_inline)) {
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            if (kb == 1 && first_half_only) break;
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                att_s16x8 vf0, vf1;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    vf0[e] = vfr[kb][p][0][e];
-                    vf0[4 + e] = vfr[kb][p][1][e];
-                    vf1[e] = vfr[kb][p][2][e];
-                    vf1[4 + e] = vfr[kb][p][3][e];
-                }
-                o0 = AttMfma<TX>::run(vf0, pf[kb][p], o0);
-                o1 = AttMfma<TX>::run(vf1, pf[kb][p], o1);
-            }
-        }
+        att_tr_mfma_tile<TX>(vfr, pf, first_half_only, o0, o1);
     };
     // one pipelined step inside an item: tile tn (in the staging registers) -> slot S, the stream's next tile
     // requested, ONE barrier, S(tn) and O += V(tn-1) P(tn-1), then P(tn) against the item's reference point
@@ -392,33 +305,7 @@ __global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, in
         pv(false);
         v_fragments(S);
         __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int v = 0; v < 16; ++v) s0[v] = __builtin_amdgcn_exp2f(s0[v]);
-#pragma unroll
-        for (int v = 0; v < 16; ++v) s1[v] = __builtin_amdgcn_exp2f(s1[v]);
-        if (masked) {  // the partly filled last tile: keys past the end weigh nothing
-            const int key0 = tn * ATT_BN + 4 * hf;
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int key = key0 + (v & 3) + 8 * (v >> 2);
-                s0[v] = key < nk ? s0[v] : 0.0f;
-                s1[v] = key + 32 < nk ? s1[v] : 0.0f;
-            }
-        }
-        float c0s = att_add(s0[0], s0[4]), c1s = att_add(s0[1], s0[5]), c2s = att_add(s0[2], s0[6]),
-              c3s = att_add(s0[3], s0[7]);
-#pragma unroll
-        for (int v = 8; v < 16; v += 4) {
-            c0s = att_add(c0s, s0[v]);     c1s = att_add(c1s, s0[v + 1]);
-            c2s = att_add(c2s, s0[v + 2]); c3s = att_add(c3s, s0[v + 3]);
-        }
-#pragma unroll
-        for (int v = 0; v < 16; v += 4) {
-            c0s = att_add(c0s, s1[v]);     c1s = att_add(c1s, s1[v + 1]);
-            c2s = att_add(c2s, s1[v + 2]); c3s = att_add(c3s, s1[v + 3]);
-        }
-        const float lsum = att_add(att_add(c0s, c1s), att_add(c2s, c3s));
-        pack_p();
+        const float lsum = att_fast_weights<TX>(s0, s1, masked, tn * ATT_BN + 4 * hf, nk, pf);
         __builtin_amdgcn_s_setprio(0);
         const float l_before = l_run;
         l_run += lsum;
@@ -441,7 +328,6 @@ __global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, in
         stream_load();
         __syncthreads();
     };
-    // out[b, q, h*64 + d] = O^T[d][q] / l (tome_attn.h's store: one 16-byte store per lane and channel group)
     // out[b, q, h*64 + d] = O^T[d][q] / l.  A lane holds 4 x 8 channels of ONE query row; stored from there, one store
     // instruction touches 32 rows x 2 x 16 bytes and the eight waves' stores queue up behind each other (measured:
     // waves 4-7 spend 2.2 us here, waves 0-3 0.7).  So the wave's 32 x 64 block goes through a region of LDS of its
@@ -451,22 +337,8 @@ __global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, in
         const float l_tot = l_run + __shfl_xor(l_run, 32);
         const float inv = __builtin_amdgcn_rcpf(l_tot);  // (1 ulp; the result is rounded to 8 or 11 bits)
         short *ow = &lds_o[0][0] + wave * (32 * ATT_KS);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            att_s16x4 w0, w1;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                w0[e] = att_bits<TX>(o0[4 * g + e] * inv);
-                w1[e] = att_bits<TX>(o1[4 * g + e] * inv);
-            }
-            unsigned a2[2], b2[2];
-            __builtin_memcpy(a2, &w0, 8);
-            __builtin_memcpy(b2, &w1, 8);
-            // (tome_attn.h's exchange: the lower lanes end up with channels 8g .. 8g+7, the upper with 32+8g .. 32+8g+7)
-            const auto s0w = __builtin_amdgcn_permlane32_swap(a2[0], b2[0], false, false);
-            const auto s1w = __builtin_amdgcn_permlane32_swap(a2[1], b2[1], false, false);
-            *reinterpret_cast<uint4 *>(ow + col * ATT_KS + 32 * hf + 8 * g) = uint4{s0w[0], s1w[0], s0w[1], s1w[1]};
-        }
+        // (att_store_row's exchange: the lower lanes end up with channels 8g .. 8g+7, the upper with 32+8g .. 32+8g+7)
+        att_store_row<TX>(ow + col * ATT_KS + 32 * hf, true, o0, o1, inv);
         const int rows = nq - c_qb * ATT_BM - wave * 32;  // rows of this wave inside the sequence (>= 1: active)
         short *op = c_o + (wave * 32 + (lane >> 3)) * o_sn + 8 * (lane & 7);
 #pragma unroll
