@@ -1259,6 +1259,11 @@ def test_trajectory_mix_against_fp32_reference(B, S, F, H, dtype, tol):
         assert out.shape == (B, S, C) and out.dtype == dtype and attn.shape == (B, H, S, F)
         assert float((attn - want_attn).abs().max()) <= 1e-4
         assert float((out.float() - want).abs().max()) <= tol
+        # ... and, element by element, to the derived bound of small_attn_fwd_oracle.py (fp64 reference)
+        import small_attn_fwd_oracle as fo
+        import traj_mix_bwd_oracle as to
+        inp = to.Inputs(q2.cpu(), k2.cpu().contiguous(), val.cpu().contiguous(), torch.zeros(B, S, C, dtype=dtype), H, scale)
+        fo.check(f"parity {B}x{S}x{F}x{H} {dtype}", dict(out=out, tattn=attn), fo.reference(inp), dtype)
         # written straight behind a class row of a [B, 1+S, C] buffer (the patched Motionformer attention: no cat),
         # without the attention map: the same bits, the neighbouring row untouched
         joined = torch.full((B, 1 + S, C), 7.0, device=DEV, dtype=dtype)
@@ -1289,6 +1294,11 @@ def test_short_attention_against_fp32_reference(B, H, N, dtype, tol):
     # the result is rounded once to the 16-bit format (tol = one ulp, relative) on top of fp32 arithmetic
     excess = (out.float() - want).abs() - (tol * want.abs() + 1e-3)
     assert float(excess.max()) <= 0.0, float(excess.max())
+    # ... and, element by element, to the derived bound of small_attn_fwd_oracle.py (fp64 reference)
+    import short_attn_bwd_oracle as so
+    import small_attn_fwd_oracle as fo
+    inp = so.Inputs(q.cpu(), k.cpu(), v.cpu(), torch.zeros(B, N, H * 64, dtype=dtype), 0.125, None)
+    fo.check(f"parity {B}x{H}x{N} {dtype}", dict(out=out), fo.reference(inp), dtype)
     sdpa = torch.nn.functional.scaled_dot_product_attention(q, k, v, scale=0.125).transpose(1, 2).reshape(B, N, H * 64)
     excess = (out.float() - sdpa.float()).abs() - (3 * tol * want.abs() + 4e-3)  # (the framework rounds P to 16 bits)
     assert float(excess.max()) <= 0.0, float(excess.max())
