@@ -3,9 +3,9 @@
 // -ffp-contract=off -shared -fPIC (csrc/build.py).  No torch, no CUDA, no portability layer.
 //
 // One translation unit: tome_common.h (types), tome_match.h, tome_ln_rows.h (the row statistics the forward LayerNorm
-// kernels and k_ln_rows_bwd_amp share), tome_merge.h, tome_merge_ln_amp.h, tome_merge_bwd.h, tome_ln_bwd.h, tome_merge_ln_bwd.h,
-// tome_gelu_bwd.h, tome_token_mean.h, tome_short_attn_bwd.h, tome_traj_bwd.h and tome_partition.h (kernels), this file
-// (host).
+// kernels and k_ln_rows_bwd_amp share), tome_merge_slab.h (the row slab the merge family walks), tome_merge.h,
+// tome_merge_ln_amp.h, tome_ln_fwd.h, tome_merge_bwd.h, tome_ln_bwd.h, tome_merge_ln_bwd.h, tome_gelu.h, tome_gelu_bwd.h,
+// tome_token_mean.h, tome_short_attn_bwd.h, tome_traj_bwd.h and tome_partition.h (kernels), this file (host).
 //
 // Launch sequence of one matching (tome_match / tome_match_keys), kernels in tome_match.h:
 //   k_unit_rows[_heads]  keys -> fp32 unit vectors, even/odd split, MFMA-fragment order (HBM bound)
@@ -16,10 +16,11 @@
 // and of one merge (tome_merge_wavg[_regrouped] / tome_merge / tome_drop / tome_unmerge), tome_merge.h:
 //   k_merge_rows_fast    streaming waves (2-4 output rows each) + edge waves (rows that receive sources);
 //                        <LN>: residual add in front and LayerNorm behind fused in (tome_merge_wavg_ln)
+//   k_merge_rows / k_unmerge_rows   generic one-wave-per-row forms                        (HBM bound)
+// and of the residual add + LayerNorm (tome_ln_fwd.h):
 //   k_add_ln_rows        second residual + the next block's first LayerNorm (tome_add_layernorm; with fp32 weight /
 //                        bias, a 16-bit y and a 16-bit or fp32 residual stream: tome_add_layernorm_amp)
 //   k_add_ln_regroup     the same in the middle of TimeSformer's block, y written regrouped (tome_add_layernorm_regrouped)
-//   k_merge_rows / k_unmerge_rows   generic one-wave-per-row forms                        (HBM bound)
 // and of its backward (tome_merge_backward[_regrouped]), tome_merge_bwd.h:
 //   k_merge_rows_bwd     gx[t] = gy[row of t] / out_div * in_mul, streaming gather             (HBM bound)
 // and of the add + LayerNorm backward (tome_layernorm_backward), tome_ln_bwd.h:
@@ -73,11 +74,14 @@
 #include "tome_match.h"
 #include "tome_match_filter.h"
 #include "tome_ln_rows.h"
+#include "tome_merge_slab.h"
 #include "tome_merge.h"
 #include "tome_merge_ln_amp.h"
+#include "tome_ln_fwd.h"
 #include "tome_merge_bwd.h"
 #include "tome_ln_bwd.h"
 #include "tome_merge_ln_bwd.h"
+#include "tome_gelu.h"
 #include "tome_gelu_bwd.h"
 #include "tome_token_mean.h"
 #include "tome_partition.h"

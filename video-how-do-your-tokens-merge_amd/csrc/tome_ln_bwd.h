@@ -51,10 +51,10 @@ __global__ __launch_bounds__(256) void k_ln_rows_bwd(const TX *__restrict__ gy, 
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         const int q = it * WAVE + lane;
-        const int rr = (q >= cpr) + (q >= 2 * cpr) + (q >= 3 * cpr);
+        const int rr = slab_row(cpr, it, lane);
         const bool slot = q < R * cpr;
         rr_of[it] = slot ? rr : -1;
-        cc_of[it] = slot ? q - rr * cpr : 0;
+        cc_of[it] = slot ? slab_col(q, rr, cpr) : 0;
         wraw[it] = *(reinterpret_cast<const uint4 *>(weight) + cc_of[it]);
     }
     float aw[NIT][VEC], ab[NIT][VEC];
@@ -90,10 +90,10 @@ __global__ __launch_bounds__(256) void k_ln_rows_bwd(const TX *__restrict__ gy, 
             const unsigned gb = (unsigned)my_g / (unsigned)group_rows;
             my_g = ((unsigned)my_g - gb * (unsigned)group_rows == 0u) ? -1 : my_g - (int)gb - 1;
         }
-        const int g0 = __builtin_amdgcn_readlane(my_g, 0), g1 = __builtin_amdgcn_readlane(my_g, 1),
-                  g2 = __builtin_amdgcn_readlane(my_g, 2), g3 = __builtin_amdgcn_readlane(my_g, 3);
+        int g0, g1, g2, g3;
+        lanes4(my_g, g0, g1, g2, g3);
         int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-        if (REGROUP) {
+        if (REGROUP) {  // (written out: through lanes4 the REGROUP form takes 134 vector registers for 132)
             c0 = __builtin_amdgcn_readlane(my_c, 0), c1 = __builtin_amdgcn_readlane(my_c, 1);
             c2 = __builtin_amdgcn_readlane(my_c, 2), c3 = __builtin_amdgcn_readlane(my_c, 3);
         }
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(256) void k_ln_rows_bwd(const TX *__restrict__ gy, 
             const int q = it * WAVE + lane;
             const bool live = q < total;
             const int rr = rr_of[it];
-            const int g = rr == 0 ? g0 : (rr == 1 ? g1 : (rr == 2 ? g2 : g3));
+            const int g = SEL4(rr, g0, g1, g2, g3);
             // unconditional loads: a lane without a chunk re-reads the slab's first chunk, a class row the start of
             // some row of gy, and ignores it
             int gr = (live && g >= 0) ? g : 0;
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256) void k_ln_rows_bwd(const TX *__restrict__ gy, 
                 __builtin_memcpy(&pg, &graw[it], 16);
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) gyf[it][e] = to_f32(pg.e[e]);
-                const int c = rr == 0 ? c0 : (rr == 1 ? c1 : (rr == 2 ? c2 : c3));
+                const int c = SEL4(rr, c0, c1, c2, c3);
                 if (live && c) {  // class row: frames 1 .. F-1 added in frame order, fp32, nothing rounded
                     const uint4 *gsrc = reinterpret_cast<const uint4 *>(gy) + (int64_t)gr * cpr + cc_of[it];
                     for (int t = 1; t < F; ++t) {
@@ -318,7 +318,7 @@ __global__ __launch_bounds__(LN_PG_RUNS * WAVE) void k_ln_param_grad(const float
 // (tome_layernorm_backward_amp; tools/train_net.py:123, tome/utils.py:54): the backward of k_add_ln_rows with fp32 parameters.
 // TG: gy, the 16-bit autocast dtype; TS: the residual stream (xs, gx_in, gx), 16-bit or fp32; weight fp32; the partial
 // rows of dweight / dbias fp32 as before, summed by k_ln_param_grad<float> into fp32 parameters.  Formula, reduction
-// rounds, packing (slots of 8 channels, tome_merge.h), slab walk and the order of every sum are those of k_ln_rows_bwd;
+// rounds, packing (slots of 8 channels, tome_ln_rows.h), slab walk and the order of every sum are those of k_ln_rows_bwd;
 // mean and rstd are recomputed from the stored row as in k_ln_rows_bwd.  gx is rounded once to TS (not
 // at all for an fp32 stream).  gx16 (fp32 stream, optional): round16(gx) from the same registers, the gradient of a
 // 16-bit addend without a cast pass; a class row's is round16(gx_in).
@@ -341,10 +341,10 @@ __global__ __launch_bounds__(256, 2) void k_ln_rows_bwd_amp(const TG *__restrict
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         const int q = it * WAVE + lane;
-        const int rr = (q >= cpr) + (q >= 2 * cpr) + (q >= 3 * cpr);
+        const int rr = slab_row(cpr, it, lane);
         const bool slot = q < R * cpr;
         rr_of[it] = slot ? rr : -1;
-        cc_of[it] = slot ? q - rr * cpr : 0;
+        cc_of[it] = slot ? slab_col(q, rr, cpr) : 0;
         slot_f32<float>(ld_param_slot<float>(weight, cc_of[it]), wgt[it]);
     }
     float aw[NIT][VEC], ab[NIT][VEC];
@@ -369,8 +369,8 @@ __global__ __launch_bounds__(256, 2) void k_ln_rows_bwd_amp(const TG *__restrict
             const unsigned gb = (unsigned)my_g / (unsigned)group_rows;
             my_g = ((unsigned)my_g - gb * (unsigned)group_rows == 0u) ? -1 : my_g - (int)gb - 1;
         }
-        const int g0 = __builtin_amdgcn_readlane(my_g, 0), g1 = __builtin_amdgcn_readlane(my_g, 1),
-                  g2 = __builtin_amdgcn_readlane(my_g, 2), g3 = __builtin_amdgcn_readlane(my_g, 3);
+        int g0, g1, g2, g3;
+        lanes4(my_g, g0, g1, g2, g3);
 
         const TS *xsl = xs + (int64_t)row0 * C;
         const TS *gil = (has_in ? gx_in : xs) + (int64_t)row0 * C;
@@ -382,7 +382,7 @@ __global__ __launch_bounds__(256, 2) void k_ln_rows_bwd_amp(const TG *__restrict
             const int q = it * WAVE + lane;
             const bool live = q < total;
             const int rr = rr_of[it];
-            const int g = rr == 0 ? g0 : (rr == 1 ? g1 : (rr == 2 ? g2 : g3));
+            const int g = SEL4(rr, g0, g1, g2, g3);
             // unconditional loads: a lane without a slot re-reads the slab's first slot, a class row the start of
             // some row of gy, and ignores it
             int gr = (live && g >= 0) ? g : 0;

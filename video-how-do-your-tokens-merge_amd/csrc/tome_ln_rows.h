@@ -1,6 +1,6 @@
 // tome_ln_rows.h -- part of the single translation unit csrc/tome_kernels.hip: the row statistics of every kernel that
 // normalises "up to four rows per wave, NIT slots per lane" -- the LayerNorm tails of k_merge_rows_fast<LN>,
-// k_add_ln_rows (16-bit and autocast forms), k_add_ln_regroup, k_merge_rows_ln_amp (tome_merge.h, tome_merge_ln_amp.h) and
+// k_add_ln_rows (16-bit and autocast forms), k_add_ln_regroup, k_merge_rows_ln_amp (tome_merge.h, tome_ln_fwd.h, tome_merge_ln_amp.h) and
 // the statistics k_ln_rows_bwd_amp recomputes (tome_ln_bwd.h).  No forward kernel saves mean or rstd: that backward
 // kernel reproduces the forward's bits because it calls the forward's own functions (ln_row_means, slot_centre,
 // ln_rstd), not a copy of them.  The 16-bit backward kernels (k_ln_rows_bwd, k_merge_ln_rows_bwd) keep a copy of the

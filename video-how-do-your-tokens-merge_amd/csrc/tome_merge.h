@@ -15,41 +15,6 @@ template <int OP> __device__ __forceinline__ float reduce_step(float acc, float 
     return acc;
 }
 
-// Where the token rows of group g live.  Contiguous [n,T,C] is {0, T*C, 0, C, 1}; the regrouped views of
-// TimeSformer / Motionformer ('b (p t) m -> (b t) p m', timesformer.py:89-90; 'b (s f) d -> (b f) s d',
-// motionformer.py:150-151) are {cls*C, (cls+P*F)*C, C, F*C, F}: no permuted copy of x is ever made.
-struct TokLayout {
-    int64_t base, outer_stride, inner_stride, tok_stride;  // elements
-    int inner;                                             // groups per outer index
-};
-
-template <typename TX> __device__ __forceinline__ TX *group_ptr(TX *p, const TokLayout &L, int g) {
-    if (L.inner == 1) return p + L.base + (int64_t)g * L.outer_stride;  // (no integer division on the plain layout)
-    return p + L.base + (int64_t)(g / L.inner) * L.outer_stride + (int64_t)(g % L.inner) * L.inner_stride;
-}
-
-// Optional LayerNorm fused behind the merge (the block's norm2 -- tome/patch/videomae.py:27 `self.norm2(x)`,
-// vivit.py:41 `layernorm_after`): y = (x' - mean) * rstd * weight + bias over the channels of every merged
-// row, fp32 statistics (two passes over the registers: mean, then centred variance), written next to x'.
-struct LnArgs {
-    const void *weight, *bias;  // [C] of the token dtype
-    void *y;                    // [n, T-r, C] of the token dtype, same row layout as x_out
-    float eps;
-    const void *addend;         // optional [n, T, C]: the tokens that are merged are round(x + addend), i.e. the
-                                // block's residual `x = x + attn(...)` (videomae.py:20,25) is taken on the fly
-    // The addend may live in a layout of its own (a_own): TimeSformer's second residual is the spatial attention's
-    // output [(b t), 1 + p, m] (timesformer.py:40-52), read where it lies instead of being permuted to 'b (p t) m'
-    // first; the class rows' addend (the class token averaged over the frames, timesformer.py:42-44) is then a
-    // separate [B, C] tensor.
-    int a_own;
-    TokLayout la;
-    const void *cls_addend;
-    // optional [C]: the rows of x_out are stored as round(x' + xbias) while y stays LayerNorm(x').  The caller's next
-    // GEMM accumulates onto x_out in place (`x = x + fc2(...)`, tome/patch/videomae.py:29, as beta = 1 on the residual
-    // buffer), so its bias has to be in the buffer beforehand and the separate residual add disappears.
-    const void *xbias;
-};
-
 // round(v + xbias[c..]) for a 16-byte pack of stored tokens
 template <typename TX, int VEC>
 __device__ __forceinline__ uint4 add_xbias(const uint4 &v, const TX *__restrict__ xb) {
@@ -71,16 +36,6 @@ __device__ __forceinline__ Pack<TX, VEC> add_packs(const Pack<TX, VEC> &x, const
 #pragma unroll
     for (int e = 0; e < VEC; ++e) o.e[e] = from_f32<TX>(__fadd_rn(to_f32(x.e[e]), to_f32(a.e[e])));
     return o;
-}
-
-// size' of one output row, and -- for the proportional-attention bias of the next block
-// (`size.log()`, tome/patch/videomae.py:62-63, timesformer.py:73-74, motionformer.py:107-111, vivit.py:103-104)
-// -- log of the STORED size, fp32 logf rounded to the size dtype: what torch's `size.log()` gives on this device.
-template <typename TS>
-__device__ __forceinline__ void store_size(TS *__restrict__ srow, TS *__restrict__ lrow, float s) {
-    const TS st = from_f32<TS>(s);
-    *srow = st;
-    if (lrow) *lrow = from_f32<TS>(logf(to_f32(st)));
 }
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -302,6 +257,7 @@ __device__ __forceinline__ void merge_dst_row_r64(const TX *__restrict__ xg, con
         }
         if (rest == 0ull) break;
         // a destination with more than NB sources (rare): the next NB, one more round trip
+        // (the block above a second time, on purpose: as one lambda k_merge_rows_fast<wavg, LN> compiles to other code)
 #pragma unroll
         for (int u = 0; u < NB; ++u) {
             have[u] = rest != 0ull;
@@ -542,17 +498,6 @@ __device__ __forceinline__ void merge_dst_row(const TX *__restrict__ xg, const T
     if (OP == OP_WAVG && lane == 0) store_size<TS>(srow, lrow, ssum);
 }
 
-// inverse of the output layout (merge.py:82-85): output row o -> (is it a B/dst row?, index in its set)
-__device__ __forceinline__ void decode_out_row(int o, int U, int distill, bool &is_dst, int &idx) {
-    if (!distill) {
-        is_dst = o >= U;
-        idx = is_dst ? o - U : o;
-    } else if (o == 0) { is_dst = false; idx = 0; }
-    else if (o == 1) { is_dst = true; idx = 0; }
-    else if (o <= U) { is_dst = false; idx = o - 1; }
-    else { is_dst = true; idx = o - U; }
-}
-
 // Generic form: one wave per output row, any C / alignment / r.  (The hot shapes go through
 // k_merge_rows_fast below; this one serves odd channel counts such as the size column or source matrices.)
 template <typename TX, typename TS, int VEC, int OP>
@@ -606,14 +551,10 @@ __global__ __launch_bounds__(256) void k_merge_rows(const TX *__restrict__ x, co
 // at most 384 chunks per R rows).  A wave owns R consecutive OUTPUT rows of one group, flattens their
 // R*cpr 16-byte chunks over its lanes (6 chunks per lane, every lane busy, stores contiguous across the
 // R rows) and issues all of its loads before touching any of them, so ~6 KiB per wave are in flight.
-// Rows that nothing merges into are moved as raw bits when their size is 1 ((x*1)/1 == x bit for bit)
-// or scaled in fp32 otherwise; the few rows that receive sources are finished by merge_dst_row.
-// How the loads stay together (checked in the ISA, tools/kernel_usage.py --keep): they are UNCONDITIONAL -- a lane
-// without a chunk re-reads the start of the wave's first row -- because hipcc sinks the first use of a conditionally
-// loaded value into the `if`, with an s_waitcnt vmcnt(0) behind every load; the size is read unconditionally for the
-// same reason; which rows receive sources is decided after the row loads are out.  Launch geometry: grid.x = the
-// blocks of one group (streaming waves, then r edge waves), grid.(y, z) = the group, class-token rows behind the
-// groups -- no wave starts with an integer division.
+// The slab walk -- per-row facts, slot map, edge rows, the rows that move as raw bits -- and what keeps its loads
+// together is tome_merge_slab.h; the few rows that receive sources are finished by merge_dst_row.  Launch geometry:
+// grid.x = the blocks of one group (streaming waves, then r edge waves), grid.(y, z) = the group, class-token rows
+// behind the groups -- no wave starts with an integer division.
 // ------------------------------------------------------------------------------------------------
 #define FAST_NIT 6
 #define FAST_MAXR 4
@@ -750,18 +691,16 @@ __global__ __launch_bounds__(256) void k_merge_rows_fast(const TX *__restrict__ 
         const int k = lw - rg_per_group;
         if (OP == OP_DROP || k >= r) return;
         const int64_t *dstg = dst_idx + (int64_t)g * r;
+        int64_t astride;
+        const TX *agp = ln_addend_rows<TX>(ln, lin, g, astride);  // (no LayerNorm: no addend, x's stride)
         if (r <= WAVE && cpr <= 2 * WAVE) {
             // the whole index list in one lane each: two memory round trips instead of five (merge_dst_row_r64)
             const int T1e = (T_ + 1) >> 1;
-            const bool add = LN && ln.addend;
             merge_dst_row_r64<TX, TS, VEC, OP, LN>(
                 group_ptr(x, lin, g), size ? size + (int64_t)g * T_ : nullptr, C, lin.tok_stride, r, g, k,
                 src_idx + (int64_t)g * r, dstg, keep, group_ptr(xout, lout, g), lout.tok_stride,
                 sout ? sout + (int64_t)g * To : nullptr, lsout ? lsout + (int64_t)g * To : nullptr, T1e - r, distill, lane,
-                &ln, LN ? group_ptr(reinterpret_cast<TX *>(ln.y), lout, g) : nullptr,
-                add ? (ln.a_own ? group_ptr(reinterpret_cast<const TX *>(ln.addend), ln.la, g)
-                                : group_ptr(reinterpret_cast<const TX *>(ln.addend), lin, g)) : nullptr,
-                ln.a_own ? ln.la.tok_stride : lin.tok_stride);
+                &ln, LN ? group_ptr(reinterpret_cast<TX *>(ln.y), lout, g) : nullptr, agp, astride);
             return;
         }
         const int j = (int)dstg[k];
@@ -778,9 +717,7 @@ __global__ __launch_bounds__(256) void k_merge_rows_fast(const TX *__restrict__ 
             src_idx + (int64_t)g * r, dstg, keep, group_ptr(xout, lout, g) + (int64_t)o * lout.tok_stride,
             sout ? sout + (int64_t)g * To + o : nullptr, lane, &ln,
             LN ? group_ptr(reinterpret_cast<TX *>(ln.y), lout, g) + (int64_t)o * lout.tok_stride : nullptr,
-            (LN && ln.addend) ? (ln.a_own ? group_ptr(reinterpret_cast<const TX *>(ln.addend), ln.la, g)
-                                          : group_ptr(reinterpret_cast<const TX *>(ln.addend), lin, g)) : nullptr,
-            lsout ? lsout + (int64_t)g * To + o : nullptr, ln.a_own ? ln.la.tok_stride : lin.tok_stride);
+            agp, lsout ? lsout + (int64_t)g * To + o : nullptr, astride);
         return;
     }
     const int o0 = lw * R;
@@ -790,102 +727,55 @@ __global__ __launch_bounds__(256) void k_merge_rows_fast(const TX *__restrict__ 
     const TS *sg = size ? size + (int64_t)g * T_ : nullptr;
     const int64_t *dstg = dst_idx ? dst_idx + (int64_t)g * r : nullptr;
 
-    // per-row facts, computed by lanes 0..R-1 in parallel and broadcast as wave-uniform scalars: source
-    // token, B-row number, "something merges into it", size.  Load order matters for latency: the first block
-    // of dst_idx and the unm_idx entries go out together; the sizes are requested as soon as the tokens are
-    // known but only READ after the token rows' own loads have been issued, so a wave waits for two memory
-    // round trips (index -> rows), not three.  (Several R-row slabs per wave behind ONE index round trip were
-    // measured in round 2: no gain for this kernel, a loss for the plain merge -- the kernel is bound by its vector
-    // instructions, not by latency.)
+    // per-row facts (fwd_slab, tome_merge_slab.h): the first block of dst_idx goes out together with its unm_idx reads.
+    // (Several R-row slabs per wave behind ONE index round trip were measured in round 2: no gain for this kernel, a
+    // loss for the plain merge -- the kernel is bound by its vector instructions, not by latency.)
     const int d_first = (OP != OP_DROP && lane < r) ? (int)dstg[lane] : -2;
-    // (branch-free: every lane computes, lanes that own no row read a harmless entry -- no divergent control flow
-    // and no wait between the index loads and the row loads)
-    float my_s = 1.0f;
-    const bool my_valid = lane < R && (o0 + lane) < To;
-    bool is_dst;
-    int idx;
-    decode_out_row(my_valid ? o0 + lane : 0, U, distill, is_dst, idx);
-    int my_tok = 2 * idx + 1, my_j = idx;
-    // a wave whose rows are all destination (odd) tokens knows its tokens without reading an index: its row loads
-    // depend on no earlier load at all
-    const bool all_dst = (!distill && o0 >= U) || o0 > U;
-    if (U > 0 && !all_dst) {  // (wave-uniform; unm_idx may be absent when every even token is merged away)
-        const int ut = 2 * (int)unm_idx[(int64_t)g * U + ((my_valid && !is_dst) ? idx : 0)];
-        my_tok = is_dst ? my_tok : ut;
-        my_j = is_dst ? my_j : -1;
-    }
-    my_tok = my_valid ? my_tok : 0;
-    my_j = my_valid ? my_j : -1;
-    // (the size is read unconditionally -- from the tokens themselves when there are no sizes -- so that no branch
-    // invites the compiler to wait for it before the row loads have been issued)
     const bool load_size = (OP == OP_WAVG) && sg;  // wave-uniform
-    const TS my_s_raw = (load_size ? sg : reinterpret_cast<const TS *>(xg))[my_tok];
-    const unsigned long long vmask = __ballot(my_valid);
-    const int tok0 = __builtin_amdgcn_readlane(my_tok, 0), tok1 = __builtin_amdgcn_readlane(my_tok, 1),
-              tok2 = __builtin_amdgcn_readlane(my_tok, 2), tok3 = __builtin_amdgcn_readlane(my_tok, 3);
-    const int j0 = __builtin_amdgcn_readlane(my_j, 0), j1 = __builtin_amdgcn_readlane(my_j, 1),
-              j2 = __builtin_amdgcn_readlane(my_j, 2), j3 = __builtin_amdgcn_readlane(my_j, 3);
-    // rows that exist; which of them receive sources (and are left to the edge waves) is decided AFTER the row loads
-    // have been issued -- a row that turns out to be one is read for nothing (r of T rows), but no row load waits for
-    // dst_idx
-    bool va0 = vmask & 1ull, va1 = vmask & 2ull, va2 = vmask & 4ull, va3 = vmask & 8ull;
+    const FwdSlab<TS> f = fwd_slab<TS>(load_size ? sg : reinterpret_cast<const TS *>(xg), unm_idx, g, o0, R, To, U,
+                                       distill, lane);
+    const int tok0 = f.tok0, tok1 = f.tok1, tok2 = f.tok2, tok3 = f.tok3;
+    bool va0 = f.vmask & 1ull, va1 = f.vmask & 2ull, va2 = f.vmask & 4ull, va3 = f.vmask & 8ull;  // rows that exist
     if (EAGER && OP != OP_DROP) {  // (r <= 64: the host's condition -- every dst_idx entry of the group is in d_first)
-        va0 = va0 && (__ballot(d_first == j0) == 0ull);
-        va1 = va1 && (__ballot(d_first == j1) == 0ull);
-        va2 = va2 && (__ballot(d_first == j2) == 0ull);
-        va3 = va3 && (__ballot(d_first == j3) == 0ull);
+        va0 = va0 && (__ballot(d_first == f.j0) == 0ull);
+        va1 = va1 && (__ballot(d_first == f.j1) == 0ull);
+        va2 = va2 && (__ballot(d_first == f.j2) == 0ull);
+        va3 = va3 && (__ballot(d_first == f.j3) == 0ull);
     }
 
-    // flattened chunk loop: chunk q of the R-row slab -> (row q / cpr, 16-byte column q % cpr)
+    // flattened chunk loop (slab_row / slab_col): every chunk of the slab requested
     const int total = R * cpr;
     uint4 raw[NIT];
     int rowof[NIT];
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         const int q = it * WAVE + lane;
-        const int rr = (q >= cpr) + (q >= 2 * cpr) + (q >= 3 * cpr);
-        const int cc = q - rr * cpr;
-        const int t = rr == 0 ? tok0 : (rr == 1 ? tok1 : (rr == 2 ? tok2 : tok3));
-        const bool ok = (rr == 0 ? va0 : (rr == 1 ? va1 : (rr == 2 ? va2 : va3))) && (q < total);
+        const int rr = slab_row(cpr, it, lane), cc = slab_col(q, rr, cpr), t = SEL4(rr, tok0, tok1, tok2, tok3);
+        const bool ok = SEL4(rr, va0, va1, va2, va3) && (q < total);
         rowof[it] = ok ? rr : -1;
-        // unconditional: a lane without a chunk re-reads the start of the wave's first row (always a real token) and
-        // ignores it -- no control flow around the loads, so all of them are in flight together
+        // unconditional: a lane without a chunk re-reads the start of the wave's first row (always a real token)
         raw[it] = ld16(reinterpret_cast<const char *>(xg + (int64_t)(ok ? t : tok0) * lin.tok_stride) + (ok ? cc : 0) * 16);
     }
     uint4 rawa[NIT];
     if (LN && ln.addend) {  // fused residual: the rows that are merged are round(x + addend)
-        const TX *agp = ln.a_own ? group_ptr(reinterpret_cast<const TX *>(ln.addend), ln.la, g)
-                                 : group_ptr(reinterpret_cast<const TX *>(ln.addend), lin, g);
-        const int64_t astride = ln.a_own ? ln.la.tok_stride : lin.tok_stride;
+        int64_t astride;
+        const TX *agp = ln_addend_rows<TX>(ln, lin, g, astride);
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             const int rr = rowof[it];
-            const int q = it * WAVE + lane;
-            const int cc = rr < 0 ? 0 : q - rr * cpr;
-            const int t = rr <= 0 ? tok0 : (rr == 1 ? tok1 : (rr == 2 ? tok2 : tok3));
+            const int cc = rr < 0 ? 0 : it * WAVE + lane - rr * cpr;
+            const int t = SEL4(rr < 0 ? 0 : rr, tok0, tok1, tok2, tok3);
             rawa[it] = ld16(reinterpret_cast<const char *>(agp + (int64_t)t * astride) + cc * 16);
         }
     }
-    bool e0 = false, e1 = false, e2 = false, e3 = false;  // rows that receive sources
-    if (OP != OP_DROP) {
-        e0 = __ballot(d_first == j0) != 0ull;
-        e1 = __ballot(d_first == j1) != 0ull;
-        e2 = __ballot(d_first == j2) != 0ull;
-        e3 = __ballot(d_first == j3) != 0ull;
-        for (int base = WAVE; base < r; base += WAVE) {
-            const int k = base + lane;
-            const int d = (k < r) ? (int)dstg[k] : -2;
-            e0 = e0 || (__ballot(d == j0) != 0ull);
-            e1 = e1 || (__ballot(d == j1) != 0ull);
-            e2 = e2 || (__ballot(d == j2) != 0ull);
-            e3 = e3 || (__ballot(d == j3) != 0ull);
-        }
-    }
+    SlabEdges e{false, false, false, false};  // rows that receive sources
+    if (OP != OP_DROP) e = slab_edge_rows(d_first, f.j0, f.j1, f.j2, f.j3, dstg, r, lane);
+    const bool e0 = e.e0, e1 = e.e1, e2 = e.e2, e3 = e.e3;
     const bool ok0 = va0 && !e0, ok1 = va1 && !e1, ok2 = va2 && !e2, ok3 = va3 && !e3;
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         const int rr = rowof[it];
-        const bool ok = rr >= 0 && (rr == 0 ? ok0 : (rr == 1 ? ok1 : (rr == 2 ? ok2 : ok3)));
+        const bool ok = rr >= 0 && SEL4(rr, ok0, ok1, ok2, ok3);
         rowof[it] = ok ? rr : -1;
     }
     if (LN && ln.addend) {
@@ -908,32 +798,17 @@ __global__ __launch_bounds__(256) void k_merge_rows_fast(const TX *__restrict__ 
             xbraw[it] = *(reinterpret_cast<const uint4 *>(ln.xbias) + (rr < 0 ? 0 : it * WAVE + lane - rr * cpr));
         }
     }
-    my_s = (load_size && my_valid) ? to_f32(my_s_raw) : 1.0f;
-    const float sz0 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_s), 0)),
-                sz1 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_s), 1)),
-                sz2 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_s), 2)),
-                sz3 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_s), 3));
-    // (x*s)/s is x itself when s is 1, and also when s is a power of two and x came from a 16-bit
-    // format (the fp32 product cannot overflow): those rows move as raw bits
-    constexpr bool narrow = sizeof(TX) == 2;
+    const float my_s = (load_size && f.my_valid) ? to_f32(f.my_s_raw) : 1.0f;
+    float sz0, sz1, sz2, sz3;
+    lanes4(my_s, sz0, sz1, sz2, sz3);
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         const int rr = rowof[it];
         if (rr < 0) continue;
         const int q = it * WAVE + lane;
-        const float s = rr == 0 ? sz0 : (rr == 1 ? sz1 : (rr == 2 ? sz2 : sz3));
+        const float s = SEL4(rr, sz0, sz1, sz2, sz3);
         uint4 outv = raw[it];
-        if (OP == OP_WAVG) {
-            const uint32_t sb = __float_as_uint(s);
-            const bool exact = (s == 1.0f) || (narrow && (sb & 0x007FFFFFu) == 0u && s >= 1.0f && s <= 65536.0f);
-            if (!exact) {
-                Pack<TX, VEC> pk;
-                __builtin_memcpy(&pk, &raw[it], 16);
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) pk.e[e] = from_f32<TX>(__fdiv_rn(__fmul_rn(to_f32(pk.e[e]), s), s));
-                __builtin_memcpy(&outv, &pk, 16);
-            }
-        }
+        if (OP == OP_WAVG && !wavg_moves_raw<TX>(s)) outv = wavg_rescaled<TX>(raw[it], s);
         const int cc = q - rr * cpr;
         char *xdst = reinterpret_cast<char *>(og + (int64_t)(o0 + rr) * lout.tok_stride) + cc * 16;
         if (LN && ln.xbias)
@@ -956,72 +831,8 @@ __global__ __launch_bounds__(256) void k_merge_rows_fast(const TX *__restrict__ 
                                      st_slot<TX>(yg + (int64_t)(o0 + rr) * ystride, cc, yv);
                                  });
     }
-    if (OP == OP_WAVG && lane < R && my_valid) {
-        const bool mine_has_edges = lane == 0 ? e0 : (lane == 1 ? e1 : (lane == 2 ? e2 : e3));
-        if (!mine_has_edges)
-            store_size<TS>(sout + (int64_t)g * To + o0 + lane, lsout ? lsout + (int64_t)g * To + o0 + lane : nullptr, my_s);
-    }
-}
-
-// k_add_ln_rows: the other residual of the patched block, fused with the LayerNorm that reads its result:
-//     x = x + mlp(norm2(x))            (tome/patch/videomae.py:29, end of ToMeBlock.forward)
-//     ... next block: self.norm1(x)    (tome/patch/videomae.py:19)
-// x' = x + a and y = LayerNorm(x') in one pass (ln_rows, tome_ln_rows.h).  A wave owns R consecutive rows, NIT slots per
-// lane, everything loaded before use.  TS: the residual stream (x, x'); TA: the addend; TY: y; TP: weight and bias.
-//   tome_add_layernorm[_skip_first]: everything of one 16-bit dtype; x' = round16(x + a)
-//   tome_add_layernorm_amp (a model under autocast, fp32 master weights): TP fp32, TY the 16-bit autocast dtype,
-//     16-bit stream: x' = round16(x + a), the same bits;  fp32 stream: x' = x + (float)a -- `x + a.float()` bit for bit
-// The statistics are taken from the STORED row; y is rounded once to TY.
-// a == nullptr: LayerNorm only (x is the finished sum -- the caller's GEMM accumulated onto it), nothing is written to
-// xout.
-// y_group > 0: rows come in groups of y_group whose FIRST row (a class token) has no place in y -- y holds the other
-// y_group - 1 rows of every group, compacted (TimeSformer's temporal_norm1 feeds only the patch tokens,
-// tome/patch/timesformer.py:24-26, so `xn[:, 1:]` regrouped '(b p) t m' is a view instead of a copy)
-template <typename TS, typename TA, typename TY, typename TP, int NIT>
-__global__ __launch_bounds__(256) void k_add_ln_rows(const TS *__restrict__ x, const TA *__restrict__ a, int64_t rows,
-                                                     int C, int R, int cpr, const TP *__restrict__ lw,
-                                                     const TP *__restrict__ lb, float eps, int y_group,
-                                                     TS *__restrict__ xout, TY *__restrict__ y) {
-    const int lane = threadIdx.x & 63;
-    const int64_t w = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t row0 = w * R;
-    if (row0 >= rows) return;
-    const int nrow = (int)((rows - row0) < R ? (rows - row0) : R);
-    const int total = nrow * cpr;
-    const bool add = a != nullptr;
-    const TS *xs = x + row0 * C;
-    const TA *as = a + row0 * C;
-    Slot<TS> raw[NIT] = {};
-    Slot<TA> rawa[NIT] = {};
-    int rowof[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int q = it * WAVE + lane;
-        rowof[it] = q < total ? (q >= cpr) + (q >= 2 * cpr) + (q >= 3 * cpr) : -1;
-        if (q < total) {
-            raw[it] = ld_slot<TS>(xs, q);
-            if (add) rawa[it] = ld_slot<TA>(as, q);
-        }
-    }
-    const LnParams<TP, NIT> prm = ln_params<TP, NIT>(lw, lb, rowof, cpr, lane);
-    if (add) {
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            if (rowof[it] < 0) continue;
-            raw[it] = slot_add<TS, TA>(raw[it], rawa[it]);
-            st_slot<TS>(xout + row0 * C, it * WAVE + lane, raw[it]);
-        }
-    }
-    ln_rows<TS, TP, TY, NIT>(raw, rowof, nrow, cpr, C, eps, prm, lane,
-                             [&](int rr, int cc, const Slot<TY> &yv) __attribute__((always_inline)) {
-                                 int64_t yrow = row0 + rr;
-                                 if (y_group > 0) {
-                                     const int64_t gb = yrow / y_group;
-                                     if (yrow - gb * y_group == 0) return;
-                                     yrow -= gb + 1;
-                                 }
-                                 st_slot<TY>(y + yrow * C, cc, yv);
-                             });
+    if (OP == OP_WAVG && lane < R && f.my_valid)
+        slab_store_size<TS>(SEL4(lane, e0, e1, e2, e3), sout, lsout, (int64_t)g * To + o0 + lane, my_s);
 }
 
 // k_unmerge_rows: merge.py:87-100 as a scatter from the merged sequence: one wave per INPUT row; a
@@ -1115,125 +926,4 @@ __global__ __launch_bounds__(256) void k_source_init(int n, int T_, int r, int d
         }
         orow[t] = (live && rt == o) ? 1.0f : 0.0f;
     }
-}
-
-// k_add_ln_regroup: the middle of TimeSformer's divided space-time block (tome/patch/timesformer.py:24-38):
-//     xt = x[:, 1:] + temporal_fc(res_temporal)                       residual of the temporal attention
-//     xs = cat(cls replicated per frame, 'b (p t) m -> (b t) p m' of xt) spatial regrouping
-//     ... self.norm1(xs)
-// One pass: x1 = cat(cls, xt) in the token layout [B, 1 + P*F, C], and y = norm1 of every row written straight to
-// its place in the regrouped [B*F, 1 + P, C] tensor (a LayerNorm is per row, so normalising before the permutation
-// is the same thing); the class row is normalised once and stored F times.  Replaces an add, a strided copy and a
-// LayerNorm (7 passes over the tokens) by 2 reads + 2 writes.  Same arithmetic as k_add_ln_rows.
-template <typename TX, int NIT>
-__global__ __launch_bounds__(256) void k_add_ln_regroup(const TX *__restrict__ x, const TX *__restrict__ a, int B, int F,
-                                                        int P, int C, int R, int cpr, LnArgs ln,
-                                                        TX *__restrict__ xout) {
-    const int lane = threadIdx.x & 63;
-    const int64_t w = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int N = 1 + P * F;
-    const int64_t rows = (int64_t)B * N;
-    const int64_t row0 = w * R;
-    if (row0 >= rows) return;
-    const int nrow = (int)((rows - row0) < R ? (rows - row0) : R);
-    const int total = nrow * cpr;
-    // per-row facts (wave-uniform): addend row (-1: class token, nothing is added) and the row of y
-    int64_t arow[FAST_MAXR], yrow[FAST_MAXR];
-#pragma unroll
-    for (int rr = 0; rr < FAST_MAXR; ++rr) {
-        const int64_t gr = row0 + (rr < nrow ? rr : 0);
-        const int64_t b = gr / N;
-        const int k = (int)(gr - b * N);
-        if (k == 0) {
-            arow[rr] = -1;
-            yrow[rr] = b * F * (1 + P);  // frame 0; frames 1..F-1 follow at (1+P) rows each
-        } else {
-            const int p = (k - 1) / F, t = (k - 1) - p * F;
-            arow[rr] = b * (int64_t)(P * F) + (k - 1);
-            yrow[rr] = (b * F + t) * (int64_t)(1 + P) + 1 + p;
-        }
-    }
-    const TX *xs = x + row0 * C;
-    Slot<TX> raw[NIT], rawa[NIT];
-    int rowof[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int q = it * WAVE + lane;
-        const int rr = (q >= cpr) + (q >= 2 * cpr) + (q >= 3 * cpr);
-        rowof[it] = q < total ? rr : -1;
-        if (q >= total) continue;
-        raw[it] = ld_slot<TX>(xs, q);
-        const int64_t ar = rr == 0 ? arow[0] : (rr == 1 ? arow[1] : (rr == 2 ? arow[2] : arow[3]));
-        if (ar >= 0) rawa[it] = ld_slot<TX>(a + ar * C, q - rr * cpr);
-    }
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int rr = rowof[it];
-        if (rr < 0) continue;
-        const int64_t ar = rr == 0 ? arow[0] : (rr == 1 ? arow[1] : (rr == 2 ? arow[2] : arow[3]));
-        if (ar >= 0) raw[it] = slot_add<TX, TX>(raw[it], rawa[it]);
-        st_slot<TX>(xout + row0 * C, it * WAVE + lane, raw[it]);
-    }
-    TX *yb = reinterpret_cast<TX *>(ln.y);
-    const LnParams<TX, NIT> prm = ln_params<TX, NIT>(reinterpret_cast<const TX *>(ln.weight),
-                                                     reinterpret_cast<const TX *>(ln.bias), rowof, cpr, lane);
-    ln_rows<TX, TX, TX, NIT>(raw, rowof, nrow, cpr, C, ln.eps, prm, lane,
-                             [&](int rr, int cc, const Slot<TX> &yv) __attribute__((always_inline)) {
-                                 const int64_t ar = rr == 0 ? arow[0] : (rr == 1 ? arow[1] : (rr == 2 ? arow[2] : arow[3]));
-                                 const int64_t yr = rr == 0 ? yrow[0] : (rr == 1 ? yrow[1] : (rr == 2 ? yrow[2] : yrow[3]));
-                                 TX *yp = yb + yr * C;
-                                 st_slot<TX>(yp, cc, yv);
-                                 if (ar < 0)  // class token: the same normalised row in front of every frame's tokens
-                                     for (int t = 1; t < F; ++t) st_slot<TX>(yp + (int64_t)t * (1 + P) * C, cc, yv);
-                             });
-}
-
-// k_gelu_erf: the activation between the two GEMMs of the MLP the patched block calls (`self.mlp(self.norm2(x))`,
-// tome/patch/videomae.py:29; nn.GELU() = exact erf form in VideoMAE / TimeSformer / Motionformer):
-//     y = x * 0.5 * (1 + erf(x / sqrt(2)))      fp32 arithmetic on 16-bit values, one rounding -- the expression and
-// operation order of the framework's kernel, so the result is bit-identical to it.  A pure streaming pass: four
-// 16-byte chunks per lane in flight, non-temporal both ways (the [tokens, 4C] activation is 1.2 GB at batch 128).
-// k_gelu_tanh: ViViT's activation (`layer.intermediate`, tome/patch/vivit.py layer forward; HF's "gelu_fast"), the same
-// pass with the tanh form of tome_common.h: y = x * sigma(2 beta (x + kappa x^3)).
-template <typename TX, int FORM>
-__device__ __forceinline__ void gelu_stream(const TX *__restrict__ x, TX *__restrict__ y, int64_t chunks) {
-    constexpr int VEC = 16 / sizeof(TX);
-    constexpr int NIT = 4;
-    const int64_t base = ((int64_t)blockIdx.x * blockDim.x) * NIT + threadIdx.x;
-    uint4 raw[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int64_t q = base + (int64_t)it * blockDim.x;
-        if (q < chunks) raw[it] = ld16(reinterpret_cast<const uint4 *>(x) + q);
-    }
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int64_t q = base + (int64_t)it * blockDim.x;
-        if (q >= chunks) continue;
-        Pack<TX, VEC> pk;
-        __builtin_memcpy(&pk, &raw[it], 16);
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-            const float v = to_f32(pk.e[e]);
-            if (FORM == GELU_TANH) {
-                float c, v2;
-                pk.e[e] = from_f32<TX>(gelu_tanh_value(v, gelu_tanh_sigmoid(v, c, v2)));
-            } else {
-                pk.e[e] = from_f32<TX>(gelu_erf_value(v, gelu_erf_one_plus(v)));
-            }
-        }
-        uint4 o;
-        __builtin_memcpy(&o, &pk, 16);
-        st16(reinterpret_cast<uint4 *>(y) + q, o);
-    }
-}
-
-template <typename TX>
-__global__ __launch_bounds__(256) void k_gelu_erf(const TX *__restrict__ x, TX *__restrict__ y, int64_t chunks) {
-    gelu_stream<TX, GELU_ERF>(x, y, chunks);
-}
-
-template <typename TX>
-__global__ __launch_bounds__(256) void k_gelu_tanh(const TX *__restrict__ x, TX *__restrict__ y, int64_t chunks) {
-    gelu_stream<TX, GELU_TANH>(x, y, chunks);
 }

@@ -12,9 +12,9 @@
 //   drop:  an even token that was merged away has no row: its gradient is 0
 // No atomics: a wave owns R consecutive INPUT-token rows of one group (the rows of gx), every row of gx is written
 // once and a row of gy is read once per token that landed in it (1 + its sources; r of them come from L2).
-// Streaming form of k_merge_rows_fast: R*cpr 16-byte chunks flattened over the lanes, all loads issued before any
-// use, non-temporal both ways, fp32 arithmetic, one rounding; a chunk whose two scales are absent or 1 moves as raw
-// bits (v / 1 * 1 == v bit for bit).  One dependent round trip more than a plain copy: row_map -> rows of gy.
+// Streaming form of k_merge_rows_fast (the slab of tome_merge_slab.h, per-row facts from bwd_slab), non-temporal both
+// ways, fp32 arithmetic, one rounding; a chunk whose two scales are absent or 1 moves as raw bits (v / 1 * 1 == v bit
+// for bit).  One dependent round trip more than a plain copy: row_map -> rows of gy.
 // Grid as k_merge_rows_fast: x = the blocks of one group, (y, z) = the group, class-token rows of the regrouped
 // callers behind the groups.
 // ------------------------------------------------------------------------------------------------
@@ -27,24 +27,6 @@ __device__ __forceinline__ uint4 bwd_scale(const uint4 &raw, float d, float m) {
     uint4 o;
     __builtin_memcpy(&o, &pk, 16);
     return o;
-}
-
-// the merged row of token t of group g, or -1 when the token has none (drop); clamped into [0, To)
-__device__ __forceinline__ int bwd_row_of(int t, int g, int T1, int U, int To, int distill, int drop,
-                                          const int *__restrict__ row_map) {
-    int o;
-    if (t & 1) o = out_row_dst(t >> 1, U, distill);
-    else {
-        o = row_map[(int64_t)g * T1 + (t >> 1)];
-        o = o < 0 ? 0 : (o >= To ? To - 1 : o);
-        if (drop) {
-            bool is_dst;
-            int idx;
-            decode_out_row(o, U, distill, is_dst, idx);
-            if (is_dst) return -1;
-        }
-    }
-    return o < 0 ? 0 : (o >= To ? To - 1 : o);
 }
 
 template <typename TX, typename TS, int NIT>
@@ -74,20 +56,9 @@ __global__ __launch_bounds__(256) void k_merge_rows_bwd(const TX *__restrict__ g
     const TX *gyg = group_ptr(gy, lgy, g);
     TX *gxg = group_ptr(gx, lgx, g);
 
-    // per-row facts by lanes 0..R-1, broadcast as wave-uniform scalars: merged row (-1: none) and the two scales.
-    // The scales are read unconditionally (from row_map when a scale is absent) so that no branch stands between
-    // the index load and the row loads.
-    const bool my_valid = lane < R && (t0 + lane) < T_;
-    const int my_t = my_valid ? t0 + lane : t0;
-    const int my_o = bwd_row_of(my_t, g, T1, U, To, distill, drop, row_map);
-    const int my_os = my_o < 0 ? 0 : my_o;
-    float my_d = 1.0f, my_m = 1.0f;
-    if (out_div) my_d = to_f32(out_div[(int64_t)g * To + my_os]);  // (wave-uniform conditions)
-    if (in_mul) my_m = to_f32(in_mul[(int64_t)g * T_ + my_t]);
-    const int my_row = my_valid ? my_o : -2;  // -2: no such token, -1: token without a row (zero gradient)
-    const int o0 = __builtin_amdgcn_readlane(my_row, 0), o1 = __builtin_amdgcn_readlane(my_row, 1),
-              o2 = __builtin_amdgcn_readlane(my_row, 2), o3 = __builtin_amdgcn_readlane(my_row, 3);
-    const int os0 = __builtin_amdgcn_readlane(my_os, 0);
+    // per-row facts (bwd_slab, tome_merge_slab.h): merged row and the two scales
+    const BwdSlab f = bwd_slab<false, TS>(out_div, in_mul, row_map, g, t0, R, T_, T1, U, To, distill, drop, lane);
+    const int o0 = f.o0, o1 = f.o1, o2 = f.o2, o3 = f.o3, os0 = f.os0;
 
     const int total = R * cpr;
     uint4 raw[NIT];
@@ -95,31 +66,24 @@ __global__ __launch_bounds__(256) void k_merge_rows_bwd(const TX *__restrict__ g
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         const int q = it * WAVE + lane;
-        const int rr = (q >= cpr) + (q >= 2 * cpr) + (q >= 3 * cpr);
-        const int cc = q - rr * cpr;
-        const int o = rr == 0 ? o0 : (rr == 1 ? o1 : (rr == 2 ? o2 : o3));
+        const int rr = slab_row(cpr, it, lane), cc = slab_col(q, rr, cpr);
+        const int o = SEL4(rr, o0, o1, o2, o3);
         const bool live = (q < total) && o >= -1;
         rowof[it] = live ? rr : -1;
         const bool ok = live && o >= 0;
         // unconditional: a lane without a chunk re-reads the start of the wave's first row of gy and ignores it
         raw[it] = ld16(reinterpret_cast<const char *>(gyg + (int64_t)(ok ? o : os0) * lgy.tok_stride) + (ok ? cc : 0) * 16);
     }
-    const float d0 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_d), 0)),
-                d1 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_d), 1)),
-                d2 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_d), 2)),
-                d3 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_d), 3));
-    const float m0 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_m), 0)),
-                m1 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_m), 1)),
-                m2 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_m), 2)),
-                m3 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_m), 3));
+    float d0, d1, d2, d3, m0, m1, m2, m3;
+    lanes4(f.my_d, d0, d1, d2, d3);
+    lanes4(f.my_m, m0, m1, m2, m3);
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         const int rr = rowof[it];
         if (rr < 0) continue;
         const int cc = it * WAVE + lane - rr * cpr;
-        const int o = rr == 0 ? o0 : (rr == 1 ? o1 : (rr == 2 ? o2 : o3));
-        const float d = rr == 0 ? d0 : (rr == 1 ? d1 : (rr == 2 ? d2 : d3));
-        const float m = rr == 0 ? m0 : (rr == 1 ? m1 : (rr == 2 ? m2 : m3));
+        const int o = SEL4(rr, o0, o1, o2, o3);
+        const float d = SEL4(rr, d0, d1, d2, d3), m = SEL4(rr, m0, m1, m2, m3);
         uint4 v = raw[it];
         if (o < 0) v = uint4{0u, 0u, 0u, 0u};
         else if (d != 1.0f || m != 1.0f) v = bwd_scale<TX, VEC>(v, d, m);

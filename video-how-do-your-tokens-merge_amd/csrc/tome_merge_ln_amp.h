@@ -14,11 +14,10 @@
 // order, one division, one rounding to TX -- none for fp32); the LayerNorm is ln_rows (tome_ln_rows.h: statistics from the
 // STORED row, two passes, centred variance, fp32 parameters, y rounded once to TY).
 // Work layout: the lane SLOTS of k_add_ln_rows (8 channels: one 16-byte move of a 16-bit row, two of an fp32 one), so
-// rows per wave and slots per lane are those of the 16-bit launch.  What keeps k_merge_rows_fast at the memory rate is kept:
-// every row load of a wave is issued before any use and is unconditional (a lane without a slot re-reads the start of the
-// wave's first row); rows that receive sources are left to edge waves (one per rank, the first edge into a destination
-// builds it); grid.x = the blocks of one group, grid.(y, z) = the group, so no wave starts with an integer division;
-// OP_DROP has no edge waves.  Flat layout only, no folded bias.
+// rows per wave and slots per lane are those of the 16-bit launch.  The slab walk is k_merge_rows_fast's, from the same
+// functions (tome_merge_slab.h); rows that receive sources are left to edge waves (one per rank, the first edge into a
+// destination builds it); grid.x = the blocks of one group, grid.(y, z) = the group; OP_DROP has no edge waves.  Flat
+// layout only, no folded bias.
 // ------------------------------------------------------------------------------------------------
 // One destination row (odd token 2j+1 plus every source merged into it) by a whole wave, two slots per lane (C <= 1024):
 // merge_dst_row's arithmetic and order, then the LayerNorm of the row as stored.  k: the rank whose edge wave this is;
@@ -144,7 +143,6 @@ __global__ __launch_bounds__(256) void k_merge_rows_ln_amp(const TX *__restrict_
                                                            const float *__restrict__ lw, const float *__restrict__ lb,
                                                            float eps, TX *__restrict__ xout, TY *__restrict__ y,
                                                            TS *__restrict__ sout, TS *__restrict__ lsout) {
-    constexpr int VEC = 8;
     const int lane = threadIdx.x & 63;
     const int To = T_ - r;
     // grid: x = the blocks of ONE group (streaming waves, then the r edge waves), (y, z) = the group
@@ -169,34 +167,15 @@ __global__ __launch_bounds__(256) void k_merge_rows_ln_amp(const TX *__restrict_
     }
     const int o0 = wg * R;
     const int64_t *dstg = OP != OP_DROP ? dst_idx + (int64_t)g * r : nullptr;
-    // per-row facts by lanes 0..R-1, broadcast as wave-uniform scalars (k_merge_rows_fast): source token, B-row number,
-    // size.  The first block of dst_idx and the unm_idx entries go out together; which rows receive sources is decided
-    // after the row loads have been issued.
+    // per-row facts, the slot walk and the edge rows: tome_merge_slab.h.  The first block of dst_idx goes out with
+    // fwd_slab's unm_idx reads; which rows receive sources is decided after the row loads have been issued.
     const int d_first = (OP != OP_DROP && lane < r) ? (int)dstg[lane] : -2;
-    const bool my_valid = lane < R && (o0 + lane) < To;
-    bool is_dst;
-    int idx;
-    decode_out_row(my_valid ? o0 + lane : 0, U, distill, is_dst, idx);
-    int my_tok = 2 * idx + 1, my_j = idx;
-    const bool all_dst = (!distill && o0 >= U) || o0 > U;
-    if (U > 0 && !all_dst) {  // (wave-uniform; unm_idx may be absent when every even token is merged away)
-        const int ut = 2 * (int)unm_idx[(int64_t)g * U + ((my_valid && !is_dst) ? idx : 0)];
-        my_tok = is_dst ? my_tok : ut;
-        my_j = is_dst ? my_j : -1;
-    }
-    my_tok = my_valid ? my_tok : 0;
-    my_j = my_valid ? my_j : -1;
-    // (read unconditionally -- from the tokens themselves when there are no sizes: no branch in front of the row loads)
     const bool load_size = sg != nullptr;  // wave-uniform
-    const TS my_s_raw = (load_size ? sg : reinterpret_cast<const TS *>(xg))[my_tok];
-    const unsigned long long vmask = __ballot(my_valid);
-    const int tok0 = __builtin_amdgcn_readlane(my_tok, 0), tok1 = __builtin_amdgcn_readlane(my_tok, 1),
-              tok2 = __builtin_amdgcn_readlane(my_tok, 2), tok3 = __builtin_amdgcn_readlane(my_tok, 3);
-    const int j0 = __builtin_amdgcn_readlane(my_j, 0), j1 = __builtin_amdgcn_readlane(my_j, 1),
-              j2 = __builtin_amdgcn_readlane(my_j, 2), j3 = __builtin_amdgcn_readlane(my_j, 3);
-    const bool va0 = vmask & 1ull, va1 = vmask & 2ull, va2 = vmask & 4ull, va3 = vmask & 8ull;
+    const FwdSlab<TS> f = fwd_slab<TS>(load_size ? sg : reinterpret_cast<const TS *>(xg), unm_idx, g, o0, R, To, U,
+                                       distill, lane);
+    const int tok0 = f.tok0, tok1 = f.tok1, tok2 = f.tok2, tok3 = f.tok3;
+    const bool va0 = f.vmask & 1ull, va1 = f.vmask & 2ull, va2 = f.vmask & 4ull, va3 = f.vmask & 8ull;
 
-    // flattened slot loop: slot q of the R-row slab -> (row q / cpr, slot column q % cpr)
     const int total = R * cpr;
     Slot<TX> raw[NIT];
     Slot<TA> rawa[NIT] = {};
@@ -204,67 +183,44 @@ __global__ __launch_bounds__(256) void k_merge_rows_ln_amp(const TX *__restrict_
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         const int q = it * WAVE + lane;
-        const int rr = (q >= cpr) + (q >= 2 * cpr) + (q >= 3 * cpr);
-        const int t = rr == 0 ? tok0 : (rr == 1 ? tok1 : (rr == 2 ? tok2 : tok3));
-        const bool ok = (rr == 0 ? va0 : (rr == 1 ? va1 : (rr == 2 ? va2 : va3))) && (q < total);
+        const int rr = slab_row(cpr, it, lane), t = SEL4(rr, tok0, tok1, tok2, tok3);
+        const bool ok = SEL4(rr, va0, va1, va2, va3) && (q < total);
         rowof[it] = ok ? rr : -1;
         const int64_t toff = (int64_t)(ok ? t : tok0) * C;
-        const int cc = ok ? q - rr * cpr : 0;
+        const int cc = ok ? slab_col(q, rr, cpr) : 0;
         raw[it] = ld_slot<TX>(xg + toff, cc);
         if (add) rawa[it] = ld_slot<TA>(ag + toff, cc);  // (wave-uniform)
     }
-    bool e0 = false, e1 = false, e2 = false, e3 = false;  // rows that receive sources: the edge waves build them
-    if (OP != OP_DROP) {
-        e0 = __ballot(d_first == j0) != 0ull;
-        e1 = __ballot(d_first == j1) != 0ull;
-        e2 = __ballot(d_first == j2) != 0ull;
-        e3 = __ballot(d_first == j3) != 0ull;
-        for (int base = WAVE; base < r; base += WAVE) {
-            const int k = base + lane;
-            const int d = (k < r) ? (int)dstg[k] : -2;
-            e0 = e0 || (__ballot(d == j0) != 0ull);
-            e1 = e1 || (__ballot(d == j1) != 0ull);
-            e2 = e2 || (__ballot(d == j2) != 0ull);
-            e3 = e3 || (__ballot(d == j3) != 0ull);
-        }
-    }
+    SlabEdges e{false, false, false, false};  // rows that receive sources: the edge waves build them
+    if (OP != OP_DROP) e = slab_edge_rows(d_first, f.j0, f.j1, f.j2, f.j3, dstg, r, lane);
+    const bool e0 = e.e0, e1 = e.e1, e2 = e.e2, e3 = e.e3;
     const bool ok0 = va0 && !e0, ok1 = va1 && !e1, ok2 = va2 && !e2, ok3 = va3 && !e3;
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         const int rr = rowof[it];
-        const bool ok = rr >= 0 && (rr == 0 ? ok0 : (rr == 1 ? ok1 : (rr == 2 ? ok2 : ok3)));
+        const bool ok = rr >= 0 && SEL4(rr, ok0, ok1, ok2, ok3);
         rowof[it] = ok ? rr : -1;
     }
     // the parameter slots of every slot column this lane holds: requested now, used after the two reductions
     const LnParams<float, NIT> prm = ln_params<float, NIT>(lw, lb, rowof, cpr, lane);
-    const float my_s = (load_size && my_valid) ? to_f32(my_s_raw) : 1.0f;
-    const float sz0 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_s), 0)),
-                sz1 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_s), 1)),
-                sz2 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_s), 2)),
-                sz3 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_s), 3));
+    const float my_s = (load_size && f.my_valid) ? to_f32(f.my_s_raw) : 1.0f;
+    float sz0, sz1, sz2, sz3;
+    lanes4(my_s, sz0, sz1, sz2, sz3);
     // x' = x + a, the merge of a row without sources ((x' s) / s: raw bits when that is x' itself) and the store
-    constexpr bool narrow = sizeof(TX) == 2;
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         const int rr = rowof[it];
         if (rr < 0) continue;
         if (add) raw[it] = slot_add<TX, TA>(raw[it], rawa[it]);
         if (OP == OP_WAVG) {
-            const float s = rr == 0 ? sz0 : (rr == 1 ? sz1 : (rr == 2 ? sz2 : sz3));
-            const uint32_t sb = __float_as_uint(s);
-            const bool exact = (s == 1.0f) || (narrow && (sb & 0x007FFFFFu) == 0u && s >= 1.0f && s <= 65536.0f);
-            if (!exact) {
-                float v[VEC];
-                slot_f32<TX>(raw[it], v);
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) v[e] = __fdiv_rn(__fmul_rn(v[e], s), s);
-                raw[it] = f32_slot<TX>(v);
-            }
+            const float s = SEL4(rr, sz0, sz1, sz2, sz3);
+            if (!wavg_moves_raw<TX>(s)) raw[it] = wavg_rescaled<TX>(raw[it], s);
         }
         st_slot<TX>(og + (int64_t)(o0 + rr) * C, it * WAVE + lane - rr * cpr, raw[it]);
     }
-    if (OP == OP_WAVG && my_valid) {
-        const bool mine_has_edges = lane == 0 ? e0 : (lane == 1 ? e1 : (lane == 2 ? e2 : e3));
+    if (OP == OP_WAVG && f.my_valid) {
+        // (this store stays here: through slab_store_size the all-bf16 form takes 98 vector registers for 96)
+        const bool mine_has_edges = SEL4(lane, e0, e1, e2, e3);
         if (!mine_has_edges)
             store_size<TS>(sout + (int64_t)g * To + o0 + lane, lsout ? lsout + (int64_t)g * To + o0 + lane : nullptr, my_s);
     }

@@ -13,9 +13,8 @@
 // mean and rstd are recomputed from x' with ln_rows' arithmetic, exactly as k_ln_rows_bwd does it: the two rounds
 // are a copy of that kernel's, kept for the same reason (through the shared rounds of tome_ln_rows.h this kernel went
 // from 44 to 78 scalar registers and measured 1.3 % slower).
-// A wave owns R consecutive INPUT-token rows of one group (the rows of gx); chunk slot q = it * 64 + lane of the wave's
-// R * cpr 16-byte chunks, the loads of a slab (x', gy, gx_out at row o(t)) issued before any use, non-temporal both
-// ways.  Per-row facts (merged row, the two scales, "owns its row") by lanes 0..R-1, broadcast as scalars.  A
+// A wave owns R consecutive INPUT-token rows of one group (the rows of gx): the slab of tome_merge_slab.h, per-row facts
+// (merged row, the two scales, "owns its row") from bwd_slab; the loads of a slab are x', gy, gx_out at row o(t).  A
 // destination with k sources has its LayerNorm term computed 1 + k times (r extra rows of T); the rows come from L2.
 // PARAMS: dweight[c] = sum gy * xhat, dbias[c] = sum gy over the MERGED rows, each counted once -- by the token that
 // owns it: an odd token its destination row, an even token its own row unless it was merged away.  The scheme is
@@ -25,21 +24,6 @@
 // Without PARAMS (frozen LayerNorm): one slab per wave, grid x = the blocks of one group, (y, z) = the group as in
 // k_merge_rows_bwd; no workspace.
 // ------------------------------------------------------------------------------------------------
-
-// bwd_row_of and whether token t is the one that owns row o(t) in the parameter sums
-__device__ __forceinline__ int bwd_row_owner(int t, int g, int T1, int U, int To, int distill, int drop,
-                                             const int *__restrict__ row_map, bool &owns) {
-    const int o = bwd_row_of(t, g, T1, U, To, distill, drop, row_map);
-    owns = o >= 0;
-    if (o >= 0 && !(t & 1)) {
-        bool is_dst;
-        int idx;
-        decode_out_row(o, U, distill, is_dst, idx);
-        owns = !is_dst;  // an even token in a destination row was merged into it: the odd token counts the row
-    }
-    return o;
-}
-
 template <typename TX, typename TS, int NIT, bool PARAMS>
 __global__ __launch_bounds__(256) void k_merge_ln_rows_bwd(const TX *__restrict__ gy, const TX *__restrict__ gx_out,
                                                            const TX *__restrict__ xs, const TS *__restrict__ out_div,
@@ -61,10 +45,10 @@ __global__ __launch_bounds__(256) void k_merge_ln_rows_bwd(const TX *__restrict_
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         const int q = it * WAVE + lane;
-        const int rr = (q >= cpr) + (q >= 2 * cpr) + (q >= 3 * cpr);
+        const int rr = slab_row(cpr, it, lane);
         const bool slot = q < R * cpr;
         rr_of[it] = slot ? rr : -1;
-        cc_of[it] = slot ? q - rr * cpr : 0;
+        cc_of[it] = slot ? slab_col(q, rr, cpr) : 0;
         wraw[it] = *(reinterpret_cast<const uint4 *>(weight) + cc_of[it]);
     }
     float aw[NIT][VEC], ab[NIT][VEC];
@@ -90,20 +74,9 @@ __global__ __launch_bounds__(256) void k_merge_ln_rows_bwd(const TX *__restrict_
         }
         const int t0 = lw * R;
 
-        // per-row facts by lanes 0..R-1, broadcast as wave-uniform scalars.  The scales are read unconditionally so
-        // that no branch stands between the index load and the row loads.
-        const bool my_valid = lane < R && (t0 + lane) < T_;
-        const int my_t = my_valid ? t0 + lane : t0;
-        bool my_owns;
-        const int my_o = bwd_row_owner(my_t, g, T1, U, To, distill, drop, row_map, my_owns);
-        const int my_os = my_o < 0 ? 0 : my_o;
-        float my_d = 1.0f, my_m = 1.0f;
-        if (out_div) my_d = to_f32(out_div[(int64_t)g * To + my_os]);  // (wave-uniform conditions)
-        if (in_mul) my_m = to_f32(in_mul[(int64_t)g * T_ + my_t]);
-        const int my_row = my_valid ? my_o : -2;  // -2: no such token, -1: token without a row (zero gradient)
-        const int o0 = __builtin_amdgcn_readlane(my_row, 0), o1 = __builtin_amdgcn_readlane(my_row, 1),
-                  o2 = __builtin_amdgcn_readlane(my_row, 2), o3 = __builtin_amdgcn_readlane(my_row, 3);
-        const int os0 = __builtin_amdgcn_readlane(my_os, 0);
+        // per-row facts (bwd_slab, tome_merge_slab.h): merged row, the two scales, "owns its row"
+        const BwdSlab f = bwd_slab<true, TS>(out_div, in_mul, row_map, g, t0, R, T_, T1, U, To, distill, drop, lane);
+        const int o0 = f.o0, o1 = f.o1, o2 = f.o2, o3 = f.o3, os0 = f.os0;
 
         const uint4 *xsg = reinterpret_cast<const uint4 *>(xs) + (int64_t)g * To * cpr;
         const uint4 *gyg = reinterpret_cast<const uint4 *>(gy) + (int64_t)g * To * cpr;
@@ -113,7 +86,7 @@ __global__ __launch_bounds__(256) void k_merge_ln_rows_bwd(const TX *__restrict_
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             const int rr = rr_of[it];
-            const int o = rr == 0 ? o0 : (rr == 1 ? o1 : (rr == 2 ? o2 : o3));
+            const int o = SEL4(rr, o0, o1, o2, o3);
             const bool live = rr >= 0 && o >= -1;
             const bool ok = live && o >= 0;
             // unconditional loads: a lane without a chunk re-reads the start of the wave's first row and ignores it
@@ -123,17 +96,11 @@ __global__ __launch_bounds__(256) void k_merge_ln_rows_bwd(const TX *__restrict_
             if (has_in) iraw[it] = ld16(gig + at);
             rowof[it] = live ? (ok ? rr : (rr | 4)) : -1;
         }
-        const int my_own_i = (my_valid && my_owns) ? 1 : 0;
-        const int w0 = __builtin_amdgcn_readlane(my_own_i, 0), w1 = __builtin_amdgcn_readlane(my_own_i, 1),
-                  w2 = __builtin_amdgcn_readlane(my_own_i, 2), w3 = __builtin_amdgcn_readlane(my_own_i, 3);
-        const float d0 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_d), 0)),
-                    d1 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_d), 1)),
-                    d2 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_d), 2)),
-                    d3 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_d), 3));
-        const float s0 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_m), 0)),
-                    s1 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_m), 1)),
-                    s2 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_m), 2)),
-                    s3 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_m), 3));
+        int w0, w1, w2, w3;
+        float d0, d1, d2, d3, s0, s1, s2, s3;
+        lanes4(f.my_owns ? 1 : 0, w0, w1, w2, w3);
+        lanes4(f.my_d, d0, d1, d2, d3);
+        lanes4(f.my_m, s0, s1, s2, s3);
 
         // round 1: mean of every row (as ln_rows)
         float p0 = 0.0f, p1 = 0.0f, p2 = 0.0f, p3 = 0.0f;
@@ -229,7 +196,7 @@ __global__ __launch_bounds__(256) void k_merge_ln_rows_bwd(const TX *__restrict_
                         kk = pick4(ro, k0, k1, k2, k3, R);
             const float dv = pick4(ro, d0, d1, d2, d3, R), mu = pick4(ro, s0, s1, s2, s3, R);
             const bool scaled = dv != 1.0f || mu != 1.0f;
-            const int own = ro == 0 ? w0 : (ro == 1 ? w1 : (ro == 2 ? w2 : w3));
+            const int own = SEL4(ro, w0, w1, w2, w3);
             Pack<TX, VEC> pi, pg, pw, po;
             if (has_in) __builtin_memcpy(&pi, &iraw[it], 16);
             __builtin_memcpy(&pg, &graw[it], 16);
