@@ -454,7 +454,8 @@ int tome_add_layernorm_amp(const void *x, int x_dtype, const void *addend, int a
  *     sources in src_idx order, one division, one rounding to x_dtype (none for fp32); rows nothing merges into, of
  *     size 1, move as raw bits.  edge_keep and distill_token as in tome_merge_wavg_ln.  The LayerNorm's statistics are
  *     taken in fp32 from the STORED x_out (two passes, centred variance), y_out is rounded once.
- *     Flat layout only, no x_out_bias, no backward.  C % 8 == 0, C <= 1024, 0 < r <= T/2, 16-byte aligned buffers; each
+ *     Flat layout only, no x_out_bias; the backward of this entry and of tome_drop_ln_amp is
+ *     tome_merge_ln_backward_amp below.  C % 8 == 0, C <= 1024, 0 < r <= T/2, 16-byte aligned buffers; each
  *     refusal is made on the host before any launch, with its own tome_last_error.
  */
 int tome_merge_wavg_ln_amp(const void *x, int x_dtype, const void *addend, int addend_dtype, const void *size,
@@ -494,6 +495,35 @@ int tome_layernorm_backward_amp(const void *gy, int gy_dtype, const void *xs, co
                                 int64_t groups, int64_t group_rows, int skip_first, int64_t C, const void *weight_f32,
                                 float eps, void *gx, void *gx16, void *dweight_f32, void *dbias_f32, void *workspace,
                                 tome_stream_t stream);
+
+/*
+ * tome_merge_ln_backward_amp  <-  the backward of tome_merge_wavg_ln_amp and tome_drop_ln_amp (flat layout) as ONE launch:
+ *     tome_merge_ln_backward's formula for a model that trains under autocast with fp32 master weights (additions to ABI
+ *     v11, no entry changed; tools/train_net.py:123 and :680, tome/utils.py:54).
+ *         gy [n,T-r,C] of gy_dtype (16-bit); xs (the forward's stored x_out), gx_out (or NULL) [n,T-r,C] and gx [n,T,C] of
+ *         x_dtype: gy_dtype or TOME_F32; weight_f32, dweight_f32, dbias_f32 [C] fp32; out_div = size_out [n,T-r],
+ *         in_mul = size [n,T] or NULL, of size_dtype (x_dtype or TOME_F32; ignored when both are NULL); row_map,
+ *         distill_token and drop as in tome_merge_ln_backward.
+ *     With o(t) the merged row of token t, gw = gy * weight, xhat = (xs - mean) * rstd:
+ *         gm[o] = gx_out[o] + rstd * (gw - mean(gw) - xhat * mean(gw * xhat))       fp32, not rounded
+ *         gx[t] = (gm[o(t)] / out_div[o(t)]) * in_mul[t]      division first; one rounding to a 16-bit x_dtype, none to fp32
+ *     drop != 0: no scales, a merged-away token gets 0.  gx16 (x_dtype == TOME_F32 only, or NULL): [n,T,C] of gy_dtype,
+ *     round16(gx) from the same registers, bit-equal to a cast of gx -- the gradient of a 16-bit addend of an fp32 stream.
+ *     mean and rstd are recomputed from xs with the arithmetic of tome_layernorm_backward_amp, and gm is that entry's
+ *     expression term for term.
+ *         dweight[c] = sum over the merged rows of gy * xhat,   dbias[c] = sum over the merged rows of gy
+ *     every merged row once, counted by the token that owns it; fp32 partial rows in `workspace` summed in a fixed order,
+ *     no atomics, same bits on every run.  Either gradient may be NULL; both NULL (frozen LayerNorm): no parameter work
+ *     and no workspace.  Otherwise workspace holds tome_merge_ln_backward_amp_workspace_bytes(n, T, C, x_dtype) bytes (0
+ *     for an illegal shape or dtype).  C % 8 == 0, C <= 1024, 0 < r <= T/2, 16-byte aligned buffers; each refusal is made
+ *     on the host before any launch, with its own tome_last_error.
+ */
+size_t tome_merge_ln_backward_amp_workspace_bytes(int64_t n, int64_t T, int64_t C, int x_dtype);
+int tome_merge_ln_backward_amp(const void *gy, int gy_dtype, const void *gx_out, const void *xs, int x_dtype,
+                               const void *out_div, const void *in_mul, int size_dtype, int64_t n, int64_t T, int64_t C,
+                               int64_t r, const int32_t *row_map, int distill_token, int drop, const void *weight_f32,
+                               float eps, void *gx, void *gx16, void *dweight_f32, void *dbias_f32, void *workspace,
+                               tome_stream_t stream);
 
 /*
  * tome_prop_attention_backward  <-  what autograd derives from the proportional attention of the patched blocks when

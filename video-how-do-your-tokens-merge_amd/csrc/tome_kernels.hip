@@ -4,8 +4,8 @@
 //
 // One translation unit: tome_common.h (types), tome_match.h, tome_ln_rows.h (the row statistics the forward LayerNorm
 // kernels and k_ln_rows_bwd_amp share), tome_merge_slab.h (the row slab the merge family walks), tome_merge.h,
-// tome_merge_ln_amp.h, tome_ln_fwd.h, tome_merge_bwd.h, tome_ln_bwd.h, tome_merge_ln_bwd.h, tome_gelu.h, tome_gelu_bwd.h,
-// tome_token_mean.h, tome_short_attn_bwd.h, tome_traj_bwd.h and tome_partition.h (kernels), this file (host).
+// tome_merge_ln_amp.h, tome_ln_fwd.h, tome_merge_bwd.h, tome_ln_bwd.h, tome_merge_ln_bwd.h, tome_merge_ln_bwd_amp.h,
+// tome_gelu.h, tome_gelu_bwd.h, tome_token_mean.h, tome_short_attn_bwd.h, tome_traj_bwd.h and tome_partition.h (kernels), this file (host).
 //
 // Launch sequence of one matching (tome_match / tome_match_keys), kernels in tome_match.h:
 //   k_unit_rows[_heads]  keys -> fp32 unit vectors, even/odd split, MFMA-fragment order (HBM bound)
@@ -34,11 +34,14 @@
 //   k_merge_ln_rows_bwd  the two above as one pass: the LayerNorm term of row o(t) in fp32, scaled and rounded once
 //                        per input token; parameter gradients over the merged rows, each counted once    (HBM bound)
 // and their mixed-precision forms for a model under autocast with fp32 master weights (tome_merge_wavg_ln_amp /
-// tome_drop_ln_amp, tome_layernorm_backward_amp), tome_merge_ln_amp.h / tome_ln_bwd.h:
+// tome_drop_ln_amp, tome_layernorm_backward_amp, tome_merge_ln_backward_amp), tome_merge_ln_amp.h / tome_ln_bwd.h /
+// tome_merge_ln_bwd_amp.h:
 //   k_merge_rows_ln_amp  k_merge_rows_fast<LN> with fp32 weight / bias, a 16-bit y and a 16-bit or fp32 residual stream
 //   k_ln_rows_bwd_amp    k_ln_rows_bwd on the forward's own rounds (tome_ln_rows.h) with a 16-bit gy, the stream's dtype
 //                        for xs / gx_in / gx, fp32 partial rows summed into fp32 parameters, optionally gx rounded
 //                        to 16 bits as a second output                                                   (HBM bound)
+//   k_merge_ln_rows_bwd_amp  k_merge_ln_rows_bwd in those dtypes, on the same shared rounds: the backward of
+//                        k_merge_rows_ln_amp as one pass                                                 (HBM bound)
 // and of TimeSformer's temporal attention (tome_short_attention_backward), tome_short_attn_bwd.h:
 //   k_short_attention_bwd  P recomputed, dq / dk / dv of sequences of <= 8 tokens in one pass, eight lanes per
 //                        (sequence, head), dk / dv accumulated in registers                           (HBM bound)
@@ -81,6 +84,7 @@
 #include "tome_merge_bwd.h"
 #include "tome_ln_bwd.h"
 #include "tome_merge_ln_bwd.h"
+#include "tome_merge_ln_bwd_amp.h"
 #include "tome_gelu.h"
 #include "tome_gelu_bwd.h"
 #include "tome_token_mean.h"
@@ -2042,6 +2046,75 @@ extern "C" int tome_merge_ln_backward(const void *gy, const void *gx_out, const 
                            (int)f.wpg, 1, eps, row_map, distill_token ? 1 : 0, drop ? 1 : 0, (TX *)gx, (float *)nullptr);
         return check_launch("k_merge_ln_rows_bwd");
     }, [&] { return fail(TOME_EINVAL, "%s: unsupported dtypes x=%d size=%d", who, x_dtype, size_dtype); });
+}
+
+// ------------------------------------------------------------------------------------------------
+// backward of tome_merge_wavg_ln_amp / tome_drop_ln_amp in the flat layout (kernel in tome_merge_ln_bwd_amp.h): the
+// launch form of tome_merge_ln_backward (merge_ln_bwd_form: slots of 8 channels, so the same for every stream dtype) in
+// the dtypes of tome_layernorm_backward_amp.  Every refusal is made here, before the launch, each with a text of its own.
+// ------------------------------------------------------------------------------------------------
+extern "C" size_t tome_merge_ln_backward_amp_workspace_bytes(int64_t n, int64_t T, int64_t C, int x_dtype) {
+    if (x_dtype != TOME_F32 && x_dtype != TOME_BF16 && x_dtype != TOME_F16) return 0;
+    return tome_merge_ln_backward_workspace_bytes(n, T, C);
+}
+
+extern "C" int tome_merge_ln_backward_amp(const void *gy, int gy_dtype, const void *gx_out, const void *xs, int x_dtype,
+                                          const void *out_div, const void *in_mul, int size_dtype, int64_t n, int64_t T,
+                                          int64_t C, int64_t r, const int32_t *row_map, int distill_token, int drop,
+                                          const void *weight_f32, float eps, void *gx, void *gx16, void *dweight_f32,
+                                          void *dbias_f32, void *workspace, tome_stream_t stream) {
+    const char *who = "tome_merge_ln_backward_amp";
+    if (!xs || !weight_f32) return fail(TOME_EINVAL, "%s: null buffer", who);
+    if (int rc = check_merge_args(who, gy, n, T, C, r, gx)) return rc;
+    if (!ln_amp_dtypes_ok(gy_dtype, x_dtype))
+        return fail(TOME_EINVAL, "%s: unsupported dtypes gy=%d x=%d (16-bit gy; x of gy's dtype or fp32)", who, gy_dtype,
+                    x_dtype);
+    if (gx16 && x_dtype != TOME_F32) return fail(TOME_EINVAL, "%s: gx16 belongs to an fp32 stream", who);
+    if (!row_map) return fail(TOME_EINVAL, "%s: null row_map", who);
+    if (drop && (out_div || in_mul)) return fail(TOME_EINVAL, "%s: drop takes no scales", who);
+    const bool scales = out_div || in_mul;
+    if (scales && size_dtype != TOME_F32 && size_dtype != x_dtype)
+        return fail(TOME_EINVAL, "%s: sizes must be of x's dtype or fp32 (x=%d size=%d)", who, x_dtype, size_dtype);
+    if (!merge_ln_bwd_shape_ok(n, T, C))
+        return fail(TOME_EINVAL, "%s: C %% 8 == 0 and C <= 1024 required (C=%lld)", who, (long long)C);
+    if (!aligned16(gy) || !aligned16(gx_out) || !aligned16(xs) || !aligned16(weight_f32) || !aligned16(gx) ||
+        !aligned16(gx16) || !aligned16(workspace))
+        return fail(TOME_EINVAL, "%s: 16-byte aligned buffers required", who);
+    const bool params = dweight_f32 || dbias_f32;
+    if (params && !workspace)  // (a null pointer, no size to fall short of: TOME_EINVAL like every refusal of this entry)
+        return fail(TOME_EINVAL, "%s: parameter gradients need a workspace of %s_workspace_bytes()", who, who);
+    const int64_t cpr = C / 8;
+    const MergeLnBwdForm f = merge_ln_bwd_form(n, T, C);
+    const int64_t bpg = (f.wpg + 3) / 4;
+    const int64_t gy_ = n < 65535 ? n : 65535, gz = (n + gy_ - 1) / gy_;
+    if (gz > 65535) return fail(TOME_EINVAL, "%s: too many groups (%lld)", who, (long long)n);
+    hipStream_t st = (hipStream_t)stream;
+    return dispatch_x<false>(gy_dtype, [&](auto tg) {
+        using TG = typename decltype(tg)::type;
+        auto go = [&](auto ts, auto tz) {
+            using TS = typename decltype(ts)::type;
+            using TZ = typename decltype(tz)::type;
+            if (params) {
+                hipLaunchKernelGGL((k_merge_ln_rows_bwd_amp<TS, TG, TZ, 3, true>), dim3((unsigned)f.parts), dim3(256), 0,
+                                   st, (const TG *)gy, (const TS *)gx_out, (const TS *)xs, (const TZ *)out_div,
+                                   (const TZ *)in_mul, (const float *)weight_f32, (int)n, (int)T, (int)C, (int)r, f.R,
+                                   (int)cpr, (int)f.wpg, (int)f.spw, eps, row_map, distill_token ? 1 : 0, drop ? 1 : 0,
+                                   (TS *)gx, (TG *)gx16, (float *)workspace);
+                if (int rc = check_launch("k_merge_ln_rows_bwd_amp")) return rc;
+                return launch_param_grad<float>(workspace, f.parts, 2 * C, C, dweight_f32, dbias_f32, st);
+            }
+            // frozen LayerNorm: one slab per wave, no column sums, no workspace
+            hipLaunchKernelGGL((k_merge_ln_rows_bwd_amp<TS, TG, TZ, 3, false>),
+                               dim3((unsigned)bpg, (unsigned)gy_, (unsigned)gz), dim3(256), 0, st, (const TG *)gy,
+                               (const TS *)gx_out, (const TS *)xs, (const TZ *)out_div, (const TZ *)in_mul,
+                               (const float *)weight_f32, (int)n, (int)T, (int)C, (int)r, f.R, (int)cpr, (int)f.wpg, 1, eps,
+                               row_map, distill_token ? 1 : 0, drop ? 1 : 0, (TS *)gx, (TG *)gx16, (float *)nullptr);
+            return check_launch("k_merge_ln_rows_bwd_amp");
+        };
+        // (no scales: the fp32 form of the scale loads, which are never made)
+        if (x_dtype == TOME_F32) return go(Dt<float>{}, Dt<float>{});
+        return (scales && size_dtype == x_dtype) ? go(tg, tg) : go(tg, Dt<float>{});
+    }, [&] { return not_16bit(who, gy_dtype, "gy"); });
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,9 +1,9 @@
 // tome_ln_rows.h -- part of the single translation unit csrc/tome_kernels.hip: the row statistics of every kernel that
 // normalises "up to four rows per wave, NIT slots per lane" -- the LayerNorm tails of k_merge_rows_fast<LN>,
 // k_add_ln_rows (16-bit and autocast forms), k_add_ln_regroup, k_merge_rows_ln_amp (tome_merge.h, tome_ln_fwd.h, tome_merge_ln_amp.h) and
-// the statistics k_ln_rows_bwd_amp recomputes (tome_ln_bwd.h).  No forward kernel saves mean or rstd: that backward
-// kernel reproduces the forward's bits because it calls the forward's own functions (ln_row_means, slot_centre,
-// ln_rstd), not a copy of them.  The 16-bit backward kernels (k_ln_rows_bwd, k_merge_ln_rows_bwd) keep a copy of the
+// the statistics k_ln_rows_bwd_amp and k_merge_ln_rows_bwd_amp recompute (tome_ln_bwd.h, tome_merge_ln_bwd_amp.h).  No
+// forward kernel saves mean or rstd: those backward kernels reproduce the forward's bits because they call the forward's
+// own functions (ln_row_means, slot_centre, ln_rstd), not a copy of them.  The 16-bit backward kernels (k_ln_rows_bwd, k_merge_ln_rows_bwd) keep a copy of the
 // two rounds, for their speed (tome_ln_bwd.h says what the shared rounds cost them); a test of bits ties k_ln_rows_bwd
 // to k_ln_rows_bwd_amp.
 #pragma once

@@ -5,7 +5,7 @@
 // scalars.  What keeps the loads together is kept HERE: they are unconditional (hipcc sinks the first use of a
 // conditionally loaded value into the `if`, an s_waitcnt vmcnt(0) behind every load), so a lane without a row is
 // clamped onto a harmless entry and a size or scale that is absent is read from a pointer the caller knows to be valid.
-// Callers: k_merge_rows_fast, k_merge_rows_ln_amp, k_merge_rows_bwd, k_merge_ln_rows_bwd; the slot map, broadcast and
+// Callers: k_merge_rows_fast, k_merge_rows_ln_amp, k_merge_rows_bwd, k_merge_ln_rows_bwd[_amp]; the slot map, broadcast and
 // select also serve tome_ln_fwd.h and tome_ln_bwd.h.  DESIGN.md, "Where the merge slab lives": who calls what, copies kept.
 #pragma once
 
@@ -178,7 +178,7 @@ __device__ __forceinline__ void slab_store_size(bool mine_has_edges, TS *__restr
     if (!mine_has_edges) store_size<TS>(sout + at, lsout ? lsout + at : nullptr, my_s);
 }
 
-// ---- backward slab facts (k_merge_rows_bwd, k_merge_ln_rows_bwd): the wave owns INPUT-token rows t0 .. t0+R-1.
+// ---- backward slab facts (k_merge_rows_bwd, k_merge_ln_rows_bwd[_amp]): the wave owns INPUT-token rows t0 .. t0+R-1.
 // the merged row of token t of group g, or -1 when the token has none (drop); clamped into [0, To)
 __device__ __forceinline__ int bwd_row_of(int t, int g, int T1, int U, int To, int distill, int drop,
                                           const int *__restrict__ row_map) {

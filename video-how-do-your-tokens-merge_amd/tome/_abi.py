@@ -95,6 +95,9 @@ SIGNATURES = {
     "tome_merge_wavg_ln_amp": (i32, [vp, i32, vp, i32, vp, i32, i64, i64, i64, i64, vp, vp, vp, i32, vp, vp, vp, f32, vp,
                                     vp, i32, vp, vp, vp], True),
     "tome_drop_ln_amp": (i32, [vp, i32, vp, i32, i64, i64, i64, i64, vp, i32, vp, vp, f32, vp, vp, i32, vp], True),
+    "tome_merge_ln_backward_amp_workspace_bytes": (sz, [i64, i64, i64, i32], True),
+    "tome_merge_ln_backward_amp": (i32, [vp, i32, vp, vp, i32, vp, vp, i32, i64, i64, i64, i64, vp, i32, i32, vp, f32, vp,
+                                        vp, vp, vp, vp, vp], True),
 }
 SYMBOLS = tuple(SIGNATURES)
 
@@ -615,6 +618,21 @@ def ln_amp_fusable(x: torch.Tensor, norm, *others) -> bool:
     addend = others[0] if others else None
     return (isinstance(norm, torch.nn.LayerNorm) and x.is_cuda and _ln_amp_of(x, norm, addend)
             and not (torch.is_grad_enabled() and needs_grad(x, norm.weight, norm.bias, *others)))
+
+
+def merge_ln_amp_trainable(x: torch.Tensor, norm, addend: Optional[torch.Tensor], merge=None) -> bool:
+    """Can `norm(merge_wavg(merge, x + addend))` (or the drop form) run under autocast as tome_merge_wavg_ln_amp /
+    tome_drop_ln_amp with tome_merge_ln_backward_amp behind it (tome/_ln.py::_MergeLnAmpFunction) when a participant
+    requires grad?  The tensors of _ln_amp_of on the device, the stock nn.LayerNorm class (a subclass may carry a forward
+    of its own, which a training run must keep) and, as for merge_ln_trainable, the even/odd matching of a MatchPlan
+    without threshold flags, on x's device, with r > 0.  merge: the callable that carries the plan; None asks about the
+    tensors alone (before the matching exists).  False whenever autocast is off."""
+    if not (x.is_cuda and x.dim() == 3 and type(norm) is torch.nn.LayerNorm and _ln_amp_of(x, norm, addend)):
+        return False
+    if merge is None:
+        return True
+    plan = getattr(merge, "plan", None)
+    return type(plan) is MatchPlan and plan.edge_keep is None and plan.r > 0 and plan.device == x.device
 
 
 def _amp_merge_args(what: str, plan: MatchPlan, x: torch.Tensor, weight, bias, y_dtype, addend):
@@ -1641,6 +1659,54 @@ def layernorm_backward_amp(gy: torch.Tensor, xs: torch.Tensor, gx_in: Optional[t
                    int(bool(skip_first)), C, weight.data_ptr(), float(eps), gx.data_ptr(), _ptr(gx16), _ptr(dweight),
                    _ptr(dbias), _ptr(ws), stream)
     _check(rc, "tome_layernorm_backward_amp")
+    return gx, gx16, dweight, dbias
+
+
+def merge_ln_backward_amp(plan: MatchPlan, gy: torch.Tensor, gx_out: Optional[torch.Tensor], xs: torch.Tensor,
+                          out_div: Optional[torch.Tensor], in_mul: Optional[torch.Tensor], weight: torch.Tensor,
+                          eps: float, drop: bool = False, want_weight: bool = True, want_bias: bool = True,
+                          want_gx16: bool = False):
+    """tome_merge_ln_backward_amp: the backward of merge_wavg_ln_amp / drop_ln_amp as one launch.  xs [n, T-r, C]: the
+    forward's stored x_out, of gy's dtype or fp32; gy the 16-bit gradient of its y_out; gx_out (or None) the gradient that
+    reaches x_out through the residual stream, of xs's dtype; out_div = size_out, in_mul = size or None (both None with
+    drop); weight fp32.  want_gx16 (fp32 xs only): also gx rounded to gy's dtype, bit-equal to `gx.to(gy.dtype)`.
+    Returns (gx [n, T, C] of xs's dtype, gx16, dweight, dbias) with fp32 parameter gradients; what is not wanted is
+    None.  No CPU path."""
+    what = "merge_ln_backward_amp"
+    require_device(xs, f"{what}(xs)")
+    if gy.dtype not in _HALF or xs.dtype not in (gy.dtype, torch.float32):
+        raise TomeHipError(f"{what}: a 16-bit gy and xs of its dtype or fp32 required, got {gy.dtype} / {xs.dtype}")
+    if want_gx16 and xs.dtype != torch.float32:
+        raise TomeHipError(f"{what}: gx16 belongs to an fp32 stream")
+    n, T, To = plan.n, plan.T, plan.T - plan.r
+    if xs.dim() != 3 or tuple(xs.shape[:2]) != (n, To):
+        raise TomeHipError(f"{what}: xs must be [{n}, {To}, C], got {tuple(xs.shape)}")
+    C = xs.shape[-1]
+    (weight,) = _f32_params(what, C, xs.device, weight)
+    if drop and (out_div is not None or in_mul is not None):
+        raise TomeHipError(f"{what}: drop takes no scales")
+    gy = _prep_grad(gy, (n, To, C), gy.dtype, xs.device, f"{what}(gy)")
+    if gx_out is not None:
+        gx_out = _prep_grad(gx_out, (n, To, C), xs.dtype, xs.device, f"{what}(gx_out)")
+    out_div, in_mul, sdtype = _prep_scales(out_div, in_mul, n, T, To, xs.dtype, xs.device, what)
+    xs = xs.detach()
+    xs = xs if xs.is_contiguous() else xs.contiguous()
+    row_map = plan_row_map(plan)
+    L = lib()
+    entry = require_symbol(L, "tome_merge_ln_backward_amp")
+    gx = torch.empty((n, T, C), dtype=xs.dtype, device=xs.device)
+    gx16 = torch.empty((n, T, C), dtype=gy.dtype, device=xs.device) if want_gx16 else None
+    dweight = torch.empty(C, dtype=torch.float32, device=xs.device) if want_weight else None
+    dbias = torch.empty(C, dtype=torch.float32, device=xs.device) if want_bias else None
+    with _on_device(xs.device):
+        stream = _stream(xs.device)
+        ws = _sized_workspace(L, "tome_merge_ln_backward_amp_workspace_bytes", (n, T, C, DTYPES[xs.dtype]), xs.device,
+                              stream, what) if want_weight or want_bias else None
+        rc = entry(gy.data_ptr(), DTYPES[gy.dtype], _ptr(gx_out), xs.data_ptr(), DTYPES[xs.dtype], _ptr(out_div),
+                   _ptr(in_mul), DTYPES[sdtype], n, T, C, plan.r, row_map.data_ptr(), int(plan.distill_token),
+                   int(bool(drop)), weight.data_ptr(), float(eps), gx.data_ptr(), _ptr(gx16), _ptr(dweight), _ptr(dbias),
+                   _ptr(ws), stream)
+    _check(rc, "tome_merge_ln_backward_amp")
     return gx, gx16, dweight, dbias
 
 

@@ -23,6 +23,8 @@ merge_ln_native(plan, x, addend, size, norm, drop, log_size) -> (x', norm(x'), s
 drop) + LayerNorm launch (tome_merge_wavg_ln / tome_drop_ln) as a Function, tome_merge_ln_backward behind it -- one
 launch each way.  Reached through tome.merge.merge_wavg_ln / drop_ln, which route (the patched blocks take them only with
 tome.patch._common.TRAIN_FUSED_LN on).
+merge_ln_amp_native: the same under autocast with fp32 LayerNorm parameters (tome_merge_wavg_ln_amp / tome_drop_ln_amp,
+tome_merge_ln_backward_amp behind them), reached by the same two calls while NATIVE_MERGE_LN_AUTOCAST_BACKWARD is on.
 The regrouped form is the middle of TimeSformer's divided space-time block (tome_add_layernorm_regrouped forward,
 tome_layernorm_backward_regrouped backward): x [B, 1 + P*T, C] and addend [B, P*T, C] receive gx and its view gx[:, 1:].
 """
@@ -49,6 +51,14 @@ NATIVE_LN_REGROUPED_BACKWARD = True
 # behaviour before tome_add_layernorm_amp existed), in both grad modes -- for A/B in tests and tools/autocast_bench.py.
 # The Function form also needs enabled() below.  What the default rests on is said in DESIGN.md section 1.
 NATIVE_LN_AUTOCAST = True
+
+# True: under autocast, when a participant wants a gradient, tome.merge.merge_wavg_ln / drop_ln (and the flat-layout blocks
+# of kinds "merge" and "drop", tome/patch/_common.py::fused_route) run the residual add, the reduction and the LayerNorm as
+# _MergeLnAmpFunction below -- tome_merge_wavg_ln_amp / tome_drop_ln_amp forward, tome_merge_ln_backward_amp backward, one
+# launch each way -- where _abi.merge_ln_amp_trainable holds, instead of the framework's add, the merge Function and
+# _AddLayerNormAmpFunction.  Needs NATIVE_LN_AUTOCAST and enabled() too.  Off by default: what that rests on is said in
+# DESIGN.md section 1 (measure with tools/autocast_merge_ln_backward_bench.py).
+NATIVE_MERGE_LN_AUTOCAST_BACKWARD = False
 
 AMP_DIRECT, AMP_FUNCTION = "amp_direct", "amp_function"
 
@@ -257,6 +267,71 @@ def _backward_amp(ctx, g_sum, g_y, want_gx16):
         g_sum = g_sum.to(xs.dtype)
     gx, gx16, dw, db = ln_backward_amp(g_y, xs, g_sum, weight, ctx.eps, ctx.skip_first, want_w, want_b, want_gx16)
     return (gx if ctx.needs_x else None), gx16, dw, db
+
+
+def merge_ln_backward_amp(plan, gy, gx_out, xs, out_div, in_mul, weight, eps, drop, want_weight, want_bias, want_gx16):
+    """The backward arithmetic of _MergeLnAmpFunction: (gx, gx16, dweight, dbias).  A seam of its own, like ln_backward."""
+    return _abi.merge_ln_backward_amp(plan, gy, gx_out, xs, out_div, in_mul, weight, eps, drop=drop,
+                                      want_weight=want_weight, want_bias=want_bias, want_gx16=want_gx16)
+
+
+class _MergeLnAmpFunction(torch.autograd.Function):
+    """_MergeLnFunction under autocast: tome_merge_wavg_ln_amp / tome_drop_ln_amp forward, tome_merge_ln_backward_amp
+    backward -- one launch each way, the gradient of the merged rows never written.  x receives gx; the addend gx when
+    it has the stream's dtype, gx16 when it is the 16-bit addend of an fp32 stream; the sizes carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, addend, size, weight, bias, eps, plan, drop, log_size, y_dtype):
+        det = lambda t: None if t is None else t.detach()  # noqa: E731
+        _abi.plan_row_map(plan)
+        if drop:
+            x_out, y = _abi.drop_ln_amp(plan, x.detach(), weight.detach(), bias.detach(), eps, y_dtype, addend=det(addend))
+            s_out = log = None
+        else:
+            x_out, y, s_out = _abi.merge_wavg_ln_amp(plan, x.detach(), det(size), weight.detach(), bias.detach(), eps,
+                                                     y_dtype, addend=det(addend), log_size=log_size)
+            log = getattr(s_out, "_tome_log", None)
+            ctx.mark_non_differentiable(*(t for t in (s_out, log) if t is not None))
+        ctx.plan, ctx.eps, ctx.drop, ctx.y_dtype = plan, float(eps), bool(drop), y_dtype
+        ctx.needs_x = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        ctx.addend16 = addend is not None and addend.dtype != x.dtype
+        ctx.save_for_backward(x_out, weight, size, s_out)
+        ctx.set_materialize_grads(False)  # an output nobody read arrives as None, not as a tensor of zeros
+        return x_out, y, s_out, log
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_x, g_y, _gs, _gl):
+        xs, weight, size, s_out = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        want_w, want_b = need[3], need[4]
+        want_gx16 = bool(ctx.addend16 and need[1])
+        if g_x is not None and g_x.dtype != xs.dtype:
+            g_x = g_x.to(xs.dtype)
+        if g_y is None:  # nothing read the LayerNorm: the merge alone, the parameters get zeros
+            gx = gx16 = None
+            if ctx.needs_x and g_x is not None:
+                gx = _abi.merge_backward(ctx.plan, g_x, out_div=s_out, in_mul=size, drop=ctx.drop)
+                gx16 = gx.to(ctx.y_dtype) if want_gx16 else None
+            dw = torch.zeros_like(weight) if want_w else None
+            db = torch.zeros_like(weight) if want_b else None
+        else:
+            if g_y.dtype != ctx.y_dtype:
+                g_y = g_y.to(ctx.y_dtype)
+            gx, gx16, dw, db = merge_ln_backward_amp(ctx.plan, g_y, g_x, xs, s_out, size, weight, ctx.eps, ctx.drop,
+                                                     want_w, want_b, want_gx16)
+        return ((gx if need[0] else None), ((gx16 if ctx.addend16 else gx) if need[1] else None), None, dw, db, None,
+                None, None, None, None)
+
+
+def merge_ln_amp_native(plan, x, addend, size, norm, drop: bool = False, log_size: bool = False):
+    """merge_ln_native under autocast (fp32 LayerNorm parameters, a stream of the autocast dtype or fp32), for
+    participants that require grad: (x, y, size or None), y in the autocast dtype."""
+    x_out, y, s_out, log = _MergeLnAmpFunction.apply(x, addend, size, norm.weight, norm.bias, norm.eps, plan, bool(drop),
+                                                     bool(log_size), _abi.autocast_dtype(x.device))
+    if log is not None:
+        s_out._tome_log = log  # (as in merge_ln_native)
+    return x_out, y, s_out
 
 
 class _AddLayerNormAmpFunction(torch.autograd.Function):

@@ -577,8 +577,11 @@ def _ln_route(merge: Optional[Callable], x: torch.Tensor, norm, residual, size=N
     """How merge_wavg_ln / drop_ln below run: "direct" (the fused launch: no gradient wanted), "function" (the same
     launch as tome/_ln.py::_MergeLnFunction, tome_merge_ln_backward behind it), "amp_direct" (under autocast, tensors of
     the kind _abi._ln_amp_of describes and no gradient wanted: tome_merge_wavg_ln_amp / tome_drop_ln_amp, while
-    tome._ln.NATIVE_LN_AUTOCAST is on) or None: the three unfused steps.  Without autocast the answers are those of the
-    first three alone.
+    tome._ln.NATIVE_LN_AUTOCAST is on), "amp_function" (under autocast with a gradient wanted of a participant other than
+    the sizes, where _abi.merge_ln_amp_trainable holds: the same launches as tome/_ln.py::_MergeLnAmpFunction,
+    tome_merge_ln_backward_amp behind them, while tome._ln.NATIVE_MERGE_LN_AUTOCAST_BACKWARD -- off by default --,
+    NATIVE_LN_AUTOCAST and _ln.enabled() hold) or None: the three unfused steps.  Without autocast the answers are those
+    of the first three alone.
     merge: the callable that carries the plan; None asks about the tensors alone, before the matching exists (the patched
     blocks: tome/patch/_common.py::fused_route).  The device is asked by each answer's own predicate in _abi."""
     from . import _ln
@@ -598,9 +601,12 @@ def _ln_route(merge: Optional[Callable], x: torch.Tensor, norm, residual, size=N
                 and _abi.ln_amp_fusable(x, norm, residual)):
             return _ln.AMP_DIRECT
         return None
-    if not same_dtype:
-        return None
     if size is not None and _wants_autograd(size):
+        return None
+    if (_ln.NATIVE_MERGE_LN_AUTOCAST_BACKWARD and _ln.NATIVE_LN_AUTOCAST and _ln.enabled()
+            and _abi.autocast_dtype(x.device) is not None and _abi.merge_ln_amp_trainable(x, norm, residual, merge)):
+        return _ln.AMP_FUNCTION
+    if not same_dtype:
         return None
     return "function" if _ln.enabled() and _abi.merge_ln_trainable(x, norm, residual, merge) else None
 
@@ -615,7 +621,9 @@ def merge_wavg_ln(merge: Callable, x: torch.Tensor, size: Optional[torch.Tensor]
     requires grad, a hybrid or partition matching, fp32 tokens, a LayerNorm subclass under grad, CPU tensors -- runs the
     three steps, so there always is an answer.  Under torch.autocast, with an fp32 LayerNorm, a 16-bit or fp32 x and no
     gradient wanted, the launch is tome_merge_wavg_ln_amp (`_ln_route`: "amp_direct"): y comes back in the autocast dtype,
-    x and size are those of the three steps bit for bit."""
+    x and size are those of the three steps bit for bit; with a gradient wanted and
+    tome._ln.NATIVE_MERGE_LN_AUTOCAST_BACKWARD on it is the same launch as a Function with tome_merge_ln_backward_amp
+    behind it ("amp_function")."""
     from . import _ln
     how = _ln_route(merge, x, norm, residual, size)
     if how == "direct":
@@ -626,6 +634,8 @@ def merge_wavg_ln(merge: Callable, x: torch.Tensor, size: Optional[torch.Tensor]
                                       _abi.autocast_dtype(x.device), addend=residual, log_size=log_size)
     if how == "function":
         return _ln.merge_ln_native(merge.plan, x, residual, size, norm, log_size=log_size)
+    if how == _ln.AMP_FUNCTION:
+        return _ln.merge_ln_amp_native(merge.plan, x, residual, size, norm, log_size=log_size)
     if residual is not None:
         x = x + residual
     x, size = merge_wavg(merge, x, size, log_size=log_size)
@@ -636,7 +646,8 @@ def drop_ln(drop: Callable, x: torch.Tensor, norm, residual: Optional[torch.Tens
             ) -> Tuple[torch.Tensor, torch.Tensor]:
     """``x = x + residual; x = drop(x); y = norm(x)`` for the callable of bipartite_soft_matching_drop: returns (x, y).
     Routed as merge_wavg_ln: tome_drop_ln, with tome_merge_ln_backward behind it under grad, tome_drop_ln_amp under
-    autocast without grad ("amp_direct"), else the three steps."""
+    autocast without grad ("amp_direct") and, behind tome._ln.NATIVE_MERGE_LN_AUTOCAST_BACKWARD, with
+    tome_merge_ln_backward_amp behind it under grad ("amp_function"), else the three steps."""
     from . import _ln
     how = _ln_route(drop, x, norm, residual)
     if how == "direct":
@@ -646,6 +657,8 @@ def drop_ln(drop: Callable, x: torch.Tensor, norm, residual: Optional[torch.Tens
                                 addend=residual)
     if how == "function":
         return _ln.merge_ln_native(drop.plan, x, residual, None, norm, drop=True)[:2]
+    if how == _ln.AMP_FUNCTION:
+        return _ln.merge_ln_amp_native(drop.plan, x, residual, None, norm, drop=True)[:2]
     if residual is not None:
         x = x + residual
     x = drop(x)

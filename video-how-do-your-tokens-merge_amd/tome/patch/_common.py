@@ -488,21 +488,28 @@ def fused_route(kind, x, norm, residual, info):
     """How a flat-layout layer runs `x + residual`, its reduction of `kind` (fused_kind) and `norm` as ONE launch, asked
     before the matching exists: "direct" (tome_merge_wavg_ln / tome_drop_ln: 16-bit tokens, nothing wants a gradient),
     "function" (the same launch as tome/_ln.py::_MergeLnFunction: TRAIN_FUSED_LN, a participant wants one),
-    _ln.AMP_DIRECT (tome_merge_wavg_ln_amp / tome_drop_ln_amp: AUTOCAST_FUSED_LN under autocast, nothing wants one), or
-    None: the three steps.  residual: what the launch would read beside x (None: x is the finished sum).
-    The two switched answers are tome.merge._ln_route's rule about the tensors, asked without a matching; the patch
-    layer's own gates go on top: the Function covers the kinds "merge" and "drop" and sizes as the previous launch left
-    them, neither answer tracks sources, and both want a clamped r > 0 up front (their launches have no r == 0 form)."""
+    _ln.AMP_DIRECT (tome_merge_wavg_ln_amp / tome_drop_ln_amp: AUTOCAST_FUSED_LN under autocast, nothing wants one),
+    _ln.AMP_FUNCTION (the same two launches as tome/_ln.py::_MergeLnAmpFunction, tome_merge_ln_backward_amp behind them:
+    tome._ln.NATIVE_MERGE_LN_AUTOCAST_BACKWARD under autocast, a participant wants one), or None: the three steps.
+    residual: what the launch would read beside x (None: x is the finished sum).
+    The switched answers are tome.merge._ln_route's rule about the tensors, asked without a matching; the patch
+    layer's own gates go on top: the Functions cover the kinds "merge" and "drop" and sizes as the previous launch left
+    them, no switched answer tracks sources, and all want a clamped r > 0 up front (their launches have no r == 0
+    form)."""
     r_list = info["r"]
     if not (_FUSE_LN and kind is not None and r_list and r_list[0] > 0):
         return None
-    if (TRAIN_FUSED_LN or AUTOCAST_FUSED_LN) and not info["trace_source"]:
+    train_amp = _ln.NATIVE_MERGE_LN_AUTOCAST_BACKWARD
+    if (TRAIN_FUSED_LN or AUTOCAST_FUSED_LN or train_amp) and not info["trace_source"]:
         size = info["size"]
         if torch.is_grad_enabled() and _abi.needs_grad(x, residual, norm.weight, norm.bias):
             want = TRAIN_FUSED_LN and kind != "hybrid" and "function"
             if size is not None and (size.device != x.device or size.shape != (x.shape[0], x.shape[1], 1)):
                 want = False
-            addend = residual  # (the Function reads the residual itself, whatever _FUSE_ADD says)
+            elif (train_amp and kind != "hybrid" and _abi.autocast_dtype(x.device) is not None
+                  and tm._ln_route(None, x, norm, residual, size) == _ln.AMP_FUNCTION):
+                want = _ln.AMP_FUNCTION  # (fp32 LayerNorm parameters under autocast: never the 16-bit Function's tensors)
+            addend = residual  # (the Functions read the residual themselves, whatever _FUSE_ADD says)
         else:
             want = AUTOCAST_FUSED_LN and _abi.autocast_dtype(x.device) is not None and _ln.AMP_DIRECT
             addend = residual if _FUSE_ADD else None  # (else the framework adds first, and the sum is asked again)
@@ -528,6 +535,10 @@ _LAUNCH = {
         log_size=info["prop_attn"]),
     (_ln.AMP_DIRECT, True): lambda m, x, info, norm, addend, fold: _abi.drop_ln_amp(
         m.plan, x, norm.weight, norm.bias, norm.eps, _abi.autocast_dtype(x.device), addend=addend),
+    # (the public calls route once more, now with the plan: _MergeLnAmpFunction while the switch holds)
+    (_ln.AMP_FUNCTION, False): lambda m, x, info, norm, addend, fold: tm.merge_wavg_ln(
+        m, x, info["size"], norm, addend, log_size=info["prop_attn"]),
+    (_ln.AMP_FUNCTION, True): lambda m, x, info, norm, addend, fold: tm.drop_ln(m, x, norm, addend),
 }
 
 
@@ -551,12 +562,13 @@ def merge_then_norm(metric, x, info, norm, reduction_function, plain_merge_fn, r
     Anything else runs the steps as the reference does.
     fold: the Linear that finishes the block (`foldable`); when the 16-bit launch runs in plain 'merge' mode (_fold_for), x
     comes back with that bias added (y is the norm of x without it) and info["_folded"] says so for finish_linear.  The
-    Function and the mixed-precision launch ignore it: their stream is the one the three steps store."""
+    Functions and the mixed-precision launch ignore it: their stream is the one the three steps store.  Both Functions
+    read the residual themselves."""
     kind = fused_kind(info["mode"], reduction_function is plain_merge_fn,
                       drop_fn is not None and reduction_function is drop_fn,
                       hybrid_fn is not None and reduction_function is hybrid_fn)
     how = fused_route(kind, x, norm, residual, info)
-    if residual is not None and how != "function":
+    if residual is not None and how != "function" and how != _ln.AMP_FUNCTION:
         # the launch reads the residual as its addend; the 16-bit one only an addend of x's dtype, without source tracking
         # and with a clamped r > 0.  Else the framework adds first, and the sum -- another tensor -- is asked again
         as_addend = how is not None and _FUSE_ADD and (how != "direct" or (
