@@ -40,8 +40,18 @@
 #endif
 
 #define ATS_BIAS_GROUP 4  // tiles per bias load (power of two; 2 * GROUP * 64 words of LDS)
-template <typename TX, bool BIAS>
-__global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, int nitems) {
+// Two forms.  PAIR = false: 208-221 registers, one workgroup per CU, a software pipeline inside the wave (tile t's
+// scores and weights around tile t-1's PV product).  PAIR = true: held to 128 registers (__launch_bounds__(512, 4):
+// four waves per SIMD) so that TWO workgroups share a CU -- four waves per SIMD from two unrelated barriers, one
+// workgroup's softmax under the other's MFMAs.  What gives the registers back:
+//   * no start values -m (16 registers): the scores start at the constant 0 and -m_ref rides on the matrix pipe, two
+//     channels of the extra k-step that the bias already takes (ref_step; att_split16) -- the reference point IS what
+//     those two channels carry, the first tile's and the general path's weights are taken against the same value;
+//   * no V fragments held from one step to the next (16): a tile's PV product is taken in the step that staged it,
+//     each fragment read right before its MFMA pair (a slot is only safe to read in the step that wrote it), so
+//     nothing of tile t-1 is live while tile t's scores are formed either (packed P: 8).
+template <typename TX, bool BIAS, bool PAIR>
+__global__ __launch_bounds__(512, PAIR ? 4 : 2) void k_prop_attention_stream(AttnArgs a, int nitems) {
     constexpr int WAVES = 8;
     constexpr int ATT_BM = 32 * WAVES;
     __shared__ __attribute__((aligned(16))) short lds_k[ATT_SLOTS][ATT_BN * ATT_KS];
@@ -98,6 +108,14 @@ __global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, in
     // (32-bit: 64 rows of at most 2^24 elements -- the host checks the strides)
     const unsigned koff = (unsigned)(((int64_t)r0 * a.k_sn + 8 * c0) * 2), koff_p = (unsigned)(((int64_t)rp * a.k_sn + 8 * c0) * 2);
     const unsigned voff = (unsigned)(((int64_t)r0 * a.v_sn + 8 * c0) * 2), voff_p = (unsigned)(((int64_t)rp * a.v_sn + 8 * c0) * 2);
+#define ATS_TID_AGAIN(t)                        \
+    int t = tid;                                \
+    asm volatile("" : "+v"(t))
+    // PAIR: a slot's offset kept a scalar (folded into the address arithmetic it becomes a multiply-add whose constant
+    // needs a vector register of its own, one per stride, through the whole loop)
+    auto slot_off = [&](int o) __attribute__((always_inline)) -> int {
+        return __builtin_amdgcn_readfirstlane(o);
+    };
     uint4 kreg, vreg;
     unsigned breg = 0u;
     int r_sub = 0, b_par = 0, b_off = 0;  // BIAS: the staged tile's place in its group, the group buffer in use
@@ -126,8 +144,17 @@ __global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, in
     // never used)
     auto stream_load = [&]() __attribute__((always_inline)) {
         const bool part = s_t >= nfull;  // wave-uniform
-        kreg = *reinterpret_cast<const uint4 *>(s_kt + (part ? koff_p : koff));
-        vreg = *reinterpret_cast<const uint4 *>(s_vt + (part ? voff_p : voff));
+        if constexpr (PAIR) {
+            // (the four offsets above and the two LDS addresses below, formed again from the thread number in every
+            // step: ~10 vector instructions against six registers held through the tile loop)
+            ATS_TID_AGAIN(t);
+            const unsigned r = min(t >> 3, (part ? max(nk - nfull * ATT_BN, 1) : ATT_BN) - 1), c16 = 16 * (t & 7);
+            kreg = *reinterpret_cast<const uint4 *>(s_kt + (r * (unsigned)(k_tile >> 6) + c16));
+            vreg = *reinterpret_cast<const uint4 *>(s_vt + (r * (unsigned)(v_tile >> 6) + c16));
+        } else {
+            kreg = *reinterpret_cast<const uint4 *>(s_kt + (part ? koff_p : koff));
+            vreg = *reinterpret_cast<const uint4 *>(s_vt + (part ? voff_p : voff));
+        }
         // BIAS: the per-key term of ATS_BIAS_GROUP tiles at a time, one key per thread -- staging it tile by tile
         // put ~25 instructions per step on wave 0 alone, and every wave waits for the slowest at the barrier
         // (measured: 10 % of the kernel)
@@ -152,8 +179,14 @@ __global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, in
     };
     short *const wk = &lds_k[0][0] + r0 * ATT_KS + 8 * c0, *const wv = &lds_v[0][0] + r0 * ATT_VS + 8 * c0;
     auto stage_write = [&](int S) __attribute__((always_inline)) {
-        *reinterpret_cast<uint4 *>(wk + S * ATT_BN * ATT_KS) = kreg;
-        *reinterpret_cast<uint4 *>(wv + S * ATT_BN * ATT_VS) = vreg;
+        if constexpr (PAIR) {
+            ATS_TID_AGAIN(t);
+            *reinterpret_cast<uint4 *>(&lds_k[0][0] + slot_off(S * ATT_BN * ATT_KS) + (t >> 3) * ATT_KS + 8 * (t & 7)) = kreg;
+            *reinterpret_cast<uint4 *>(&lds_v[0][0] + slot_off(S * ATT_BN * ATT_VS) + (t >> 3) * ATT_VS + 8 * (t & 7)) = vreg;
+        } else {
+            *reinterpret_cast<uint4 *>(wk + S * ATT_BN * ATT_KS) = kreg;
+            *reinterpret_cast<uint4 *>(wv + S * ATT_BN * ATT_VS) = vreg;
+        }
         if (BIAS) {  // (wave-uniform) a tile that opens a group brings the group's bias words along
             if (r_sub == 0) {
                 b_par ^= 1;
@@ -166,6 +199,12 @@ __global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, in
     // ---- per-item state of the computing side
     const int lrow0 = wave * 32 + col;  // this lane's query row inside a block
     const int q_sn = (int)a.q_sn, o_sn = (int)a.o_sn;  // (< 2^24: host)
+    // PAIR: what only the step between two items computes from the lane number (Q and output addresses, row numbers)
+    // starts from an opaque copy of it there: hoisted out of the item loop, those ~20 values per lane would have to
+    // live through the tile loop, where there is no register for them
+#define ATS_LANE_AGAIN(l)                       \
+    int l = lane;                               \
+    if constexpr (PAIR) asm volatile("" : "+v"(l))
     int c_qb = 0;             // the item's query block
     short *c_o = nullptr;     // where its output block starts
     int qrow = 0;
@@ -180,15 +219,17 @@ __global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, in
     auto q_request = [&]() __attribute__((always_inline)) {
         t_qb = n_qb;
         t_o = n_o;
-        const int lrow = max(min(lrow0, nq - 1 - t_qb * ATT_BM), 0);
-        const short *qp = n_q + lrow * q_sn + 8 * hf;
+        ATS_LANE_AGAIN(ln);
+        const int lrow = max(min(PAIR ? wave * 32 + (ln & 31) : lrow0, nq - 1 - t_qb * ATT_BM), 0);
+        const short *qp = n_q + lrow * q_sn + 8 * (PAIR ? ln >> 5 : hf);
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) qraw[ks] = *reinterpret_cast<const uint4 *>(qp + 16 * ks);
     };
     auto item_take = [&]() __attribute__((always_inline)) {
         c_qb = t_qb;
         c_o = t_o;
-        qrow = c_qb * ATT_BM + lrow0;
+        ATS_LANE_AGAIN(ln);
+        qrow = c_qb * ATT_BM + (PAIR ? wave * 32 + (ln & 31) : lrow0);
         active = c_qb * ATT_BM + wave * 32 < nq;  // wave-uniform
         bfac = (bias_skip && qrow == 0) ? 0.0f : 1.0f;
     };
@@ -197,7 +238,7 @@ __global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, in
         for (int ks = 0; ks < 4; ++ks) {
             att_s16x8 raw;
             __builtin_memcpy(&raw, &qraw[ks], 16);
-            qf[ks] = att_scaled<TX>(raw, sl);
+            qf[ks] = att_scaled<TX>(raw, PAIR ? fresh()->scale * LOG2E : sl);
         }
     };
 
@@ -233,6 +274,37 @@ __global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, in
         s0 = AttMfma<TX>::run(f0, fq, s0);
         s1 = AttMfma<TX>::run(f1, fq, s1);
     };
+    // PAIR: that k-step also brings the reference point -- channels 0, 1 as above (BIAS), the next two channels K side
+    // 1, Q side qref = -m_ref as hi | lo << 16 (0 while a softmax looks for its maximum).  Without a bias the step
+    // exists for the reference point alone: 2 MFMAs per tile on the pipe that is not binding.
+    unsigned qref = 0u;
+    auto ref_set = [&](float m) __attribute__((always_inline)) -> float {  // -> the reference point the step carries
+        float carried;
+        const unsigned w = att_split16<TX>(-m, carried);
+        qref = w;
+        return -carried;
+    };
+    auto ref_step = [&](unsigned ref, bool first_half_only, int col, int hf) __attribute__((always_inline)) {
+        ref = hf ? 0u : ref;
+        const unsigned one = (unsigned)(unsigned short)att_bits<TX>(1.0f), ones = hf ? 0u : (one | (one << 16));
+        uint4 q5, k0, k1;
+        if (BIAS) {
+            const unsigned w0 = lds_bias[0][b_off + col], w1 = lds_bias[0][b_off + 32 + col];
+            const unsigned bf = (unsigned)(unsigned short)att_bits<TX>(bfac);
+            q5 = make_uint4(hf ? 0u : (bf | (bf << 16)), ref, 0u, 0u);
+            k0 = make_uint4(hf ? 0u : w0, ones, 0u, 0u);
+            k1 = make_uint4(hf ? 0u : w1, ones, 0u, 0u);
+        } else {
+            q5 = make_uint4(ref, 0u, 0u, 0u);
+            k0 = k1 = make_uint4(ones, 0u, 0u, 0u);
+        }
+        att_s16x8 fq, f0, f1;
+        __builtin_memcpy(&fq, &q5, 16);
+        __builtin_memcpy(&f0, &k0, 16);
+        __builtin_memcpy(&f1, &k1, 16);
+        s0 = AttMfma<TX>::run(f0, fq, s0);
+        if (!first_half_only) s1 = AttMfma<TX>::run(f1, fq, s1);
+    };
     auto scores = [&](int S, const att_f32x16 &cinit, bool first_half_only) __attribute__((always_inline)) {
         const short *kt = &lds_k[0][0] + S * ATT_BN * ATT_KS;
         s0 = cinit;
@@ -241,26 +313,48 @@ __global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, in
         att_rows_block<TX>(kt, col, hf, 0, qf, s0);
         if (!first_half_only) att_rows_block<TX>(kt, col, hf, 1, qf, s1);
     };
+    // PAIR: the scores of the tile in slot S minus the reference point in `ref` (qref, or 0), from the constant 0
+    auto scores_ref = [&](int S, unsigned ref, bool first_half_only) __attribute__((always_inline)) {
+        ATS_LANE_AGAIN(ln);  // (the lane's place in the fragments formed again: see q_request)
+        const int col = ln & 31, hf = ln >> 5;
+        const short *kt = &lds_k[0][0] + slot_off(S * ATT_BN * ATT_KS);
+#pragma unroll
+        for (int v = 0; v < 16; ++v) s0[v] = s1[v] = 0.0f;
+        ref_step(ref, first_half_only, col, hf);
+        att_rows_block<TX>(kt, col, hf, 0, qf, s0);
+        if (!first_half_only) att_rows_block<TX>(kt, col, hf, 1, qf, s1);
+    };
     att_s16x8 pf[2][2];
     // general softmax of tile t from scores that start at zero: range mask, maximum, rescale of O and l
     auto general_softmax = [&](int t, int S) __attribute__((always_inline)) {
-        att_f32x16 zero;
+        if constexpr (PAIR) {
+            scores_ref(S, 0u, false);
+            ATS_LANE_AGAIN(ln);
+            att_general_softmax_at<TX>(s0, s1, t * ATT_BN + 4 * (ln >> 5), nk, m_run, l_run, o0, o1, pf, ref_set);
+        } else {
+            att_f32x16 zero;
 #pragma unroll
-        for (int v = 0; v < 16; ++v) zero[v] = 0.0f;
-        scores(S, zero, false);
-        att_general_softmax<TX>(s0, s1, t * ATT_BN + 4 * hf, nk, m_run, l_run, o0, o1, negm, pf);
+            for (int v = 0; v < 16; ++v) zero[v] = 0.0f;
+            scores(S, zero, false);
+            att_general_softmax<TX>(s0, s1, t * ATT_BN + 4 * hf, nk, m_run, l_run, o0, o1, negm, pf);
+        }
     };
     // the first tile of an item (full: an item has at least two tiles): nothing to rescale, nothing to mask --
     // m = the tile's row maximum, P = exp2(s - m), l = the row sum
     auto first_softmax = [&](int S) __attribute__((always_inline)) {
-        att_f32x16 zero;
+        if constexpr (PAIR) {
+            scores_ref(S, 0u, false);
+        } else {
+            att_f32x16 zero;
 #pragma unroll
-        for (int v = 0; v < 16; ++v) zero[v] = 0.0f;
-        scores(S, zero, false);
+            for (int v = 0; v < 16; ++v) zero[v] = 0.0f;
+            scores(S, zero, false);
+        }
         float mt = fmaxf(s0[0], s1[0]);
 #pragma unroll
         for (int v = 1; v < 16; ++v) mt = fmaxf(mt, fmaxf(s0[v], s1[v]));
         mt = att_half_max(mt);
+        if constexpr (PAIR) mt = ref_set(mt);  // (the value the later tiles' scores will have had subtracted)
         float lsum = 0.0f;
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
@@ -276,6 +370,36 @@ __global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, in
     };
     auto pv = [&](bool first_half_only) __attribute__((always_inline)) {
         att_tr_mfma_tile<TX>(vfr, pf, first_half_only, o0, o1);
+    };
+    // PAIR: O += V P of the tile in slot S, in the step that staged it
+    auto pv_slot = [&](int S, bool first_half_only) __attribute__((always_inline)) {
+        ATS_LANE_AGAIN(ln);
+        att_tr_tile_product<TX>(att_tr_base(&lds_v[0][0], ln, 0) + slot_off(S * ATT_BN * ATT_VS), pf, first_half_only, o0, o1);
+    };
+    // PAIR: one step inside an item, nothing carried from the step before but O, l and the reference point: tile tn ->
+    // slot S, the stream's next tile requested, ONE barrier, S(tn) - m_ref, P(tn), the guard, O += V(tn) P(tn)
+    auto pair_step = [&](int S, int tn, bool masked) __attribute__((always_inline)) {
+        stage_write(S);
+        stream_load();
+        __syncthreads();
+        // (priority on the score product, not on the weights as in fast_step: with four waves on the SIMD the wave
+        // that has just passed its barrier gets its reads and MFMAs in first and the others' softmax fills in behind
+        // -- measured at 384 x 12 x 1568 with the bias: 3.64 ms against 3.73 with the priority on the weights, 3.70
+        // with none)
+        __builtin_amdgcn_s_setprio(1);
+        scores_ref(S, qref, masked && last_half);
+        __builtin_amdgcn_s_setprio(0);
+        ATS_LANE_AGAIN(ln);
+        const float lsum = att_fast_weights<TX>(s0, s1, masked, tn * ATT_BN + 4 * (ln >> 5), nk, pf);
+        const float l_before = l_run;
+        l_run += lsum;
+#ifndef ATS_NOGUARD
+        if (__builtin_amdgcn_ballot_w64(!(lsum <= AttLimit<TX>::value)) != 0) {  // (fast_step's guard)
+            l_run = l_before;
+            general_softmax(tn, S);
+        }
+#endif
+        pv_slot(S, masked && last_half);
     };
     // one pipelined step inside an item: tile tn (in the staging registers) -> slot S, the stream's next tile
     // requested, ONE barrier, S(tn) and O += V(tn-1) P(tn-1), then P(tn) against the item's reference point
@@ -334,18 +458,21 @@ __global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, in
     // own (row stride 144 B, the K tile's conflict-free stride) and leaves as whole 128-byte rows: 8 rows per store
     // instruction.  LDS operations of one wave execute in order: no barrier.
     auto store_item = [&]() __attribute__((always_inline)) {
-        const float l_tot = l_run + __shfl_xor(l_run, 32);
+        const float l_tot = PAIR ? att_half_sum(l_run) : l_run + __shfl_xor(l_run, 32);
         const float inv = __builtin_amdgcn_rcpf(l_tot);  // (1 ulp; the result is rounded to 8 or 11 bits)
+        ATS_LANE_AGAIN(ln);  // (PAIR: see q_request; the other form keeps the values it holds)
+#define ATS_SI_LANE (PAIR ? ln : lane)
         short *ow = &lds_o[0][0] + wave * (32 * ATT_KS);
         // (att_store_row's exchange: the lower lanes end up with channels 8g .. 8g+7, the upper with 32+8g .. 32+8g+7)
-        att_store_row<TX>(ow + col * ATT_KS + 32 * hf, true, o0, o1, inv);
+        att_store_row<TX>(ow + (PAIR ? ln & 31 : col) * ATT_KS + 32 * (PAIR ? ln >> 5 : hf), true, o0, o1, inv);
         const int rows = nq - c_qb * ATT_BM - wave * 32;  // rows of this wave inside the sequence (>= 1: active)
-        short *op = c_o + (wave * 32 + (lane >> 3)) * o_sn + 8 * (lane & 7);
+        short *op = c_o + (wave * 32 + (ATS_SI_LANE >> 3)) * o_sn + 8 * (ATS_SI_LANE & 7);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const uint4 row16 = *reinterpret_cast<const uint4 *>(ow + ((lane >> 3) + 8 * i) * ATT_KS + 8 * (lane & 7));
-            if ((lane >> 3) + 8 * i < rows) *reinterpret_cast<uint4 *>(op + 8 * i * o_sn) = row16;
+            const uint4 row16 = *reinterpret_cast<const uint4 *>(ow + ((ATS_SI_LANE >> 3) + 8 * i) * ATT_KS + 8 * (ATS_SI_LANE & 7));
+            if ((ATS_SI_LANE >> 3) + 8 * i < rows) *reinterpret_cast<uint4 *>(op + 8 * i * o_sn) = row16;
         }
+#undef ATS_SI_LANE
     };
     // first item of a workgroup: nothing is in flight yet
     auto cold_start = [&](int L) __attribute__((always_inline)) {
@@ -360,7 +487,8 @@ __global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, in
         __syncthreads();
         if (active) {
             first_softmax(0);
-            v_fragments(0);
+            if constexpr (PAIR) pv_slot(0, false);
+            else v_fragments(0);
         }
     };
 
@@ -373,8 +501,13 @@ __global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, in
         // ---- steps inside the item: tiles 1 .. ntiles-1 (tile tn -> slot (par + tn) & 1)
         if (active) {
             int tn = 1;
-            for (; tn < nfull; ++tn) fast_step((par + tn) & 1, tn, false);
-            if (tn < ntiles) fast_step((par + tn) & 1, tn, true);  // the partly filled last tile
+            if constexpr (PAIR) {
+                for (; tn < nfull; ++tn) pair_step((par + tn) & 1, tn, false);
+                if (tn < ntiles) pair_step((par + tn) & 1, tn, true);
+            } else {
+                for (; tn < nfull; ++tn) fast_step((par + tn) & 1, tn, false);
+                if (tn < ntiles) fast_step((par + tn) & 1, tn, true);  // the partly filled last tile
+            }
         } else {
             for (int tn = 1; tn < ntiles; ++tn) helper_step((par + tn) & 1);
         }
@@ -393,6 +526,15 @@ __global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, in
         const int next = item + G;
         const bool has_next = item_ok(next);  // workgroup-uniform
         const int Sn = (par + ntiles) & 1;
+        if constexpr (PAIR) {
+            // (the last item leaves here: behind this point the compiler knows that the Q rows requested below are
+            // the only ones alive -- left to the two `has_next` tests further down it carries the previous item's 16
+            // raw Q registers through the whole tile loop)
+            if (!has_next) {
+                if (active) store_item();
+                return;
+            }
+        }
         if (has_next) {
             stage_write(Sn);
             q_request();    // (the stream is at the next item since two steps)
@@ -400,7 +542,7 @@ __global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, in
         }
         const bool was_active = active;
         if (was_active) {
-            pv(last_half);
+            if constexpr (!PAIR) pv(last_half);
             store_item();
             ATS_STAMP(2);  // stores issued
             if (!has_next) return;
@@ -418,7 +560,8 @@ __global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, in
         ATS_STAMP(4);  // Q fragment ready
         if (active) {
             first_softmax(Sn);
-            v_fragments(Sn);
+            if constexpr (PAIR) pv_slot(Sn, false);
+            else v_fragments(Sn);
         }
         ATS_STAMP(5);  // first tile's weights
 #ifdef ATT_DIAG
@@ -426,3 +569,5 @@ __global__ __launch_bounds__(512, 2) void k_prop_attention_stream(AttnArgs a, in
 #endif
     }
 }
+#undef ATS_LANE_AGAIN
+#undef ATS_TID_AGAIN

@@ -71,6 +71,20 @@ template <typename TX> __device__ __forceinline__ short att_bits(float f) {
     return s;
 }
 
+// x as two terms hi + lo of the 16-bit format, packed hi | lo << 16: what a value costs to ride on the matrix pipe (two
+// channels of a k-step against a constant 1).  `carried` = hi + lo, exact in fp32 (16 significant bits at most; what
+// is left of x is below 2^-16 |x| for bf16, 2^-22 |x| for fp16 above its subnormals).
+template <typename TX> __device__ __forceinline__ unsigned att_split16(float x, float &carried) {
+    const short bh = att_bits<TX>(x);
+    TX th, tl;
+    __builtin_memcpy(&th, &bh, 2);
+    const float hi = to_f32(th);
+    const short bl = att_bits<TX>(x - hi);
+    __builtin_memcpy(&tl, &bl, 2);
+    carried = hi + to_f32(tl);
+    return (unsigned)(unsigned short)bh | ((unsigned)(unsigned short)bl << 16);
+}
+
 // workgroup L -> (item, block): the `blocks` blocks of one item get ids congruent mod 8, i.e. one XCD, whose L2 then
 // serves the K/V (forward, dq), Q/dO (dkv) or Q rows (resident: the blocks are the segments) they all stream.
 // False: L lies past the last of `count` items.
@@ -210,6 +224,23 @@ __device__ __forceinline__ void att_tr_mfma_tile(const att_s16x4 (&vfr)[2][2][4]
     }
 }
 
+// The same products with every fragment read right before its MFMA pair (4 registers of fragments live instead of a
+// tile's 16): for a kernel that multiplies the tile in the step that staged it and has other waves to cover the reads.
+template <typename TX>
+__device__ __forceinline__ void att_tr_tile_product(const short *vs, const att_s16x8 (&pf)[2][2], bool first_half_only,
+                                                    att_f32x16 &o0, att_f32x16 &o1) {
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+        if (kb == 1 && first_half_only) break;
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            att_s16x4 f0, f1, f2, f3;
+            att_tr_read(vs + (32 * kb + 16 * p) * ATT_VS, f0, f1, f2, f3);
+            att_tr_mfma<TX>(f0, f1, f2, f3, pf[kb][p], o0, o1);
+        }
+    }
+}
+
 // Rows of a block past the end: register v holds row row0 + (v & 3) + 8 (v >> 2), row0 = the block's first row + 4 hf;
 // rows >= n get `fill` (-inf in front of a maximum, 0 for a weight).
 __device__ __forceinline__ void att_fill_tail(att_f32x16 &s, int row0, int n, float fill) {
@@ -221,6 +252,13 @@ __device__ __forceinline__ float att_half_max(float mt) {
     const unsigned mb = __float_as_uint(mt);
     const auto sw = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);
     return fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
+}
+// own + partner of the same lane pair (the same bits as own + __shfl_xor(own, 32): the addition commutes), without the
+// lane number a shuffle needs
+__device__ __forceinline__ float att_half_sum(float x) {
+    const unsigned xb = __float_as_uint(x);
+    const auto sw = __builtin_amdgcn_permlane32_swap(xb, xb, false, false);
+    return __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
 }
 // Keys past nk masked to -inf, then the column maximum of the 64-key tile (s0: keys key0 + ..., s1: 32 further on;
 // key0 = the tile's first key + 4 hf) or of one 32-key block.
@@ -289,7 +327,32 @@ __device__ __forceinline__ float att_fast_weights(att_f32x16 &s0, att_f32x16 &s1
 }
 
 // General softmax of a 64-key tile whose scores (s0, s1) started at zero: range mask, maximum, rescale of O and l,
-// the new reference point as the start values -m of the scores to come (negm), weights and their fragments.
+// weights and their fragments.  The new reference point is ref(maximum so far): the value the caller can subtract from
+// the scores to come (the maximum itself, or the nearest value it can carry on the matrix pipe); it ends up in m_run.
+template <typename TX, typename Ref>
+__device__ __forceinline__ void att_general_softmax_at(att_f32x16 &s0, att_f32x16 &s1, int key0, int nk, float &m_run,
+                                                       float &l_run, att_f32x16 &o0, att_f32x16 &o1,
+                                                       att_s16x8 (&pf)[2][2], Ref &&ref) {
+    const float mt = att_masked_max(s0, s1, key0, nk);
+    const float m_new = ref(fmaxf(m_run, mt));  // finite: every tile holds at least one key in range
+    const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+    float lsum = 0.0f;
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+        s0[v] = __builtin_amdgcn_exp2f(s0[v] - m_new);
+        s1[v] = __builtin_amdgcn_exp2f(s1[v] - m_new);
+        lsum += s0[v] + s1[v];
+    }
+    l_run = l_run * alpha + lsum;
+    m_run = m_new;
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+        o0[v] *= alpha;
+        o1[v] *= alpha;
+    }
+    att_pack_tile<TX>(s0, s1, pf);
+}
+// The same with the reference point at the maximum, handed on as the start values -m of the scores to come (negm).
 template <typename TX>
 __device__ __forceinline__ void att_general_softmax(att_f32x16 &s0, att_f32x16 &s1, int key0, int nk, float &m_run,
                                                     float &l_run, att_f32x16 &o0, att_f32x16 &o1, att_f32x16 &negm,

@@ -1276,7 +1276,8 @@ static int dispatch_attn(int dtype, bool bias, F &&f, Bad &&bad) {
 // TOME_ATTN_* variables are measurement switches, read per call and not cached: the tests force each form on small
 // inputs.
 enum AttnKernel { ATTN_RESIDENT, ATTN_STREAM, ATTN_PLAIN };
-struct AttnForm { AttnKernel kernel; int waves; };  // waves: per workgroup of the plain kernel, 4 or 8
+// waves: per workgroup of the plain kernel, 4 or 8; pair: the persistent kernel's 128-register form, -1 = by launch size
+struct AttnForm { AttnKernel kernel; int waves; int pair; };
 static AttnForm attn_form(const AttnArgs &a, int64_t B, int64_t H, int64_t N, int64_t Nk, int64_t nseg) {
     const char *re = getenv("TOME_ATTN_RESIDENT"), *we = getenv("TOME_ATTN_WAVES"), *se = getenv("TOME_ATTN_STREAM");
     // Short key sequences (TimeSformer's 1 + p <= 197 tokens per frame, Motionformer's <= 196 keys per frame segment):
@@ -1285,7 +1286,7 @@ static AttnForm attn_form(const AttnArgs &a, int64_t B, int64_t H, int64_t N, in
     // (the kernel addresses the tokens of one (batch, head) slice with 32-bit element offsets)
     const bool off32 = N * a.q_sn < (1ll << 31) && Nk * a.k_sn < (1ll << 31) && Nk * a.v_sn < (1ll << 31) &&
                        N * a.o_sn < (1ll << 31);
-    if (Nk <= RES_ROWS && off32 && !(re && re[0] == '0')) return AttnForm{ATTN_RESIDENT, 0};
+    if (Nk <= RES_ROWS && off32 && !(re && re[0] == '0')) return AttnForm{ATTN_RESIDENT, 0, 0};
     // queries per workgroup: 256 (eight waves share every staged K/V tile: staging costs 18 % with four) unless the
     // sequence is short.  (Measured: 5, 6 or 7 waves per workgroup, chosen to leave no part-empty last block, are
     // 10-30 % slower per block than eight -- uneven staging passes and SIMD load -- and lose more than they save.)
@@ -1304,8 +1305,11 @@ static AttnForm attn_form(const AttnArgs &a, int64_t B, int64_t H, int64_t N, in
     // level at 16 x 12 x 197 and below, where the launch is the cost; the 4-wave persistent form was built and
     // measured too: 17-20 % slower than this one at 197 .. 1568 tokens, not kept)
     const bool stream_ok = Nk > ATT_BN && sn_ok && !(se && se[0] == '0');
-    if (stream_ok && (waves == 8 || (!waves_env && N > 128))) return AttnForm{ATTN_STREAM, waves};
-    return AttnForm{ATTN_PLAIN, waves};
+    // TOME_ATTN_STREAM=2 / =1: the persistent kernel as two 128-register workgroups per CU
+    // (k_prop_attention_stream<.., true>) / as one workgroup per CU, whatever the launch size
+    const int pair = (se && se[0] == '2') ? 1 : (se && se[0] == '1') ? 0 : -1;
+    if (stream_ok && (waves == 8 || (!waves_env && N > 128))) return AttnForm{ATTN_STREAM, waves, pair};
+    return AttnForm{ATTN_PLAIN, waves, 0};
 }
 
 static int prop_attention_impl(const void *q, const void *k, const void *v, int dtype, int64_t B, int64_t H,
@@ -1374,10 +1378,31 @@ static int prop_attention_impl(const void *q, const void *k, const void *v, int 
             return n / 8 * 8;
         }();
         const int nitems = (int)(bh8 * ((N + 255) / 256));
-        const dim3 pgrid((unsigned)(nitems < cus ? nitems : cus));
+        // Two workgroups per CU (four waves per SIMD from two unrelated barriers, one workgroup's softmax under the
+        // other's MFMAs: tome_attn_stream.h, PAIR) take the launches that have items for more than one workgroup per
+        // CU.  Measured at 384 x 12 x 1568 / 1392 alone: 3.64 / 2.98 ms against 3.80 / 3.20 with the bias, where the
+        // reference point rides for nothing on the k-step the bias takes anyway, and 3.47 / 2.87 against 3.39 / 2.81
+        // without, where it costs two MFMAs per tile of its own; inside the VideoMAE forward (no bias, the matching
+        // on the side stream) every one of the twelve layers' launches is 0.4-4 % shorter in the pair form and the
+        // benchmark 0.9-1.3 % faster (profiles/attention_pair_ab.txt).
+        const bool pair = form.pair < 0 ? nitems > cus : form.pair != 0;
+        // TOME_ATTN_GRID: the persistent kernels' workgroup count (a measurement switch like the three above; rounded
+        // down to the multiple of 8 the item numbering needs) -- one workgroup per CU for the pair form, or a handful
+        // of workgroups that each walk many items of a small input
+        int wgs = pair ? 2 * cus : cus;
+        if (const char *ge = getenv("TOME_ATTN_GRID")) {
+            const int g = atoi(ge) / 8 * 8;
+            if (g >= 8) wgs = g;
+        }
+        const dim3 pgrid((unsigned)(nitems < wgs ? nitems : wgs));
         return dispatch_attn(dtype, log_size != nullptr, [&](auto tx, auto bias) {
-            hipLaunchKernelGGL((k_prop_attention_stream<typename decltype(tx)::type, decltype(bias)::value != 0>), pgrid,
-                               dim3(512), 0, st, a, nitems);
+            using TX = typename decltype(tx)::type;
+            constexpr bool BIAS = decltype(bias)::value != 0;
+            if (pair) {
+                hipLaunchKernelGGL((k_prop_attention_stream<TX, BIAS, true>), pgrid, dim3(512), 0, st, a, nitems);
+                return check_launch("k_prop_attention_stream<.., true>");
+            }
+            hipLaunchKernelGGL((k_prop_attention_stream<TX, BIAS, false>), pgrid, dim3(512), 0, st, a, nitems);
             return check_launch("k_prop_attention_stream");
         }, bad_dtype);
     }
