@@ -28,10 +28,13 @@ FORMS = {
     "resident": {},
     "wave4": {"TOME_ATTN_RESIDENT": "0", "TOME_ATTN_WAVES": "4"},
     "wave8": {"TOME_ATTN_RESIDENT": "0", "TOME_ATTN_WAVES": "8", "TOME_ATTN_STREAM": "0"},
-    "stream": {"TOME_ATTN_RESIDENT": "0", "TOME_ATTN_WAVES": "8"},
+    "stream": {"TOME_ATTN_RESIDENT": "0", "TOME_ATTN_WAVES": "8", "TOME_ATTN_STREAM": "1"},
+    "pair": {"TOME_ATTN_RESIDENT": "0", "TOME_ATTN_WAVES": "8", "TOME_ATTN_STREAM": "2"},
 }
 FORM_KERNEL = {"resident": "k_resident_attention", "wave4": "k_prop_attention<.., 4, ..>",
-               "wave8": "k_prop_attention<.., 8, ..>", "stream": "k_prop_attention_stream"}
+               "wave8": "k_prop_attention<.., 8, ..>", "stream": "k_prop_attention_stream<.., PAIR = false>",
+               "pair": "k_prop_attention_stream<.., PAIR = true>"}
+ATT_LIMIT_LOG2 = {torch.bfloat16: 60.0, torch.float16: 15.0}  # log2 of AttLimit (tome_attn_tile.h): the overflow guard
 
 
 def unit_roundoff(dtype) -> float:
@@ -44,10 +47,13 @@ def unit_roundoff(dtype) -> float:
 
 
 def expected_form(N: int, Nk: int, items: int, env: Optional[dict] = None, off32: bool = True,
-                  sn_ok: bool = True) -> str:
-    """Which launch form attn_form (csrc/tome_kernels.hip) gives prop_attention_impl for N queries against Nk keys per item,
-    items = B * H * nseg, under the switches in `env`.  off32: the resident kernel's 32-bit token offsets fit (N and
-    Nk times the token strides < 2^31); sn_ok: every token stride < 2^22 (the stream kernel's 32-bit tile offsets)."""
+                  sn_ok: bool = True, cus: int = 256) -> str:
+    """Which launch form attn_form and prop_attention_impl (csrc/tome_kernels.hip) give N queries against Nk keys per
+    item, items = B * H * nseg, under the switches in `env`.  off32: the resident kernel's 32-bit token offsets fit (N
+    and Nk times the token strides < 2^31); sn_ok: every token stride < 2^22 (the stream kernel's 32-bit tile offsets).
+    cus: the device's compute units -- the persistent kernel runs as two 128-register workgroups per CU ("pair") when
+    TOME_ATTN_STREAM=2 says so or, with that switch unset, when the launch has more items (query blocks of 256 rows,
+    the slices rounded up to a multiple of 8) than CUs (rounded down to one); TOME_ATTN_STREAM=1 keeps one per CU."""
     env = env or {}
     res = env.get("TOME_ATTN_RESIDENT", "")
     if Nk <= RES_ROWS and off32 and not res.startswith("0"):
@@ -57,7 +63,11 @@ def expected_form(N: int, Nk: int, items: int, env: Optional[dict] = None, off32
     waves = waves_env or (8 if N > 128 and items * ((N + 255) // 256) >= 1024 else 4)
     se = env.get("TOME_ATTN_STREAM", "")
     if Nk > ATT_BN and sn_ok and not se.startswith("0") and (waves == 8 or (not waves_env and N > 128)):
-        return "stream"
+        if se.startswith("2"):
+            return "pair"
+        if se.startswith("1"):
+            return "stream"
+        return "pair" if ((items + 7) // 8 * 8) * ((N + 255) // 256) > cus // 8 * 8 else "stream"
     return "wave8" if waves == 8 else "wave4"
 
 
@@ -78,11 +88,18 @@ def channel_of(B: int, H: int, Nk: int, enc: str, device="cpu") -> torch.Tensor:
     return (base.view(1, 1, Nk) + rot) % 64
 
 
-def onehot_values(B: int, H: int, Nk: int, enc: str, dtype, device="cpu") -> torch.Tensor:
-    """v[b, h, j] = e_c, c = channel_of(...)[b, h, j].  -> [B, H, Nk, 64] of `dtype`"""
+def onehot_values(B: int, H: int, Nk: int, enc: str, dtype, device="cpu",
+                  gain: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """v[b, h, j] = e_c, c = channel_of(...)[b, h, j] -- or gain[j] * e_c (gain [Nk]: powers of two that `dtype`
+    holds exactly, see weighted_reference).  -> [B, H, Nk, 64] of `dtype`"""
     chan = channel_of(B, H, Nk, enc, device)
     v = torch.zeros(B, H, Nk, 64, dtype=dtype, device=device)
-    v.scatter_(-1, chan.unsqueeze(-1), 1.0)
+    if gain is None:
+        v.scatter_(-1, chan.unsqueeze(-1), 1.0)
+    else:
+        g16 = gain.to(device=device, dtype=dtype)
+        assert gain.shape == (Nk,) and torch.equal(g16.double().cpu(), gain.double().cpu()), "gain not exact in dtype"
+        v.scatter_(-1, chan.unsqueeze(-1), g16.view(1, 1, Nk, 1).expand(B, H, Nk, 1))
     return v
 
 
@@ -173,7 +190,8 @@ def log2_bias(log_bias: Optional[torch.Tensor], skip: bool, N: int, Nk: int, dev
 
 
 def weighted_reference(q: torch.Tensor, k: torch.Tensor, log_bias: Optional[torch.Tensor], skip: bool, scale: float,
-                       v_enc: str, nseg: int = 1, beta: Optional[torch.Tensor] = None) -> Reference:
+                       v_enc: str, nseg: int = 1, beta: Optional[torch.Tensor] = None,
+                       gain: Optional[torch.Tensor] = None) -> Reference:
     """fp64 attention of q [B, H, N, 64] against k [B, H, nseg * P, 64] with one-hot values of encoding `v_enc`: the
     output channel c of a row is the weight mass of the keys of channel c over the row's total.  Logits in log2
     units from the exact 16-bit Q~ (kernel_q) and k, plus log_bias * log2 e from the exact fp32 log_bias
@@ -187,7 +205,10 @@ def weighted_reference(q: torch.Tensor, k: torch.Tensor, log_bias: Optional[torc
         pipe as two 16-bit terms hi + lo: the residual is below u^2 |x| (u = 2^-8: 2^-16; fp16 2^-22, plus 2^-25
         absolute where lo is subnormal).  A weight then carries a factor 2^e, |e| <= u^2 (|m| + |bias|) + ..., and a
         channel's share moves by at most 2 ln2 |e| (numerator and row sum).  |m| <= max |logit| of the row.
-    beta: a log2-unit bias [B or 1, 1, N, Nk] to use instead of log_bias (the tests' deliberately wrong biases)."""
+    beta: a log2-unit bias [B or 1, 1, N, Nk] to use instead of log_bias (the tests' deliberately wrong biases).
+    gain: float64 [Nk], powers of two -- key j's value is gain[j] * e_c (onehot_values(gain=...)), so the channel mass
+      is sum w_j gain[j] over the unchanged row total: a key whose weight is 2^-65 of the row's largest still shows
+      in its channel (staircase_inputs).  `weights` stay the plain w_j."""
     B, H, N, D = q.shape
     Nk = k.shape[2]
     assert Nk % nseg == 0 and not (skip and nseg != 1)
@@ -203,7 +224,8 @@ def weighted_reference(q: torch.Tensor, k: torch.Tensor, log_bias: Optional[torc
     w = torch.exp2(s - s.amax(-1, keepdim=True))
     chan = channel_of(B, H, Nk, v_enc, q.device).view(B, H, nseg, P)
     idx = chan.unsqueeze(2).expand(B, H, N, nseg, P)
-    mass = torch.zeros(B, H, N, nseg, 64, dtype=torch.float64, device=q.device).scatter_add_(-1, idx, w)
+    wv = w if gain is None else w * gain.to(q.device).double().view(nseg, P)
+    mass = torch.zeros(B, H, N, nseg, 64, dtype=torch.float64, device=q.device).scatter_add_(-1, idx, wv)
     ref = mass / w.sum(-1, keepdim=True)                      # [B, H, N, nseg, 64]
     rho, tau = (u * u, 0.0) if dt == torch.bfloat16 else (u * u, 2.0 ** -25)
     smax = s.abs().amax(-1, keepdim=True)
@@ -229,7 +251,11 @@ def weighted_bound(ref_c: torch.Tensor, dtype, nk: int, eta=2.0 ** -16) -> torch
     floor: fp16 has no range below 2^-24 -- weights under it are flushed and subnormal ones lose their relative
     precision, at most 2^-24 each; the reference point of every kernel is a key's own logit, so l >= 1 and the flushed
     mass of a channel is at most nk * 2^-24 of the output.  bf16 has fp32's range: a floor of 1e-6 for what
-    underflows nowhere in practice.  A channel with no keys is exactly 0 (0 * P16 sums to 0)."""
+    underflows nowhere in practice.  A channel with no keys is exactly 0 (0 * P16 sums to 0).
+    Values gain * e_c (weighted_reference's `gain`) need no further term: a power of two times P16 is exact in the
+    fp32 product (the staircase keeps it inside fp32's range), the channel is still a sum of positive terms, whose
+    fp32 accumulation error stays relative to the sum, and the rescaling by alpha = exp2(m_old - m_new) when the
+    reference point moves multiplies O and l alike (one v_exp_f32 and one product each per move: inside eta)."""
     u = unit_roundoff(dtype)
     floor = nk * 2.0 ** -24 if dtype == torch.float16 else 1e-6
     return (2 * u + eta) * ref_c + floor
@@ -271,3 +297,63 @@ def sensitivity(ref: Reference, dtype) -> float:
     live = (mass > 0) & (mass < W)
     assert bool(live.any()), "no channel where a single key shows"
     return float((delta / bound)[live].min())
+
+
+# ---- a reference point that has to move ---------------------------------------------------------------------------
+
+def staircase_inputs(B: int, H: int, N: int, Nk: int, dtype, step: int, generator: torch.Generator):
+    """Inputs whose logits climb by `step` log2 units (at scale 1/8) from one 64-key tile to the next, so that the
+    first pass's reference point (tile 0's maximum) falls behind by more than the 16-bit weights hold and has to move
+    -- and values that keep every tile visible in the result all the same:
+      q = 8 d + 0.05 noise along a unit direction d per (b, h); k_j = (step * (j // 64) / log2 e) d + 0.05 noise;
+      bf16: gain[j] = 2^(step * (ntiles - 1 - j // 64)), for onehot_values / weighted_reference -- tile t's weights are
+        ~2^(-step (ntiles - 1 - t)) of the last tile's, its values that much larger: every key contributes about
+        equally to its channel, and a factor lost between the tiles before and after a move of the reference point
+        shows in every channel;
+      fp16: gain = None -- its range (65504) cannot hold the gains; with a channel per tile ("tile") its 2u = 2^-10
+        and floor still show the tiles within two steps of the last one.
+    Drawn on the generator's device.  -> q [B, H, N, 64], k [B, H, Nk, 64] of `dtype`, gain float64 [Nk] or None"""
+    assert float(step).is_integer() and step > 0
+    dev = generator.device
+    d = torch.randn(B, H, 1, 64, generator=generator, device=dev)
+    d = d / d.norm(dim=-1, keepdim=True)
+    tile = torch.arange(Nk, device=dev) // ATT_BN
+    ntiles = (Nk + ATT_BN - 1) // ATT_BN
+    q = (8.0 * d + 0.05 * torch.randn(B, H, N, 64, generator=generator, device=dev)).to(dtype)
+    amp = (float(step) / LOG2E) * tile.float().view(1, 1, Nk, 1)
+    k = (amp * d + 0.05 * torch.randn(B, H, Nk, 64, generator=generator, device=dev)).to(dtype)
+    gain = torch.exp2(float(step) * (ntiles - 1 - tile).double()) if dtype == torch.bfloat16 else None
+    return q, k, gain
+
+
+def rise(ref: Reference) -> float:
+    """The smallest, over the rows, of (largest logit of the last tile) - (largest logit of tile 0), in log2 units,
+    read from the reference's weights (log2 w = logit - row maximum).  Above log2(AttLimit) the lane that holds the
+    row's largest key of the last tile sums >= 2^rise there against tile 0's reference point: a guard that has not
+    tripped before the last tile must trip in it."""
+    w = ref.weights
+    assert w.shape[3] == 1, "one softmax per row"
+    lw = torch.log2(w[:, :, :, 0])
+    last0 = (ref.nk - 1) // ATT_BN * ATT_BN
+    return float((lw[..., last0:].amax(-1) - lw[..., :ATT_BN].amax(-1)).min())
+
+
+def tile_visibility(ref: Reference, gain: Optional[torch.Tensor], dtype, tiles=None) -> float:
+    """The smallest, over the rows, the 64-key tiles (all, or `tiles`) and the channels a tile touches, of that
+    tile's contribution to the channel (sum of w_j gain[j] over its keys of the channel, over the row total) divided
+    by the channel's bound; > 1: no tile can go missing, or be scaled away, inside the bound."""
+    w, chan = ref.weights, ref.chan
+    B, H, N, S, P = w.shape
+    assert S == 1
+    wv = w[:, :, :, 0] if gain is None else w[:, :, :, 0] * gain.to(w.device).double()
+    W = w[:, :, :, 0].sum(-1, keepdim=True)
+    bound = weighted_bound(ref.out, dtype, P, ref.eta).permute(0, 2, 1, 3)   # [B, H, N, 64]
+    ntiles = (P + ATT_BN - 1) // ATT_BN
+    worst = float("inf")
+    for t in (range(ntiles) if tiles is None else tiles):
+        lo, hi = t * ATT_BN, min((t + 1) * ATT_BN, P)
+        idx = chan[:, :, 0, lo:hi].unsqueeze(2).expand(B, H, N, hi - lo)
+        part = torch.zeros(B, H, N, 64, dtype=torch.float64, device=w.device).scatter_add_(-1, idx, wv[..., lo:hi] / W)
+        touched = torch.zeros(B, H, N, 64, dtype=torch.bool, device=w.device).scatter_(-1, idx, True)
+        worst = min(worst, float((part / bound)[touched].min()))
+    return worst

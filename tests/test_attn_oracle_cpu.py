@@ -2,7 +2,9 @@
 attention -- a key dropped, counted twice, a tile dropped, the size bias on the neighbouring key, the TimeSformer
 form's class query or class key biased, another batch's or head's values -- computed in fp64 and rounded to the
 16-bit format as a kernel would, must all fail the checks the GPU tests apply (test_attention_accounting_gpu.py),
-and the correct output must pass them.  So those tests catch these bug classes at the shapes they run."""
+and the correct output must pass them.  So those tests catch these bug classes at the shapes they run.  Also here:
+the mirror of the dispatcher's rule (five launch forms), the grids of the GPU tests against it, and the conditions
+that make the staircase inputs (a reference point that has to move) a check and not a formality."""
 import pytest
 import torch
 
@@ -191,8 +193,25 @@ def test_expected_form_mirrors_the_dispatcher():
     f = A.expected_form
     assert f(197, 197, 64 * 12) == "resident" and f(1568, 196, 2 * 12 * 8) == "resident"
     assert f(1, 225, 24) == "wave4" and f(1, 1569, 24) == "wave4"       # Motionformer's class query, > 224 keys
-    assert f(1568, 1568, 6) == "stream" and f(1568, 1568, 8 * 12) == "stream"  # N > 128: streamed either way
+    assert f(1568, 1568, 6) == "stream" and f(1568, 1568, 8 * 12, cus=1024) == "stream"  # N > 128: streamed either way
+    assert f(1568, 1568, 8 * 12) == "pair"                              # 96 x 7 = 672 items > 256 CUs: two per CU
     assert f(128, 1568, 6) == "wave4" and f(129, 1568, 6) == "stream"
+    # the persistent kernel's two forms: by the switch ...
+    one, two = {"TOME_ATTN_STREAM": "1"}, {"TOME_ATTN_STREAM": "2"}
+    assert f(1568, 1568, 8 * 12, one) == "stream" and f(1568, 1568, 6, two) == "pair"
+    assert f(1568, 64, 6, dict(two, TOME_ATTN_RESIDENT="0")) == "wave4"  # (one tile: the switch picks no kernel)
+    assert f(128, 1568, 6, two) == "wave4" and f(128, 1568, 6, dict(two, TOME_ATTN_WAVES="8")) == "pair"
+    assert f(33, 700, 6, A.FORMS["pair"]) == "pair" and f(33, 700, 6, A.FORMS["stream"]) == "stream"
+    # ... or by the launch size: items = slices rounded up to 8, times the 256-row query blocks, against the CUs
+    # rounded down to 8
+    assert f(300, 300, 128) == "stream" and f(300, 300, 129) == "pair"   # 2 x 128 = 256 items; 2 x 136
+    assert f(256, 300, 256) == "stream" and f(257, 300, 256) == "pair"   # one query block of 256 rows; two
+    assert f(200, 300, 249) == "stream" and f(200, 300, 250, cus=255) == "pair"   # 256 items; 255 CUs count as 248
+    assert f(200, 300, 248, cus=255) == "stream" and f(200, 300, 249, cus=255) == "pair"
+    assert f(200, 300, 256, cus=263) == "stream" and f(200, 300, 256, cus=264) == "stream"
+    assert f(200, 300, 257, cus=263) == "pair" and f(200, 300, 257, cus=264) == "stream"   # 264 items
+    off = {"TOME_ATTN_STREAM": "0"}
+    assert f(300, 300, 6, off) == "wave4" and f(300, 300, 1024, off) == "wave8"
     assert f(1568, 64, 6, {"TOME_ATTN_RESIDENT": "0"}) == "wave4"       # one tile: never streamed
     assert f(1568, 64, 1024, {"TOME_ATTN_RESIDENT": "0"}) == "wave8"
     env8 = A.FORMS["stream"]
@@ -204,9 +223,99 @@ def test_expected_form_mirrors_the_dispatcher():
 
 
 def test_gpu_grids_reach_every_launch_form():
-    """The parametrisation of the GPU tests covers all four kernels (what their ids name is what the dispatcher
-    picks: expected_form)."""
+    """The parametrisation of the GPU tests covers all five launch forms (what their ids name is what the dispatcher
+    picks: expected_form) in every grid; the walk grid the two persistent kernels, the only ones that walk."""
     import test_attention_accounting_gpu as G
-    for grid in (G.COUNT_GRID, G.WEIGHT_GRID):
+    import test_hip_parity
+    assert set(A.FORMS) == set(A.FORM_KERNEL) == {"resident", "wave4", "wave8", "stream", "pair"}
+    for grid in (G.COUNT_GRID, G.WEIGHT_GRID, G.OUT_GRID, G.MOTIONFORMER_GRID, G.SEGMENT_GRID):
         assert {p.values[2] for p in grid} == set(A.FORMS)
+    assert {p.values[1] for p in test_hip_parity.RERUN_GRID} == set(A.FORMS)
+    assert {p.values[3] for p in G.STAIR_GRID} == set(A.FORMS)
+    assert {p.values[2] for p in G.WALK_GRID} == {"stream", "pair"}
     assert {(N, Nk) for N, Nk, _ in (p.values for p in G.COUNT_GRID)} == set(G.COUNT_SHAPES)
+    assert {(N, Nk) for N, Nk, _ in (p.values for p in G.WALK_GRID)} == set(G.WALK_SHAPES)
+    # every form's switches pin it: no form is left to the size of the launch
+    for form, env in A.FORMS.items():
+        if form != "resident":
+            for items in (6, 24, 4096):
+                assert A.expected_form(300, 300, items, env) == form, (form, items)
+    # wherever the one-workgroup-per-CU form is reachable, so is the pair form
+    for grid in (G.COUNT_GRID, G.WEIGHT_GRID, G.OUT_GRID, G.MOTIONFORMER_GRID, G.SEGMENT_GRID):
+        by_form = {f: {p.values[:2] for p in grid if p.values[2] == f} for f in ("stream", "pair")}
+        assert by_form["stream"] == by_form["pair"] and by_form["pair"]
+
+
+def test_gain_scales_the_values_not_the_weights():
+    """gain = ones is the reference without it, bit for bit; a two-key case by hand."""
+    q, k, sizes = _inputs(5, 200, torch.bfloat16, 77, 1.0)
+    lb = sizes.log()
+    plain = A.weighted_reference(q, k, lb, False, 0.125, "mod")
+    ones = A.weighted_reference(q, k, lb, False, 0.125, "mod", gain=torch.ones(200, dtype=torch.float64))
+    for a, b in zip(plain, ones):
+        assert a == b if isinstance(a, int) else torch.equal(a, b)
+    assert torch.equal(A.onehot_values(B, H, 200, "mod", torch.bfloat16),
+                       A.onehot_values(B, H, 200, "mod", torch.bfloat16, gain=torch.ones(200, dtype=torch.float64)))
+    # two keys, q = 0, sizes 1 and 3 (weights 1/3 and 1 against the row maximum), gains 8 and 2: channel of key 0
+    # holds (1/3 * 8) / (4/3) = 2, that of key 1 (1 * 2) / (4/3) = 1.5 -- batch 0, head 0: channels 0 and 1
+    q0 = torch.zeros(1, 1, 1, 64, dtype=torch.bfloat16)
+    k2 = torch.randn(1, 1, 2, 64, generator=torch.Generator().manual_seed(1)).bfloat16()
+    gain = torch.tensor([8.0, 2.0], dtype=torch.float64)
+    ref = A.weighted_reference(q0, k2, torch.tensor([[1.0, 3.0]]).log(), False, 0.125, "mod", gain=gain)
+    want = torch.zeros(64, dtype=torch.float64)
+    want[0], want[1] = 2.0, 1.5
+    assert torch.allclose(ref.out[0, 0, 0], want, rtol=1e-7, atol=0.0)   # (fp32 log of 3: not the exact 3)
+    assert torch.allclose(ref.weights.flatten(), torch.tensor([1 / 3, 1.0], dtype=torch.float64), rtol=1e-7)
+    v = A.onehot_values(1, 1, 2, "mod", torch.bfloat16, gain=gain)
+    assert v[0, 0, 0, 0] == 8.0 and v[0, 0, 1, 1] == 2.0 and float(v.sum()) == 10.0
+    with pytest.raises(AssertionError, match="not exact"):
+        A.onehot_values(1, 1, 2, "mod", torch.float16, gain=torch.tensor([2.0 ** 30, 1.0], dtype=torch.float64))
+
+
+def _stair_inputs():
+    """(dtype, step, Nk, walk) of every input set test_reference_point_moves_every_form runs."""
+    import test_attention_accounting_gpu as G
+    return sorted({(p.values[0], p.values[1], p.values[2], bool(p.values[4])) for p in G.STAIR_GRID}, key=str)
+
+
+@pytest.mark.parametrize("dtype,step,Nk,walk", _stair_inputs(),
+                         ids=lambda v: {torch.bfloat16: "bf16", torch.float16: "fp16"}.get(v, str(v)))
+def test_staircase_inputs_meet_their_conditions(dtype, step, Nk, walk):
+    """The very tensors of the GPU test (drawn on the CPU there too), without a bias and with integer sizes:
+    (a) rise > log2(AttLimit) (60 / 15: AttLimit in csrc/tome_attn_tile.h) -- the guard has to trip;
+    (b) every tile's contribution to every channel it touches exceeds the channel's bound (tile_visibility > 1);
+    (c) the reference rounded to the 16-bit format passes check_weighted;
+    (d) rejected by check_weighted: every tile before tile T weighted by 2^0.25 against the rest (what a reference
+        point that lost u |m| = 0.25 at |m| = 64 between the two sides of a move gives), T the last tile and the one
+        before it; one whole tile left out, each tile in turn.
+    bf16 (gains): all of it under the "mod" encoding, where every channel collects a key of every tile, and under
+    "tile".  fp16 (unit values, so tile t weighs 2^(-step (ntiles - 1 - t)) of the last): (b) and (d) under "tile",
+    a channel per tile, for the last three tiles -- what is more than two steps behind the last tile is below the
+    format's floor nk 2^-24 whatever the encoding.  Under "mod" every channel is the same mix of tiles when the
+    values are all 1, a factor between tiles cancels against the row total, and only (a) and (c) are asserted."""
+    import test_attention_accounting_gpu as G
+    _, _, q, k, gain, sizes = G.staircase_case(dtype, step, Nk, walk)
+    ntiles = (Nk + 63) // 64
+    bf16 = dtype == torch.bfloat16
+    for lb in (None, sizes.log()):
+        right = A.log2_bias(lb, False, G.STAIR_N, Nk)
+        for enc in ("mod", "tile"):
+            ref = A.weighted_reference(q, k, lb, False, 0.125, enc, gain=gain)
+            assert A.rise(ref) > A.ATT_LIMIT_LOG2[dtype]                                          # (a)
+            assert A.check_weighted(ref.out.to(dtype), ref, "correct") <= 1.0                     # (c)
+            if not bf16 and enc == "mod":
+                continue
+            seen = range(ntiles) if bf16 else range(ntiles - 3, ntiles)
+            assert A.tile_visibility(ref, gain, dtype, seen) > 1.0                                # (b)
+            for T in (ntiles - 1, ntiles - 2):                                                    # (d)
+                beta = right.clone()
+                beta[..., :64 * T] += 0.25
+                wrong = A.weighted_reference(q, k, None, False, 0.125, enc, beta=beta, gain=gain)
+                with pytest.raises(AssertionError):
+                    A.check_weighted(wrong.out.to(dtype), ref, f"tiles before {T} at 2^0.25")
+            for t in seen:
+                beta = right.clone()
+                beta[..., 64 * t:64 * (t + 1)] -= 1e9
+                wrong = A.weighted_reference(q, k, None, False, 0.125, enc, beta=beta, gain=gain)
+                with pytest.raises(AssertionError):
+                    A.check_weighted(wrong.out.to(dtype), ref, f"tile {t} left out")
