@@ -5,8 +5,18 @@
 The reference's `tome.patch.{videomae,timesformer,motionformer}` and the slowfast model files they patch
 are imported from /root/reference with the missing third-party modules (timm, fvcore, torchvision, ...)
 replaced by minimal in-memory stand-ins that provide only names (no arithmetic): the arithmetic that
-produces the fixtures is the reference's own.  ViViT cannot be imported (installed transformers lacks
-VivitSelfAttention) and has no block-level fixture.
+produces the fixtures is the reference's own.
+
+ViViT: the reference's `tome/patch/vivit.py` imports `VivitLayer` / `VivitAttention` / `VivitSelfAttention` of
+transformers 4.x, which the installed transformers no longer has, and slowfast's `ViViT` wrapper.
+Both names are pointed at tests/golden/vivit_tree.py, a plain module tree with the 4.x layout that
+tests/test_vivit_tree_cpu.py (and `assert_tree_is_hf` here, before any ViViT fixture is stored) holds to the
+installed `VivitForVideoClassification`: same weights, same logits.  The patch replaces every `forward` on the
+path (layer, attention, self-attention) and brings `vivit_merge / drop / hybrid`: that arithmetic is the
+reference's own.  The leaf modules it calls (Linear, LayerNorm, the activation, the residual add of VivitOutput)
+are the tree's.  ViViT is the one family whose matching runs with class_token=True in-model; before a ViViT
+fixture is stored, row 0 must be a source in no layer and the same clip traced with class_token=False must give
+other indices (`assert_class_token_matters`).
 
 Per model the fixture (models_<name>.npz) holds: the logits of the patched forward, the final token sizes and
 per layer the matching's indices; the manifest holds the clip seed, the weight seed (weights are filled by
@@ -16,7 +26,8 @@ run's upstream GEMMs differ from CPU in the last bits, so margins must be wide).
 
 Three groups of fixtures (see `specs` in main): embed 32 / head dim 16 (generic kernels), embed 128 / head dim 64
 (the production path: tome_match_keys on the qkv buffer's keys in-model) with proportional attention on and off,
-and `apply_duplicate_patch` (videomae.py:154-157, timesformer.py:170-172, motionformer.py:230-232) per family.
+and `apply_duplicate_patch` (videomae.py:154-157, timesformer.py:170-172, motionformer.py:230-232, vivit.py:207-211)
+per family.
     python tests/golden/generate_models.py [fixture names ...]     # no names: all of them
 A run with names carries every other manifest entry over and refuses to start if it would leave a models_<name>.npz
 without one (check_partial_run).
@@ -52,6 +63,21 @@ def install_stubs():
         m.__path__ = [path] if path else []
         sys.modules[name] = m
         return m
+
+    # The installed transformers' own ViViT and the stand-in tree (which takes its activation from transformers) are
+    # imported FIRST, in front of the name-only torchvision below, which transformers would trip over; the real classes
+    # are kept for assert_tree_is_hf.
+    global HF_VIVIT
+    try:
+        from transformers import VivitConfig as hf_config, VivitForVideoClassification as hf_model
+        from transformers.activations import ACT2FN
+        importlib.import_module("transformers.models.vivit")
+        HF_VIVIT = (hf_config, hf_model)
+    except Exception:  # no transformers, or one without ViViT: no comparison possible (assert_tree_is_hf says so)
+        HF_VIVIT = None
+    import vivit_tree
+    if HF_VIVIT is not None:
+        assert vivit_tree._gelu_fast is ACT2FN["gelu_fast"] or type(vivit_tree._gelu_fast) is type(ACT2FN["gelu_fast"])
 
     pkg("slowfast", os.path.join(REF, "slowfast"))
     pkg("slowfast.models", os.path.join(REF, "slowfast", "models"))
@@ -99,6 +125,81 @@ def install_stubs():
     tvu.make_grid = tvu.save_image = None  # names only
     sys.modules["torchvision.utils"] = tvu
     tv.utils = tvu
+    # ViViT: the two modules tome/patch/vivit.py imports its base classes from, names only, pointing at the stand-in tree
+    if HF_VIVIT is None:
+        for name in ("transformers", "transformers.models", "transformers.models.vivit"):
+            if name not in sys.modules:
+                pkg(name)
+    mv = types.ModuleType("transformers.models.vivit.modeling_vivit")
+    mv.VivitLayer, mv.VivitAttention, mv.VivitSelfAttention = (vivit_tree.VivitLayer, vivit_tree.VivitAttention,
+                                                               vivit_tree.VivitSelfAttention)
+    sys.modules["transformers.models.vivit.modeling_vivit"] = mv
+    sb = types.ModuleType("slowfast.models.vivit_video_model_builder")
+    sb.ViViT = vivit_tree.ViViT
+    sys.modules["slowfast.models.vivit_video_model_builder"] = sb
+
+
+HF_VIVIT = None
+
+
+def assert_tree_is_hf(build, embed):
+    """The UNPATCHED stand-in tree of a ViViT fixture configuration, with the fixture's weights, gives the logits of the
+    installed transformers' ViViT (rename map and tolerances of tests/test_vivit_host_vs_hf.py).  Skipped, loudly, where
+    transformers has no ViViT."""
+    if HF_VIVIT is None:
+        print("assert_tree_is_hf: no ViViT in the installed transformers, the tree is NOT compared", flush=True)
+        return
+    hf_config, hf_model = HF_VIVIT
+    model, cfg, clip_shape, wseed = build(embed)
+    synth.fill_parameters(model, wseed)
+    hf = hf_model(hf_config(image_size=cfg["image_size"], num_frames=cfg["num_frames"], tubelet_size=cfg["tubelet_size"],
+                            hidden_size=embed, num_hidden_layers=cfg["depth"], num_attention_heads=cfg["num_heads"],
+                            intermediate_size=cfg["intermediate_size"], num_labels=cfg["num_classes"],
+                            hidden_act="gelu_fast", layer_norm_eps=cfg["layer_norm_eps"], qkv_bias=cfg["qkv_bias"],
+                            attn_implementation="eager")).eval()
+
+    def to_tree(k):
+        k = k.replace("vivit.layers.", "vivit.encoder.layer.")
+        for a, b in ((".attention.q_proj.", ".attention.attention.query."), (".attention.k_proj.", ".attention.attention.key."),
+                     (".attention.v_proj.", ".attention.attention.value."), (".attention.o_proj.", ".attention.output.dense."),
+                     (".mlp.fc1.", ".intermediate.dense."), (".mlp.fc2.", ".output.dense.")):
+            k = k.replace(a, b)
+        return k
+    mine = model.state_dict()
+    theirs = {k: mine[to_tree(k)] for k in hf.state_dict()}
+    assert len(theirs) == len(mine) and {to_tree(k) for k in theirs} == set(mine)
+    hf.load_state_dict(theirs)
+    clip = clip_of(clip_shape, [1, 2])
+    with torch.no_grad():
+        want = hf(pixel_values=clip.permute(0, 2, 1, 3, 4)).logits
+        got = model([clip])
+    torch.testing.assert_close(got, want, rtol=1e-4, atol=1e-5)
+    print(f"assert_tree_is_hf: embed {embed}: the stand-in tree equals the installed transformers' ViViT "
+          f"(max |diff| {float((got - want).abs().max()):.2e})", flush=True)
+
+
+def assert_class_token_matters(name, patch_mod, model, clip, r, layers):
+    """A ViViT fixture (class_token=True in-model): the protected row 0 is a source in no layer, and the same clip
+    traced with class_token=False gives other indices in at least one layer -- a run that forgot the protection cannot
+    reproduce the fixture."""
+    info = model._tome_info
+    assert info["class_token"] is True, name
+    assert all((l["src"] != 0).all() for l in layers), f"{name}: row 0 is a source"
+    assert all((l["unm"][:, 0] == 0).all() and (np.diff(l["unm"].astype(np.int64), axis=1) > 0).all() for l in layers), name
+    keep = {k: info[k] for k in ("size", "source")}
+    info["class_token"] = False
+    try:
+        _, other = run_traced(patch_mod, model, clip, r)
+    finally:
+        info["class_token"] = True
+        info.update(keep)
+    differ = [i for i, (a, b) in enumerate(zip(layers, other))
+              if any(k in a and (a[k].shape != b[k].shape or not np.array_equal(a[k], b[k])) for k in ("src", "dst", "unm"))]
+    assert differ, f"{name}: class_token=False gives the same indices in every layer"
+    first_src = [i for i, (a, b) in enumerate(zip(layers, other))
+                 if a["src"].shape != b["src"].shape or not np.array_equal(a["src"], b["src"])]
+    print(f"{name}: row 0 a source nowhere; with class_token=False the indices differ in layers {differ} "
+          f"(the sources in layers {first_src})", flush=True)
 
 
 def certificate(metric: torch.Tensor, r: int, cls: bool):
@@ -230,7 +331,10 @@ def emit(name, model, wrapper_info, clip_shape, r, patch_mod, cls, extra, out_di
         seeds.append(best[1])
     out, layers = run_traced(patch_mod, model, clip_of(clip_shape, seeds), r, cls)
     margins = [certificate(l["metric"], l["r"], cls) for l in layers]
-    arrays = {"logits": out.numpy(), "size": wrapper_info()["size"].numpy()}
+    size = wrapper_info()["size"].clone()
+    if cls:
+        assert_class_token_matters(name, patch_mod, model, clip_of(clip_shape, seeds), r, layers)
+    arrays = {"logits": out.numpy(), "size": size.numpy()}
     for i, l in enumerate(layers):
         arrays[f"L{i}_src"], arrays[f"L{i}_dst"], arrays[f"L{i}_unm"] = l["src"], l["dst"], l["unm"]
     np.savez_compressed(os.path.join(out_dir, f"models_{name}.npz"), **arrays)
@@ -462,14 +566,15 @@ def emit_full(out_dir, key, attempts=24, clips=2):
     return meta
 
 
-def emit_mode(name, build, patch_mod, r, mode, prop, out_dir, max_attempts=3000):
+def emit_mode(name, build, patch_mod, r, mode, prop, out_dir, max_attempts=3000, cls=False):
     """A reduced-width fixture of the patch-level DROP / HYBRID glue (tome/patch/videomae.py:102-151,
     timesformer.py:111-185, motionformer.py:172-245): apply_patch(mode=..., trace_source=True[, threshold]) on the
     reference's model, every layer's matching certified (margin > TAU; hybrid: no selected edge within TAU of the
     threshold either).  The hybrid threshold is the median of layer 0's selected edges' scores in a first plain forward of
     the chosen clip, so that some destinations keep their own contribution and some lose it (merge.py:326).  Stored:
     logits, final sizes (drop: the fp32 ones the patch resets them to), the final source matrix (drop: `drop(eye)`),
-    per layer src / unm (/ dst) and, for hybrid, the per-edge keep flags in src_idx order."""
+    per layer src / unm (/ dst) and, for hybrid, the per-edge keep flags in src_idx order.  cls: the family's matching
+    runs with class_token=True (ViViT): certificates with row 0 masked, and assert_class_token_matters."""
     model, cfg, clip_shape, wseed = build(128)
     names = synth.fill_parameters(model, wseed)
     patch_mod.apply_patch(model, prop_attn=prop, mode=mode, trace_source=True, threshold=-1.0)
@@ -478,7 +583,7 @@ def emit_mode(name, build, patch_mod, r, mode, prop, out_dir, max_attempts=3000)
     seeds, thr = [], None
 
     def margins_of(layers, threshold):
-        ms = [certificate(l["metric"], l["r"], False) for l in layers]
+        ms = [certificate(l["metric"], l["r"], cls) for l in layers]
         if threshold is not None:
             for l in layers:
                 sel = l["node_max"].sort(-1, descending=True).values[:, :l["r"]].double()
@@ -514,6 +619,9 @@ def emit_mode(name, build, patch_mod, r, mode, prop, out_dir, max_attempts=3000)
     out, layers = run_traced(patch_mod, model, clip_of(clip_shape, seeds), r, keep_node_max=True)
     margins = margins_of(layers, thr)
     arrays = {"logits": out.numpy(), "size": info["size"].numpy(), "source": info["source"].numpy().astype(np.uint8)}
+    if cls:
+        assert info["class_token"] is True
+        assert_class_token_matters(name, patch_mod, model, clip_of(clip_shape, seeds), r, layers)
     kept = []
     for i, l in enumerate(layers):
         arrays[f"L{i}_src"], arrays[f"L{i}_unm"] = l["src"], l["unm"]
@@ -665,7 +773,7 @@ def record_spread(names, specs):
 
 
 def reduced_families():
-    """name -> (builder(embed) -> (model, cfg, clip shape, weight seed), the reference's patch module, r) of the three
+    """name -> (builder(embed) -> (model, cfg, clip shape, weight seed), the reference's patch module, r) of the four
     reduced-width families.  (After install_stubs.)"""
     vm = importlib.import_module("slowfast.models.videomae_video_model_builder")
     pv = importlib.import_module("tome.patch.videomae")
@@ -673,6 +781,9 @@ def reduced_families():
     pt = importlib.import_module("tome.patch.timesformer")
     mb = importlib.import_module("slowfast.models.motionformer_video_model_builder")
     pm = importlib.import_module("tome.patch.motionformer")
+    vb = importlib.import_module("slowfast.models.vivit_video_model_builder")  # (install_stubs: the stand-in tree)
+    pvv = importlib.import_module("tome.patch.vivit")
+    import vivit_tree as vt
     ln = lambda d: torch.nn.LayerNorm(d, eps=1e-6)  # noqa: E731
 
     def videomae(embed):
@@ -704,7 +815,24 @@ def reduced_families():
         torch.manual_seed(13)
         return mb.Motionformer(mcfg).eval(), cfg, (2, 3, 8, 224, 224), 303
 
-    return {"videomae": (videomae, pv, 5), "timesformer": (timesformer, pt, 6), "motionformer": (motionformer, pm, 5)}
+    def vivit(embed):
+        # 4 x 4 x 4 tubelets + the class token = 65 tokens, r = 5: 65 -> 60 -> 55 -> 50, row 0 protected.  embed_dim /
+        # num_heads / depth are what the tests read (head dimension, block count); the rest is the builder's
+        cfg = dict(image_size=32, num_frames=8, tubelet_size=[2, 8, 8], embed_dim=embed, depth=4, num_heads=2,
+                   intermediate_size=4 * embed, num_classes=10, layer_norm_eps=1e-6, qkv_bias=True)
+        torch.manual_seed(14)
+        tree_cfg = vt.VivitConfig(image_size=cfg["image_size"], num_frames=cfg["num_frames"],
+                                  tubelet_size=cfg["tubelet_size"], hidden_size=embed, num_hidden_layers=cfg["depth"],
+                                  num_attention_heads=cfg["num_heads"], intermediate_size=cfg["intermediate_size"],
+                                  layer_norm_eps=cfg["layer_norm_eps"], qkv_bias=cfg["qkv_bias"])
+        return vb.ViViT(tree_cfg, num_classes=cfg["num_classes"]).eval(), cfg, (2, 3, 8, 32, 32), 404
+
+    return {"videomae": (videomae, pv, 5), "timesformer": (timesformer, pt, 6), "motionformer": (motionformer, pm, 5),
+            "vivit": (vivit, pvv, 5)}
+
+
+# families whose matching runs with class_token=True in-model (apply_patch: `cls_token is not None`, vivit.py:242)
+CLS_FAMILIES = ("vivit",)
 
 
 def main():
@@ -712,10 +840,9 @@ def main():
     torch.manual_seed(0)
     metas = []
     families = reduced_families()
-    # layer-0 r-boundary gap demanded of the three VideoMAE head-dim-64 fixtures (16-bit cosine noise is ~3e-3: the
+    # layer-0 r-boundary gap demanded of the VideoMAE and ViViT head-dim-64 fixtures (16-bit cosine noise is ~3e-3: the
     # bf16 run of these fixtures then has every group's source SET to answer for, not only destinations)
-    L0_GAP = {"videomae_hd64_prop0": 1e-2, "videomae_hd64_prop1": 1e-2, "videomae_hd64_dup": 1e-2,
-              "videomae_hd64_concat": 1e-2}
+    L0_GAP = {f"{fam}_hd64_{kind}": 1e-2 for fam in ("videomae", "vivit") for kind in ("prop0", "prop1", "dup", "concat")}
     # (fixture name, family, embed width, prop_attn, duplicate (layer, quantity) or None)
     #   embed 32  -> head dim 16: the first round's fixtures (generic kernels)
     #   embed 128 -> head dim 64: the production path in-model (tome_match_keys on the per-head keys of the qkv buffer,
@@ -733,24 +860,36 @@ def main():
              ("motionformer_hd64_dup", "motionformer", 128, True, (1, 2)),
              # head_aggregation="concat" (videomae.py:74-75; experiments.sh:164-169): the metric is the keys of all
              # heads side by side (D = 128 here, 768 at full size)
-             ("videomae_hd64_concat", "videomae", 128, False, None)]
+             ("videomae_hd64_concat", "videomae", 128, False, None),
+             # ViViT (vivit.py over the stand-in tree, see the module docstring): class_token=True in-model
+             ("vivit_prop1", "vivit", 32, True, None),
+             ("vivit_hd64_prop0", "vivit", 128, False, None), ("vivit_hd64_prop1", "vivit", 128, True, None),
+             ("vivit_hd64_dup", "vivit", 128, True, (1, 2)), ("vivit_hd64_concat", "vivit", 128, True, None)]
     argv = sys.argv[1:]
     if "--spread" in argv:
         return record_spread([a for a in argv if a != "--spread"], {s[0]: s for s in specs})
     only = set(argv)
     man_path = os.path.join(HERE, "manifest.json")
     manifest = json.load(open(man_path))
-    mode_names = [f"{fam}_hd64_{mode}" for fam in ("videomae", "timesformer", "motionformer") for mode in ("drop", "hybrid")]
+    mode_families = ("videomae", "timesformer", "motionformer", "vivit")
+    mode_names = [f"{fam}_hd64_{mode}" for fam in mode_families for mode in ("drop", "hybrid")]
     sections = {"models": [s[0] for s in specs], "config0": ["config0_videomae_b"], "modes": mode_names,
                 "full": list(FULL_SPECS)}
     check_partial_run(only, manifest, sections, HERE)
     old = {m["name"]: m for m in manifest.get("models", [])}
+    tree_checked = set()
+
+    def check_tree(fam, embed):  # before the first ViViT fixture of a width is stored
+        if fam == "vivit" and embed not in tree_checked:
+            assert_tree_is_hf(families[fam][0], embed)
+            tree_checked.add(embed)
     for name, fam, embed, prop, dup in specs:
         if only and name not in only:
             if name in old:
                 metas.append(old[name])
             continue
         build, patch_mod, r = families[fam]
+        check_tree(fam, embed)
         model, cfg, clip_shape, wseed = build(embed)
         names = synth.fill_parameters(model, wseed)  # (the reference zero-inits Motionformer's tubelet conv: duplicate tokens)
         extra = dict(host=fam, cfg=cfg, weight_seed=wseed, param_names=names)
@@ -765,14 +904,15 @@ def main():
             patch_mod.apply_patch(model, prop_attn=prop, head_aggregation="concat")
         else:
             patch_mod.apply_patch(model, prop_attn=prop)
-        metas.append(emit(name, model, lambda: model._tome_info, clip_shape, r_arg, patch_mod, False, extra, HERE, prop,
+        metas.append(emit(name, model, lambda: model._tome_info, clip_shape, r_arg, patch_mod, fam in CLS_FAMILIES, extra, HERE,
+                          prop,
                           l0_set_gap=L0_GAP.get(name, 0.0)))
     manifest["models"] = metas + retired(only, old, sections["models"])
     if not only or "config0_videomae_b" in only:
         manifest["config0"] = emit_config0(HERE)
     mode_old = {m["name"]: m for m in manifest.get("modes", [])}
     mode_metas = []
-    for fam in ("videomae", "timesformer", "motionformer"):
+    for fam in mode_families:
         for mode in ("drop", "hybrid"):
             name = f"{fam}_hd64_{mode}"
             if only and name not in only:
@@ -780,7 +920,8 @@ def main():
                     mode_metas.append(mode_old[name])
                 continue
             build, patch_mod, r = families[fam]
-            mode_metas.append(emit_mode(name, build, patch_mod, r, mode, fam != "videomae", HERE))
+            check_tree(fam, 128)
+            mode_metas.append(emit_mode(name, build, patch_mod, r, mode, fam != "videomae", HERE, cls=fam in CLS_FAMILIES))
     manifest["modes"] = mode_metas + retired(only, mode_old, mode_names)
     full_old = {m["name"]: m for m in manifest.get("full", [])}
     manifest["full"] = [emit_full(HERE, key, attempts=int(os.environ.get("TOME_FULL_ATTEMPTS", "24")))

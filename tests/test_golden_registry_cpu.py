@@ -41,8 +41,29 @@ def test_every_model_fixture_file_is_named_by_exactly_one_entry():
 
 def test_the_mode_fixtures_cover_drop_and_hybrid_of_every_family():
     got = sorted((m["host"], m["mode"]) for s, m in _entries() if s == "modes")
-    want = sorted((h, mode) for h in ("videomae", "timesformer", "motionformer") for mode in ("drop", "hybrid"))
+    want = sorted((h, mode) for h in ("videomae", "timesformer", "motionformer", "vivit") for mode in ("drop", "hybrid"))
     assert got == want
+
+
+def test_the_vivit_fixtures_are_the_seven_of_the_reference_patch():
+    """ViViT's fixtures (tome/patch/vivit.py of the reference over tests/golden/vivit_tree.py): head dim 16, head dim 64
+    with proportional attention off / on, the duplicate patch, `concat`, drop and hybrid -- each over 65 tokens (a
+    class token in front of 4 x 4 x 4 tubelets), and each records that the matching protected row 0: `unm` starts with
+    row 0 and is sorted, no source is row 0."""
+    got = sorted(m["name"] for _, m in _entries() if m["host"] == "vivit")
+    assert got == sorted(["vivit_prop1", "vivit_hd64_prop0", "vivit_hd64_prop1", "vivit_hd64_dup", "vivit_hd64_concat",
+                          "vivit_hd64_drop", "vivit_hd64_hybrid"])
+    for _, meta in _entries():
+        if meta["host"] != "vivit":
+            continue
+        assert meta["tokens"][0] == 65 and all(t % 5 == 0 for t in meta["tokens"]) and meta["certified"] is True
+        assert {"embed_dim", "num_heads", "depth"} <= set(meta["cfg"])
+        z = np.load(os.path.join(G.GOLDEN, f"models_{meta['name']}.npz"))
+        for i in range(len(meta["tokens"])):
+            src, unm = z[f"L{i}_src"].astype(np.int64), z[f"L{i}_unm"].astype(np.int64)
+            assert (src != 0).all() and (unm[:, 0] == 0).all() and (np.diff(unm, axis=1) > 0).all(), (meta["name"], i)
+        if meta["cfg"]["embed_dim"] // meta["cfg"]["num_heads"] == 64 and "mode" not in meta:
+            assert meta["l0_set_gap"] > 1e-2
 
 
 @pytest.mark.parametrize("section,meta", _entries(), ids=lambda v: v["name"] if isinstance(v, dict) else v)

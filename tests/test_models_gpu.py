@@ -1,12 +1,15 @@
 """Patched-model parity on the GPU (`-m gpu`): this repository's host models + `tome.patch.*` (HIP merge
 path) against golden vectors of the reference's own patched models (tests/golden/generate_models.py ran
-tome/patch/{videomae,timesformer,motionformer}.py over the slowfast model files on CPU).
+tome/patch/{videomae,timesformer,motionformer}.py over the slowfast model files on CPU, and tome/patch/vivit.py
+over tests/golden/vivit_tree.py, a stand-in module tree that tests/test_vivit_tree_cpu.py holds to the installed
+transformers' ViViT).
 
 Weights are filled by name (tests/synth.fill_parameters) on both sides, the clip comes from its seed.
 Checked per layer: token counts, r_eff, src/dst/unm indices (bit-exact: the fixtures' seeds were chosen
 so that every layer's decision margins are >= 5e-5, far above the fp32 GEMM noise between CPU and GPU);
 at the end: token sizes exactly, logits within 2e-4 (fp32 attention/MLP run on different BLAS).
-ViViT has no reference fixture (parity unpinned); it gets structural checks only.
+ViViT is the one family whose matching runs with class_token=True in-model: row 0 is protected, `unm_idx` is
+sorted, and the helpers that recompute row maxima from a metric mask row 0 as the matching does (`_CLS_HOSTS`).
 """
 import os
 import sys
@@ -39,6 +42,14 @@ def _build(meta):
         model = H["timesformer"].TimeSformer(num_frames=cfg.pop("num_frames"), num_classes=cfg.pop("num_classes"),
                                              attention_type=cfg.pop("attention_type"), **cfg)
         patch = tome.patch.timesformer
+    elif meta["host"] == "vivit":
+        V = H["vivit"]
+        model = V.ViViT(V.VivitConfig(image_size=cfg["image_size"], num_frames=cfg["num_frames"],
+                                      tubelet_size=tuple(cfg["tubelet_size"]), hidden_size=cfg["embed_dim"],
+                                      num_hidden_layers=cfg["depth"], num_attention_heads=cfg["num_heads"],
+                                      intermediate_size=cfg["intermediate_size"], layer_norm_eps=cfg["layer_norm_eps"],
+                                      qkv_bias=cfg["qkv_bias"]), num_classes=cfg["num_classes"])
+        patch = tome.patch.vivit
     else:
         model = H["motionformer"].Motionformer(**cfg)
         patch = tome.patch.motionformer
@@ -112,6 +123,16 @@ def _patched(meta, dtype=torch.float32):
     return tome, model.to(dtype)
 
 
+_CLS_HOSTS = ("vivit",)  # families whose in-model matching protects a class token (tome/patch/vivit.py:242 of the reference)
+
+
+def _blocks(model, meta):
+    """The list of transformer blocks of a host model (what apply_duplicate_patch grows)."""
+    if meta["host"] == "vivit":
+        return model.vivit.encoder.layer
+    return model.blocks if meta["host"] == "motionformer" else model.model.blocks
+
+
 def _clip(meta):
     """The fixture's clip batch: one synth.uniform01 clip per stored seed (tests/golden/generate_models.py)."""
     one = (1,) + tuple(meta["clip_shape"][1:])
@@ -154,8 +175,9 @@ def test_patched_model_matches_reference(meta, monkeypatch):
         assert calls.n["match_keys"] == len(plans) and calls.n["match"] == 0, calls.n
     if meta.get("duplicate"):
         lay, q = meta["duplicate"]
-        blocks = model.blocks if meta["host"] == "motionformer" else model.model.blocks
-        assert len(blocks) == meta["cfg"]["depth"] + q - 1 and len(plans) == q
+        assert len(_blocks(model, meta)) == meta["cfg"]["depth"] + q - 1 and len(plans) == q
+    if meta["host"] in _CLS_HOSTS:
+        assert model._tome_info["class_token"] is True and all(p.class_token for _, p in plans)
 
 
 _HD64 = [m for m in G.manifest()["models"] if m["cfg"]["embed_dim"] // m["cfg"]["num_heads"] == 64]
@@ -308,6 +330,12 @@ def _assert_production_calls(calls, meta, n_layers, n_match=None):
     if not meta.get("duplicate"):  # (a duplicate block only attends and merges: no LayerNorm behind that merge)
         fused = calls.n["merge_wavg_ln"] + calls.n["merge_wavg_regrouped"]
         assert fused == n_layers and calls.n["merge_wavg"] == 0, calls.n
+    if meta["host"] == "vivit":
+        # one joint sequence: the first residual, the merge and layernorm_after are ONE tome_merge_wavg_ln launch per
+        # layer that has a LayerNorm behind its merge (a duplicate layer has none: a plain merge_wavg), nothing regrouped
+        assert calls.n["merge_wavg_regrouped"] == 0 and calls.n["trajectory_mix"] == 0 and calls.n["short_attention"] == 0
+        n_dup = meta["duplicate"][1] - 1 if meta.get("duplicate") else 0
+        assert calls.n["merge_wavg_ln"] == n_layers - n_dup and calls.n["merge_wavg"] == n_dup, calls.n
 
 
 def _check_layer0_and_logits(meta, z, plans32, plans16, out16):
@@ -317,6 +345,12 @@ def _check_layer0_and_logits(meta, z, plans32, plans16, out16):
         return u[:, ::2] @ u[:, 1::2].transpose(-1, -2)
     s32, s16 = cos(plans32[0][2]), cos(plans16[0][2])
     noise = float((s32 - s16).abs().max())
+    if meta["host"] in _CLS_HOSTS:
+        # class_token=True: row 0 competes for nothing, exactly as the matching masks it (merge.py:59-60) -- its scores
+        # still count for the noise above, they are cosines of the same keys
+        assert plans32[0][1].class_token and plans16[0][1].class_token
+        s32[:, 0, :] = -float("inf")
+        s16[:, 0, :] = -float("inf")
     r = plans32[0][1].r
     nm, _ = s32.max(-1)
     snm = nm.sort(dim=-1, descending=True).values
@@ -485,8 +519,8 @@ def test_duplicate_layer_patches():
 def test_vivit_duplicate_layer_patch(dtype):
     """tome.patch.duplicate_vivit (tome/patch/vivit.py:207-211): deep copies that only attend + merge are inserted in
     front of the duplicated layer, `config.num_hidden_layers` grows by `quantity` as in the reference, the per-layer r
-    list walks the expected token counts, and the result equals running the layer's attention + merge by hand.  (No
-    reference fixture: the reference's ViViT patch cannot be imported here, SURVEY.md 8c -- parity unpinned.)  The
+    list walks the expected token counts, and the result equals running the layer's attention + merge by hand.  (Parity
+    with the reference's own duplicate patch: the `vivit_hd64_dup` fixture of test_patched_model_matches_reference.)  The
     16-bit run also crosses a duplicated layer with the fused residual / LayerNorm hand-over switched on."""
     tome, H = _hosts()
     torch.manual_seed(0)
@@ -856,8 +890,8 @@ def test_mode_fixtures_production_path_bf16_against_the_reference(meta, monkeypa
     tome, model16, patch = _build(meta)
     model16 = model16.to(torch.bfloat16)
     patch(model16, **kw)
-    blocks = model16.blocks if meta["host"] == "motionformer" else model16.model.blocks
-    counted = Counters(monkeypatch, [b.norm2 for b in blocks])
+    blocks = _blocks(model16, meta)
+    counted = Counters(monkeypatch, [b.layernorm_after if meta["host"] == "vivit" else b.norm2 for b in blocks])
     out16, plans16 = _trace(tome, model16, clip32.bfloat16(), meta["r"], keep_metric=True)
     assert [s[1] for s, *_ in plans16] == meta["tokens"] and [p.r for _, p, _ in plans16] == meta["r_eff"]
     assert [s[0] for s, *_ in plans16] == meta["groups"]

@@ -1,10 +1,11 @@
 """Structural cross-check of the ViViT host model (hosts/vivit.py) against the ViViT implementation of the
 installed HF `transformers` (third party, 5.x: `VivitForVideoClassification`): same weights -> same logits.
 
-This does NOT pin the reference's ToMe patch for ViViT (tome/patch/vivit.py needs `VivitSelfAttention`, which
-this transformers release no longer has -- SURVEY.md 8c: block-level parity of the ViViT *patch* stays unpinned);
-it pins the architecture the patch sits in: tubelet embedding, class token, learned positions, pre-LN layers
-with gelu_fast, final layernorm, logits from token 0.  CPU only."""
+This pins the architecture the ToMe patch sits in: tubelet embedding, class token, learned positions, pre-LN layers
+with gelu_fast, final layernorm, logits from token 0.  The reference's patch itself (tome/patch/vivit.py needs
+`VivitSelfAttention`, which this transformers release no longer has -- SURVEY.md 8c) is pinned by the `vivit_*`
+fixtures of tests/test_models_gpu.py, which the reference's patch made over tests/golden/vivit_tree.py; that tree is
+held to the installed ViViT by tests/test_vivit_tree_cpu.py with the rename map and tolerances of this file.  CPU only."""
 import os
 import sys
 

@@ -2,8 +2,10 @@
 out and slowfast/models/vivit_video_model_builder.py:13-67 wraps it in the reference): tubelet Conv3d
 embedding, class token, learned positions, pre-LN layers, final layernorm, logits from token 0.  Module
 names follow HF's `VivitModel` (embeddings / encoder.layer[i].attention.attention.{query,key,value} / ...)
-so HF checkpoints map onto it.  Block-level parity with HF is unpinned here: the installed
-transformers no longer has the class the reference patches."""
+so HF checkpoints map onto it.  The installed transformers no longer has the class the reference patches
+(SURVEY.md 8c); this tree is pinned to it twice over: tests/test_vivit_host_vs_hf.py (same weights, the installed
+ViViT's logits) and, patched, the seven `vivit_*` fixtures of tests/test_models_gpu.py, made by the reference's own
+ViViT patch over a stand-in tree with these names (tests/golden/vivit_tree.py)."""
 from __future__ import annotations
 
 import math
